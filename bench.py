@@ -10,11 +10,19 @@ Linear+BatchNorm1d head, 5-layer GRU over the packed captions, vocabulary projec
 entropy, full backward, optimizer step.  Workload = BASELINE.json configs[1]: bf16, B=128/GPU,
 E=H=512, L=5, V=10000, SGD(lr=0.01, momentum=0.9) (main.py:48-51 defaults).
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the MFMA implicit-GEMM
-convolution): algorithmic FLOPs of its launches / their summed duration, measured with HIP events
-on the launch stream in extra, separately instrumented steps right after the timed region (the
-timed steps themselves run uninstrumented).  `cpu_baseline` times the oracle's CPU restatement of
-the same step on the host cores (rank 0, N=1 only) on a bounded sample.
+Prints ONE JSON line (rank 0): the headline (`value` images/sec, `ms_per_step`) of the timed steps.
+A plain run does nothing else: set up, warm up, time the steps, print.
+
+--dump-outputs DIR writes what the last timed step computed (the loss, and the model it left: the
+trainable parameters after the update, the BatchNorm running statistics) to DIR/<name>.npy; the
+inputs are seeded, so two builds can be compared output for output.
+
+--full adds everything measured beside the headline, after the timed region.  `roofline` is for
+the dominant kernel (the MFMA implicit-GEMM convolution): algorithmic FLOPs of its launches / their
+summed duration, measured with HIP events on the launch stream in extra, separately instrumented
+steps (the timed steps themselves run uninstrumented).  `phases` splits one plain step, `secondary`
+times decode / beam / attention / input transform configurations, and `cpu_baseline` times the
+oracle's CPU restatement of the same step on the host cores (rank 0, N=1 only) on a bounded sample.
 """
 import argparse
 import ctypes as C
@@ -166,86 +174,9 @@ def self_launch(n):
     return 0
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)    # >= 50 timed steps after 10 warm-up
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--batch", type=int, default=128, help="images per GPU (BASELINE: 128)")
-    ap.add_argument("--vocab", type=int, default=10000)
-    ap.add_argument("--no-pipeline", action="store_true", help="do not issue the next minibatch's frozen backbone ahead on a second stream")
-    ap.add_argument("--optimizer", default="SGD", choices=["SGD", "Adam"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--profile-steps", type=int, default=2)
-    a = ap.parse_args()
-
-    if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # `python bench.py --gpus N` without a launcher: start the N ranks as fresh child processes (one per GPU) BEFORE this
-        # process touches the GPU, relay rank 0's JSON line and the launcher's return code.  Never exec.
-        return self_launch(a.gpus)
-
-    from showtell_amd import optim, parallel
+def roofline(a, rank, trainer, image, caption, lens):
+    """Roofline of the dominant kernel (rank 0; None elsewhere): instrumented steps, HIP events on the launch stream."""
     from showtell_amd._lib import lib
-    from showtell_amd.cnn import ResNet
-    from showtell_amd.rnn import RNN
-    from showtell_amd.train import Trainer, synthetic_batch
-
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs an MI355X (the HIP path has no CPU fallback)")
-    ndev = torch.cuda.device_count()
-    # RCCL (backend "nccl") is the product path; SHOWTELL_DIST_BACKEND=gloo only exists to rehearse N>1 on a 1-GPU box
-    backend = os.environ.get("SHOWTELL_DIST_BACKEND", "nccl")
-    _progress("start")
-    rank, world, local = parallel.init_from_env(backend, device_index=(int(os.environ.get("LOCAL_RANK", "0")) % max(1, ndev)))
-    if world != a.gpus:
-        raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {a.gpus}")
-    local = local % max(1, ndev)
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-    dtype = torch.bfloat16
-    E, H, L, V, B = 512, 512, 5, a.vocab, a.batch
-
-    torch.manual_seed(1)                                     # main.py:26-27
-    cnn = ResNet(101, E, dtype=dtype).to(dev).train()        # main.py:92,125
-    rnn = RNN(E, H, V, L, dtype=dtype).to(dev).train()       # main.py:93,126
-    params = Trainer.trainable_params(cnn, rnn)              # main.py:96
-    opt = optim.SGD(params, lr=0.01, momentum=0.9) if a.optimizer == "SGD" else optim.Adam(params, lr=1e-4)
-    trainer = Trainer(cnn, rnn, opt, world)
-    image, caption, lens = synthetic_batch(B, V, seed=1 + rank, device=dev)
-
-    def barrier():
-        torch.cuda.synchronize()
-        if world > 1:
-            torch.distributed.barrier()
-        torch.cuda.synchronize()
-
-    # Steps are software-pipelined: the frozen backbone forwards of minibatches k+1 .. k+3 are issued on side streams
-    # while step k runs its trainable part (train.py).  Nothing is carried across the timing boundaries: the last warm-up
-    # steps and the last timed steps prefetch nothing beyond their loop, so the timed region holds exactly `steps` complete
-    # steps (the first one unpipelined, the second half-pipelined).
-    pipe = not a.no_pipeline
-    def ahead(k, n):   # the minibatches after step k that exist inside this loop (never across a timing boundary)
-        return dict(upcoming=[image] * min(trainer.depth, n - 1 - k) if pipe else ())
-    _progress("warm-up")
-    for k in range(a.warmup):
-        trainer.step(image, caption, lens, **ahead(k, a.warmup))
-    trainer.flush()
-    barrier()
-    t0 = time.perf_counter()
-    loss = None
-    for k in range(a.steps):
-        loss = trainer.step(image, caption, lens, **ahead(k, a.steps))
-    trainer.flush()
-    barrier()
-    dt = time.perf_counter() - t0
-    if world > 1:
-        t = torch.tensor([dt], device=dev, dtype=torch.float64)
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        dt = float(t.item())
-    final_loss = float(loss.item()) if loss is not None else float("nan")
-
-    _progress("timed region done: %.3f ms/step" % (dt / a.steps * 1e3))
-    # ---- roofline of the dominant kernel: instrumented steps, HIP events on the launch stream --------------
     roof = None
     if rank == 0:
         lib().st_prof_enable(1)
@@ -305,10 +236,129 @@ def main():
                 "all_conv_ms_per_step": round(tot_ms / max(1, a.profile_steps), 3),
                 "by_kernel": {names.get(i, f"variant{i}").split(" (")[0].split(":")[0]: {"ms_per_step": round(ms[i] / max(1, a.profile_steps), 3), "launches": int(n[i]),
                                                                        "TFLOPs": round(fl[i] / (ms[i] * 1e-3) / 1e12, 1)} for i in range(32) if n[i] > 0}}
-    _progress("phases")
+    return roof
+
+
+DUMP_SAMPLE = 1 << 18                 # --dump-outputs: elements kept of a larger array (a fixed sample, the same in every run)
+
+
+def dump_outputs(out_dir, loss, cnn, rnn):
+    """What the last timed step handed back: its loss (float64) and the model it left (float32): the trainable parameters
+    after the optimizer update (`param.*`) and the BatchNorm running statistics the train-mode forward updated (`buffer.*`).
+    Gradients are left out: some are analytically zero (a bias in front of a BatchNorm) and hold rounding noise only.
+    An array of more than DUMP_SAMPLE elements is written as the elements at DUMP_SAMPLE sorted indices drawn without
+    replacement by numpy's default_rng seeded with the array's size."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": np.asarray(float(loss.item()), dtype=np.float64)}
+    trainable = [("rnn." + n, p) for n, p in rnn.named_parameters()]
+    trainable += [("cnn." + n, p) for n, p in cnn.named_parameters() if n.startswith(("linear_secondlast_layer.", "last_layer."))]
+    buffers = [("cnn." + n, b) for n, b in cnn.named_buffers() if b.is_floating_point()]
+    tensors = [("param." + n, p.detach()) for n, p in trainable] + [("buffer." + n, b) for n, b in buffers]
+    for name, t in tensors:
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(flat.numel()).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arrays[name] = flat.float().cpu().numpy()
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= 64 << 20, "outputs of %d bytes exceed 64 MB" % total
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    _progress("outputs: %d arrays, %.1f MB in %s" % (len(arrays), total / 2**20, out_dir))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=50)    # SURVEY 8(d) config 2: >= 50 timed steps after 10 warm-up
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--batch", type=int, default=128, help="images per GPU (BASELINE: 128)")
+    ap.add_argument("--vocab", type=int, default=10000)
+    ap.add_argument("--no-pipeline", action="store_true", help="do not issue the next minibatch's frozen backbone ahead on a second stream")
+    ap.add_argument("--optimizer", default="SGD", choices=["SGD", "Adam"])
+    ap.add_argument("--full", action="store_true", help="also measure roofline, phases, secondary configurations and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--profile-steps", type=int, default=2, help="with --full: instrumented steps of the roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+
+    if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        # `python bench.py --gpus N` without a launcher: start the N ranks as fresh child processes (one per GPU) BEFORE this
+        # process touches the GPU, relay rank 0's JSON line and the launcher's return code.  Never exec.
+        return self_launch(a.gpus)
+
+    from showtell_amd import optim, parallel
+    from showtell_amd.cnn import ResNet
+    from showtell_amd.rnn import RNN
+    from showtell_amd.train import Trainer, synthetic_batch
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench.py needs an MI355X (the HIP path has no CPU fallback)")
+    ndev = torch.cuda.device_count()
+    # RCCL (backend "nccl") is the product path; SHOWTELL_DIST_BACKEND=gloo only exists to rehearse N>1 on a 1-GPU box
+    backend = os.environ.get("SHOWTELL_DIST_BACKEND", "nccl")
+    _progress("start")
+    rank, world, local = parallel.init_from_env(backend, device_index=(int(os.environ.get("LOCAL_RANK", "0")) % max(1, ndev)))
+    if world != a.gpus:
+        raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {a.gpus}")
+    local = local % max(1, ndev)
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    dtype = torch.bfloat16
+    E, H, L, V, B = 512, 512, 5, a.vocab, a.batch
+
+    torch.manual_seed(1)                                     # main.py:26-27
+    cnn = ResNet(101, E, dtype=dtype).to(dev).train()        # main.py:92,125
+    rnn = RNN(E, H, V, L, dtype=dtype).to(dev).train()       # main.py:93,126
+    params = Trainer.trainable_params(cnn, rnn)              # main.py:96
+    opt = optim.SGD(params, lr=0.01, momentum=0.9) if a.optimizer == "SGD" else optim.Adam(params, lr=1e-4)
+    trainer = Trainer(cnn, rnn, opt, world)
+    image, caption, lens = synthetic_batch(B, V, seed=1 + rank, device=dev)
+
+    def barrier():
+        torch.cuda.synchronize()
+        if world > 1:
+            torch.distributed.barrier()
+        torch.cuda.synchronize()
+
+    # Steps are software-pipelined: the frozen backbone forwards of minibatches k+1 .. k+3 are issued on side streams
+    # while step k runs its trainable part (train.py).  Nothing is carried across the timing boundaries: the last warm-up
+    # steps and the last timed steps prefetch nothing beyond their loop, so the timed region holds exactly `steps` complete
+    # steps (the first one unpipelined, the second half-pipelined).
+    pipe = not a.no_pipeline
+    def ahead(k, n):   # the minibatches after step k that exist inside this loop (never across a timing boundary)
+        return dict(upcoming=[image] * min(trainer.depth, n - 1 - k) if pipe else ())
+    _progress("warm-up")
+    for k in range(a.warmup):
+        trainer.step(image, caption, lens, **ahead(k, a.warmup))
+    trainer.flush()
+    barrier()
+    t0 = time.perf_counter()
+    loss = None
+    for k in range(a.steps):
+        loss = trainer.step(image, caption, lens, **ahead(k, a.steps))
+    trainer.flush()
+    barrier()
+    dt = time.perf_counter() - t0
+    if world > 1:
+        t = torch.tensor([dt], device=dev, dtype=torch.float64)
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+        dt = float(t.item())
+    final_loss = float(loss.item()) if loss is not None else float("nan")
+
+    _progress("timed region done: %.3f ms/step" % (dt / a.steps * 1e3))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, loss, cnn, rnn)
+    # ---- everything below the headline: --full only ----------------------------------------------------------------------
+    roof = phases = secondary = None
+    if a.full:
+        roof = roofline(a, rank, trainer, image, caption, lens)
+        _progress("phases")
     # ---- per-phase split of one plain (unpipelined) step, SURVEY 8(d) config 2: HIP events on the launch stream ----------
-    phases = None
-    if rank == 0 and world == 1:
+    if a.full and rank == 0 and world == 1:
         try:
             from showtell_amd.head import linear_bn1d
             ev = [[torch.cuda.Event(enable_timing=True) for _ in range(5)] for _ in range(3)]
@@ -348,10 +398,9 @@ def main():
             phases["unit"] = "ms per plain step (no forwards in flight); the pipelined step overlaps the encoder of later minibatches with the rest"
         except Exception as e:
             phases = {"error": repr(e)}
-    _progress("secondary: decode / beam / attention / input transform")
     # ---- secondary (rank 0, N=1): greedy decode step against the HBM roofline, beam=5 captions/sec -------------
-    secondary = None
-    if rank == 0 and world == 1:
+    if a.full and rank == 0 and world == 1:
+        _progress("secondary: decode / beam / attention / input transform")
         try:
             rnn.eval()
             feat = torch.randn(B, E, device=dev)
@@ -590,7 +639,7 @@ def main():
                                        "every step's full work is inside the timed region") if pipe else "plain loop (--no-pipeline)",
                           "final_loss": round(final_loss, 4)},
                "roofline": roof, "phases": phases, "secondary": secondary}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             ncpu = host_cores()
             _progress("cpu baseline on %d cores" % ncpu)
             try:

@@ -1,7 +1,7 @@
 """Load the reference's decoder classes in the authoring container (TEST INFRASTRUCTURE).
 
-Used only by ``oracle/gen_golden.py`` and ``tests/test_oracle_pin.py``; both
-skip when ``/root/reference`` is absent (it never travels to the GPU box).
+Used only by ``oracle/gen_golden.py``, which stores the reference's outputs as
+fixtures under ``tests/golden/``; the tests read those, never the reference.
 
 The reference files are imported unmodified.  ``rnn.py`` imports torchvision
 (absent here) at module top although ``RNN`` itself only needs ``torch.nn``, so

@@ -1,6 +1,6 @@
 """Generate tests/golden/*.npz by RUNNING THE REFERENCE's own classes (authoring container only).
 
-    PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden.py
+    PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden.py [eval | pin]
 
 Each fixture holds data only: random-init weights (seeded), inputs and the
 reference's outputs (logits, loss, gradients, greedy / beam token ids).  No
@@ -188,10 +188,48 @@ def gen_eval(ref, name):
         json.dump(cases, f)
 
 
+def gen_pin(ref, name, eval_name):
+    """Inputs + outputs of the reference's decoders on the random shapes of tests/test_oracle_pin.py, and of its evaluate()
+    on the random captions of tests/test_evaluation.py: the oracle is pinned to these wherever the reference is absent."""
+    d = {}
+    for seed in (0, 1, 2):
+        rng = np.random.RandomState(seed)
+        E, H, V, L, B = int(rng.choice([16, 32])), int(rng.choice([16, 48])), 30, int(rng.randint(1, 4)), int(rng.randint(1, 6))
+        torch.manual_seed(seed)
+        m = ref.rnn.RNN(E, H, V, L).eval()
+        cap, lens = R.synthetic_captions(B, V, seed=seed, mean=6, std=2, lo=3, hi=9)
+        feat = torch.randn(B, E)
+        with torch.no_grad():
+            d.update(sd_np(m, "gru%d/p/" % seed))
+            d.update({"gru%d/feat" % seed: feat.numpy(), "gru%d/caption" % seed: cap.numpy(), "gru%d/lens" % seed: np.array(lens),
+                      "gru%d/logits" % seed: m(feat, cap, lens).numpy(), "gru%d/greedy" % seed: m.sentence_index(feat).numpy()})
+    torch.manual_seed(3)
+    m = ref.rnn_attn.RNN_Attn(16, 24, 20, 32, 30, 2).eval()
+    cap, lens = R.synthetic_captions(3, 30, seed=3, mean=6, std=2, lo=3, hi=9)
+    feat = torch.randn(3, 24, 49)
+    with torch.no_grad(), _refload.cpu_cuda():
+        lg, al = m(feat, cap, lens)
+    d.update(sd_np(m, "attn/p/"))
+    d.update({"attn/feat": feat.numpy(), "attn/caption": cap.numpy(), "attn/lens": np.array(lens),
+              "attn/logits": lg.numpy(), "attn/alphas": al.numpy()})
+    np.savez_compressed(os.path.join(OUT, name), **d)
+    print(name, len(d), "arrays")
+    rng = np.random.RandomState(17)
+    words = ["w%d" % i for i in range(9)]
+    target = [[[str(w) for w in rng.choice(words, size=rng.randint(2, 9))] for _ in range(rng.randint(1, 4))] for _ in range(10)]
+    predicted = [[str(w) for w in rng.choice(words, size=rng.randint(1, 9))] for _ in range(10)]
+    scores = {k: float(v) for k, v in ref.metrics.evaluate(target, predicted).items()}
+    with open(os.path.join(OUT, eval_name), "w") as f:
+        json.dump({"target": target, "predicted": predicted, "scores": scores}, f)
+    print(eval_name, scores)
+
+
 def main():
     assert _refload.available(), "reference not present"
     if sys.argv[1:] == ["eval"]:
         return gen_eval(_refload.load_reference(), "eval_small.json")
+    if sys.argv[1:] == ["pin"]:
+        return gen_pin(_refload.load_reference(), "oracle_pin.npz", "eval_random.json")
     os.makedirs(OUT, exist_ok=True)
     ref = _refload.load_reference()
     gen_rnn(ref, "gru", "gru_small.npz")
@@ -201,6 +239,7 @@ def main():
     gen_beam(ref, "beam_small.npz")
     gen_bleu(ref, "bleu_small.json")
     gen_eval(ref, "eval_small.json")
+    gen_pin(ref, "oracle_pin.npz", "eval_random.json")
 
 
 if __name__ == "__main__":

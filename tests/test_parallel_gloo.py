@@ -19,10 +19,15 @@ def _free_port():
     return p
 
 
+def _device(rank):
+    """The device a rank binds to where GPUs are visible: ranks share them (bench.py's rule), one GPU serves both ranks."""
+    return rank % max(1, torch.cuda.device_count())
+
+
 def _worker(rank, world, port, n, bucket, out_dir):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     from showtell_amd import parallel
-    r, w, _ = parallel.init_from_env("gloo")
+    r, w, _ = parallel.init_from_env("gloo", device_index=_device(rank))
     assert (r, w) == (rank, world)
     g = torch.Generator().manual_seed(100 + rank)
     flat = torch.randn(n, generator=g)
@@ -57,7 +62,7 @@ def test_single_process_is_a_noop():
 def _bcast_worker(rank, world, port, out_dir):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     from showtell_amd import parallel
-    parallel.init_from_env("gloo")
+    parallel.init_from_env("gloo", device_index=_device(rank))
     torch.manual_seed(rank)                                    # every rank starts from DIFFERENT weights and buffers
     m = torch.nn.Sequential(torch.nn.Linear(5, 3), torch.nn.BatchNorm1d(3))
     with torch.no_grad():
