@@ -375,6 +375,13 @@ int st_resnet_forward(const st_resnet* r, const float* images_nchw, int B, int H
 
 int st_resnet_update_running(const st_resnet* r, const void* workspace, float* bn_running_mean, float* bn_running_var,
                              float momentum, void* stream);
+/* The launch list st_resnet_forward would issue for (B, H, W, train), planned on the host (no device call): one text line per
+ * launch, in launch order, the ST_LAYER_LOG format
+ *   family,what,cin,cout,k,stride,hin,win,flops,bytes,replicas_out,replicas_in
+ * (replicas_out: BatchNorm statistics replicas the launch writes; replicas_in: replicas of the input BatchNorm it reads, 0 without
+ * one; bn_reduce_replicas: 1, the replicas it sums).  Returns the text's length and writes it with a terminating NUL when
+ * bytes > that length (buf = NULL, bytes = 0 asks for the length); -1 on an error (st_last_error). */
+int st_resnet_plan(const st_resnet* r, int B, int H, int W, int train, char* buf, size_t bytes);
 
 int st_cast2d(const void* x, void* y, int from_dtype, int to_dtype, int rows, int cols, int ldx, int ldy, void* stream);
 

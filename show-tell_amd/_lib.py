@@ -194,6 +194,7 @@ _SIGS = {
     "st_resnet_forward": ([c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_p, C.c_size_t,
                            c_p, c_p, c_i, c_p, c_p], c_i),
     "st_resnet_update_running": ([c_p, c_p, c_p, c_p, c_f, c_p], c_i),
+    "st_resnet_plan": ([c_p, c_i, c_i, c_i, c_i, C.c_char_p, C.c_size_t], c_i),
 }
 
 _lib = None

@@ -17,6 +17,7 @@
 #include <map>
 #include <mutex>
 #include <new>
+#include <string>
 #include <string.h>
 #include <stdlib.h>
 
@@ -221,28 +222,21 @@ extern "C" int st_resnet_set_taps(st_resnet* r, void* buf, size_t bytes) {
 
 namespace {
 // ST_LAYER_LOG=<file>: one line per kernel launch of a forward, in launch order -- which kernel family took which layer, its
-// geometry, algorithmic FLOPs and HBM bytes (tools/layer_table.py joins it with the rocprofv3 kernel trace of the same process)
+// geometry, algorithmic FLOPs and HBM bytes, statistics replicas written / read (tools/layer_table.py joins it with the rocprofv3
+// kernel trace of the same process).  The same lines as st_resnet_plan.
 FILE* layer_log() {
   static FILE* f = [] { const char* e = getenv("ST_LAYER_LOG"); return e && *e ? fopen(e, "w") : nullptr; }();
   return f;
 }
-void log_launch(const char* kernel, const char* what, int cin, int cout, int k, int stride, int hin, int win, double flops, double bytes) {
-  if (FILE* f = layer_log()) {
-    fprintf(f, "%s,%s,%d,%d,%d,%d,%d,%d,%.0f,%.0f\n", kernel, what, cin, cout, k, stride, hin, win, flops, bytes);
-    fflush(f);
-  }
-}
-struct Plan {
-  size_t in_bytes, s2dw_bytes, stem_bytes, wide_bytes, narrow_bytes, stats_bytes, fold_bytes, total;
-};
+struct Layout { size_t in_bytes, s2dw_bytes, stem_bytes, wide_bytes, narrow_bytes, stats_bytes, fold_bytes, total; };
 // Space-to-depth stem (even H, W): the 7x7 stride-2 pad-3 conv over 3 channels is the same sum as a 4x4 stride-1
 // conv over the 2x2-blocked image (12 channels, padded to 16; 2 zero rows/cols before, 1 after).  Four neighbouring
 // blocked pixels are 128 contiguous bytes, so each filter row is one whole-line tap of the fast loader
 // (st_conv sliding-window form) instead of 49 scattered 16-byte gathers per output pixel.
 inline bool stem_s2d(int H, int W) { return H % 2 == 0 && W % 2 == 0; }
-Plan make_plan(const st_resnet* r, int B, int H, int W) {
+Layout make_layout(const st_resnet* r, int B, int H, int W) {
   const size_t es = st_dtype_size(r->dtype);
-  Plan p;
+  Layout p;
   p.in_bytes = align256((size_t)B * H * W * r->cpad0 * es);
   if (stem_s2d(H, W)) { const size_t b2 = align256((size_t)B * (H / 2 + 3) * (W / 2 + 3) * 16 * es); if (b2 > p.in_bytes) p.in_bytes = b2; }
   p.s2dw_bytes = align256((size_t)64 * 256 * es);
@@ -258,11 +252,277 @@ Plan make_plan(const st_resnet* r, int B, int H, int W) {
   p.total = p.in_bytes + p.s2dw_bytes + p.stem_bytes + 3 * p.wide_bytes + 2 * p.narrow_bytes + p.stats_bytes + p.fold_bytes;
   return p;
 }
+
+// A forward is planned on the host first (plan_forward: every kernel choice, replica count and workspace slot), then the
+// executor (st_resnet_forward) fills one descriptor per entry and launches it.
+enum Route {
+  R_IGEMM, R_IMG, R_S2, R_WREG, R_ASTAT, R_KSTREAM,   // one conv on st_conv / st_conv3x3_img / st_conv3x3_s2 / the pointwise kernels
+  R_KFUSE, R_B2B, R_B2B0, R_C3C1,                     // the previous block's end fused into this conv1 (b2b N = 0: no conv1)
+  R_STEM, R_STEM_POOL, R_MAXPOOL,                     // generic stem conv (st_conv), its pool; the fused bf16 stem
+  R_BN_ACT, R_REDUCE, R_TAP                           // normalise pass, statistics replicas -> replica 0, st_resnet_set_taps copy
+};
+// workspace slots: input, stem output, wide[3] (block inputs / outputs), narrow[2] (conv1 / conv2 outputs)
+enum Slot { S_NONE = -1, S_IN, S_STEM, S_WIDE, S_NARROW = S_WIDE + 3, S_COUNT = S_NARROW + 2 };
+
+struct Launch {
+  Route route;
+  int ci;               // the conv (bn_act / reduce: whose statistics; tap: whose output; kfuse / b2b / c3c1: the next conv1)
+  int hin, win;         // input map (bn_act / tap: the tensor's map)
+  int x, y, res, xout;  // slots: input (b2b / c3c1: raw conv2 output), output (S_NONE: statistics only), identity or eval
+                        // residual, block output formed on the way (kfuse / b2b / c3c1)
+  int relu;             // eval epilogue
+  int in_ci;            // conv whose BatchNorm (+ ReLU) the loader applies (kfuse: the previous conv3; b2b / c3c1: its bn2)
+  int pc;               // kfuse / b2b / c3c1: the previous block's conv3 (b2b N = 0: this block's)
+  int id_ci;            // the identity's BatchNorm source (a downsample conv), -1: none
+  int rep_out, rep_in;  // statistics replicas written / read (reduce: summed)
+};
+constexpr int kMaxLaunches = 768;   // >= 8 + 14 per block (ResNet-152: 50 blocks)
+struct FwdPlan { int n; bool s2d; int h, w, out; BnTable tab; Launch l[kMaxLaunches]; };
+
+int plan_forward(const st_resnet* r, int B, int H, int W, bool train, FwdPlan& p) {
+  const int nconv = (int)r->convs.size(), nblk = (int)r->blocks.size();
+  ST_CHECK(nconv <= 160 && 8 + 14 * nblk <= kMaxLaunches, "st_resnet_forward: too many layers");
+  const bool bf16 = r->dtype == ST_BF16;
+  BnTable& tab = p.tab;
+  tab.n = nconv;
+  for (int i = 0; i < nconv; ++i) { tab.end[i] = (int)(r->convs[i].bnoff + r->convs[i].cout); tab.count[i] = 1.f; tab.soff[i] = 0; tab.rep[i] = 1; }
+  // pass 1: every conv's input map and the kernel it runs on by itself (res: eval epilogue with a residual)
+  int hin[160], win[160], hout[160], wout[160];
+  Route rt[160];
+  auto geo = [&](int ci, int h, int w, bool res) {
+    const ConvL& c = r->convs[ci];
+    hin[ci] = h; win[ci] = w;
+    hout[ci] = conv_out(h, c.k, c.stride, c.pad); wout[ci] = conv_out(w, c.k, c.stride, c.pad);
+    tab.count[ci] = (float)((long)B * hout[ci] * wout[ci]);
+    // (eval mode: conv3 takes the block's identity in its epilogue -- the register-filter and activation-stationary kernels have that
+    // form for stride 1 and <= 512 input channels, i.e. every conv3 of a Bottleneck; the 3x3 kernels do not have it)
+    rt[ci] = R_IGEMM;
+    if (!bf16 || c.ntw == 0) return;
+    if (c.k == 1 && (!res || (c.stride == 1 && c.cin <= 512))) rt[ci] = use_astat(c) ? R_ASTAT : c.cin > 512 ? R_KSTREAM : R_WREG;
+    else if (c.k == 3 && c.stride == 1 && !res && st_conv3x3_img_supported(h, w, c.cin, c.cout) == c.ntw) rt[ci] = R_IMG;
+    else if (c.k == 3 && c.stride == 2 && !res && st_conv3x3_s2_supported(c.cin, c.cout) == c.ntw && (long)B * h * w * c.cin * 2 < (1L << 31))
+      rt[ci] = R_S2;
+  };
+  geo(0, H, W, false);
+  rt[0] = R_STEM;
+  int h = conv_out(hout[0], 3, 2, 1), w = conv_out(wout[0], 3, 2, 1);
+  for (const BlockL& b : r->blocks) {
+    geo(b.c1, h, w, false);
+    if (b.ds >= 0) geo(b.ds, h, w, false);
+    if (r->bottleneck) { geo(b.c2, hout[b.c1], wout[b.c1], false); geo(b.c3, hout[b.c2], wout[b.c2], !train); }
+    else geo(b.c2, hout[b.c1], wout[b.c1], !train);
+    h = hout[r->bottleneck ? b.c3 : b.c2]; w = wout[r->bottleneck ? b.c3 : b.c2];
+  }
+  p.h = h; p.w = w;
+
+  // pass 2: the launches.  rep_in is read when the consumer is added, so it is final: a producer's reduction runs right behind it.
+  p.n = 0;
+  int stats_used = 0;   // floats handed out so far
+  auto add = [&](Route k, int ci, int x, int y, int in_ci) -> Launch& {
+    Launch& l = p.l[p.n++];
+    l = Launch{k, ci, hin[ci], win[ci], x, y, S_NONE, S_NONE, 1, in_ci, -1, -1, 0, in_ci >= 0 ? tab.rep[in_ci] : 0};
+    return l;
+  };
+  // train: the conv's kernel writes rep_out replicas of its statistics.  Every consumer sums up to 16 replicas itself (bn_act, the
+  // conv_img.hip / b2b / c3c1 loaders, the running-buffer update) except igemm's input transform and the stem's pool (rep0): those
+  // read replica 0, behind a reduction launch
+  auto produce = [&](Launch& l, bool rep0) {
+    if (!train) return;
+    const ConvL& c = r->convs[l.ci];
+    const auto fits = [&](int rep) { return rep * 2 * c.cout <= kStatsRepFloats; };
+    int rep = 1;
+    if (l.route == R_IGEMM || l.route == R_STEM) {
+      // keep ~128-256 pixel tiles per replica (same-address atomics serialise)
+      const long tiles = ((long)B * hout[l.ci] * wout[l.ci] + 127) / 128;
+      while (rep < 64 && tiles / (rep * 2) >= 128 && fits(rep * 2)) rep *= 2;
+    } else if (l.route == R_IMG) {
+      const long items = (long)B * ((l.hin * (l.win + 2) + 223) / 224);   // ~ workgroups along M
+      while (rep < 4 && items / (rep * 2) >= 4 && fits(rep * 2)) rep *= 2;
+    } else {
+      // four replicas: the statistics leave a workgroup as full-wave atomics over consecutive channels (block_stats_flush), so the
+      // same-address queue is what is left to spread -- and every consumer adds the replicas up in its prologue (cheap at 4)
+      while (rep < 4 && fits(rep * 2)) rep *= 2;
+    }
+    tab.soff[l.ci] = stats_used; tab.rep[l.ci] = l.rep_out = rep;
+    stats_used += rep * 2 * c.cout;
+    if (rep > 1 && (rep0 || rep > 16)) {
+      Launch& q = add(R_REDUCE, l.ci, S_NONE, S_NONE, -1);
+      q.rep_out = 1; q.rep_in = rep;
+      tab.rep[l.ci] = 1;
+    }
+  };
+  auto bnact = [&](int ci, int x, int res, int id_ci) {      // train-mode normalise (+identity [+its BN]) + ReLU, in place
+    Launch& l = add(R_BN_ACT, ci, x, x, ci);
+    l.hin = hout[ci]; l.win = wout[ci]; l.res = res; l.id_ci = id_ci;
+  };
+  auto tap = [&](int ci, int slot) { Launch& l = add(R_TAP, ci, slot, S_NONE, -1); l.hin = hout[ci]; l.win = wout[ci]; };
+
+  // bf16 bottleneck nets on even image sizes: the whole stem (conv1 + statistics + maxpool) is ONE kernel (conv_stem.hip).  In train
+  // mode it leaves the pooled RAW conv output in wide[0]; bn1 + relu are applied by the loaders of its two consumers (conv1 and the
+  // downsample conv of the first block, both on st_conv1x1_wreg: they sum the 8 replicas) -- pooling commutes with the monotone
+  // per-channel map, see conv_stem.hip.
+  p.s2d = stem_s2d(H, W);
+  const BlockL* b0 = nblk ? &r->blocks[0] : nullptr;
+  const bool stem_fused = p.s2d && r->bottleneck && b0 && b0->ds >= 0 && rt[b0->c1] == R_WREG && rt[b0->ds] == R_WREG;
+  if (stem_fused) {
+    Launch& l = add(R_STEM_POOL, 0, S_IN, S_WIDE, -1);
+    if (train) { tab.soff[0] = stats_used; tab.rep[0] = l.rep_out = 8; stats_used += 8 * 2 * r->convs[0].cout; }
+  } else {
+    produce(add(R_STEM, 0, S_IN, S_STEM, -1), true);
+    Launch& l = add(R_MAXPOOL, 0, S_STEM, S_WIDE, train ? 0 : -1);   // train: bn1 + relu folded into the pool
+    l.hin = hout[0]; l.win = wout[0];
+  }
+  const int stem_in = (stem_fused && train) ? 0 : -1;   // the first block's conv1 / downsample read relu(bn1(.)) of wide[0] in their loaders
+
+  // a block whose end the NEXT block's conv1 launch forms (kfuse / b2b / c3c1): wide[raw] holds its raw conv3 output (b2b / c3c1:
+  // never written), wide[res] its identity
+  struct Pending { bool on; Route k; int pc, c2, id_ci, raw, res; } pend{false, R_KFUSE, -1, -1, -1, 0, 0};
+  int cur = 0;  // wide[cur] holds the block input
+  for (int bi = 0; bi < nblk; ++bi) {
+    const BlockL& b = r->blocks[bi];
+    int x1 = S_WIDE + cur;
+    if (pend.on) {   // the buffer that is neither the raw conv3 output nor the identity takes x (b2b / c3c1: conv3's buffer)
+      x1 = pend.k == R_KFUSE ? S_WIDE + pend.raw : S_NARROW + 1;
+      cur = pend.k == R_KFUSE ? 3 - pend.raw - pend.res : pend.raw;
+    }
+    const int xin = S_WIDE + cur, oth = (cur + 1) % 3, dsb = (cur + 2) % 3;
+    const int res = b.ds >= 0 ? S_WIDE + dsb : xin;
+    const int in0 = bi == 0 ? stem_in : -1;
+    const ConvL& c2 = r->convs[b.c2];
+    if (r->bottleneck) {
+      const ConvL& c3 = r->convs[b.c3];
+      // train: bn1 + relu ride in conv2's loader -- the image-resident and stride-2 kernels sum conv1's replicas, st_conv (igemm
+      // MODE 2, padding taps stay zero) reads replica 0 behind a reduction (5 us against a 14 - 44 us pass over the tensor)
+      const bool in1 = train && bf16 && (rt[b.c2] == R_IMG || c2.cin % 64 == 0);
+      // train: bn2 + relu ride in conv3's loader; needs whole 64-channel (f32: 32) K tiles, which every bottleneck width satisfies
+      const bool in2 = train && c3.cin % 64 == 0;
+      // 14 x 14 blocks (256 -> 1024 -> next conv1 1024 -> 256) and 28 x 28 blocks (128 -> 512 -> 128), train AND eval: conv3 + block
+      // end + next conv1 as one kernel (st_conv_c3c1).  Train: conv3 runs here as a statistics-only pass (y == NULL); an identity that
+      // still needs its own BatchNorm (the block behind a downsample conv) rides in the kernel's IDBN form.  Eval: conv3 is not
+      // launched at all.  The kernel indexes both fragment-major filter copies with fixed tile permutations: conv3 packed with
+      // ntw = 2, conv1 with N / 64 (as st_conv_b2b, conv_b2b.hip:63-65: a retuned pw_cfg table / ST_PW_CFG must not reach them).
+      const ConvL* n1 = bi + 1 < nblk ? &r->convs[r->blocks[bi + 1].c1] : nullptr;
+      const bool c3c1 = n1 && c3.ntw == 2 && n1->ntw == n1->cout / 64 && st_conv_c3c1_supported(c3.cin, c3.cout, n1->cout) &&
+                        (!train || in2) && (long)B * hout[b.c2] * wout[b.c2] * c3.cout * 2 < (1L << 31);
+      // Train, 256-channel block inputs (layer1 and the first block of layer2): the block-end pass relu(bn3(raw) + identity) is formed
+      // by the NEXT block's conv1 loader (st_conv1x1_kfuse) -- that pass and conv1 are both HBM time there and the fusion drops one full
+      // read of the widest tensor (measured 168 -> 125 us per transition at 56 x 56, B = 128).  Wider inputs stay separate: their conv1
+      // needs several channel slices per row (each would re-read both inputs) or, at 1024 channels, is MFMA-bound (measured slower fused).
+      const bool kfuse = n1 && !c3c1 && train && rt[r->blocks[bi + 1].c1] == R_WREG && n1->cin == 256 &&
+                         st_conv1x1_kfuse_supported(n1->cin, n1->cout) == n1->ntw;
+      // conv3 recomputed inside st_conv_b2b, run here for its statistics only: at the 56 x 56 boundaries with the next conv1 (64 -> 256
+      // -> 64 / 128), at 28 x 28 (128 -> 512, N = 0) stopping at the block output x = relu(bn3(conv3(..)) + identity) -- the raw
+      // 512-channel tensor (103 MB at B = 128) is neither written nor read
+      const bool b2b = !c3c1 && in2 && rt[b.c3] == R_WREG && c3.ntw == 2 && (!kfuse || n1->ntw == n1->cout / 64) &&
+                       st_conv_b2b_supported(c3.cin, c3.cout, kfuse ? n1->cout : 0);
+
+      Launch& l1 = add(pend.on ? pend.k : rt[b.c1], b.c1, x1, S_NARROW, pend.on ? (pend.k == R_KFUSE ? pend.pc : train ? pend.c2 : -1) : in0);
+      if (pend.on) { l1.pc = pend.pc; l1.res = S_WIDE + pend.res; l1.id_ci = pend.id_ci; l1.xout = xin; }
+      produce(l1, in1 && rt[b.c2] == R_IGEMM);
+      if (pend.on) tap(pend.pc, xin);      // the PREVIOUS block's output was formed by this conv1's loader
+      if (train && !in1) bnact(b.c1, S_NARROW, S_NONE, -1);
+      produce(add(rt[b.c2], b.c2, S_NARROW, S_NARROW + 1, in1 ? b.c1 : -1), in2 && rt[b.c3] == R_IGEMM);
+      if (train && !in2) bnact(b.c2, S_NARROW + 1, S_NONE, -1);
+      if (b.ds >= 0) { Launch& d = add(rt[b.ds], b.ds, xin, res, in0); d.relu = 0; produce(d, false); }
+      if (train || !c3c1) {
+        Launch& l3 = add(rt[b.c3], b.c3, S_NARROW + 1, (c3c1 || b2b) ? S_NONE : S_WIDE + oth, in2 ? b.c2 : -1);
+        l3.res = train ? S_NONE : res;
+        produce(l3, false);
+      }
+      pend = Pending{c3c1 || kfuse, c3c1 ? R_C3C1 : b2b ? R_B2B : R_KFUSE, b.c3, b.c2, b.ds, oth, b.ds >= 0 ? dsb : cur};
+      if (b2b && !kfuse) {
+        Launch& l = add(R_B2B0, b.c3, S_NARROW + 1, S_NONE, b.c2);
+        l.pc = b.c3; l.res = res; l.id_ci = b.ds; l.xout = S_WIDE + oth;
+      } else if (train && !pend.on) bnact(b.c3, S_WIDE + oth, res, b.ds);
+    } else {
+      const bool in1 = train && rt[b.c2] == R_IMG;   // bn1 + relu ride in conv2's fill
+      produce(add(rt[b.c1], b.c1, xin, S_NARROW, -1), false);
+      if (train && !in1) bnact(b.c1, S_NARROW, S_NONE, -1);
+      if (b.ds >= 0) { Launch& d = add(rt[b.ds], b.ds, xin, res, -1); d.relu = 0; produce(d, false); }
+      Launch& l2 = add(rt[b.c2], b.c2, S_NARROW, S_WIDE + oth, in1 ? b.c1 : -1);
+      l2.res = train ? S_NONE : res;
+      produce(l2, false);
+      if (train) bnact(b.c2, S_WIDE + oth, res, b.ds);
+    }
+    cur = oth;
+    if (!pend.on) tap(r->bottleneck ? b.c3 : b.c2, S_WIDE + cur);
+  }
+  p.out = S_WIDE + cur;
+  return 0;
+}
+
+// The ST_LAYER_LOG / st_resnet_plan line of a launch (0: a launch that is not logged)
+int format_launch(const st_resnet* r, int B, const Launch& l, char* buf, size_t n) {
+  const ConvL& c = r->convs[l.ci];
+  const ConvL& pc = r->convs[l.pc >= 0 ? l.pc : l.ci];
+  const double es = (double)st_dtype_size(r->dtype), rows = (double)B * l.hin * l.win;
+  const double rows_o = (double)B * conv_out(l.hin, c.k, c.stride, c.pad) * conv_out(l.win, c.k, c.stride, c.pad);
+  const char *fam = "", *what = "";
+  int cin = c.cin, cout = c.cout, k = c.k, stride = c.stride, hin = l.hin, win = l.win;
+  double fl = 0.0, by = 0.0;
+  switch (l.route) {
+    case R_STEM: case R_IGEMM: {
+      const int cin_p = c.cin == 3 ? r->cpad0 : c.cin;
+      fam = "igemm"; what = l.res != S_NONE ? "conv + residual (eval)" : "conv";
+      fl = 2.0 * rows_o * c.k * c.k * c.cin * c.cout;
+      by = (rows * cin_p + (double)c.k * c.k * cin_p * c.cout + rows_o * c.cout * (l.res != S_NONE ? 2.0 : 1.0)) * es;
+      break;
+    }
+    case R_WREG: case R_ASTAT: case R_KSTREAM:
+      fam = l.route == R_WREG ? "conv1x1_wreg" : l.route == R_ASTAT ? "conv1x1_astat" : "conv1x1_kstream";
+      what = l.route == R_WREG && l.y == S_NONE ? "1x1 statistics only" : "1x1";
+      fl = 2.0 * rows_o * c.cin * c.cout;
+      by = (rows_o * c.cin + (double)c.cin * c.cout + (l.y != S_NONE ? rows_o * c.cout * (l.res != S_NONE ? 2.0 : 1.0) : 0.0)) * es; break;
+    case R_IMG:
+      fam = "conv3x3_img"; what = "3x3"; fl = 2.0 * rows * 9.0 * c.cin * c.cout; by = (rows * (c.cin + c.cout) + 9.0 * c.cin * c.cout) * es; break;
+    case R_S2:
+      fam = "conv3x3_s2"; what = "3x3 stride 2"; fl = 2.0 * rows_o * 9.0 * c.cin * c.cout;
+      by = (rows * c.cin + rows_o * c.cout + 9.0 * c.cin * c.cout) * es; break;
+    case R_KFUSE:
+      fam = "conv1x1_wreg"; what = "block end (bn3 + identity + relu) fused into conv1";
+      fl = 2.0 * rows * c.cin * c.cout; by = rows * (3.0 * c.cin + c.cout) * es; break;
+    case R_B2B:
+      fam = "conv_b2b"; what = "conv3 recomputed + bn3 + identity + relu + next conv1"; cin = pc.cin;
+      fl = 2.0 * rows * ((double)pc.cin * pc.cout + (double)c.cin * c.cout); by = rows * (pc.cin + 2.0 * pc.cout + c.cout) * es; break;
+    case R_B2B0:
+      fam = "conv_b2b"; what = "conv3 recomputed + bn3 + identity + relu";
+      fl = 2.0 * rows * c.cin * c.cout; by = rows * (c.cin + 2.0 * c.cout) * es; break;
+    case R_C3C1:
+      fam = "conv_c3c1"; what = "conv3 + block end (bn3 + identity + relu) + next conv1"; cin = pc.cin;
+      fl = 2.0 * rows * ((double)pc.cin * pc.cout + (double)c.cin * c.cout);
+      by = (rows * (pc.cin + 2.0 * pc.cout + c.cout) + (double)pc.cin * pc.cout + (double)c.cin * c.cout) * es; break;
+    case R_STEM_POOL: {
+      const int h = conv_out(l.hin, 7, 2, 3), w = conv_out(l.win, 7, 2, 3);
+      fam = "stem_pool"; what = "7x7/2 conv + statistics + 3x3/2 pool";
+      fl = 2.0 * B * h * w * 147.0 * 64;
+      by = (double)B * (l.hin / 2 + 3) * (l.win / 2 + 3) * 16 * es + (double)B * conv_out(h, 3, 2, 1) * conv_out(w, 3, 2, 1) * 64 * es;
+      break;
+    }
+    case R_BN_ACT:
+      fam = "bn_act"; what = l.res != S_NONE ? "bn + identity + relu" : "bn + relu"; cin = c.cout; k = stride = hin = win = 0;
+      by = rows * c.cout * (l.res != S_NONE ? 3.0 : 2.0) * es; break;
+    case R_REDUCE:
+      fam = "bn_reduce_replicas"; what = "statistics replicas -> replica 0"; cin = c.cout; k = stride = hin = win = 0; break;
+    default: return 0;
+  }
+  return snprintf(buf, n, "%s,%s,%d,%d,%d,%d,%d,%d,%.0f,%.0f,%d,%d\n", fam, what, cin, cout, k, stride, hin, win, fl, by, l.rep_out, l.rep_in);
+}
 }  // namespace
 
 extern "C" size_t st_resnet_workspace_bytes(const st_resnet* r, int B, int H, int W) {
   if (!r || B <= 0 || H < 32 || W < 32) return 0;
-  return make_plan(r, B, H, W).total;
+  return make_layout(r, B, H, W).total;
+}
+
+extern "C" int st_resnet_plan(const st_resnet* r, int B, int H, int W, int train, char* buf, size_t bytes) {
+  if (!r || B <= 0 || H < 32 || W < 32) { st_set_error("st_resnet_plan: bad arguments"); return -1; }
+  FwdPlan p;
+  if (plan_forward(r, B, H, W, train != 0, p)) return -1;
+  std::string text;
+  char line[256];
+  for (int i = 0; i < p.n; ++i) text.append(line, format_launch(r, B, p.l[i], line, sizeof(line)));
+  if (buf && bytes > text.size()) memcpy(buf, text.c_str(), text.size() + 1);
+  return (int)text.size();
 }
 
 extern "C" int st_resnet_forward(const st_resnet* r, const float* images_nchw, int B, int H, int W,
@@ -275,435 +535,184 @@ extern "C" int st_resnet_forward(const st_resnet* r, const float* images_nchw, i
   ST_CHECK(r && images_nchw && weights && bn_gamma && bn_beta && bn_running_mean && bn_running_var && workspace,
            "st_resnet_forward: null pointer");
   ST_CHECK(B > 0 && H >= 32 && W >= 32, "st_resnet_forward: bad input size %dx%dx%d", B, H, W);
-  const Plan p = make_plan(r, B, H, W);
-  ST_CHECK(workspace_bytes >= p.total, "st_resnet_forward: workspace too small (%zu < %zu)", workspace_bytes, p.total);
+  const Layout lay = make_layout(r, B, H, W);
+  ST_CHECK(workspace_bytes >= lay.total, "st_resnet_forward: workspace too small (%zu < %zu)", workspace_bytes, lay.total);
+  FwdPlan p;
+  if (plan_forward(r, B, H, W, train != 0, p)) return 1;
+  const BnTable& tab = p.tab;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int dt = r->dtype;
   const size_t es = st_dtype_size(dt);
   char* ws = reinterpret_cast<char*>(workspace);
-  char* in8 = ws; ws += p.in_bytes;
-  char* s2dw = ws; ws += p.s2dw_bytes;
-  char* stem = ws; ws += p.stem_bytes;
-  char* wide[3] = {ws, ws + p.wide_bytes, ws + 2 * p.wide_bytes}; ws += 3 * p.wide_bytes;
-  char* narrow[2] = {ws, ws + p.narrow_bytes}; ws += 2 * p.narrow_bytes;
-  float* stats = reinterpret_cast<float*>(ws); ws += p.stats_bytes;
+  char* slot[S_COUNT];
+  slot[S_IN] = ws; ws += lay.in_bytes;
+  char* s2dw = ws; ws += lay.s2dw_bytes;
+  slot[S_STEM] = ws; ws += lay.stem_bytes;
+  for (int i = 0; i < 3; ++i) { slot[S_WIDE + i] = ws; ws += lay.wide_bytes; }
+  for (int i = 0; i < 2; ++i) { slot[S_NARROW + i] = ws; ws += lay.narrow_bytes; }
+  float* stats = reinterpret_cast<float*>(ws); ws += lay.stats_bytes;
   float* fold = reinterpret_cast<float*>(ws);
   const int total = (int)r->bntotal;
   float* fscale = fold; float* fshift = fold + total;
 
   if (train) {
-    if (hipMemsetAsync(stats, 0, p.stats_bytes, st) != hipSuccess) { st_set_error("memset failed"); return 1; }
+    if (hipMemsetAsync(stats, 0, lay.stats_bytes, st) != hipSuccess) { st_set_error("memset failed"); return 1; }
   } else {
     hipLaunchKernelGGL(bn_fold_kernel, dim3((total + 255) / 256), dim3(256), 0, st, bn_gamma, bn_beta, bn_running_mean,
                        bn_running_var, fscale, fshift, total, eps);
     ST_LAUNCH_CHECK();
   }
-  const bool s2d = stem_s2d(H, W);
-  if (s2d) {
-    if (st_nchw_to_s2d16(images_nchw, in8, dt, B, H, W, stream)) return 1;
-  } else if (st_nchw_to_nhwc(images_nchw, in8, dt, B, 3, H, W, r->cpad0, stream)) return 1;
+  if (p.s2d) {
+    if (st_nchw_to_s2d16(images_nchw, slot[S_IN], dt, B, H, W, stream)) return 1;
+  } else if (st_nchw_to_nhwc(images_nchw, slot[S_IN], dt, B, 3, H, W, r->cpad0, stream)) return 1;
 
-  BnTable tab; tab.n = (int)r->convs.size();
-  ST_CHECK(tab.n <= 160, "st_resnet_forward: too many layers");
-  for (int i = 0; i < tab.n; ++i) {
-    tab.end[i] = (int)(r->convs[i].bnoff + r->convs[i].cout); tab.count[i] = 1.f; tab.soff[i] = 0; tab.rep[i] = 1;
-  }
-  int stats_used = 0;   // floats handed out so far
-  static const bool img_env = [] { const char* e = getenv("ST_CONV_IMG"); return !e || atoi(e) != 0; }();
-  const bool use_img = img_env && dt == ST_BF16;   // ST_CONV_IMG=0: every 3x3 through st_conv (A/B switch)
-  static const bool s2_env = [] { const char* e = getenv("ST_CONV_S2"); return !e || atoi(e) != 0; }();
-  const bool use_s2 = use_img && s2_env;            // ST_CONV_S2=0: the stride-2 3x3 convs stay on st_conv
-
-  // conv: train -> raw output + statistics; eval -> folded BN (+residual)(+ReLU) in the epilogue
-  // in_ci >= 0 (train): x is the RAW output of conv in_ci; this conv reads relu(bn_{in_ci}(x)) in its loader
-  // keep_rep: the consumer of this layer's statistics sums the replicas itself (everything but st_conv's input transform and
-  // the stem's pool): no reduction launch
-  // fz (train): x is the RAW conv3 output of the previous block (conv fz->ci); the loader forms relu(bn(x) + identity) itself, writes
-  // it to fz->xout (this block's input / identity) and the previous block's separate normalise pass does not run (st_conv1x1_kfuse)
-  // b2b: conv fz->ci itself (64 -> 256) is recomputed too, from its RAW input fz->raw2 (output of conv fz->c2ci): st_conv_b2b
-  struct FuseIn { int ci; const void* res; int res_ci; void* xout; bool b2b; const void* raw2; int c2ci; };
-  auto conv = [&](int ci, const void* x, int hin, int win, void* y, const void* eval_res, int eval_relu,
-                  int* ho, int* wo, int in_ci = -1, bool keep_rep = true, const FuseIn* fz = nullptr) -> int {
-    const ConvL& c = r->convs[ci];
-    st_conv_desc d;
-    memset(&d, 0, sizeof(d));
-    const int cin_p = c.cin == 3 ? r->cpad0 : c.cin;
-    d.x = x; d.w = reinterpret_cast<const char*>(weights) + c.woff * es; d.y = y;
-    d.dtype = dt; d.out_dtype = dt;
-    d.B = B; d.Hin = hin; d.Win = win; d.Cin = cin_p;
-    d.Ho = conv_out(hin, c.k, c.stride, c.pad); d.Wo = conv_out(win, c.k, c.stride, c.pad);
-    d.N = c.cout; d.KH = c.k; d.KW = c.k; d.stride = c.stride; d.pad = c.pad;
-    d.ldx = cin_p; d.ldw = c.k * c.k * cin_p; d.ldy = c.cout; d.Cin_logical = c.cin; d.k_order = c.korder;
-    if (ci == 0 && s2d) {
-      d.w = s2dw; d.Hin = hin / 2 + 3; d.Win = win / 2 + 3; d.Cin = 64; d.ldx = 16; d.KH = 4; d.KW = 1; d.stride = 1; d.pad = 0;
-      d.ldw = 256; d.Cin_logical = 36;   // 4 rows x 36 = 144 of the 147 real taps: the profiler's FLOP count stays below the algorithmic one
-    }
-    if (train && in_ci >= 0) {
-      const ConvL& pc = r->convs[in_ci];
-      d.in_stats = stats + tab.soff[in_ci]; d.in_gamma = bn_gamma + pc.bnoff; d.in_beta = bn_beta + pc.bnoff;
-      d.in_count = tab.count[in_ci]; d.in_eps = eps;
-    }
-    if (train) {
-      // replicas: keep ~128-256 pixel tiles per replica (same-address atomics serialise), at most kStatsRepFloats per layer
-      const long tiles = ((long)B * d.Ho * d.Wo + 127) / 128;
-      int rep = 1;
-      while (rep < 64 && tiles / (rep * 2) >= 128 && (rep * 2) * 2 * c.cout <= kStatsRepFloats) rep *= 2;
-      tab.soff[ci] = stats_used; tab.rep[ci] = rep;
-      stats_used += rep * 2 * c.cout;
-      d.stats = stats + tab.soff[ci]; d.stats_replicas = rep;
-    } else {
-      d.scale = fscale + c.bnoff; d.shift = fshift + c.bnoff; d.residual = eval_res; d.relu = eval_relu;
-    }
-    *ho = d.Ho; *wo = d.Wo;
-    tab.count[ci] = (float)((long)B * d.Ho * d.Wo);
-    // (eval mode: conv3 takes the block's identity in its epilogue -- the register-filter and activation-stationary kernels have that
-    // form for stride 1 and <= 512 input channels, i.e. every conv3 of a Bottleneck)
-    if (c.ntw > 0 && c.k == 1 && use_img && (!d.residual || (c.stride == 1 && c.cin <= 512))) {
-      // pointwise, filter slice in registers (conv_img.hip): producer's BatchNorm + ReLU in the row loader, replicated statistics
-      st_conv1x1_wreg_desc g;
-      memset(&g, 0, sizeof(g));
-      g.x = x; g.w_frag = reinterpret_cast<const char*>(weights) + c.woff_frag * es; g.y = y;
-      g.B = B; g.Hin = hin; g.Win = win; g.C = c.cin; g.N = c.cout; g.stride = c.stride;
-      g.in_stats = d.in_stats; g.in_gamma = d.in_gamma; g.in_beta = d.in_beta; g.in_count = d.in_count; g.in_eps = d.in_eps;
-      g.in_stats_replicas = in_ci >= 0 ? tab.rep[in_ci] : 0;
-      g.scale = d.scale; g.shift = d.shift; g.relu = d.relu; g.residual = d.residual;
-      if (train) {
-        // four replicas: the statistics leave a workgroup as full-wave atomics over consecutive channels (block_stats_flush), so the
-        // same-address queue is what is left to spread -- and every consumer adds the replicas up in its prologue (cheap at 4)
-        int rep = 1;
-        while (rep < 4 && (rep * 2) * 2 * c.cout <= kStatsRepFloats) rep *= 2;
-        stats_used -= tab.rep[ci] * 2 * c.cout;
-        tab.rep[ci] = rep; stats_used += rep * 2 * c.cout;
-        g.stats = stats + tab.soff[ci]; g.stats_replicas = rep;
-      }
-      if (fz && fz->b2b && st_conv_c3c1_supported(r->convs[fz->ci].cin, r->convs[fz->ci].cout, c.cout)) {
-        // 14 x 14 and 28 x 28 blocks: conv3 of the previous block (statistics-only pass already run in train mode), its block end and
-        // this conv1 in ONE kernel (conv_c3c1.hip) -- conv3's output chunks are this conv1's K-slabs
-        const ConvL& pc = r->convs[fz->ci];
-        const ConvL& c2 = r->convs[fz->c2ci];
-        st_conv_c3c1_desc k;
-        memset(&k, 0, sizeof(k));
-        k.x2 = fz->raw2; k.w3_frag = reinterpret_cast<const char*>(weights) + pc.woff_frag * es; k.identity = fz->res; k.x_out = fz->xout;
-        k.w1_frag = g.w_frag; k.y = y;
-        if (train) {
-          k.stats = g.stats; k.stats_replicas = g.stats_replicas;
-          k.bn2_stats = stats + tab.soff[fz->c2ci]; k.bn2_gamma = bn_gamma + c2.bnoff; k.bn2_beta = bn_beta + c2.bnoff; k.bn2_replicas = tab.rep[fz->c2ci];
-          k.bn3_stats = stats + tab.soff[fz->ci]; k.bn3_gamma = bn_gamma + pc.bnoff; k.bn3_beta = bn_beta + pc.bnoff; k.bn3_replicas = tab.rep[fz->ci];
-          if (fz->res_ci >= 0) {     // the identity is a raw downsample-conv output: its BatchNorm rides in the kernel's epilogue
-            const ConvL& rc = r->convs[fz->res_ci];
-            k.id_stats = stats + tab.soff[fz->res_ci]; k.id_gamma = bn_gamma + rc.bnoff; k.id_beta = bn_beta + rc.bnoff; k.id_replicas = tab.rep[fz->res_ci];
-          }
-          k.count = tab.count[fz->ci]; k.eps = eps;
-        } else {
-          k.scale3 = fscale + pc.bnoff; k.shift3 = fshift + pc.bnoff; k.scale1 = d.scale; k.shift1 = d.shift; k.relu1 = d.relu;
-        }
-        k.rows = (long)B * hin * win; k.C1 = pc.cin; k.C2 = pc.cout; k.N = c.cout;
-        if (st_conv_c3c1(&k, stream)) return 1;
-        log_launch("conv_c3c1", "conv3 + block end (bn3 + identity + relu) + next conv1", pc.cin, c.cout, 1, 1, hin, win,
-                   2.0 * k.rows * ((double)pc.cin * pc.cout + (double)c.cin * c.cout),
-                   ((double)k.rows * (pc.cin + 2.0 * pc.cout + c.cout) + (double)pc.cin * pc.cout + (double)c.cin * c.cout) * es);
-      } else if (fz && fz->b2b) {
-        const ConvL& pc = r->convs[fz->ci];
-        const ConvL& c2 = r->convs[fz->c2ci];
-        st_conv_b2b_desc k;
-        memset(&k, 0, sizeof(k));
-        k.raw2 = fz->raw2; k.w3_frag = reinterpret_cast<const char*>(weights) + pc.woff_frag * es; k.identity = fz->res; k.x_out = fz->xout;
-        k.w1_frag = g.w_frag; k.y = y; k.stats = g.stats; k.stats_replicas = g.stats_replicas;
-        k.bn2_stats = stats + tab.soff[fz->c2ci]; k.bn2_gamma = bn_gamma + c2.bnoff; k.bn2_beta = bn_beta + c2.bnoff; k.bn2_replicas = tab.rep[fz->c2ci];
-        k.bn3_stats = stats + tab.soff[fz->ci]; k.bn3_gamma = bn_gamma + pc.bnoff; k.bn3_beta = bn_beta + pc.bnoff; k.bn3_replicas = tab.rep[fz->ci];
-        if (fz->res_ci >= 0) {
-          const ConvL& rc = r->convs[fz->res_ci];
-          k.id_stats = stats + tab.soff[fz->res_ci]; k.id_gamma = bn_gamma + rc.bnoff; k.id_beta = bn_beta + rc.bnoff; k.id_replicas = tab.rep[fz->res_ci];
-        }
-        k.count = tab.count[fz->ci]; k.eps = eps; k.rows = (long)B * hin * win; k.C1 = pc.cin; k.C2 = c.cin; k.N = c.cout;
-        if (st_conv_b2b(&k, stream)) return 1;
-        log_launch("conv_b2b", "conv3 recomputed + bn3 + identity + relu + next conv1", pc.cin, c.cout, 1, 1, hin, win,
-                   2.0 * k.rows * ((double)pc.cin * pc.cout + (double)c.cin * c.cout), (double)k.rows * (pc.cin + 2.0 * pc.cout + c.cout) * es);
-      } else if (fz) {
-        const ConvL& pc = r->convs[fz->ci];
-        st_conv1x1_kfuse_desc k;
-        memset(&k, 0, sizeof(k));
-        k.raw = x; k.identity = fz->res; k.x_out = fz->xout; k.w_frag = g.w_frag; k.y = y;
-        k.stats = g.stats; k.stats_replicas = g.stats_replicas;
-        k.f_stats = stats + tab.soff[fz->ci]; k.f_gamma = bn_gamma + pc.bnoff; k.f_beta = bn_beta + pc.bnoff;
-        k.f_count = tab.count[fz->ci]; k.f_eps = eps; k.f_stats_replicas = tab.rep[fz->ci];
-        k.rows = (long)B * hin * win; k.C = c.cin; k.N = c.cout;
-        if (fz->res_ci >= 0) {
-          const ConvL& rc = r->convs[fz->res_ci];
-          k.id_stats = stats + tab.soff[fz->res_ci]; k.id_gamma = bn_gamma + rc.bnoff; k.id_beta = bn_beta + rc.bnoff;
-          k.id_stats_replicas = tab.rep[fz->res_ci];
-        }
-        if (st_conv1x1_kfuse(&k, stream)) return 1;
-        log_launch("conv1x1_wreg", "block end (bn3 + identity + relu) fused into conv1", c.cin, c.cout, 1, 1, hin, win,
-                   2.0 * k.rows * (double)c.cin * c.cout, (double)k.rows * (3.0 * c.cin + c.cout) * es);
-      } else {
-        const double rows_o = (double)B * d.Ho * d.Wo;
-        const double fl = 2.0 * rows_o * c.cin * c.cout;
-        const double by = (rows_o * c.cin + (double)c.cin * c.cout + (y ? rows_o * c.cout * (g.residual ? 2.0 : 1.0) : 0.0)) * es;
-        if (use_astat(c)) {
-          if (st_conv1x1_astat(&g, stream)) return 1;
-          log_launch("conv1x1_astat", "1x1", c.cin, c.cout, 1, c.stride, hin, win, fl, by);
-        } else if (c.cin > 512) {
-          ST_CHECK(!g.in_stats, "st_resnet_forward: the long-K pointwise kernel has no input transform");
-          if (st_conv1x1_kstream(&g, stream)) return 1;
-          log_launch("conv1x1_kstream", "1x1", c.cin, c.cout, 1, c.stride, hin, win, fl, by);
-        } else {
-          if (st_conv1x1_wreg(&g, stream)) return 1;
-          log_launch("conv1x1_wreg", y ? "1x1" : "1x1 statistics only", c.cin, c.cout, 1, c.stride, hin, win, fl, by);
-        }
-      }
-    } else if (c.ntw > 0 && c.k == 3 && c.stride == 1 && use_img && !d.residual && st_conv3x3_img_supported(hin, win, c.cin, c.cout) == c.ntw) {
-      // image-resident 3x3 (conv_img.hip): the producer's BatchNorm + ReLU ride in its fill, replicated statistics in and out
-      st_conv3x3_img_desc g;
-      memset(&g, 0, sizeof(g));
-      g.x = x; g.w_frag = reinterpret_cast<const char*>(weights) + c.woff_frag * es; g.y = y;
-      g.B = B; g.H = hin; g.W = win; g.C = c.cin; g.N = c.cout;
-      g.in_stats = d.in_stats; g.in_gamma = d.in_gamma; g.in_beta = d.in_beta; g.in_count = d.in_count; g.in_eps = d.in_eps;
-      g.in_stats_replicas = in_ci >= 0 ? tab.rep[in_ci] : 0;
-      g.scale = d.scale; g.shift = d.shift; g.relu = d.relu;
-      if (train) {
-        int rep = 1;
-        const long items = (long)B * ((hin * (win + 2) + 223) / 224);         // ~ workgroups along M
-        while (rep < 4 && items / (rep * 2) >= 4 && (rep * 2) * 2 * c.cout <= kStatsRepFloats) rep *= 2;
-        stats_used -= tab.rep[ci] * 2 * c.cout;                                // re-plan this layer's replicas
-        tab.rep[ci] = rep; stats_used += rep * 2 * c.cout;
-        g.stats = stats + tab.soff[ci]; g.stats_replicas = rep;
-      }
-      if (st_conv3x3_img(&g, stream)) return 1;
-      log_launch("conv3x3_img", "3x3", c.cin, c.cout, 3, 1, hin, win, 2.0 * B * hin * win * 9.0 * c.cin * c.cout,
-                 ((double)B * hin * win * (c.cin + c.cout) + 9.0 * c.cin * c.cout) * es);
-    } else if (c.ntw > 0 && c.k == 3 && c.stride == 2 && use_s2 && !d.residual && st_conv3x3_s2_supported(c.cin, c.cout) == c.ntw &&
-               (long)B * hin * win * c.cin * 2 < (1L << 31)) {
-      // stride-2 3x3 (conv_s2.hip): K-streaming implicit GEMM with gathered rows; bn1 + ReLU of the producer in its loader
-      st_conv3x3_img_desc g;
-      memset(&g, 0, sizeof(g));
-      g.x = x; g.w_frag = reinterpret_cast<const char*>(weights) + c.woff_frag * es; g.y = y;
-      g.B = B; g.H = hin; g.W = win; g.C = c.cin; g.N = c.cout;
-      g.in_stats = d.in_stats; g.in_gamma = d.in_gamma; g.in_beta = d.in_beta; g.in_count = d.in_count; g.in_eps = d.in_eps;
-      g.in_stats_replicas = in_ci >= 0 ? tab.rep[in_ci] : 0;
-      g.scale = d.scale; g.shift = d.shift; g.relu = d.relu;
-      if (train) {
-        int rep = 1;
-        while (rep < 4 && (rep * 2) * 2 * c.cout <= kStatsRepFloats) rep *= 2;
-        stats_used -= tab.rep[ci] * 2 * c.cout;
-        tab.rep[ci] = rep; stats_used += rep * 2 * c.cout;
-        g.stats = stats + tab.soff[ci]; g.stats_replicas = rep;
-      }
-      if (st_conv3x3_s2(&g, stream)) return 1;
-      log_launch("conv3x3_s2", "3x3 stride 2", c.cin, c.cout, 3, 2, hin, win, 2.0 * B * d.Ho * d.Wo * 9.0 * c.cin * c.cout,
-                 ((double)B * hin * win * c.cin + (double)B * d.Ho * d.Wo * c.cout + 9.0 * c.cin * c.cout) * es);
-    } else {
-      if (st_conv(&d, stream)) return 1;
-      const double rows_o = (double)B * d.Ho * d.Wo;
-      log_launch("igemm", d.residual ? "conv + residual (eval)" : "conv", c.cin, c.cout, c.k, c.stride, hin, win, 2.0 * rows_o * c.k * c.k * c.cin * c.cout,
-                 ((double)B * hin * win * cin_p + (double)c.k * c.k * cin_p * c.cout + rows_o * c.cout * (d.residual ? 2.0 : 1.0)) * es);
-    }
-    // every consumer of a layer's statistics sums up to 16 replicas itself (bn_act's register-coefficient kernel, the
-    // conv_img.hip loaders, the running-buffer update); only st_conv's input transform and the stem's pool read replica 0
-    if (train && tab.rep[ci] > 1 && !(keep_rep && tab.rep[ci] <= 16)) {
-      const int c2 = 2 * c.cout;
-      hipLaunchKernelGGL(bn_reduce_replicas_kernel, dim3((c2 + 255) / 256), dim3(256), 0, st, stats + tab.soff[ci], tab.rep[ci], c2);
-      ST_LAUNCH_CHECK();
-      log_launch("bn_reduce_replicas", "statistics replicas -> replica 0", c.cout, c.cout, 0, 0, 0, 0, 0.0, 0.0);
-      tab.rep[ci] = 1;   // consumers (bn_act, running-buffer update) read replica 0
-    }
-    return 0;
+  auto S = [&](int s) -> void* { return s == S_NONE ? nullptr : slot[s]; };
+  auto wts = [&](size_t off) { return reinterpret_cast<const char*>(weights) + off * es; };
+  // the BatchNorm of conv ci as its consumers read it: statistics, gamma, beta, replicas
+  struct BnRef { const float* stats; const float* gamma; const float* beta; int rep; };
+  auto bn = [&](int ci) { const ConvL& c = r->convs[ci]; return BnRef{stats + tab.soff[ci], bn_gamma + c.bnoff, bn_beta + c.bnoff, tab.rep[ci]}; };
+  auto set_in = [&](auto& d, const Launch& l) {    // the producer's BatchNorm + ReLU in the loader
+    if (l.in_ci < 0) return;
+    const BnRef b = bn(l.in_ci);
+    d.in_stats = b.stats; d.in_gamma = b.gamma; d.in_beta = b.beta; d.in_count = tab.count[l.in_ci]; d.in_eps = eps;
   };
-  // train-mode normalise (+residual [+its BN]) (+ReLU), in place
-  auto bnact = [&](int ci, void* x, long rows, int relu, const void* res, int res_ci) -> int {
-    const ConvL& c = r->convs[ci];
-    st_bn_act_desc d;
-    memset(&d, 0, sizeof(d));
-    d.x = x; d.y = x; d.res = res;
-    d.stats = stats + tab.soff[ci]; d.stats_replicas = tab.rep[ci]; d.gamma = bn_gamma + c.bnoff; d.beta = bn_beta + c.bnoff;
-    if (res_ci >= 0) {
-      const ConvL& rc = r->convs[res_ci];
-      d.res_bn = 1; d.res_stats = stats + tab.soff[res_ci]; d.res_stats_replicas = tab.rep[res_ci]; d.res_gamma = bn_gamma + rc.bnoff; d.res_beta = bn_beta + rc.bnoff;
-    }
-    d.dtype = dt; d.rows = rows; d.C = c.cout; d.count = (float)rows; d.eps = eps; d.relu = relu;
-    if (st_bn_act(&d, stream)) return 1;
-    log_launch("bn_act", res ? "bn + identity + relu" : "bn + relu", c.cout, c.cout, 0, 0, 0, 0, 0.0, (double)rows * c.cout * (res ? 3.0 : 2.0) * es);
-    return 0;
+  auto set_out = [&](auto& d, const Launch& l) {   // train: replicated statistics; eval: folded BatchNorm (+ReLU) in the epilogue
+    const ConvL& c = r->convs[l.ci];
+    if (train) { d.stats = stats + tab.soff[l.ci]; d.stats_replicas = l.rep_out; }
+    else { d.scale = fscale + c.bnoff; d.shift = fshift + c.bnoff; d.relu = l.relu; }
   };
-
-  int h, w;
-  // bf16 bottleneck nets on even image sizes: the whole stem (conv1 + statistics + maxpool) is ONE kernel (conv_stem.hip).  In train
-  // mode it leaves the pooled RAW conv output in wide[0]; bn1 + relu are applied by the loaders of its two consumers (conv1 and the
-  // downsample conv of the first block) -- pooling commutes with the monotone per-channel map, see conv_stem.hip.
-  static const bool stem_env = [] { const char* e = getenv("ST_STEM_FUSE"); return !e || atoi(e) != 0; }();
-  bool stem_fused = stem_env && s2d && use_img && r->bottleneck && !r->blocks.empty();
-  if (stem_fused) {
-    const BlockL& b0 = r->blocks[0];
-    stem_fused = b0.ds >= 0 && r->convs[b0.c1].k == 1 && r->convs[b0.c1].stride == 1 && r->convs[b0.c1].ntw > 0 && r->convs[b0.ds].ntw > 0 &&
-                 r->convs[b0.c1].cin == 64 && !use_astat(r->convs[b0.ds]);
-  }
-  if (stem_fused) {
-    const ConvL& c0 = r->convs[0];
-    char* wfrag = stem;                                 // the 205-MB raw-output buffer is free in this form: 32 KB of it hold the filters
-    if (st_stem_weight_frag_packed(reinterpret_cast<const char*>(weights) + r->convs[0].woff * es, r->cpad0, wfrag, stream)) return 1;
-    st_stem_conv_pool_desc sd;
-    memset(&sd, 0, sizeof(sd));
-    sd.x_s2d = in8; sd.w_frag = wfrag; sd.y = wide[0]; sd.B = B; sd.H = H; sd.W = W;
-    h = conv_out(H, 7, 2, 3); w = conv_out(W, 7, 2, 3);
-    tab.count[0] = (float)((long)B * h * w);
-    if (train) {
-      tab.soff[0] = stats_used; tab.rep[0] = 8; stats_used += 8 * 2 * c0.cout;
-      sd.stats = stats + tab.soff[0]; sd.stats_replicas = 8; sd.gamma = bn_gamma + c0.bnoff;
-    } else {
-      sd.scale = fscale + c0.bnoff; sd.shift = fshift + c0.bnoff;
-    }
-    if (st_stem_conv_pool(&sd, stream)) return 1;
-    log_launch("stem_pool", "7x7/2 conv + statistics + 3x3/2 pool", 3, 64, 7, 2, H, W, 2.0 * B * h * w * 147.0 * 64,
-               (double)B * (H / 2 + 3) * (W / 2 + 3) * 16 * es + (double)B * conv_out(h, 3, 2, 1) * conv_out(w, 3, 2, 1) * 64 * es);
-  } else {
-    if (s2d && st_stem_weight_s2d(reinterpret_cast<const char*>(weights) + r->convs[0].woff * es, s2dw, dt, r->cpad0, stream)) return 1;
-    if (conv(0, in8, H, W, stem, nullptr, 1, &h, &w, -1, false)) return 1;
-    if (train) {   // bn1 + relu folded into the pool: the 64-channel 112x112 map is read once instead of three times
-      const ConvL& c0 = r->convs[0];
-      if (st_maxpool3x3s2_bn(stem, wide[0], dt, B, h, w, 64, stats + tab.soff[0], bn_gamma + c0.bnoff, bn_beta + c0.bnoff,
-                             nullptr, nullptr, (float)((long)B * h * w), eps, stream)) return 1;
-    } else if (st_maxpool3x3s2(stem, wide[0], dt, B, h, w, 64, stream)) return 1;
-  }
-  h = conv_out(h, 3, 2, 1); w = conv_out(w, 3, 2, 1);
-  const int stem_in = (stem_fused && train) ? 0 : -1;   // the first block's conv1 / downsample read relu(bn1(.)) of wide[0] in their loaders
-  int cur = 0;  // wide[cur] holds the block input
+  auto set_fused = [&](auto& k, const Launch& l) {   // b2b / c3c1: bn2 of the raw input, bn3 of the (re)computed conv3, the identity's BN
+    const BnRef b2 = bn(l.in_ci), b3 = bn(l.pc);
+    k.bn2_stats = b2.stats; k.bn2_gamma = b2.gamma; k.bn2_beta = b2.beta; k.bn2_replicas = b2.rep;
+    k.bn3_stats = b3.stats; k.bn3_gamma = b3.gamma; k.bn3_beta = b3.beta; k.bn3_replicas = b3.rep;
+    if (l.id_ci >= 0) { const BnRef i = bn(l.id_ci); k.id_stats = i.stats; k.id_gamma = i.gamma; k.id_beta = i.beta; k.id_replicas = i.rep; }
+    k.count = tab.count[l.pc]; k.eps = eps;
+  };
   size_t taps_used = 0;
-  auto tap = [&](const void* src, int hh, int ww, int C) -> int {     // st_resnet_set_taps: block outputs, one after the other
-    if (!r->taps) return 0;
-    const size_t nb = (size_t)B * hh * ww * C * es;
-    ST_CHECK(taps_used + nb <= r->taps_bytes, "st_resnet_forward: taps buffer too small (%zu needed so far, %zu given)", taps_used + nb, r->taps_bytes);
-    if (hipMemcpyAsync(reinterpret_cast<char*>(r->taps) + taps_used, src, nb, hipMemcpyDeviceToDevice, st) != hipSuccess) { st_set_error("st_resnet_forward: tap copy failed"); return 1; }
-    taps_used += nb;
+  auto run = [&](const Launch& l) -> int {
+    const ConvL& c = r->convs[l.ci];
+    const long rows = (long)B * l.hin * l.win;
+    switch (l.route) {
+      case R_STEM: case R_IGEMM: {
+        st_conv_desc d{};
+        const int cin_p = c.cin == 3 ? r->cpad0 : c.cin;
+        d.x = S(l.x); d.w = wts(c.woff); d.y = S(l.y); d.residual = S(l.res);
+        d.dtype = dt; d.out_dtype = dt;
+        d.B = B; d.Hin = l.hin; d.Win = l.win; d.Cin = cin_p;
+        d.Ho = conv_out(l.hin, c.k, c.stride, c.pad); d.Wo = conv_out(l.win, c.k, c.stride, c.pad);
+        d.N = c.cout; d.KH = c.k; d.KW = c.k; d.stride = c.stride; d.pad = c.pad;
+        d.ldx = cin_p; d.ldw = c.k * c.k * cin_p; d.ldy = c.cout; d.Cin_logical = c.cin; d.k_order = c.korder;
+        if (l.route == R_STEM && p.s2d) {
+          if (st_stem_weight_s2d(wts(c.woff), s2dw, dt, r->cpad0, stream)) return 1;
+          d.w = s2dw; d.Hin = l.hin / 2 + 3; d.Win = l.win / 2 + 3; d.Cin = 64; d.ldx = 16; d.KH = 4; d.KW = 1; d.stride = 1; d.pad = 0;
+          d.ldw = 256; d.Cin_logical = 36;   // 4 rows x 36 = 144 of the 147 real taps: the profiler's FLOP count stays below the algorithmic one
+        }
+        set_in(d, l); set_out(d, l);
+        return st_conv(&d, stream);
+      }
+      case R_IMG: case R_S2: {
+        // image-resident 3x3 (conv_img.hip) / stride-2 K-streaming implicit GEMM with gathered rows (conv_s2.hip)
+        st_conv3x3_img_desc g{};
+        g.x = S(l.x); g.w_frag = wts(c.woff_frag); g.y = S(l.y);
+        g.B = B; g.H = l.hin; g.W = l.win; g.C = c.cin; g.N = c.cout; g.in_stats_replicas = l.rep_in;
+        set_in(g, l); set_out(g, l);
+        return l.route == R_IMG ? st_conv3x3_img(&g, stream) : st_conv3x3_s2(&g, stream);
+      }
+      case R_WREG: case R_ASTAT: case R_KSTREAM: {
+        st_conv1x1_wreg_desc g{};
+        g.x = S(l.x); g.w_frag = wts(c.woff_frag); g.y = S(l.y); g.residual = S(l.res);
+        g.B = B; g.Hin = l.hin; g.Win = l.win; g.C = c.cin; g.N = c.cout; g.stride = c.stride; g.in_stats_replicas = l.rep_in;
+        set_in(g, l); set_out(g, l);
+        if (l.route == R_WREG) return st_conv1x1_wreg(&g, stream);
+        if (l.route == R_ASTAT) return st_conv1x1_astat(&g, stream);
+        ST_CHECK(!g.in_stats, "st_resnet_forward: the long-K pointwise kernel has no input transform");
+        return st_conv1x1_kstream(&g, stream);
+      }
+      case R_KFUSE: {
+        st_conv1x1_kfuse_desc k{};
+        const BnRef f = bn(l.pc);
+        k.raw = S(l.x); k.identity = S(l.res); k.x_out = S(l.xout); k.w_frag = wts(c.woff_frag); k.y = S(l.y);
+        k.stats = stats + tab.soff[l.ci]; k.stats_replicas = l.rep_out;
+        k.f_stats = f.stats; k.f_gamma = f.gamma; k.f_beta = f.beta; k.f_count = tab.count[l.pc]; k.f_eps = eps; k.f_stats_replicas = f.rep;
+        k.rows = rows; k.C = c.cin; k.N = c.cout;
+        if (l.id_ci >= 0) { const BnRef i = bn(l.id_ci); k.id_stats = i.stats; k.id_gamma = i.gamma; k.id_beta = i.beta; k.id_stats_replicas = i.rep; }
+        return st_conv1x1_kfuse(&k, stream);
+      }
+      case R_B2B: case R_B2B0: {
+        const ConvL& c3 = r->convs[l.pc];
+        st_conv_b2b_desc k{};
+        k.raw2 = S(l.x); k.w3_frag = wts(c3.woff_frag); k.identity = S(l.res); k.x_out = S(l.xout);
+        set_fused(k, l);
+        k.rows = rows; k.C1 = c3.cin; k.C2 = c3.cout;
+        if (l.route == R_B2B) {
+          k.w1_frag = wts(c.woff_frag); k.y = S(l.y); k.stats = stats + tab.soff[l.ci]; k.stats_replicas = l.rep_out; k.N = c.cout;
+        }
+        return st_conv_b2b(&k, stream);
+      }
+      case R_C3C1: {
+        const ConvL& c3 = r->convs[l.pc];
+        st_conv_c3c1_desc k{};
+        k.x2 = S(l.x); k.w3_frag = wts(c3.woff_frag); k.identity = S(l.res); k.x_out = S(l.xout); k.w1_frag = wts(c.woff_frag); k.y = S(l.y);
+        if (train) {
+          k.stats = stats + tab.soff[l.ci]; k.stats_replicas = l.rep_out;
+          set_fused(k, l);
+        } else {
+          k.scale3 = fscale + c3.bnoff; k.shift3 = fshift + c3.bnoff; k.scale1 = fscale + c.bnoff; k.shift1 = fshift + c.bnoff; k.relu1 = l.relu;
+        }
+        k.rows = rows; k.C1 = c3.cin; k.C2 = c3.cout; k.N = c.cout;
+        return st_conv_c3c1(&k, stream);
+      }
+      case R_STEM_POOL: {
+        // the raw-output buffer is free in this form: 32 KB of it hold the filters
+        if (st_stem_weight_frag_packed(wts(c.woff), r->cpad0, slot[S_STEM], stream)) return 1;
+        st_stem_conv_pool_desc sd{};
+        sd.x_s2d = S(l.x); sd.w_frag = slot[S_STEM]; sd.y = S(l.y); sd.B = B; sd.H = l.hin; sd.W = l.win;
+        if (train) { sd.stats = stats + tab.soff[l.ci]; sd.stats_replicas = l.rep_out; sd.gamma = bn_gamma + c.bnoff; }
+        else { sd.scale = fscale + c.bnoff; sd.shift = fshift + c.bnoff; }
+        return st_stem_conv_pool(&sd, stream);
+      }
+      case R_MAXPOOL:
+        if (l.in_ci < 0) return st_maxpool3x3s2(S(l.x), S(l.y), dt, B, l.hin, l.win, c.cout, stream);
+        return st_maxpool3x3s2_bn(S(l.x), S(l.y), dt, B, l.hin, l.win, c.cout, stats + tab.soff[l.ci], bn_gamma + c.bnoff, bn_beta + c.bnoff,
+                                  nullptr, nullptr, tab.count[l.ci], eps, stream);
+      case R_BN_ACT: {
+        st_bn_act_desc d{};
+        const BnRef b = bn(l.ci);
+        d.x = S(l.x); d.y = S(l.x); d.res = S(l.res);
+        d.stats = b.stats; d.stats_replicas = b.rep; d.gamma = b.gamma; d.beta = b.beta;
+        if (l.id_ci >= 0) { const BnRef i = bn(l.id_ci); d.res_bn = 1; d.res_stats = i.stats; d.res_stats_replicas = i.rep; d.res_gamma = i.gamma; d.res_beta = i.beta; }
+        d.dtype = dt; d.rows = rows; d.C = c.cout; d.count = (float)rows; d.eps = eps; d.relu = 1;
+        return st_bn_act(&d, stream);
+      }
+      case R_REDUCE:
+        hipLaunchKernelGGL(bn_reduce_replicas_kernel, dim3((2 * c.cout + 255) / 256), dim3(256), 0, st, stats + tab.soff[l.ci], l.rep_in, 2 * c.cout);
+        ST_LAUNCH_CHECK();
+        return 0;
+      case R_TAP: {      // st_resnet_set_taps: block outputs, one after the other
+        if (!r->taps) return 0;
+        const size_t nb = (size_t)rows * c.cout * es;
+        ST_CHECK(taps_used + nb <= r->taps_bytes, "st_resnet_forward: taps buffer too small (%zu needed so far, %zu given)", taps_used + nb, r->taps_bytes);
+        if (hipMemcpyAsync(reinterpret_cast<char*>(r->taps) + taps_used, S(l.x), nb, hipMemcpyDeviceToDevice, st) != hipSuccess) { st_set_error("st_resnet_forward: tap copy failed"); return 1; }
+        taps_used += nb;
+        return 0;
+      }
+    }
     return 0;
   };
-
-  // Train, 256-channel block inputs (layer1 and the first block of layer2): the block-end pass relu(bn3(raw) + identity) is formed by
-  // the NEXT block's conv1 loader (st_conv1x1_kfuse) -- that pass and conv1 are both HBM time there and the fusion drops one full read
-  // of the widest tensor (measured 168 -> 125 us per transition at 56 x 56, B = 128).  Wider inputs stay separate: their conv1 needs
-  // several channel slices per row (each would re-read both inputs) or, at 1024 channels, is MFMA-bound (measured slower fused).
-  static const bool kfuse_env = [] { const char* e = getenv("ST_BLOCK_FUSE"); return !e || atoi(e) != 0; }();
-  static const bool b2b_env = [] { const char* e = getenv("ST_BLOCK_B2B"); return !e || atoi(e) != 0; }();
-  struct Pending { bool on; int ci; const void* res; int res_ci; int raw_buf, res_buf; bool b2b; const void* raw2; int c2ci; } pend{false, -1, nullptr, -1, 0, 0, false, nullptr, -1};
-  for (size_t bi = 0; bi < r->blocks.size(); ++bi) {
-    const BlockL& b = r->blocks[bi];
-    FuseIn fzv; const FuseIn* fz = nullptr;
-    if (pend.on) {   // wide[cur] holds the previous block's RAW conv3 output; the buffer that is neither it nor the identity takes x
-                     // (b2b: conv3's output was never written -- its buffer takes x)
-      const int freeb = pend.b2b ? pend.raw_buf : 3 - pend.raw_buf - pend.res_buf;
-      fzv = FuseIn{pend.ci, pend.res, pend.res_ci, wide[freeb], pend.b2b, pend.raw2, pend.c2ci};
-      fz = &fzv;
-      cur = freeb;
-    }
-    const int oth = (cur + 1) % 3, dsb = (cur + 2) % 3;
-    int h1, w1, h2, w2, h3, w3, hd, wd;
-    const void* xin = wide[cur];
-    const void* c1_in = fz ? static_cast<const void*>(wide[pend.raw_buf]) : xin;
-    pend.on = false;
-    if (r->bottleneck) {
-      // train: bn1 + relu ride in conv2's fill when the image-resident kernel takes conv2 (one pass over the tensor less)
-      const ConvL& c2 = r->convs[b.c2];
-      const ConvL& c3 = r->convs[b.c3];
-      const bool fuse1 = train && use_img && c2.ntw > 0 && c2.stride == 1 && st_conv3x3_img_supported(h, w, c2.cin, c2.cout) == c2.ntw;   // conv1 keeps the map size
-      const bool c3_sums = train && use_img && c3.ntw > 0;       // conv3 on st_conv1x1_wreg: sums conv2's replicated statistics itself
-      // conv2 on st_conv (the three stride-2 3x3s): its loader takes bn1 + relu too (igemm MODE 2, padding taps stay zero); it reads
-      // replica 0 of conv1's statistics, so conv1's replicas are reduced by a launch (5 us against a 14 - 44 us pass over the tensor)
-      static const bool xf_env = [] { const char* e = getenv("ST_CONV2_XF"); return !e || atoi(e) != 0; }();
-      const bool fuse1x = xf_env && train && use_img && !fuse1 && c2.k == 3 && c2.cin % 64 == 0;
-      // (the K-streaming stride-2 kernel sums conv1's statistics replicas itself: no reduction launch in front of it)
-      const bool c2_s2k = use_s2 && c2.k == 3 && c2.stride == 2 && c2.ntw > 0 && st_conv3x3_s2_supported(c2.cin, c2.cout) == c2.ntw;
-      if (conv(b.c1, c1_in, h, w, narrow[0], nullptr, 1, &h1, &w1, bi == 0 ? stem_in : -1, !fuse1x || c2_s2k, fz)) return 1;
-      if (fz && tap(xin, h, w, r->convs[b.c1].cin)) return 1;      // the PREVIOUS block's output was formed by this conv1's loader
-      if (train && !fuse1 && !fuse1x && bnact(b.c1, narrow[0], (long)B * h1 * w1, 1, nullptr, -1)) return 1;
-      const bool fuse2_ = train && c3.cin % 64 == 0;              // conv3 applies bn2 + relu in its loader
-      if (conv(b.c2, narrow[0], h1, w1, narrow[1], nullptr, 1, &h2, &w2, (fuse1 || fuse1x) ? b.c1 : -1, c3_sums || !fuse2_)) return 1;
-      // train: bn2 + relu are applied by conv3's loader (no separate pass over the 3x3 output); needs whole 64-channel
-      // (f32: 32) K tiles, which every bottleneck width satisfies
-      const bool fuse2 = train && r->convs[b.c3].cin % 64 == 0;
-      if (train && !fuse2 && bnact(b.c2, narrow[1], (long)B * h2 * w2, 1, nullptr, -1)) return 1;
-      const void* res = xin;
-      if (b.ds >= 0) {
-        if (conv(b.ds, xin, h, w, wide[dsb], nullptr, 0, &hd, &wd, bi == 0 ? stem_in : -1)) return 1;
-        res = wide[dsb];
-      }
-      bool defer = false, b2b = false;
-      // 14 x 14 blocks (256 -> 1024 -> next conv1 1024 -> 256) and 28 x 28 blocks (128 -> 512 -> 128), train AND eval: conv3 + block
-      // end + next conv1 as one kernel (st_conv_c3c1).  Train: conv3 runs here as a statistics-only pass (y == NULL); an identity that
-      // still needs its own BatchNorm (the block after a downsample conv) keeps the separate path.  Eval: conv3 is not launched at all.
-      // ST_C3C1: bit 0 = the 14 x 14 blocks, bit 1 = the 28 x 28 blocks (A/B switch; default both)
-      static const int c3c1_env = [] { const char* e = getenv("ST_C3C1"); return e ? atoi(e) : 3; }();
-      // the block behind a downsample conv (its identity still needs that conv's BatchNorm): the kernel's IDBN form.  ST_C3C1_IDBN=0: A/B switch
-      static const bool c3c1_idbn = [] { const char* e = getenv("ST_C3C1_IDBN"); return !e || atoi(e) != 0; }();
-      bool c3c1 = false;
-      if (use_img && (c3c1_env & (c3.cout == 1024 ? 1 : 2)) && bi + 1 < r->blocks.size()) {
-        const BlockL& nb = r->blocks[bi + 1];
-        const ConvL& n1 = r->convs[nb.c1];
-        // the kernel indexes both fragment-major filter copies with fixed tile permutations: conv3 packed with ntw = 2, conv1 with N / 64
-        c3c1 = n1.k == 1 && n1.stride == 1 && c3.k == 1 && c3.stride == 1 && c3.cout == n1.cin && st_conv_c3c1_supported(c3.cin, c3.cout, n1.cout) &&
-               c3.ntw == 2 && n1.ntw == n1.cout / 64 && (!train || (fuse2_ && (b.ds < 0 || c3c1_idbn))) && (long)B * h2 * w2 * c3.cout * 2 < (1L << 31);
-      }
-      if (c3c1) { defer = true; b2b = true; }
-      else if (train && use_img && kfuse_env && bi + 1 < r->blocks.size()) {
-        const BlockL& nb = r->blocks[bi + 1];
-        const ConvL& n1 = r->convs[nb.c1];
-        defer = n1.k == 1 && n1.stride == 1 && n1.cin == 256 && n1.ntw > 0 && !use_astat(n1) && c3.cout == n1.cin &&
-                st_conv1x1_kfuse_supported(n1.cin, n1.cout) == n1.ntw;
-        // the 56 x 56 boundaries: conv3 (64 -> 256) is recomputed inside the fused kernel (st_conv_b2b) and runs here for its statistics only
-        // conv_b2b_kernel indexes the fragment-major filters with FIXED tile permutations: conv3 packed with ntw = 2, the next conv1
-        // with ntw = N / 64 (conv_b2b.hip:63-65); a retuned pw_cfg table / ST_PW_CFG that packs another ntw must not reach it
-        b2b = defer && b2b_env && fuse2 && c3.k == 1 && c3.stride == 1 && c3.ntw == 2 && !use_astat(c3) &&
-              c3.ntw == st_conv1x1_wreg_supported(c3.cin, c3.cout) && n1.ntw == st_conv1x1_wreg_supported(n1.cin, n1.cout) &&
-              n1.ntw == n1.cout / 64 && st_conv_b2b_supported(c3.cin, c3.cout, n1.cout);
-      }
-      // the 28 x 28 blocks (conv3 128 -> 512): the same recomputation, stopping at the block output -- conv3 runs for its statistics,
-      // st_conv_b2b (N = 0) forms x = relu(bn3(conv3(..)) + identity) from the narrow tensor: the raw 512-channel tensor (103 MB at
-      // B = 128) is neither written nor read
-      const bool lite = !defer && train && use_img && b2b_env && fuse2 && c3.k == 1 && c3.stride == 1 && c3.ntw == 2 && !use_astat(c3) &&
-                        c3.ntw == st_conv1x1_wreg_supported(c3.cin, c3.cout) && st_conv_b2b_supported(c3.cin, c3.cout, 0);
-      if (c3c1 && !train) { h3 = h2; w3 = w2; }                  // eval: conv3 is computed where it is consumed (the next block's conv1 launch)
-      else if (conv(b.c3, narrow[1], h2, w2, (b2b || lite) ? nullptr : wide[oth], res, 1, &h3, &w3, fuse2 ? b.c2 : -1)) return 1;
-      if (defer) pend = Pending{true, b.c3, res, b.ds, oth, b.ds >= 0 ? dsb : cur, b2b, narrow[1], b.c2};
-      else if (lite) {
-        const ConvL& c2l = r->convs[b.c2];
-        st_conv_b2b_desc k;
-        memset(&k, 0, sizeof(k));
-        k.raw2 = narrow[1]; k.w3_frag = reinterpret_cast<const char*>(weights) + c3.woff_frag * es; k.identity = res; k.x_out = wide[oth];
-        k.bn2_stats = stats + tab.soff[b.c2]; k.bn2_gamma = bn_gamma + c2l.bnoff; k.bn2_beta = bn_beta + c2l.bnoff; k.bn2_replicas = tab.rep[b.c2];
-        k.bn3_stats = stats + tab.soff[b.c3]; k.bn3_gamma = bn_gamma + c3.bnoff; k.bn3_beta = bn_beta + c3.bnoff; k.bn3_replicas = tab.rep[b.c3];
-        if (b.ds >= 0) {
-          const ConvL& rc = r->convs[b.ds];
-          k.id_stats = stats + tab.soff[b.ds]; k.id_gamma = bn_gamma + rc.bnoff; k.id_beta = bn_beta + rc.bnoff; k.id_replicas = tab.rep[b.ds];
-        }
-        k.count = tab.count[b.c3]; k.eps = eps; k.rows = (long)B * h3 * w3; k.C1 = c3.cin; k.C2 = c3.cout; k.N = 0;
-        if (st_conv_b2b(&k, stream)) return 1;
-      } else if (train && bnact(b.c3, wide[oth], (long)B * h3 * w3, 1, res, b.ds)) return 1;
-    } else {
-      const ConvL& c1 = r->convs[b.c1];
-      const ConvL& c2 = r->convs[b.c2];
-      const int h1p = conv_out(h, c1.k, c1.stride, c1.pad), w1p = conv_out(w, c1.k, c1.stride, c1.pad);
-      const bool fuse1 = train && use_img && c2.ntw > 0 && st_conv3x3_img_supported(h1p, w1p, c2.cin, c2.cout) == c2.ntw;
-      if (conv(b.c1, xin, h, w, narrow[0], nullptr, 1, &h1, &w1)) return 1;
-      if (train && !fuse1 && bnact(b.c1, narrow[0], (long)B * h1 * w1, 1, nullptr, -1)) return 1;
-      const void* res = xin;
-      if (b.ds >= 0) {
-        if (conv(b.ds, xin, h, w, wide[dsb], nullptr, 0, &hd, &wd)) return 1;
-        res = wide[dsb];
-      }
-      // (eval mode hands the residual to the conv epilogue, which the image-resident kernel does not have: st_conv there)
-      if (conv(b.c2, narrow[0], h1, w1, wide[oth], res, 1, &h3, &w3, fuse1 ? b.c1 : -1)) return 1;
-      if (train && bnact(b.c2, wide[oth], (long)B * h3 * w3, 1, res, b.ds)) return 1;
-    }
-    h = h3; w = w3; cur = oth;
-    if (!pend.on && tap(wide[cur], h, w, r->bottleneck ? r->convs[b.c3].cout : r->convs[b.c2].cout)) return 1;
+  FILE* log = layer_log();
+  char line[256];
+  for (int i = 0; i < p.n; ++i) {
+    if (run(p.l[i])) return 1;
+    if (log && format_launch(r, B, p.l[i], line, sizeof(line)) > 0) { fputs(line, log); fflush(log); }
   }
 
-  const size_t feat_bytes = (size_t)B * h * w * r->feat_dim * es;
-  if (feat_nhwc_out) {
-    if (hipMemcpyAsync(feat_nhwc_out, wide[cur], feat_bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-      st_set_error("st_resnet_forward: copy failed"); return 1;
-    }
+  const void* out = slot[p.out];
+  const size_t feat_bytes = (size_t)B * p.h * p.w * r->feat_dim * es;
+  if (feat_nhwc_out && hipMemcpyAsync(feat_nhwc_out, out, feat_bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+    st_set_error("st_resnet_forward: copy failed"); return 1;
   }
-  if (pooled_out && st_global_avgpool(wide[cur], pooled_out, dt, pooled_dtype, B, h * w, r->feat_dim, stream)) return 1;
-  if (ncp_out && st_nhwc_to_ncp_f32(wide[cur], ncp_out, dt, B, h * w, r->feat_dim, stream)) return 1;
+  if (pooled_out && st_global_avgpool(out, pooled_out, dt, pooled_dtype, B, p.h * p.w, r->feat_dim, stream)) return 1;
+  if (ncp_out && st_nhwc_to_ncp_f32(out, ncp_out, dt, B, p.h * p.w, r->feat_dim, stream)) return 1;
 
   if (train == 2) {
     std::lock_guard<std::mutex> lk(r->mu);
@@ -715,6 +724,7 @@ extern "C" int st_resnet_forward(const st_resnet* r, const float* images_nchw, i
   }
   return 0;
 }
+
 
 // Second half of a train == 2 forward: the momentum update of every running_mean / running_var from the statistics that
 // forward left in `workspace`.  Stream-ordered after that forward by the caller; calls for successive minibatches must be

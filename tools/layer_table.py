@@ -4,8 +4,9 @@ MI355X_MICROARCH) of the layer's algorithmic bytes).
 
 Inputs (both written by ONE run of tools/time_encoder.py under rocprofv3, see tools/prof_layers.sh):
   * the kernel trace (*kernel_trace.csv) -- start / end of every launch;
-  * the engine's launch log (ST_LAYER_LOG=<file>, csrc/resnet.cpp:log_launch) -- one line per conv / normalise launch in launch order:
-    kernel family, what it computes, geometry, algorithmic FLOPs and bytes.
+  * the engine's launch log (ST_LAYER_LOG=<file>, csrc/resnet.cpp:format_launch) -- one line per conv / normalise launch in launch order:
+    kernel family, what it computes, geometry, algorithmic FLOPs and bytes, then two columns read here only as text (statistics
+    replicas written / read; the same lines as st_resnet_plan).
 The two are joined forward by forward (a forward starts at its stem kernel) and launch by launch (the next trace row whose kernel name
 contains the logged family).
 
