@@ -479,6 +479,10 @@ int st_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
 size_t st_rnn_greedy_workspace_bytes(const st_rnn_params* p, int B);
 int st_rnn_greedy(const st_rnn_params* p, const void* feat, int B, int steps, void* workspace, size_t workspace_bytes,
                   long* ids_out, float* logits_out, void* stream);
+/* Which route the calling thread's last st_rnn_greedy took: 0 = the pipelined decoder (csrc/decode_pipe.hip) ran;
+ * 1 = the launch chain, because the call is not eligible for the pipe (configuration, logits_out, steps, stream capture,
+ * ST_DECODE_PIPE=0); 2 = the launch chain after the pipe gave up (no co-resident grid, uneven XCD placement, CU count). */
+int st_rnn_greedy_last_route(void);
 
 /* Building blocks of the beam decoders (rnn.py:60-108 and beam_search.py:45-97):
  * st_rnn_step: one timestep of the L-layer cell for n independent rows, states [L][n][H] in `dtype`

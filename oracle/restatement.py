@@ -184,6 +184,43 @@ def rnn_greedy(params, cnn_feature, cell="gru", steps=CAP_MAX, return_logits=Fal
     return out
 
 
+def _round_bf16(x):
+    return x.to(torch.bfloat16).to(x.dtype)
+
+
+def rnn_greedy_bf16_storage(params, cnn_feature, cell="gru", steps=CAP_MAX):
+    """rnn_greedy for the bf16 decoders: computed in the dtype of ``params`` (float64 for a tight oracle) but rounded to
+    bf16 wherever the kernels store a value -- the input feature, the embedding rows fed back, h after every cell and c
+    of the LSTM.  Weights are expected bf16-representable already.  Returns (ids (B, steps), logits (B, steps, V))."""
+    B = cnn_feature.shape[0]
+    L = num_layers_of(params)
+    H = params["unit.weight_hh_l0"].shape[1]
+    h = cnn_feature.new_zeros(L, B, H)
+    c = cnn_feature.new_zeros(L, B, H) if cell != "gru" else None
+    x = _round_bf16(cnn_feature)
+    ids, all_logits = [], []
+    for _ in range(steps):
+        hs, cs, inp = [], [], x
+        for l in range(L):
+            w = _layer_w(params, l)
+            if cell == "gru":
+                hl = _round_bf16(gru_cell(inp, h[l], *w))
+            else:
+                hl, cl = lstm_cell(inp, h[l], c[l], *w)
+                hl, cl = _round_bf16(hl), _round_bf16(cl)
+                cs.append(cl)
+            hs.append(hl)
+            inp = hl
+        h = torch.stack(hs, 0)
+        c = torch.stack(cs, 0) if cell != "gru" else None
+        logits = inp @ params["linear.weight"].t() + params["linear.bias"]
+        tok = logits.max(1)[1]
+        ids.append(tok)
+        all_logits.append(logits)
+        x = _round_bf16(params["embeddings.weight"][tok])
+    return torch.stack(ids, 1), torch.stack(all_logits, 1)
+
+
 # --------------------------------------------------------------------------
 # A7: the live "beam" of rnn.py:60-108 (bs=1; shared hidden state threaded
 # through every beam; ranking by current-step raw logit only)

@@ -165,6 +165,7 @@ _SIGS = {
                          c_p, c_p, c_p], c_i),
     "st_rnn_greedy_workspace_bytes": ([C.POINTER(RnnParams), c_i], C.c_size_t),
     "st_rnn_greedy": ([C.POINTER(RnnParams), c_p, c_i, c_i, c_p, C.c_size_t, c_p, c_p, c_p], c_i),
+    "st_rnn_greedy_last_route": ([], c_i),
     "st_rnn_step": ([C.POINTER(RnnParams), c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p], c_i),
     "st_embedding_rows": ([c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p], c_i),
     "st_gather_state": ([c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p], c_i),

@@ -578,8 +578,13 @@ extern "C" size_t st_rnn_greedy_workspace_bytes(const st_rnn_params* p, int B) {
          rnn_greedy_pipe_bytes(p, B, kPipeSteps);                // the pipelined decoder's buffers (0 when the configuration is not eligible)
 }
 
+static thread_local int g_greedy_route = 1;             // st_rnn_greedy_last_route (include/showtell_hip.h)
+
+extern "C" int st_rnn_greedy_last_route(void) { return g_greedy_route; }
+
 extern "C" int st_rnn_greedy(const st_rnn_params* p, const void* feat, int B, int steps, void* workspace, size_t workspace_bytes,
                              long* ids_out, float* logits_out, void* stream) {
+  g_greedy_route = 1;
   ST_CHECK(p && feat && workspace && ids_out, "st_rnn_greedy: null pointer");
   ST_CHECK(p->L >= 1 && p->L <= ST_MAX_LAYERS && p->in0 == p->E, "st_rnn_greedy: bad decoder configuration");
   ST_CHECK(p->H % 8 == 0 && p->E % 8 == 0, "st_rnn_greedy: E=%d and H=%d must be multiples of 8", p->E, p->H);
@@ -596,12 +601,13 @@ extern "C" int st_rnn_greedy(const st_rnn_params* p, const void* feat, int B, in
   float* logits = reinterpret_cast<float*>(xbuf + al((size_t)B * E * es));
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(logits) + al((size_t)B * Vp * sizeof(float)));
   // bf16 GRU at the BASELINE decoder shape: the whole loop as ONE persistent kernel, a layer per XCD (csrc/decode_pipe.hip); it gives
-  // up (rc 2) when the configuration is not eligible or the grid could not be made co-resident -- then the launch chain below runs
+  // up (rc 2: the grid could not be made co-resident) or does not run (rc 3: not eligible) -- then the launch chain below runs
   if (!logits_out && steps <= kPipeSteps) {
     const size_t pipe_bytes = rnn_greedy_pipe_bytes(p, B, kPipeSteps);
     if (pipe_bytes) {
       const size_t base = st_rnn_greedy_workspace_bytes(p, B) - pipe_bytes;
       const int rc = rnn_greedy_pipe(p, feat, B, steps, ws + base, pipe_bytes, ids_out, st);
+      g_greedy_route = rc == 0 ? 0 : rc == 2 ? 2 : 1;
       if (rc == 0) return 0;
       if (rc == 1) return 1;
     }

@@ -385,14 +385,15 @@ size_t rnn_greedy_pipe_bytes(const st_rnn_params* p, int B, int steps) {
   return al256((size_t)steps * p->L * nch * CR * PH * 2) + al256((size_t)steps * nch * CR * 8) + al256((size_t)steps * (p->L + 1) * nch * 128) + 256;
 }
 
-// 0: ids_out holds the result; 1: error (st_last_error); 2: not run / gave up -- the caller runs the launch chain
+// 0: ids_out holds the result; 1: error (st_last_error); 2: gave up; 3: not run (not eligible, or ST_DECODE_PIPE=0) -- on 2 and 3
+// the caller runs the launch chain
 int rnn_greedy_pipe(const st_rnn_params* p, const void* feat, int B, int steps, void* ws, size_t ws_bytes, long* ids_out, hipStream_t st) {
   const char* env = getenv("ST_DECODE_PIPE");                     // read per call: ST_DECODE_PIPE=0 keeps the launch chain (A/B runs, tests)
   const bool on = !env || atoi(env) != 0;
   const size_t need = rnn_greedy_pipe_bytes(p, B, steps);
-  if (!on || need == 0 || ws_bytes < need) return 2;
+  if (!on || need == 0 || ws_bytes < need) return 3;
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return 2;   // the result check below synchronises
+  if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return 3;   // the result check below synchronises
   int dev = 0, ncu = 0;
   (void)hipGetDevice(&dev);
   if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu != 256) return 2;

@@ -62,7 +62,8 @@ __device__ __forceinline__ float st_lstm_unit(float pi, float pf, float pg, floa
 #endif
 
 // the pipelined (layer-per-XCD) greedy decoder, csrc/decode_pipe.hip: bytes it needs behind the launch chain's workspace (0: the
-// configuration stays on the launch chain) and the run itself (0: done, 1: error, 2: not run / gave up -- use the launch chain)
+// configuration stays on the launch chain) and the run itself (0: done, 1: error, 2: gave up (machine-dependent), 3: not run (not
+// eligible, or ST_DECODE_PIPE=0) -- on 2 and 3 use the launch chain)
 size_t rnn_greedy_pipe_bytes(const st_rnn_params* p, int B, int steps);
 int rnn_greedy_pipe(const st_rnn_params* p, const void* feat, int B, int steps, void* ws, size_t ws_bytes, long* ids_out, hipStream_t st);
 

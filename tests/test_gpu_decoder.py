@@ -333,11 +333,16 @@ def test_pipelined_greedy_decoder_equals_launch_chain(B, L, V, cell, monkeypatch
                 sd[k] = sd[k] * 5.0
     m = (RNN if cell == "gru" else RNN_LSTM)(E, H, V, L, dtype=torch.bfloat16); m.load_state_dict(sd); m = m.cuda().eval()
     feat = torch.randn(B, E, generator=torch.Generator().manual_seed(B)).cuda()
+    from showtell_amd._lib import lib
+    from tests.test_gpu_decoder_bench_shape import assert_pipe_ran
     monkeypatch.setenv("ST_DECODE_PIPE", "0")
     ids_chain = m.sentence_index(feat)
+    assert lib().st_rnn_greedy_last_route() == 1
     monkeypatch.setenv("ST_DECODE_PIPE", "1")
     ids_pipe = m.sentence_index(feat)
+    assert_pipe_ran()                                      # the pipe ran: otherwise the chain is compared with itself
     ids_pipe2 = m.sentence_index(feat)                     # a second run on a reused workspace (stale buffers must not matter)
+    assert_pipe_ran()
     torch.cuda.synchronize()
     assert ids_pipe.shape == ids_chain.shape == (B, 25)
     assert torch.equal(ids_pipe, ids_chain)
