@@ -544,6 +544,19 @@ int st_attn_reg_loss(const float* alphas, int B, int T, int P, float alpha_c, fl
 size_t st_attn_greedy_workspace_bytes(const st_attn_params* p, int B);
 int st_attn_greedy(const st_attn_params* p, const float* cnn_feature, int B, int steps, long start_id,
                    void* workspace, size_t workspace_bytes, long* ids_out, void* stream);
+/* st_attn_greedy plus the attention map of every step: alphas_out[B][steps][P] fp32 (same workspace as st_attn_greedy) */
+int st_attn_greedy_alphas(const st_attn_params* p, const float* cnn_feature, int B, int steps, long start_id,
+                          void* workspace, size_t workspace_bytes, long* ids_out, float* alphas_out, void* stream);
+/* beam_search.py:45-97 on the attention decoder for B images, W slots each (1 <= W <= 8, so W*min(W,V) <= 64): initial state
+ * h0 = init_h(mean_p feat) (and c0) over all layers, generate = one test-branch step (rnn_attn.py:77-94) from the node's token.
+ * Rows are fixed (image, slot) pairs b*W + w.  Records use beam.py's layout: rec_tok/rec_cost/rec_par [max_length+1][B][W]
+ * (fringe after each iteration; slot 0 of fringe 0 is start_id at cost 0), rec_end [max_length][B][W] (harvest flags),
+ * rec_alpha [max_length][B*W][P] fp32 (nullable): the attention map of every row at every iteration, so the extras of node
+ * (t >= 1, w) are rec_alpha[t-1][b*W + rec_par[t][b][w]].  The whole search in one call; nothing synchronised inside. */
+size_t st_attn_beam_workspace_bytes(const st_attn_params* p, int B, int W);
+int st_attn_beam_search(const st_attn_params* p, const float* cnn_feature, int B, int W, int max_length,
+                        long start_id, long end_id, void* workspace, size_t workspace_bytes,
+                        long* rec_tok, float* rec_cost, int* rec_par, uint8_t* rec_end, float* rec_alpha, void* stream);
 
 #ifdef __cplusplus
 }

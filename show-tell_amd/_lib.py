@@ -177,6 +177,9 @@ _SIGS = {
     "st_attn_reg_loss": ([c_p, c_i, c_i, c_i, c_f, c_p, c_p], c_i),
     "st_attn_greedy_workspace_bytes": ([c_p, c_i], C.c_size_t),
     "st_attn_greedy": ([c_p, c_p, c_i, c_i, c_l, c_p, C.c_size_t, c_p, c_p], c_i),
+    "st_attn_greedy_alphas": ([c_p, c_p, c_i, c_i, c_l, c_p, C.c_size_t, c_p, c_p, c_p], c_i),
+    "st_attn_beam_workspace_bytes": ([c_p, c_i, c_i], C.c_size_t),
+    "st_attn_beam_search": ([c_p, c_p, c_i, c_i, c_i, c_l, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p, c_p], c_i),
     "st_cross_entropy": ([c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_f, c_p, c_p], c_i),
     "st_head_workspace_bytes": ([c_i, c_i, c_i, c_i], C.c_size_t),
     "st_linear_bn1d_forward": ([c_p] * 7 + [c_i, c_i, c_i, c_i, c_i, c_f, c_f] + [c_p] * 6, c_i),

@@ -143,6 +143,18 @@ def beam_search(rnn, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50,
             state = st.gather(new_state, gidx)
             tok, cost = ntok, ncost
         h_tok, h_cost, h_par, h_end = rec_tok.cpu().numpy(), rec_cost.cpu().numpy(), rec_par.cpu().numpy(), rec_end.cpu().numpy()
+    return replay_hypotheses(h_tok, h_cost, h_par, h_end, num_hypotheses)
+
+
+def replay_hypotheses(h_tok, h_cost, h_par, h_end, num_hypotheses, alphas=None):
+    """The Node bookkeeping of beam_search.py:69-97, replayed on the host from the records of a device search over fixed
+    (image, slot) rows: h_tok / h_cost / h_par [max_length+1][B][W] (fringe after each iteration, parent slots),
+    h_end [max_length][B][W] (harvest flags).  Returns, per image, at most `num_hypotheses` (tokens, cost) pairs.
+
+    With `alphas` ([max_length][B*W][P], the attention map of every row at every iteration) each pair becomes
+    (tokens, cost, extras), extras a float32 tensor (len(tokens) - 1, P): the extras of a node are the alpha computed while
+    producing it, i.e. that of its PARENT's row one iteration earlier, alphas[t-1][b*W + parent slot] for node (t, w)."""
+    B, W = h_tok.shape[1], h_tok.shape[2]
     out = []
     for b in range(B):
         hyp = []                                                                      # (iteration of the node, slot, cost) in harvest order
@@ -150,12 +162,22 @@ def beam_search(rnn, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50,
             hyp.append((int(t), int(w), h_cost[t, b, w]))
         res = []
         for t, w, c in sorted(hyp, key=lambda e: e[2])[:num_hypotheses]:              # beam_search.py:96 (stable)
-            seq = []
+            seq, ext = [], []
             while t >= 0 and w >= 0:
                 seq.append(int(h_tok[t, b, w]))
-                w = int(h_par[t, b, w]) if t > 0 else -1
+                if t > 0:
+                    par = int(h_par[t, b, w])
+                    if alphas is not None:
+                        ext.append(alphas[t - 1, b * W + par])
+                    w = par
+                else:
+                    w = -1
                 t -= 1
-            res.append((seq[::-1], float(c)))
+            if alphas is None:
+                res.append((seq[::-1], float(c)))
+            else:
+                ex = np.stack(ext[::-1]) if ext else np.zeros((0, alphas.shape[2]), dtype=np.float32)
+                res.append((seq[::-1], float(c), torch.from_numpy(np.ascontiguousarray(ex, dtype=np.float32))))
         out.append(res)
     return out
 

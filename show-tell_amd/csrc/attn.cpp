@@ -403,14 +403,16 @@ extern "C" size_t st_attn_greedy_workspace_bytes(const st_attn_params* p, int B)
   return make_gplan(p, B).total;
 }
 
-extern "C" int st_attn_greedy(const st_attn_params* p, const float* cnn_feature, int B, int steps, long start_id,
-                              void* workspace, size_t workspace_bytes, long* ids_out, void* stream) {
-  if (check_common(p, nullptr, "st_attn_greedy")) return 1;
-  ST_CHECK(cnn_feature && workspace && ids_out && B > 0 && steps > 0, "st_attn_greedy: bad arguments");
+namespace {
+// rnn_attn.py:120-145; alphas_out [B][steps][P] keeps every step's attention map (else it goes to a scratch row)
+int attn_greedy_run(const st_attn_params* p, const float* cnn_feature, int B, int steps, long start_id, void* workspace,
+                    size_t workspace_bytes, long* ids_out, float* alphas_out, void* stream, const char* who) {
+  if (check_common(p, nullptr, who)) return 1;
+  ST_CHECK(cnn_feature && workspace && ids_out && B > 0 && steps > 0, "%s: bad arguments", who);
   const st_rnn_params& r = p->rnn;
-  ST_CHECK(r.w_lin && r.b_lin, "st_attn_greedy: null vocabulary projection");
+  ST_CHECK(r.w_lin && r.b_lin, "%s: null vocabulary projection", who);
   const GPlan q = make_gplan(p, B);
-  ST_CHECK(workspace_bytes >= q.total, "st_attn_greedy: workspace too small");
+  ST_CHECK(workspace_bytes >= q.total, "%s: workspace too small", who);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   char* ws = reinterpret_cast<char*>(workspace);
   const int dt = r.dtype, H = r.H, E = r.E, L = r.L, P = p->P, A = p->A, F = p->F, Vp = up8(r.V);
@@ -428,14 +430,129 @@ extern "C" int st_attn_greedy(const st_attn_params* p, const float* cnn_feature,
   for (int t = 0; t < steps; ++t) {
     const int nx = c ^ 1;
     const char* htop = ws + q.h[c] + (size_t)(L - 1) * B * H * es;
+    float* alpha_t = alphas_out ? alphas_out + (size_t)t * P : alpha_scratch;
+    const long alpha_stride = alphas_out ? (long)steps * P : (long)P;
     if (skinny(htop, H, p->w_dec, H, att2, A, B, A, H, p->b_dec, 0, dt, st)) return 1;
-    if (attn_fwd_launch(ws + q.att1, att2, p->w_full, p->b_full, ws + q.feat, alpha_scratch, P, ws + q.z, B, P, A, F, dt, st)) return 1;
+    if (attn_fwd_launch(ws + q.att1, att2, p->w_full, p->b_full, ws + q.feat, alpha_t, alpha_stride, ws + q.z, B, P, A, F, dt, st)) return 1;
     if (st_embedding_rows(r.emb, cur, ws + q.x, B, E, r.V, 2 * E, dt, stream)) return 1;
     if (skinny_t(ws + q.z, F, p->w_embed, F, ws + q.x + (size_t)E * es, 2 * E, B, E, F, p->b_embed, dt, st)) return 1;
     if (st_rnn_step(&r, ws + q.x, B, ws + q.h[c], ws + q.c[c], ws + q.h[nx], ws + q.c[nx], logits, Vp, stream)) return 1;
     hipLaunchKernelGGL(argmax_kernel, dim3(B), dim3(256), 0, st, logits, Vp, r.V, ids_out, steps, t, cur);
     ST_LAUNCH_CHECK();
     c = nx;
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" int st_attn_greedy(const st_attn_params* p, const float* cnn_feature, int B, int steps, long start_id,
+                              void* workspace, size_t workspace_bytes, long* ids_out, void* stream) {
+  return attn_greedy_run(p, cnn_feature, B, steps, start_id, workspace, workspace_bytes, ids_out, nullptr, stream, "st_attn_greedy");
+}
+
+extern "C" int st_attn_greedy_alphas(const st_attn_params* p, const float* cnn_feature, int B, int steps, long start_id,
+                                     void* workspace, size_t workspace_bytes, long* ids_out, float* alphas_out, void* stream) {
+  ST_CHECK(alphas_out, "st_attn_greedy_alphas: null alphas_out");
+  return attn_greedy_run(p, cnn_feature, B, steps, start_id, workspace, workspace_bytes, ids_out, alphas_out, stream, "st_attn_greedy_alphas");
+}
+
+// ---- beam search (beam_search.py:45-97 driven by the test branch rnn_attn.py:77-94) --------------------------------
+// Fixed (image, slot) rows b*W + w as in beam.py: every iteration is one set of launches over the B*W rows and the fringe
+// selection runs on the device (st_beam_select), so the caller reads the records back once and replays the Node bookkeeping.
+namespace {
+struct BPlan { int n, k; size_t feat, mean, h0, c0, att1, h[2], c[2], x, z, att2, logits, tp, ti, gidx, slot, done, alpha, total; };
+BPlan make_bplan(const st_attn_params* p, int B, int W) {
+  const st_rnn_params& r = p->rnn;
+  const size_t es = st_dtype_size(r.dtype);
+  BPlan q; size_t o = 0;
+  auto take = [&](size_t bytes) { size_t x = o; o += al(bytes); return x; };
+  const size_t n = (size_t)B * W;
+  q.n = (int)n;
+  q.k = W < r.V ? W : r.V;
+  q.feat = take((size_t)B * p->P * p->F * es); q.mean = take((size_t)B * p->F * es);
+  q.h0 = take((size_t)B * r.H * es); q.c0 = take((size_t)B * r.H * es);
+  q.att1 = take((size_t)B * p->P * p->A * es);
+  const size_t cs = r.cell == ST_CELL_LSTM ? (size_t)r.L * n * r.H * es : 0;
+  for (int i = 0; i < 2; ++i) { q.h[i] = take((size_t)r.L * n * r.H * es); q.c[i] = take(cs); }
+  q.x = take(n * 2 * r.E * es); q.z = take(n * p->F * es);
+  q.att2 = take(n * p->A * sizeof(float));
+  q.logits = take(n * up8(r.V) * sizeof(float));
+  q.tp = take(n * q.k * sizeof(float)); q.ti = take(n * q.k * sizeof(long));
+  q.gidx = take(n * sizeof(int)); q.slot = take(n * sizeof(int)); q.done = take((size_t)B);
+  q.alpha = take(n * p->P * sizeof(float));
+  q.total = o;
+  return q;
+}
+
+// slot (b, w) <- image b; fringe 0 = the root alone: slot 0 holds start_id at cost 0, the others are empty (cost +inf)
+__global__ void beam_seed_kernel(int B, int W, long start_id, int* __restrict__ slot, long* __restrict__ tok0, float* __restrict__ cost0,
+                                 int* __restrict__ par0, uint8_t* __restrict__ done) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < B * W) {
+    const int w = i % W;
+    slot[i] = i / W;
+    tok0[i] = w == 0 ? start_id : 0;
+    cost0[i] = w == 0 ? 0.f : INFINITY;
+    par0[i] = -1;
+  }
+  if (i < B) done[i] = 0;
+}
+}  // namespace
+
+extern "C" size_t st_attn_beam_workspace_bytes(const st_attn_params* p, int B, int W) {
+  if (!p || B <= 0 || W < 1 || W > 8) return 0;
+  return make_bplan(p, B, W).total;
+}
+
+extern "C" int st_attn_beam_search(const st_attn_params* p, const float* cnn_feature, int B, int W, int max_length,
+                                   long start_id, long end_id, void* workspace, size_t workspace_bytes,
+                                   long* rec_tok, float* rec_cost, int* rec_par, uint8_t* rec_end, float* rec_alpha, void* stream) {
+  if (check_common(p, nullptr, "st_attn_beam_search")) return 1;
+  ST_CHECK(cnn_feature && workspace && rec_tok && rec_cost && rec_par && rec_end && B > 0, "st_attn_beam_search: bad arguments");
+  ST_CHECK(W >= 1 && W <= 8, "st_attn_beam_search: beam width must be 1..8 (got %d)", W);
+  ST_CHECK(max_length >= 1, "st_attn_beam_search: max_length must be >= 1 (got %d)", max_length);
+  const st_rnn_params& r = p->rnn;
+  ST_CHECK(r.w_lin && r.b_lin, "st_attn_beam_search: null vocabulary projection");
+  const BPlan q = make_bplan(p, B, W);
+  ST_CHECK(workspace_bytes >= q.total, "st_attn_beam_search: workspace too small (%zu < %zu)", workspace_bytes, q.total);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  char* ws = reinterpret_cast<char*>(workspace);
+  const int dt = r.dtype, H = r.H, E = r.E, L = r.L, P = p->P, A = p->A, F = p->F, Vp = up8(r.V), n = q.n, k = q.k;
+  const size_t es = st_dtype_size(dt);
+  const bool lstm = r.cell == ST_CELL_LSTM;
+  int* slot = reinterpret_cast<int*>(ws + q.slot);
+  int* gidx = reinterpret_cast<int*>(ws + q.gidx);
+  uint8_t* done = reinterpret_cast<uint8_t*>(ws + q.done);
+  float* att2 = reinterpret_cast<float*>(ws + q.att2);
+  float* logits = reinterpret_cast<float*>(ws + q.logits);
+  float* tp = reinterpret_cast<float*>(ws + q.tp);
+  long* ti = reinterpret_cast<long*>(ws + q.ti);
+
+  if (prepare(p, cnn_feature, B, ws + q.feat, ws + q.mean, ws + q.h0, ws + q.c0, ws + q.att1, stream)) return 1;
+  hipLaunchKernelGGL(beam_seed_kernel, dim3((n + 255) / 256), dim3(256), 0, st, B, W, start_id, slot, rec_tok, rec_cost, rec_par, done);
+  ST_LAUNCH_CHECK();
+  // h0 (c0) repeated over the layers (rnn_attn.py:62), then scattered to the slots of its image
+  if (replicate_rows_launch(ws + q.h0, ws + q.h[1], (long)B * H, L, dt, st)) return 1;
+  if (st_gather_state(ws + q.h[1], slot, ws + q.h[0], L, B, n, H, dt, stream)) return 1;
+  if (lstm) {
+    if (replicate_rows_launch(ws + q.c0, ws + q.c[1], (long)B * H, L, dt, st)) return 1;
+    if (st_gather_state(ws + q.c[1], slot, ws + q.c[0], L, B, n, H, dt, stream)) return 1;
+  }
+  for (int t = 0; t < max_length; ++t) {                                                   // beam_search.py:69
+    const long* tok = rec_tok + (size_t)t * n;
+    const float* cost = rec_cost + (size_t)t * n;
+    const char* htop = ws + q.h[0] + (size_t)(L - 1) * n * H * es;                           // keyed on the previous top-layer state
+    float* alpha_t = rec_alpha ? rec_alpha + (size_t)t * n * P : reinterpret_cast<float*>(ws + q.alpha);
+    if (st_embedding_rows(r.emb, tok, ws + q.x, n, E, r.V, 2 * E, dt, stream)) return 1;
+    if (skinny(htop, H, p->w_dec, H, att2, A, n, A, H, p->b_dec, 0, dt, st)) return 1;
+    if (attn_beam_fwd_launch(ws + q.att1, att2, p->w_full, p->b_full, ws + q.feat, alpha_t, ws + q.z, B, W, P, A, F, dt, st)) return 1;
+    if (skinny_t(ws + q.z, F, p->w_embed, F, ws + q.x + (size_t)E * es, 2 * E, n, E, F, p->b_embed, dt, st)) return 1;
+    if (st_rnn_step(&r, ws + q.x, n, ws + q.h[0], lstm ? ws + q.c[0] : nullptr, ws + q.h[1], lstm ? ws + q.c[1] : nullptr, logits, Vp, stream)) return 1;
+    if (st_softmax_topk(logits, Vp, n, r.V, k, tp, ti, 0, stream)) return 1;
+    if (st_beam_select(tok, cost, done, tp, ti, B, W, k, end_id, rec_tok + (size_t)(t + 1) * n, rec_cost + (size_t)(t + 1) * n,
+                       rec_par + (size_t)(t + 1) * n, rec_end + (size_t)t * n, gidx, stream)) return 1;
+    if (st_gather_state(ws + q.h[1], gidx, ws + q.h[0], L, n, n, H, dt, stream)) return 1;   // a child inherits its parent's state
+    if (lstm && st_gather_state(ws + q.c[1], gidx, ws + q.c[0], L, n, n, H, dt, stream)) return 1;
   }
   return 0;
 }

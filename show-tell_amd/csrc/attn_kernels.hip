@@ -143,6 +143,124 @@ __global__ __launch_bounds__(1024) void attn_fwd_kernel(const T* __restrict__ at
   }
 }
 
+// One attention step over beam rows (image b, slot w) = row b*W + w.  A row's image never changes, so ONE workgroup per image
+// serves all W slots and att1[b] (P x A) and feat[b] (P x F) are read once per step, not W times as the per-row kernel would:
+//   score:   each att1 chunk is loaded once and applied to the W att2 rows staged in LDS;
+//   softmax: one wave per slot;
+//   context: each 16-byte feat chunk is loaded once and accumulated into W register accumulators.
+// Every slot's arithmetic is the per-row kernel's at 1024 threads, in the same order (att1 lanes, then the wave sum; pixel
+// groups added group 0 first), so a row's result depends neither on B nor on the other slots.
+template <typename T, int W>
+__global__ __launch_bounds__(1024) void attn_beam_fwd_kernel(const T* __restrict__ att1, const float* __restrict__ att2,
+                                                             const float* __restrict__ wf, const float* __restrict__ bf,
+                                                             const T* __restrict__ feat, float* __restrict__ alpha_out,
+                                                             T* __restrict__ z, int P, int A, int F) {
+  __shared__ float al[W][kMaxP];
+  extern __shared__ float stage[];                     // score: att2 rows [W][A]; context: partial sums [G-1][F] of one slot
+  constexpr int N = V16<T>::N;
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const long row0 = (long)b * W;
+  for (int i = threadIdx.x; i < W * A; i += blockDim.x) stage[i] = att2[row0 * A + i];
+  __syncthreads();
+  const T* a1 = att1 + (long)b * P * A;
+  for (int p = wid; p < P; p += nw) {
+    float s[W];
+#pragma unroll
+    for (int w = 0; w < W; ++w) s[w] = 0.f;
+    for (int c = lane * N; c < A; c += 64 * N) {
+      float v[N], wv[N];
+      V16<T>::load(a1 + (long)p * A + c, v);
+#pragma unroll
+      for (int k = 0; k < N; ++k) wv[k] = wf[c + k];
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        const float* a2 = stage + w * A + c;
+#pragma unroll
+        for (int k = 0; k < N; ++k) s[w] += wv[k] * lrelu(v[k] + a2[k]);
+      }
+    }
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      const float t = wave_sum(s[w]);
+      if (lane == 0) al[w][p] = t + bf[0];
+    }
+  }
+  __syncthreads();
+  for (int w = wid; w < W; w += nw) {
+    const float v = lane < P ? al[w][lane] : -INFINITY;
+    const float m = wave_max(v);
+    const float ex = lane < P ? expf(v - m) : 0.f;
+    const float sum = wave_sum(ex);
+    if (lane < P) {
+      const float a = ex / sum;
+      al[w][lane] = a;
+      alpha_out[(row0 + w) * P + lane] = a;
+    }
+  }
+  __syncthreads();
+  const T* fb = feat + (long)b * P * F;
+  const int nchunk = F / N;
+  const int G = (int)blockDim.x >= 2 * nchunk ? (int)blockDim.x / nchunk : 1;
+  if (G == 1) {
+    for (int c = threadIdx.x * N; c < F; c += blockDim.x * N) {
+      float acc[W][N];
+#pragma unroll
+      for (int w = 0; w < W; ++w)
+#pragma unroll
+        for (int k = 0; k < N; ++k) acc[w][k] = 0.f;
+      for (int p = 0; p < P; ++p) {
+        float v[N];
+        V16<T>::load(fb + (long)p * F + c, v);
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+          const float a = al[w][p];
+#pragma unroll
+          for (int k = 0; k < N; ++k) acc[w][k] += a * v[k];
+        }
+      }
+#pragma unroll
+      for (int w = 0; w < W; ++w) V16<T>::store(z + (row0 + w) * F + c, acc[w]);
+    }
+    return;
+  }
+  const int ci = threadIdx.x % nchunk, g = threadIdx.x / nchunk, c = ci * N;
+  float acc[W][N];
+#pragma unroll
+  for (int w = 0; w < W; ++w)
+#pragma unroll
+    for (int k = 0; k < N; ++k) acc[w][k] = 0.f;
+  if (g < G) {
+    const int per = (P + G - 1) / G, p0 = g * per, p1 = p0 + per < P ? p0 + per : P;
+    constexpr int kU = W * N >= 56 ? 2 : 4;            // loads in flight, bounded so that W*N accumulators never spill
+#pragma unroll kU
+    for (int p = p0; p < p1; ++p) {
+      float v[N];
+      V16<T>::load(fb + (long)p * F + c, v);
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        const float a = al[w][p];
+#pragma unroll
+        for (int k = 0; k < N; ++k) acc[w][k] += a * v[k];
+      }
+    }
+  }
+  // the groups meet in LDS one slot at a time ((G-1) x F floats), group 0 adds them in group order
+#pragma unroll
+  for (int w = 0; w < W; ++w) {
+    if (g >= 1 && g < G)
+#pragma unroll
+      for (int k = 0; k < N; ++k) stage[(long)(g - 1) * F + c + k] = acc[w][k];
+    __syncthreads();
+    if (g == 0) {
+      for (int q = 1; q < G; ++q)
+#pragma unroll
+        for (int k = 0; k < N; ++k) acc[w][k] += stage[(long)(q - 1) * F + c + k];
+      V16<T>::store(z + (row0 + w) * F + c, acc[w]);
+    }
+    __syncthreads();
+  }
+}
+
 // backward of one attention step for sample b (see attn.cpp for the algebra).  One workgroup per sample, but 16 waves of it
 // (1024 threads): at B = 64 only 64 workgroups exist, so the parallelism has to come from inside -- the 49 dz . feat_p dot
 // products take 4 rounds of the 16 waves instead of 13 of 4, and the channel pass is split over (channel, pixel group).
@@ -297,6 +415,47 @@ int attn_fwd_launch(const void* att1, const float* att2, const float* wf, const 
   const size_t lds = G > 1 ? (size_t)G * F * sizeof(float) : 0;
   if (dtype == ST_BF16) hipLaunchKernelGGL(attn_fwd_kernel<bf16_t>, dim3(n), dim3(threads), lds, st, (const bf16_t*)att1, att2, wf, bf, (const bf16_t*)feat, alpha_out, alpha_stride, (bf16_t*)z, P, A, F);
   else hipLaunchKernelGGL(attn_fwd_kernel<float>, dim3(n), dim3(threads), lds, st, (const float*)att1, att2, wf, bf, (const float*)feat, alpha_out, alpha_stride, (float*)z, P, A, F);
+  ST_LAUNCH_CHECK();
+  return 0;
+}
+
+namespace {
+constexpr int kBeamThreads = 1024;
+template <typename T, int W>
+void beam_fwd_go(const void* att1, const float* att2, const float* wf, const float* bf, const void* feat, float* alpha_out, void* z,
+                 int B, int P, int A, int F, size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL((attn_beam_fwd_kernel<T, W>), dim3(B), dim3(kBeamThreads), lds, st, (const T*)att1, att2, wf, bf, (const T*)feat,
+                     alpha_out, (T*)z, P, A, F);
+}
+template <typename T>
+void beam_fwd_dispatch(int W, const void* att1, const float* att2, const float* wf, const float* bf, const void* feat, float* alpha_out,
+                       void* z, int B, int P, int A, int F, size_t lds, hipStream_t st) {
+  switch (W) {
+    case 1: beam_fwd_go<T, 1>(att1, att2, wf, bf, feat, alpha_out, z, B, P, A, F, lds, st); break;
+    case 2: beam_fwd_go<T, 2>(att1, att2, wf, bf, feat, alpha_out, z, B, P, A, F, lds, st); break;
+    case 3: beam_fwd_go<T, 3>(att1, att2, wf, bf, feat, alpha_out, z, B, P, A, F, lds, st); break;
+    case 4: beam_fwd_go<T, 4>(att1, att2, wf, bf, feat, alpha_out, z, B, P, A, F, lds, st); break;
+    case 5: beam_fwd_go<T, 5>(att1, att2, wf, bf, feat, alpha_out, z, B, P, A, F, lds, st); break;
+    case 6: beam_fwd_go<T, 6>(att1, att2, wf, bf, feat, alpha_out, z, B, P, A, F, lds, st); break;
+    case 7: beam_fwd_go<T, 7>(att1, att2, wf, bf, feat, alpha_out, z, B, P, A, F, lds, st); break;
+    default: beam_fwd_go<T, 8>(att1, att2, wf, bf, feat, alpha_out, z, B, P, A, F, lds, st); break;
+  }
+}
+}  // namespace
+
+int attn_beam_fwd_launch(const void* att1, const float* att2, const float* wf, const float* bf, const void* feat, float* alpha_out,
+                         void* z, int B, int W, int P, int A, int F, int dtype, hipStream_t st) {
+  if (B <= 0) return 0;
+  const int nn = dtype == ST_BF16 ? 8 : 4;
+  ST_CHECK(W >= 1 && W <= 8, "beam attention: 1 <= W <= 8 (got W=%d)", W);
+  ST_CHECK(A % nn == 0 && F % nn == 0 && P >= 1 && P <= kMaxP, "beam attention: A=%d and F=%d must be multiples of %d, P=%d <= %d",
+           A, F, nn, P, kMaxP);
+  const int nchunk = F / nn;
+  const int G = kBeamThreads >= 2 * nchunk ? kBeamThreads / nchunk : 1;
+  const size_t lds = (size_t)(W * A > (G - 1) * F ? W * A : (G - 1) * F) * sizeof(float);
+  ST_CHECK(lds <= 64 * 1024, "beam attention: W*A=%d floats of att2 do not fit the workgroup's 64 KB of LDS", W * A);
+  if (dtype == ST_BF16) beam_fwd_dispatch<bf16_t>(W, att1, att2, wf, bf, feat, alpha_out, z, B, P, A, F, lds, st);
+  else beam_fwd_dispatch<float>(W, att1, att2, wf, bf, feat, alpha_out, z, B, P, A, F, lds, st);
   ST_LAUNCH_CHECK();
   return 0;
 }

@@ -3,10 +3,12 @@ through the ``cell`` switch, ``Attention/rnn_attn_LSTM.py``.
 
     logits, alphas = rnn(cnn_feature, image_caption, caption_size)    # (N_tok, V) packed rows, (B, T, P) zero padded
     ids            = rnn.sentence_index(cnn_feature, vocab)           # Long(B, 25)
+    ids, alphas    = rnn.sentence_index(cnn_feature, vocab, return_alphas=True)   # + (B, 25, P) attention maps
+    hyps           = rnn.beam_search(cnn_feature, beam_width=5, return_alphas=True)   # per image [(tokens, cost, (len-1, P))]
 
 Same constructor, attribute names (``embeddings, unit, linear, init_h, attn.{encoder_att, decoder_att,
 full_att}, embed`` [+ ``init_c``]) and ``state_dict`` keys as the reference; the sub-modules are parameter
-containers, the arithmetic runs in st_attn_forward / st_attn_backward / st_attn_greedy.
+containers, the arithmetic runs in st_attn_forward / st_attn_backward / st_attn_greedy / st_attn_beam_search.
 
 Reference quirks kept: the input token at step t is ``caption[:, t]`` (the same token
 that is the target of that step), the initial hidden state is replicated over all layers, attention is keyed
@@ -15,6 +17,7 @@ module does not hard-code ``.cuda()`` but still requires a HIP device.
 """
 import ctypes as C
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -200,19 +203,68 @@ class RNN_Attn(nn.Module):
         out, _ = _AttnFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "loss", float(alpha_c), torch.is_grad_enabled())
         return out
 
-    def sentence_index(self, cnn_feature, vocab):
-        """rnn_attn.py:120-145: greedy decode from vocab('<start>'), exactly cap_max_size steps."""
+    def _decode_inputs(self, cnn_feature):
+        if not cnn_feature.is_cuda:
+            raise _lib.ShowTellHipError("cnn_feature must be on the HIP device (no CPU fallback)")
+        prm, keep = self._c_params()
+        B, Fd, P = cnn_feature.shape
+        prm.P = self.num_pixels_checked(P)
+        return prm, keep, cnn_feature.detach().float().contiguous(), B, P
+
+    def sentence_index(self, cnn_feature, vocab, return_alphas=False):
+        """rnn_attn.py:120-145: greedy decode from vocab('<start>'), exactly cap_max_size steps.  With `return_alphas`,
+        (ids, alphas): alphas (B, cap_max_size, P) fp32 on the device, the attention map of every step."""
         ind = vocab('<start>')                                               # rnn_attn.py:127
         with torch.no_grad():
-            if not cnn_feature.is_cuda:
-                raise _lib.ShowTellHipError("cnn_feature must be on the HIP device (no CPU fallback)")
-            prm, keep = self._c_params()
-            B, Fd, P = cnn_feature.shape
-            prm.P = self.num_pixels_checked(P)
-            featc = cnn_feature.detach().float().contiguous()
+            prm, keep, featc, B, P = self._decode_inputs(cnn_feature)
             nbytes = lib().st_attn_greedy_workspace_bytes(C.byref(prm), B)
             ws = torch.empty(nbytes, device=featc.device, dtype=torch.uint8)
             ids = torch.empty(B, self.cap_max_size, device=featc.device, dtype=torch.long)
+            if return_alphas:
+                alphas = torch.empty(B, self.cap_max_size, P, device=featc.device, dtype=torch.float32)
+                check(lib().st_attn_greedy_alphas(C.byref(prm), _cp(featc), B, self.cap_max_size, int(ind), _cp(ws), nbytes, _cp(ids),
+                                                  _cp(alphas), _stream()), "st_attn_greedy_alphas")
+                return ids.squeeze(), alphas
             check(lib().st_attn_greedy(C.byref(prm), _cp(featc), B, self.cap_max_size, int(ind), _cp(ws), nbytes, _cp(ids), _stream()),
                   "st_attn_greedy")
         return ids.squeeze()                                                 # rnn_attn.py:143
+
+    def beam_search(self, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50, start_id=1, end_id=2, return_alphas=False):
+        """beam_search.py:45-97 for every image of the batch, driven by the test branch of rnn_attn.py:77-94: the root holds
+        start_id with h0 = init_h(mean feature) over all layers (and c0 for the LSTM); a node's successors come from one step
+        fed with the node's token, attention keyed on its top-layer state.  The whole search is one st_attn_beam_search call
+        and one device-to-host copy of its records; the Node bookkeeping is replayed on the host (beam.replay_hypotheses).
+
+        Returns, per image, at most `num_hypotheses` (tokens, cost) pairs, as RNN.beam_search ([] when nothing ended in time).
+        With `return_alphas`: (tokens, cost, alphas), alphas a CPU float32 tensor (len(tokens) - 1, P) holding the extras of
+        the nodes after the root: the attention map computed while producing each token."""
+        from .beam import replay_hypotheses
+        if not 1 <= beam_width <= 8:
+            raise ValueError(f"beam_width must be 1..8 (got {beam_width})")
+        if max_length < 1:
+            raise ValueError(f"max_length must be >= 1 (got {max_length})")
+        with torch.no_grad():
+            prm, keep, featc, B, P = self._decode_inputs(cnn_feature)
+            W, T = beam_width, max_length
+            n = B * W
+            nbytes = lib().st_attn_beam_workspace_bytes(C.byref(prm), B, W)
+            ws = torch.empty(nbytes, device=featc.device, dtype=torch.uint8)
+            # the records share one buffer, so that the search ends in ONE device-to-host copy
+            layout = [("tok", torch.long, (T + 1, B, W)), ("cost", torch.float32, (T + 1, B, W)), ("par", torch.int32, (T + 1, B, W)),
+                      ("end", torch.uint8, (T, B, W))]
+            if return_alphas:
+                layout.append(("alpha", torch.float32, (T, n, P)))
+            offs, o = {}, 0
+            for name, dt, shape in layout:
+                nb = int(np.prod(shape)) * torch.empty((), dtype=dt).element_size()
+                offs[name] = (o, nb)
+                o += (nb + 255) // 256 * 256
+            rec = torch.empty(o, device=featc.device, dtype=torch.uint8)
+            view = {name: rec[offs[name][0]:offs[name][0] + offs[name][1]].view(dt).view(shape) for name, dt, shape in layout}
+            check(lib().st_attn_beam_search(C.byref(prm), _cp(featc), B, W, T, int(start_id), int(end_id), _cp(ws), nbytes,
+                                            _cp(view["tok"]), _cp(view["cost"]), _cp(view["par"]), _cp(view["end"]),
+                                            _cp(view.get("alpha")), _stream()), "st_attn_beam_search")
+            host = rec.cpu().numpy()
+        npdt = {torch.long: np.int64, torch.float32: np.float32, torch.int32: np.int32, torch.uint8: np.uint8}
+        h = {name: host[offs[name][0]:offs[name][0] + offs[name][1]].view(npdt[dt]).reshape(shape) for name, dt, shape in layout}
+        return replay_hypotheses(h["tok"], h["cost"], h["par"], h["end"], num_hypotheses, h.get("alpha"))
