@@ -132,7 +132,11 @@ class _Backbone:
         """(Re)build the flat BN arrays on `device` and point every BN tensor at its view."""
         self._ensure_handle()
         total = lib().st_resnet_bn_channels(self.handle)
-        new = {k: torch.empty(total, device=device, dtype=torch.float32) for k in ("gamma", "beta", "rm", "rv")}
+        new = {k: torch.empty(total, device=device, dtype=torch.float32) for k in ("gamma", "beta")}
+        # running means and running vars are ONE fp32 allocation: one copy saves or restores both (restore_running).
+        # num_batches_tracked stays a tensor of its own (torch.save refuses one storage viewed as two dtypes)
+        running = torch.empty(2 * total, device=device, dtype=torch.float32)
+        new["rm"], new["rv"] = running[:total], running[total:]
         nbt = torch.zeros(len(self.pairs), device=device, dtype=torch.long)
         for i, (_, bn) in enumerate(self.pairs):
             o, c = self.info[i]["bnoff"], self.info[i]["cout"]
@@ -142,7 +146,7 @@ class _Backbone:
                 t.data = view
             nbt[i] = bn.num_batches_tracked.item() if bn.num_batches_tracked.numel() else 0
             bn.num_batches_tracked.data = nbt[i]
-        self.flat, self.nbt = new, nbt
+        self.flat, self.nbt, self.running = new, nbt, running
 
     def _bn_ok(self, device):
         if self.flat is None or self.flat["gamma"].device != device:
@@ -173,9 +177,10 @@ class _Backbone:
                                                      inf["cout"], inf["cin"], inf["k"], inf["k"], inf["ntw"], st), "st_pack_conv_weight_frag")
         self.packed_key = key
 
-    def block_outputs(self, x, train):
+    def block_outputs(self, x, train, want_ncp=False):
         """Diagnosis / test aid (st_resnet_set_taps): one forward that also returns every residual block's output as the engine
-        stored it -- a list of (B, h, w, C) NHWC tensors in the compute dtype, in network order."""
+        stored it -- a list of (B, h, w, C) NHWC tensors in the compute dtype, in network order -- and the pooled features.
+        want_ncp: the same forward's (B, F, h * w) fp32 map (cnn_attn.ResNet's output) is returned third."""
         self._ensure_handle()
         B, _, H, W = x.shape
         h = ((H + 6 - 7) // 2 + 1 - 1) // 2 + 1
@@ -192,7 +197,7 @@ class _Backbone:
         buf = torch.empty(n, device=x.device, dtype=self.dtype)
         check(lib().st_resnet_set_taps(self.handle, C.c_void_p(buf.data_ptr()), buf.numel() * buf.element_size()), "st_resnet_set_taps")
         try:
-            pooled, _ = self.forward(x, train, True, False)
+            pooled, ncp = self.forward(x, train, True, want_ncp)
             torch.cuda.synchronize()
         finally:
             check(lib().st_resnet_set_taps(self.handle, None, 0), "st_resnet_set_taps")
@@ -201,9 +206,26 @@ class _Backbone:
             k = sh[0] * sh[1] * sh[2] * sh[3]
             outs.append(buf[o:o + k].view(sh))
             o += k
-        return outs, pooled
+        return (outs, pooled, ncp) if want_ncp else (outs, pooled)
 
-    def forward(self, x, train, want_pooled, want_ncp, pooled_dtype=torch.float32):
+    def restore_running(self, undos):
+        """Undo the momentum updates of a run of forwards: `undos` holds what forward(undo=...) left for each, oldest first, and no
+        train-mode forward was issued after them.  The running buffers go back to what the first train-mode forward among them
+        saved; num_batches_tracked goes down by the number of train-mode forwards (each added exactly 1).  Stream-ordered behind
+        the last update issued, on the current stream."""
+        undos = [u for u in undos if u]      # eval-mode forwards saved nothing and updated nothing
+        if not undos:
+            return
+        cur = torch.cuda.current_stream()
+        if self._upd_event is not None:
+            cur.wait_event(self._upd_event)
+        self.running.copy_(undos[0][0])
+        undos[0][0].record_stream(cur)
+        self.nbt.sub_(len(undos))
+        self._upd_event = torch.cuda.Event()
+        self._upd_event.record(cur)
+
+    def forward(self, x, train, want_pooled, want_ncp, pooled_dtype=torch.float32, undo=None):
         if not x.is_cuda:
             raise _lib.ShowTellHipError("ResNet.forward needs a HIP device tensor (no CPU fallback in the MI355X build)")
         if x.dim() != 4 or x.shape[1] != 3:
@@ -249,6 +271,8 @@ class _Backbone:
             # the forwards themselves overlap on different streams: an event chain over the small update kernel
             if self._upd_event is not None:
                 cur.wait_event(self._upd_event)
+            if undo is not None:    # the running means / vars as this update finds them, for restore_running
+                undo[:] = [self.running.clone()]
             check(lib().st_resnet_update_running(self.handle, p(ws), p(fl["rm"]), p(fl["rv"]), 0.1, C.c_void_p(cur.cuda_stream)),
                   "st_resnet_update_running")
             self.nbt.add_(1)
@@ -289,10 +313,16 @@ class ResNet(nn.Module):
         self._bb.packed = None
         return out
 
-    def backbone_features(self, x):
-        """Pooled (B,F) fp32 backbone output, detached (cnn.py:46-48)."""
-        pooled, _ = self._bb.forward(x, self.training, True, False)
+    def backbone_features(self, x, undo=None):
+        """Pooled (B,F) fp32 backbone output, detached (cnn.py:46-48).  undo (a list): in train mode, filled with what
+        restore_running needs to take this forward's running-buffer update back."""
+        pooled, _ = self._bb.forward(x, self.training, True, False, undo=undo)
         return pooled
+
+    def restore_running(self, undos):
+        """Undo the running-buffer updates of the forwards whose backbone_features(undo=...) lists are `undos` (oldest first;
+        the last forwards issued)."""
+        self._bb.restore_running(undos)
 
     def forward(self, x):
         from .head import linear_bn1d

@@ -51,7 +51,7 @@ class Trainer:
             broadcast_state([cnn, rnn], optimizer)         # replicas start from rank 0's weights and BN buffers
         self.pending = False
         optimizer._pending_owner = self                    # optimizer.state_dict() / utils.create_checkpoint flush the deferred step
-        self._pre = []        # FIFO of (images, pooled features, event): backbone forwards issued ahead on the side streams
+        self._pre = []        # FIFO of (images, pooled features, event, undo): backbone forwards issued ahead on the side streams
         self._side = []
         self._rr = 0
         self.depth = int(os.environ.get("ST_PIPE_DEPTH", "3"))        # backbone forwards kept in flight ahead of the trainable part (B=128 step: depth 1: 6.8 ms per forward, 2: 5.6, 3: 5.3 = 5.96 ms/step; 4: 6.35 ms/step, 5: 7.46 -- more forwards in flight evict each other's activations from the 256 MB Infinity Cache)
@@ -72,14 +72,22 @@ class Trainer:
         flight is this batch."""
         main = torch.cuda.current_stream()
         if self._pre and self._pre[0][0] is image:
-            _, pooled, ev = self._pre.pop(0)
+            _, pooled, ev, _ = self._pre.pop(0)
             main.wait_event(ev)
             pooled.record_stream(main)
             return pooled
-        for s_ in self._side:                          # unexpected batch: drop what was prefetched, stay ordered with the side streams
-            main.wait_stream(s_)
-        self._pre = []
+        self._drop(0)                                  # unexpected batch: drop what was prefetched
         return self.cnn.backbone_features(image)
+
+    def _drop(self, j):
+        """Forget the prefetched forwards from the j-th on.  Their momentum updates of the running BatchNorm buffers (and
+        num_batches_tracked) were already issued: they are undone, so that the buffers follow only the minibatches trained on,
+        in order.  The current stream is ordered behind the side streams."""
+        main = torch.cuda.current_stream()
+        for s_ in self._side:
+            main.wait_stream(s_)
+        self.cnn.restore_running([e[3] for e in self._pre[j:]])
+        self._pre = self._pre[:j]
 
     def _prefetch(self, image):
         if not self._side:
@@ -87,11 +95,12 @@ class Trainer:
         side = self._side[self._rr % len(self._side)]
         self._rr += 1
         side.wait_stream(torch.cuda.current_stream())  # after everything already queued on the main stream
+        undo = []
         with torch.cuda.stream(side):
-            pooled = self.cnn.backbone_features(image)
+            pooled = self.cnn.backbone_features(image, undo=undo)
             ev = torch.cuda.Event()
             ev.record(side)
-        self._pre.append((image, pooled, ev))
+        self._pre.append((image, pooled, ev, undo))
 
     def step(self, image, caption, caption_len, upcoming=()):
         """One training step.  `upcoming`: the images of the next minibatches, in order (at most `depth` are used)."""
@@ -102,9 +111,7 @@ class Trainer:
         for j, im in enumerate(upcoming):
             if j < len(self._pre):
                 if self._pre[j][0] is not im:          # the caller changed its mind: start over from here
-                    for s_ in self._side:
-                        torch.cuda.current_stream().wait_stream(s_)
-                    self._pre = self._pre[:j]
+                    self._drop(j)
                     self._prefetch(im)
             else:
                 self._prefetch(im)

@@ -44,6 +44,27 @@ def test_checkpoint_roundtrip(tmp_path):
         assert torch.equal(v, cnn2.state_dict()[k])
 
 
+def test_encoder_state_dict_saves_directly_once_flattened(tmp_path):
+    """After the first forward the BatchNorm tensors are views into the engine's flat arrays (cnn._Backbone.flatten_bn, laid
+    out here on the CPU as a forward lays them out on its device).  The reference's checkpoint code saves cnn.state_dict()
+    as it stands, with no copy: torch.save must accept it (one storage is never viewed as two dtypes) and load it back."""
+    from showtell_amd.cnn import ResNet
+    cnn = ResNet(18, 16)
+    cnn._bb.flatten_bn(torch.device("cpu"))
+    cnn._bb.nbt.add_(3)
+    with torch.no_grad():
+        cnn._bb.flat["rv"].uniform_(0.5, 1.5)
+    path = os.path.join(tmp_path, "enc.ckpt")
+    torch.save({"encoder_state_dict": cnn.state_dict()}, path)
+    back = torch.load(path, weights_only=True)["encoder_state_dict"]
+    cnn2 = ResNet(18, 16)
+    cnn2.load_state_dict(back)
+    for k, v in cnn.state_dict().items():
+        assert back[k].dtype == v.dtype and torch.equal(back[k], v), k
+        assert torch.equal(cnn2.state_dict()[k], v), k
+    assert int(back["model.1.num_batches_tracked"]) == 3
+
+
 def test_caption_word_format():
     from showtell_amd.utils import create_caption_word_format
 
