@@ -417,6 +417,151 @@ def gru_beam_callbacks(params, cnn_feature_row):
 
 
 # --------------------------------------------------------------------------
+# Teacher-forced beam steps over fixed (image, slot) rows b*W + w, as show-tell_amd/beam.py and st_attn_beam_search lay
+# them out.  Computed in the dtype of ``params`` (float64 for a tight oracle); with ``storage`` every value is rounded to
+# bf16 exactly where the bf16 kernels store it, without it nothing is rounded (the fp32 kernels).  Parameters are expected
+# bf16-representable already when ``storage`` is on.  A state is (h, c), each (L, B*W, H); c is None for the GRU.
+# --------------------------------------------------------------------------
+
+def _store(x, storage):
+    return _round_bf16(x) if storage else x
+
+
+def _cells_storage(params, x, h, c, cell, storage):
+    """All layers of one step; h after every cell and c of the LSTM are stored in the compute dtype (st_rnn_step's
+    h_out / c_out, as rnn_greedy_bf16_storage).  Returns (top, h', c')."""
+    hs, cs, inp = [], [], x
+    for l in range(num_layers_of(params)):
+        w = _layer_w(params, l)
+        if cell == "gru":
+            hl = _store(gru_cell(inp, h[l], *w), storage)
+        else:
+            hl, cl = lstm_cell(inp, h[l], c[l], *w)
+            hl, cl = _store(hl, storage), _store(cl, storage)
+            cs.append(cl)
+        hs.append(hl)
+        inp = hl
+    return inp, torch.stack(hs, 0), (torch.stack(cs, 0) if cell != "gru" else None)
+
+
+def beam_gather_state(state, par, W):
+    """State of slot (b, w) <- state of slot (b, par[b, w]) (st_gather_state with st_beam_select's gather row; an empty
+    slot, par = -1, reads slot 0 of its image as the kernel does: its state is never used)."""
+    par = torch.as_tensor(np.asarray(par), dtype=torch.long).clamp_min(0)
+    B = par.shape[0]
+    g = (torch.arange(B)[:, None] * W + par).reshape(-1)
+    return tuple(None if s is None else s[:, g] for s in state)
+
+
+def rnn_beam_init_bf16_storage(params, cnn_feature, W, cell="gru", storage=True):
+    """State of every slot before iteration 0: the state after the image-feature step (rnn.py:41,49), the feature stored
+    in the compute dtype (beam.py ``_feat``), every slot of an image a copy of it."""
+    B = cnn_feature.shape[0]
+    L = num_layers_of(params)
+    H = params["unit.weight_hh_l0"].shape[1]
+    h = cnn_feature.new_zeros(L, B, H)
+    c = cnn_feature.new_zeros(L, B, H) if cell != "gru" else None
+    _, h, c = _cells_storage(params, _store(cnn_feature, storage), h, c, cell, storage)
+    return h.repeat_interleave(W, 1), (None if c is None else c.repeat_interleave(W, 1))
+
+
+def rnn_beam_step_bf16_storage(params, tok, state, par_next=None, cell="gru", storage=True):
+    """One beam iteration of the plain decoder for all B*W rows, teacher-forced: row (b, w) is fed tok[b, w] (the
+    recorded fringe of iteration t) from ``state``.  Rounded to bf16 where the kernels store: the embedding rows fed
+    back (st_embedding_rows), h after every cell and c of the LSTM (st_rnn_step); the logits stay unrounded (fp32 in the
+    kernels).  Returns (log_softmax rows (B*W, V), new state); with ``par_next`` (the recorded par[t+1], (B, W)) the
+    new state is already that of iteration t+1: slot (b, w) <- this step's state of slot (b, par_next[b, w])."""
+    tok = torch.as_tensor(np.asarray(tok), dtype=torch.long)
+    W = tok.shape[1]
+    x = _store(params["embeddings.weight"][tok.reshape(-1)], storage)
+    top, h, c = _cells_storage(params, x, state[0], state[1], cell, storage)
+    logp = torch.log_softmax(top @ params["linear.weight"].t() + params["linear.bias"], 1)
+    new = (h, c)
+    return logp, (new if par_next is None else beam_gather_state(new, par_next, W))
+
+
+def attn_beam_init_bf16_storage(params, cnn_feature, W, cell="gru", storage=True):
+    """What csrc/attn.cpp ``prepare`` leaves in the workspace, and the root state.  Stored in the compute dtype:
+    feat (ncp_to_pf_launch, attn.cpp:149), mean (st_global_avgpool of the STORED feat, :150), h0 / c0 (gemm_nt with the
+    bias, :151-152), att1 (the hoisted encoder_att, :153).  h0 (c0) is replicated over the layers and scattered to the W
+    slots of its image (:535-539).  Returns (ctx = dict(feat (B, P, F), att1 (B, P, A)), state)."""
+    L = num_layers_of(params)
+    feat = _store(cnn_feature, storage).transpose(1, 2).contiguous()          # (B, P, F)
+    mean = _store(feat.mean(dim=1), storage)
+    h0 = _store(mean @ params["init_h.weight"].t() + params["init_h.bias"], storage)
+    h = h0.unsqueeze(0).repeat(L, 1, 1).repeat_interleave(W, 1)
+    c = None
+    if cell != "gru":
+        c0 = _store(mean @ params["init_c.weight"].t() + params["init_c.bias"], storage)
+        c = c0.unsqueeze(0).repeat(L, 1, 1).repeat_interleave(W, 1)
+    att1 = _store(feat @ params["attn.encoder_att.weight"].t() + params["attn.encoder_att.bias"], storage)
+    return dict(feat=feat, att1=att1), (h, c)
+
+
+def attn_beam_step_bf16_storage(params, ctx, tok, state, par_next=None, cell="gru", storage=True):
+    """One iteration of st_attn_beam_search's loop (attn.cpp:541-556) for all B*W rows, teacher-forced as
+    rnn_beam_step_bf16_storage.  fp32 in the kernels, so unrounded here: att2 (BPlan.att2, skinny at :547), the scores
+    and alpha (attn_beam_fwd_kernel's LDS / alpha_out), the logits (BPlan.logits).  Stored in the compute dtype, so
+    rounded here: z (BPlan.z, written by attn_beam_fwd_kernel, :548), both halves of x (BPlan.x: the embedding row from
+    st_embedding_rows :546, embed(z) from skinny_t :549), h after every cell and c (BPlan.h / .c, st_rnn_step :550).
+    Returns (log_softmax rows (B*W, V), alpha (B*W, P), new state), the state gathered by ``par_next`` when given."""
+    tok = torch.as_tensor(np.asarray(tok), dtype=torch.long)
+    B, W = tok.shape
+    h, c = state
+    feat, att1 = ctx["feat"], ctx["att1"]
+    att2 = h[-1] @ params["attn.decoder_att.weight"].t() + params["attn.decoder_att.bias"]          # (B*W, A)
+    e = F.leaky_relu(att1.unsqueeze(1) + att2.view(B, W, 1, -1), 0.2)                                  # (B, W, P, A)
+    att = (e @ params["attn.full_att.weight"].reshape(-1)) + params["attn.full_att.bias"]             # (B, W, P)
+    alpha = torch.softmax(att, dim=2)
+    z = _store(torch.bmm(alpha, feat).reshape(B * W, -1), storage)                                    # (B*W, F)
+    ez = _store(z @ params["embed.weight"].t() + params["embed.bias"], storage)
+    x = torch.cat([_store(params["embeddings.weight"][tok.reshape(-1)], storage), ez], 1)
+    top, h, c = _cells_storage(params, x, h, c, cell, storage)
+    logp = torch.log_softmax(top @ params["linear.weight"].t() + params["linear.bias"], 1)
+    new = (h, c)
+    return logp, alpha.reshape(B * W, -1), (new if par_next is None else beam_gather_state(new, par_next, W))
+
+
+def beam_free_run(step, state, B, W, T, start_id=1, end_id=2, cost_dtype=np.float64, keep=None):
+    """beam_search.py:45-97 for B images at once over fixed (image, slot) rows, driven by the step functions above:
+    ``step(tok (B, W), state) -> (logp, [alpha,] new state)``.  The search is the oracle's own (free running).  Bookkeeping
+    as st_beam_select / beam.beam_search_host: candidates node-major, a node's W successors in ascending probability, cut
+    by a stable sort on the cumulative cost (accumulated in ``cost_dtype``: np.float32 reproduces the reference under
+    NumPy 2), <end> nodes harvested at the start of the next iteration, an image without live nodes is finished.  Returns
+    the records dict(tok, cost, par [T+1][B][W], end [T][B][W]) that beam.replay_hypotheses reads.  ``keep(t, out, cost_t,
+    live)`` receives each iteration's step output, the fringe costs and the live mask."""
+    tok = np.zeros((T + 1, B, W), np.int64); tok[0, :, 0] = start_id
+    cost = np.full((T + 1, B, W), np.inf, cost_dtype); cost[0, :, 0] = 0
+    par = np.full((T + 1, B, W), -1, np.int32)
+    end = np.zeros((T, B, W), np.uint8)
+    done = np.zeros(B, bool)
+    for t in range(T):
+        out = step(torch.from_numpy(tok[t]), state)
+        logp, new = out[0], out[-1]
+        k = min(W, logp.shape[1])
+        tv, ti = torch.topk(logp, k, dim=1)                                                  # beam_search.py:84
+        tv, ti = tv.numpy().astype(cost_dtype), ti.numpy()
+        occupied = np.isfinite(cost[t])
+        ended = occupied & (tok[t] == end_id) & ~done[:, None]
+        live = occupied & ~ended & ~done[:, None]
+        done |= ~live.any(1)
+        live &= ~done[:, None]
+        end[t] = ended
+        if keep is not None:
+            keep(t, out, cost[t], live)
+        cand = (cost[t][:, :, None] - tv[:, ::-1].reshape(B, W, k)).astype(cost_dtype)      # ascending probability
+        flat = np.where(live[:, :, None], cand, np.inf).reshape(B, W * k)
+        order = np.argsort(flat, axis=1, kind="stable")[:, :W]                              # beam_search.py:94
+        ncost = np.take_along_axis(flat, order, 1)
+        ok = np.isfinite(ncost)
+        tok[t + 1] = np.where(ok, np.take_along_axis(ti[:, ::-1].reshape(B, W * k), order, 1), 0)
+        par[t + 1] = np.where(ok, order // k, -1)
+        cost[t + 1] = np.where(ok, ncost, np.inf)
+        state = beam_gather_state(new, par[t + 1], W)
+    return dict(tok=tok, cost=cost, par=par, end=end)
+
+
+# --------------------------------------------------------------------------
 # A1-A3: encoder.  Backbone restated from the published torchvision ResNet
 # v1.5 definition (stride on the 3x3; BN eps 1e-5, momentum 0.1).
 # --------------------------------------------------------------------------

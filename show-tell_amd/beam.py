@@ -115,6 +115,15 @@ def beam_search(rnn, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50,
     k = min(beam_width, rnn.vocab_size)
     if not on_device or beam_width * k > 64:
         return beam_search_host(rnn, cnn_feature, beam_width, num_hypotheses, max_length, start_id, end_id)
+    r = beam_search_records(rnn, cnn_feature, beam_width, max_length, start_id, end_id)
+    return replay_hypotheses(r["tok"], r["cost"], r["par"], r["end"], num_hypotheses)
+
+
+def beam_search_records(rnn, cnn_feature, beam_width=4, max_length=50, start_id=1, end_id=2):
+    """The device loop of ``beam_search`` on its own: every iteration's fringe over fixed (image, slot) rows, as numpy arrays
+    dict(tok, cost, par [max_length+1][B][W], end [max_length][B][W]) -- what ``replay_hypotheses`` reads.  Needs
+    beam_width * min(beam_width, V) <= 64 (st_beam_select)."""
+    k = min(beam_width, rnn.vocab_size)
     with torch.no_grad():
         st = _Stepper(rnn)
         dev = st.dev
@@ -142,8 +151,7 @@ def beam_search(rnn, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50,
                                        _cp(rec_par[t + 1]), _cp(rec_end[t]), _cp(gidx), _stream()), "st_beam_select")
             state = st.gather(new_state, gidx)
             tok, cost = ntok, ncost
-        h_tok, h_cost, h_par, h_end = rec_tok.cpu().numpy(), rec_cost.cpu().numpy(), rec_par.cpu().numpy(), rec_end.cpu().numpy()
-    return replay_hypotheses(h_tok, h_cost, h_par, h_end, num_hypotheses)
+        return dict(tok=rec_tok.cpu().numpy(), cost=rec_cost.cpu().numpy(), par=rec_par.cpu().numpy(), end=rec_end.cpu().numpy())
 
 
 def replay_hypotheses(h_tok, h_cost, h_par, h_end, num_hypotheses, alphas=None):

@@ -229,7 +229,8 @@ class RNN_Attn(nn.Module):
                   "st_attn_greedy")
         return ids.squeeze()                                                 # rnn_attn.py:143
 
-    def beam_search(self, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50, start_id=1, end_id=2, return_alphas=False):
+    def beam_search(self, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50, start_id=1, end_id=2, return_alphas=False,
+                    return_records=False):
         """beam_search.py:45-97 for every image of the batch, driven by the test branch of rnn_attn.py:77-94: the root holds
         start_id with h0 = init_h(mean feature) over all layers (and c0 for the LSTM); a node's successors come from one step
         fed with the node's token, attention keyed on its top-layer state.  The whole search is one st_attn_beam_search call
@@ -237,7 +238,9 @@ class RNN_Attn(nn.Module):
 
         Returns, per image, at most `num_hypotheses` (tokens, cost) pairs, as RNN.beam_search ([] when nothing ended in time).
         With `return_alphas`: (tokens, cost, alphas), alphas a CPU float32 tensor (len(tokens) - 1, P) holding the extras of
-        the nodes after the root: the attention map computed while producing each token."""
+        the nodes after the root: the attention map computed while producing each token.
+        With `return_records`: (hypotheses, records), records the search's own numpy arrays dict(tok, cost, par
+        [max_length+1][B][W], end [max_length][B][W]) and, with `return_alphas`, alpha [max_length][B*W][P]."""
         from .beam import replay_hypotheses
         if not 1 <= beam_width <= 8:
             raise ValueError(f"beam_width must be 1..8 (got {beam_width})")
@@ -267,4 +270,5 @@ class RNN_Attn(nn.Module):
             host = rec.cpu().numpy()
         npdt = {torch.long: np.int64, torch.float32: np.float32, torch.int32: np.int32, torch.uint8: np.uint8}
         h = {name: host[offs[name][0]:offs[name][0] + offs[name][1]].view(npdt[dt]).reshape(shape) for name, dt, shape in layout}
-        return replay_hypotheses(h["tok"], h["cost"], h["par"], h["end"], num_hypotheses, h.get("alpha"))
+        hyps = replay_hypotheses(h["tok"], h["cost"], h["par"], h["end"], num_hypotheses, h.get("alpha"))
+        return (hyps, h) if return_records else hyps

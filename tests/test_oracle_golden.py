@@ -88,6 +88,60 @@ def test_beam_search_sequences_exact(bw, nh):
             assert abs(h.cum_cost - d[f"bw{bw}_cost"][b, i]) < 1e-4
 
 
+@pytest.mark.parametrize("bw,nh", [(5, 3), (4, 1)])
+def test_beam_step_oracle_free_running_reproduces_reference_vectors(bw, nh):
+    """The batched beam-step oracle (R.rnn_beam_step_bf16_storage under R.beam_free_run) with the storage rounding switched
+    off, in fp32: the reference's own sequences and costs, exactly as R.beam_search gives them above."""
+    from showtell_amd.beam import replay_hypotheses
+    params, _, d = load_fixture("beam_small.npz")
+    feat = torch.from_numpy(d["feat"])
+    B, ml = feat.shape[0], int(d[f"bw{bw}_maxlen"])
+    with torch.no_grad():
+        state = R.rnn_beam_init_bf16_storage(params, feat, bw, "gru", storage=False)
+        rec = R.beam_free_run(lambda tok, st: R.rnn_beam_step_bf16_storage(params, tok, st, None, "gru", storage=False),
+                              state, B, bw, ml, 1, 2, cost_dtype=np.float32)
+    out = replay_hypotheses(rec["tok"], rec["cost"], rec["par"], rec["end"], nh)
+    assert sum(1 for h in out if h) >= 1
+    for b, hyp in enumerate(out):
+        lens = d[f"bw{bw}_len"][b]
+        assert len(hyp) == int((lens > 0).sum())
+        for i, (seq, cost) in enumerate(hyp):
+            assert seq == d[f"bw{bw}_seq"][b, i, :lens[i]].tolist()
+            assert abs(cost - d[f"bw{bw}_cost"][b, i]) < 1e-4
+    # teacher-forced on its own records, the step function gives the recorded costs back (state gathered by par)
+    with torch.no_grad():
+        state = R.rnn_beam_init_bf16_storage(params, feat, bw, "gru", storage=False)
+        for t in range(ml):
+            logp, state = R.rnn_beam_step_bf16_storage(params, rec["tok"][t], state, rec["par"][t + 1], "gru", storage=False)
+            lp = logp.view(B, bw, -1).numpy()
+            for b, w in zip(*np.nonzero(rec["par"][t + 1] >= 0)):
+                pw = rec["par"][t + 1][b, w]
+                want = rec["cost"][t][b, pw] - lp[b, pw, rec["tok"][t + 1][b, w]]
+                assert abs(rec["cost"][t + 1][b, w] - want) < 1e-5
+
+
+@pytest.mark.parametrize("cell,name,end_id", [("gru", "attn_gru_small.npz", 2), ("lstm", "attn_lstm_small.npz", 32)])
+def test_attention_beam_step_oracle_width1_is_the_reference_greedy_caption(cell, name, end_id):
+    """R.attn_beam_step_bf16_storage, unrounded in fp32, W = 1: one node per image is the reference's greedy decode up to
+    the first end_id, and its alpha is R.attention_net's."""
+    from showtell_amd.beam import replay_hypotheses
+    params, _, d = load_fixture(name)
+    feat = torch.from_numpy(d["feat"])
+    B = feat.shape[0]
+    alphas = {}
+    with torch.no_grad():
+        ctx, state = R.attn_beam_init_bf16_storage(params, feat, 1, cell, storage=False)
+        h0, _ = R._attn_init(params, feat, cell)
+        np.testing.assert_allclose(state[0].numpy(), h0.numpy(), atol=ATOL)
+        _, a0 = R.attention_net(params, feat.transpose(1, 2), h0[-1])
+        rec = R.beam_free_run(lambda tok, st: R.attn_beam_step_bf16_storage(params, ctx, tok, st, None, cell, storage=False),
+                              state, B, 1, 25, 1, end_id, cost_dtype=np.float32, keep=lambda t, out, *_: alphas.__setitem__(t, out[1]))
+    np.testing.assert_allclose(alphas[0].numpy(), a0.numpy(), atol=ATOL)
+    out = replay_hypotheses(rec["tok"], rec["cost"], rec["par"], rec["end"], 1)
+    for b, g in enumerate(d["greedy"].tolist()):
+        assert len(out[b]) == 1 and out[b][0][0] == [1] + g[:g.index(end_id) + 1], b
+
+
 def test_bleu_matches_reference_scorer():
     with open(os.path.join(GOLDEN, "bleu_small.json")) as f:
         j = json.load(f)
