@@ -504,6 +504,28 @@ int st_softmax_topk(const float* logits, int ldl, int n, int V, int k, float* to
 int st_beam_select(const long* tok, const float* cost, uint8_t* done, const float* top_p, const long* top_id, int B, int W, int k,
                    long end_id, long* new_tok, float* new_cost, int* parent, uint8_t* ended, int* gather, void* stream);
 
+/* Caption sampling (the multinomial counterpart of the max(1)[1] of rnn.py:52 and rnn_attn.py:141).  The kernels hold no
+ * random-number generator: the caller supplies one uniform in [0, 1) per row and step.
+ * st_sample_rows: for n rows of fp32 logits [n][ldl] (V valid entries, as st_rnn_step writes them) draw one token per row from
+ *   u[r * u_stride].  With z_v = logits[v] * inv_temperature (inv_temperature > 0) the kept set K is every v < V (top_k == 0)
+ *   or exactly the indices st_softmax_topk returns for the row (1 <= top_k <= min(32, V): the largest logits, the lowest index
+ *   first among equal values); p_v = exp(z_v - max_K z) / sum_K exp(z - max_K z); the token is the smallest v of K, in index
+ *   order, whose inclusive cumulative probability over K exceeds u (the largest v of K if rounding leaves none);
+ *   logp = z_tok - max - log(sum), the log-probability under the distribution sampled from (0 with top_k == 1).
+ *   A row needs at least one finite entry (st_rnn_step's logits have): with none the token is 0 and logp is NaN.
+ *   finished[n] (bytes, read and written): a row finished on entry gets token 0 (<pad>) and logp 0 and stays finished, a row
+ *   that draws end_id is marked finished after the draw.  The token goes to ids_out[r * out_stride + t] and to cur[r] (the
+ *   buffer the next st_embedding_rows reads; nullable), logp to logp_out[r * out_stride + t].
+ * st_rnn_sample: the loop of rnn.py:37-58 with the draw in place of max(1)[1]: step 0 feeds feat [n][E] (dtype) from a zero
+ *   state, each later step the embedding of the row's last token, exactly `steps` iterations of st_rnn_step (with logits),
+ *   st_sample_rows, st_embedding_rows.  u [n][steps] fp32; ids_out [n][steps] int64 and logp_out [n][steps] fp32.
+ * Nothing is allocated or synchronised inside these calls. */
+int st_sample_rows(const float* logits, int ldl, int n, int V, const float* u, int u_stride, float inv_temperature, int top_k,
+                   long end_id, uint8_t* finished, long* ids_out, float* logp_out, int out_stride, int t, long* cur, void* stream);
+size_t st_rnn_sample_workspace_bytes(const st_rnn_params* p, int n);
+int st_rnn_sample(const st_rnn_params* p, const void* feat, int n, int steps, const float* u, float inv_temperature, int top_k,
+                  long end_id, void* workspace, size_t workspace_bytes, long* ids_out, float* logp_out, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Soft-attention decoder (Attention/rnn_attn.py, rnn_attn_LSTM.py; train step Attention/main_attn.py:123-134).
  *   features: cnn_feature (B,F,P) fp32 as cnn_attn.py:49 returns it; caption_T: int64 [Tcap][B] (transposed captions).
@@ -547,6 +569,12 @@ int st_attn_greedy(const st_attn_params* p, const float* cnn_feature, int B, int
 /* st_attn_greedy plus the attention map of every step: alphas_out[B][steps][P] fp32 (same workspace as st_attn_greedy) */
 int st_attn_greedy_alphas(const st_attn_params* p, const float* cnn_feature, int B, int steps, long start_id,
                           void* workspace, size_t workspace_bytes, long* ids_out, float* alphas_out, void* stream);
+/* The same loop (rnn_attn.py:120-145, test branch 77-94) with st_sample_rows in place of the arg-max of rnn_attn.py:141:
+ * n rows, u [n][steps] fp32 uniforms, ids_out [n][steps] int64, logp_out [n][steps] fp32, alphas_out [n][steps][P] fp32 or NULL. */
+size_t st_attn_sample_workspace_bytes(const st_attn_params* p, int n);
+int st_attn_sample(const st_attn_params* p, const float* cnn_feature, int n, int steps, long start_id, const float* u,
+                   float inv_temperature, int top_k, long end_id, void* workspace, size_t workspace_bytes,
+                   long* ids_out, float* logp_out, float* alphas_out, void* stream);
 /* beam_search.py:45-97 on the attention decoder for B images, W slots each (1 <= W <= 8, so W*min(W,V) <= 64): initial state
  * h0 = init_h(mean_p feat) (and c0) over all layers, generate = one test-branch step (rnn_attn.py:77-94) from the node's token.
  * Rows are fixed (image, slot) pairs b*W + w.  Records use beam.py's layout: rec_tok/rec_cost/rec_par [max_length+1][B][W]

@@ -171,6 +171,9 @@ _SIGS = {
     "st_gather_state": ([c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p], c_i),
     "st_softmax_topk": ([c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p], c_i),
     "st_beam_select": ([c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_p, c_p, c_p, c_p, c_p, c_p], c_i),
+    "st_sample_rows": ([c_p, c_i, c_i, c_i, c_p, c_i, c_f, c_i, c_l, c_p, c_p, c_p, c_i, c_i, c_p, c_p], c_i),
+    "st_rnn_sample_workspace_bytes": ([C.POINTER(RnnParams), c_i], C.c_size_t),
+    "st_rnn_sample": ([C.POINTER(RnnParams), c_p, c_i, c_i, c_p, c_f, c_i, c_l, c_p, C.c_size_t, c_p, c_p, c_p], c_i),
     "st_attn_workspace_bytes": ([c_p, c_p], C.c_size_t),
     "st_attn_forward": ([c_p, c_p, c_p, c_p, c_p, C.c_size_t, c_p, c_i, c_i, c_p, c_i, c_p], c_i),
     "st_attn_backward": ([c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_f, c_p, c_p, C.c_size_t, c_p], c_i),
@@ -178,6 +181,8 @@ _SIGS = {
     "st_attn_greedy_workspace_bytes": ([c_p, c_i], C.c_size_t),
     "st_attn_greedy": ([c_p, c_p, c_i, c_i, c_l, c_p, C.c_size_t, c_p, c_p], c_i),
     "st_attn_greedy_alphas": ([c_p, c_p, c_i, c_i, c_l, c_p, C.c_size_t, c_p, c_p, c_p], c_i),
+    "st_attn_sample_workspace_bytes": ([c_p, c_i], C.c_size_t),
+    "st_attn_sample": ([c_p, c_p, c_i, c_i, c_l, c_p, c_f, c_i, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p], c_i),
     "st_attn_beam_workspace_bytes": ([c_p, c_i, c_i], C.c_size_t),
     "st_attn_beam_search": ([c_p, c_p, c_i, c_i, c_i, c_l, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p, c_p], c_i),
     "st_cross_entropy": ([c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_f, c_p, c_p], c_i),

@@ -404,17 +404,23 @@ extern "C" size_t st_attn_greedy_workspace_bytes(const st_attn_params* p, int B)
 }
 
 namespace {
-// rnn_attn.py:120-145; alphas_out [B][steps][P] keeps every step's attention map (else it goes to a scratch row)
+// how a step turns its logits into the next token: NULL = arg-max (rnn_attn.py:141), else a draw by st_sample_rows
+struct SampleSpec { const float* u; float inv_temperature; int top_k; long end_id; float* logp_out; };
+
+// rnn_attn.py:120-145; alphas_out [B][steps][P] keeps every step's attention map (else it goes to a scratch row).
+// The greedy and the sampling searches share this loop; sampling keeps its per-row finished bytes behind the greedy plan.
 int attn_greedy_run(const st_attn_params* p, const float* cnn_feature, int B, int steps, long start_id, void* workspace,
-                    size_t workspace_bytes, long* ids_out, float* alphas_out, void* stream, const char* who) {
+                    size_t workspace_bytes, long* ids_out, float* alphas_out, void* stream, const char* who, const SampleSpec* sp = nullptr) {
   if (check_common(p, nullptr, who)) return 1;
   ST_CHECK(cnn_feature && workspace && ids_out && B > 0 && steps > 0, "%s: bad arguments", who);
   const st_rnn_params& r = p->rnn;
   ST_CHECK(r.w_lin && r.b_lin, "%s: null vocabulary projection", who);
   const GPlan q = make_gplan(p, B);
-  ST_CHECK(workspace_bytes >= q.total, "%s: workspace too small", who);
+  ST_CHECK(workspace_bytes >= q.total + (sp ? al((size_t)B) : 0), "%s: workspace too small", who);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   char* ws = reinterpret_cast<char*>(workspace);
+  uint8_t* fin = reinterpret_cast<uint8_t*>(ws + q.total);
+  if (sp && hipMemsetAsync(fin, 0, (size_t)B, st) != hipSuccess) { st_set_error("%s: memset failed", who); return 1; }
   const int dt = r.dtype, H = r.H, E = r.E, L = r.L, P = p->P, A = p->A, F = p->F, Vp = up8(r.V);
   const size_t es = st_dtype_size(dt);
   if (prepare(p, cnn_feature, B, ws + q.feat, ws + q.mean, ws + q.h0, ws + q.c0, ws + q.att1, stream)) return 1;
@@ -437,8 +443,13 @@ int attn_greedy_run(const st_attn_params* p, const float* cnn_feature, int B, in
     if (st_embedding_rows(r.emb, cur, ws + q.x, B, E, r.V, 2 * E, dt, stream)) return 1;
     if (skinny_t(ws + q.z, F, p->w_embed, F, ws + q.x + (size_t)E * es, 2 * E, B, E, F, p->b_embed, dt, st)) return 1;
     if (st_rnn_step(&r, ws + q.x, B, ws + q.h[c], ws + q.c[c], ws + q.h[nx], ws + q.c[nx], logits, Vp, stream)) return 1;
-    hipLaunchKernelGGL(argmax_kernel, dim3(B), dim3(256), 0, st, logits, Vp, r.V, ids_out, steps, t, cur);
-    ST_LAUNCH_CHECK();
+    if (sp) {
+      if (st_sample_rows(logits, Vp, B, r.V, sp->u + t, steps, sp->inv_temperature, sp->top_k, sp->end_id, fin, ids_out, sp->logp_out, steps, t,
+                         cur, stream)) return 1;
+    } else {
+      hipLaunchKernelGGL(argmax_kernel, dim3(B), dim3(256), 0, st, logits, Vp, r.V, ids_out, steps, t, cur);
+      ST_LAUNCH_CHECK();
+    }
     c = nx;
   }
   return 0;
@@ -454,6 +465,19 @@ extern "C" int st_attn_greedy_alphas(const st_attn_params* p, const float* cnn_f
                                      void* workspace, size_t workspace_bytes, long* ids_out, float* alphas_out, void* stream) {
   ST_CHECK(alphas_out, "st_attn_greedy_alphas: null alphas_out");
   return attn_greedy_run(p, cnn_feature, B, steps, start_id, workspace, workspace_bytes, ids_out, alphas_out, stream, "st_attn_greedy_alphas");
+}
+
+extern "C" size_t st_attn_sample_workspace_bytes(const st_attn_params* p, int n) {
+  if (!p || n <= 0) return 0;
+  return make_gplan(p, n).total + al((size_t)n);
+}
+
+extern "C" int st_attn_sample(const st_attn_params* p, const float* cnn_feature, int n, int steps, long start_id, const float* u,
+                              float inv_temperature, int top_k, long end_id, void* workspace, size_t workspace_bytes,
+                              long* ids_out, float* logp_out, float* alphas_out, void* stream) {
+  ST_CHECK(u && logp_out, "st_attn_sample: null pointer");
+  const SampleSpec sp = {u, inv_temperature, top_k, end_id, logp_out};
+  return attn_greedy_run(p, cnn_feature, n, steps, start_id, workspace, workspace_bytes, ids_out, alphas_out, stream, "st_attn_sample", &sp);
 }
 
 // ---- beam search (beam_search.py:45-97 driven by the test branch rnn_attn.py:77-94) --------------------------------

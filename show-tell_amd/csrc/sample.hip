@@ -1,0 +1,276 @@
+// Caption sampling: one token per row drawn from softmax(logits / temperature), optionally restricted to the top_k largest
+// logits, with the token's log-probability (include/showtell_hip.h: st_sample_rows, st_rnn_sample).  The multinomial
+// counterpart of the max(1)[1] of rnn.py:52 / rnn_attn.py:141.  No random-number generator lives here: the caller hands
+// in one uniform per row and step, so every draw is a deterministic function of (logits, u).
+//
+// One workgroup per row; thread t owns the CONTIGUOUS index range [t * chunk, (t + 1) * chunk), so that index order is
+// (thread, position) order:
+//   pass 1  per-thread maximum -> row maximum; with top_k > 0 the k-th largest THREAD maximum T0 is a lower bound of the
+//           row's k-th largest element (the idea of softmax_topk_thr_kernel), the elements >= T0 go to a candidate list
+//           in LDS and the candidate of rank k - 1 (value descending, index ascending: st_softmax_topk's order) is the
+//           last kept element (T, Ti): v is kept iff v > T or (v == T and index <= Ti);
+//   pass 2  per-thread sum of exp over the kept elements of its range, block scan of the 256 partial sums;
+//   pass 3  the first thread whose inclusive sum exceeds u * sum walks its own range (at most `chunk` elements).
+// No lane ever sums a whole row.  Rows of up to 256 x 40 entries (V = 10000) are read ONCE, with all of a thread's loads in
+// flight together, and stay in registers between the passes; longer or unaligned rows take the passes over memory.
+// A row needs at least one finite entry: with none (all -inf or NaN) the token is 0 and logp is NaN.
+#include "common.h"
+
+namespace {
+
+inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
+inline int up8(int v) { return (v + 7) & ~7; }
+
+constexpr int kSampleThreads = 256;
+constexpr int kSampleCap = 1024;      // candidate list; more elements >= T0 (rows of equal logits): exact selection by rounds
+
+// a ranks before b in st_softmax_topk's order: value descending, index ascending
+__device__ __forceinline__ bool ranks_before(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
+
+// f(value, index) for every index of [lo, hi) in increasing order; lo is a multiple of 4 (16-byte loads when VEC: the row
+// is padded to a multiple of 4 entries, so the last load stays inside the row)
+template <bool VEC, typename F>
+__device__ __forceinline__ void for_range(const float* __restrict__ l, int lo, int hi, F&& f) {
+  for (int j = lo; j < hi; j += 4) {
+    float v[4];
+    if (VEC) {
+      const f32x4 q = *reinterpret_cast<const f32x4*>(l + j);
+      v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = j + e < hi ? l[j + e] : 0.f;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) if (j + e < hi) f(v[e], j + e);
+  }
+}
+
+// A thread's view of its index range [lo, hi) of the row: each(f) calls f(value, index) in increasing index order.
+template <bool VEC>
+struct RowMem {
+  const float* l; int lo, hi;
+  __device__ __forceinline__ RowMem(const float* l_, int lo_, int hi_) : l(l_), lo(lo_), hi(hi_) {}
+  template <typename F> __device__ __forceinline__ void each(F&& f) const { for_range<VEC>(l, lo, hi, f); }
+};
+constexpr int kSampleRegs = 40;       // entries per thread of the register-resident form
+struct RowReg {
+  float rv[kSampleRegs]; int lo, hi;
+  __device__ __forceinline__ RowReg(const float* l, int lo_, int hi_) : lo(lo_), hi(hi_) {
+#pragma unroll
+    for (int j = 0; j < kSampleRegs; j += 4) {         // unconditional address arithmetic, predicated loads: all in flight at once
+      f32x4 q = {0.f, 0.f, 0.f, 0.f};
+      if (lo + j < hi) q = *reinterpret_cast<const f32x4*>(l + lo + j);
+      rv[j] = q[0]; rv[j + 1] = q[1]; rv[j + 2] = q[2]; rv[j + 3] = q[3];
+    }
+  }
+  template <typename F> __device__ __forceinline__ void each(F&& f) const {
+#pragma unroll
+    for (int j = 0; j < kSampleRegs; ++j) if (lo + j < hi) f(rv[j], lo + j);
+  }
+};
+
+// block-wide first element in st_softmax_topk's order (4 waves); every thread returns the winner
+__device__ __forceinline__ void block_first(float& v, int& i, float* sv, int* si) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(v, o, 64); const int oi = __shfl_xor(i, o, 64);
+    if (ranks_before(ov, oi, v, i)) { v = ov; i = oi; }
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = v; si[threadIdx.x >> 6] = i; }
+  __syncthreads();
+  v = sv[0]; i = si[0];
+  for (int w = 1; w < 4; ++w) if (ranks_before(sv[w], si[w], v, i)) { v = sv[w]; i = si[w]; }
+}
+
+template <typename Row>
+__global__ __launch_bounds__(kSampleThreads) void sample_rows_kernel(const float* __restrict__ logits, int ldl, int V, const float* __restrict__ u,
+                                                                     int u_stride, float inv_t, int top_k, long end_id, uint8_t* __restrict__ finished,
+                                                                     long* __restrict__ ids_out, float* __restrict__ logp_out, int out_stride, int t,
+                                                                     long* __restrict__ cur) {
+  __shared__ float s_tm[kSampleThreads];
+  __shared__ float c_v[kSampleCap]; __shared__ int c_i[kSampleCap];
+  __shared__ float s_max[4], s_sum[4], s_bv[4]; __shared__ int s_bi[4], s_last[4], s_first[4];
+  __shared__ int s_cnt, s_Ti, s_tok; __shared__ float s_T;
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const long out = (long)row * out_stride + t;
+  if (finished[row]) {                                       // (block-uniform) <pad> after <end>
+    if (tid == 0) { ids_out[out] = 0; logp_out[out] = 0.f; if (cur) cur[row] = 0; }
+    return;
+  }
+  const float* l = logits + (long)row * ldl;
+  const int chunk = ((V + kSampleThreads - 1) / kSampleThreads + 3) & ~3;
+  const int lo = tid * chunk < V ? tid * chunk : V, hi = lo + chunk < V ? lo + chunk : V;
+  const Row row_part(l, lo, hi);
+
+  // ---- pass 1: maximum (and the top_k boundary) ----
+  float tm = -INFINITY;
+  row_part.each([&](float v, int) { tm = fmaxf(tm, v); });
+  float M = wave_max(tm);
+  if (lane == 0) s_max[wid] = M;
+  s_tm[tid] = tm;
+  if (tid == 0) s_cnt = 0;
+  __syncthreads();
+  M = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
+  float T = -INFINITY; int Ti = 0x7fffffff;                  // top_k == 0 (or V): everything is kept
+  if (top_k > 0 && top_k < V) {
+    int rank = 0;                                            // of this thread's maximum among the 256 (a total order: one thread per rank)
+    for (int o = 0; o < kSampleThreads; ++o) rank += ranks_before(s_tm[o], o, tm, tid) ? 1 : 0;
+    if (rank == top_k - 1) s_T = tm;
+    __syncthreads();
+    const float T0 = s_T;                                    // >= top_k elements are >= T0 (T0 = -inf: all V of them)
+    row_part.each([&](float v, int i) {
+      if (v >= T0) { const int p = atomicAdd(&s_cnt, 1); if (p < kSampleCap) { c_v[p] = v; c_i[p] = i; } }
+    });
+    __syncthreads();
+    const int n = s_cnt;
+    if (n <= kSampleCap) {
+      for (int c = tid; c < n; c += kSampleThreads) {
+        const float v = c_v[c]; const int i = c_i[c];
+        int r = 0;
+        for (int o = 0; o < n; ++o) r += ranks_before(c_v[o], c_i[o], v, i) ? 1 : 0;
+        if (r == top_k - 1) { s_T = v; s_Ti = i; }
+      }
+    } else {                                                 // (block-uniform) round j picks the first element after round j-1's
+      float pv = INFINITY; int pi = -1;
+      for (int j = 0; j < top_k; ++j) {
+        float bv = -INFINITY; int bi = 0x7fffffff;
+        row_part.each([&](float v, int i) {
+          if (ranks_before(pv, pi, v, i) && ranks_before(v, i, bv, bi)) { bv = v; bi = i; }
+        });
+        block_first(bv, bi, s_bv, s_bi);
+        pv = bv; pi = bi;
+      }
+      if (tid == 0) { s_T = pv; s_Ti = pi; }
+    }
+    __syncthreads();
+    T = s_T; Ti = s_Ti;
+  }
+  auto kept = [&](float v, int i) { return v > T || (v == T && i <= Ti); };
+  // (v - M) * inv_t, not v * inv_t - M * inv_t: exactly 0 at the maximum, and no product feeds an addition that the
+  // compiler could contract into a fused multiply-add in one pass and not in the other
+  auto weight = [&](float v) { return expf((v - M) * inv_t); };
+
+  // ---- pass 2: partial sums over contiguous ranges, block scan ----
+  float loc = 0.f; int lastk = -1;
+  row_part.each([&](float v, int i) { if (kept(v, i)) { loc += weight(v); lastk = i; } });
+  float inc = loc;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const float y = __shfl_up(inc, o, 64); if (lane >= o) inc += y; }
+  float excl = __shfl_up(inc, 1, 64);
+  if (lane == 0) excl = 0.f;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) lastk = max(lastk, __shfl_xor(lastk, o, 64));
+  if (lane == 63) s_sum[wid] = inc;
+  if (lane == 0) s_last[wid] = lastk;
+  __syncthreads();
+  float woff = 0.f;
+  for (int w = 0; w < wid; ++w) woff += s_sum[w];
+  excl += woff;
+  const float S = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
+  const float target = u[(long)row * u_stride] * S;
+
+  // ---- pass 3: the first range that crosses u * S, and a walk inside it ----
+  int first = (loc > 0.f && excl + loc > target) ? tid : kSampleThreads;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, 64));
+  if (lane == 0) s_first[wid] = first;
+  __syncthreads();
+  first = min(min(s_first[0], s_first[1]), min(s_first[2], s_first[3]));
+  if (tid == first) {                                        // the same additions in the same order as pass 2: run ends at loc
+    float run = 0.f; int tok = -1;
+    row_part.each([&](float v, int i) {
+      if (kept(v, i)) { run += weight(v); if (tok < 0 && excl + run > target) tok = i; }
+    });
+    s_tok = tok;
+  } else if (first == kSampleThreads && tid == 0) {          // rounding left no crossing: the largest kept index
+    s_tok = max(max(s_last[0], s_last[1]), max(s_last[2], s_last[3]));
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int tok = s_tok;
+    if (tok < 0 || tok >= V) tok = 0;                        // a row without a finite entry: keep the index in range (logp is NaN)
+    ids_out[out] = tok;
+    logp_out[out] = (l[tok] - M) * inv_t - logf(S);
+    if (cur) cur[row] = tok;
+    if (tok == end_id) finished[row] = 1;
+  }
+}
+
+}  // namespace
+
+extern "C" int st_sample_rows(const float* logits, int ldl, int n, int V, const float* u, int u_stride, float inv_temperature, int top_k,
+                              long end_id, uint8_t* finished, long* ids_out, float* logp_out, int out_stride, int t, long* cur, void* stream) {
+  ST_CHECK(logits && u && finished && ids_out && logp_out, "st_sample_rows: null pointer");
+  ST_CHECK(V >= 1 && ldl >= V, "st_sample_rows: need 1 <= V <= ldl (got V=%d ldl=%d)", V, ldl);
+  ST_CHECK(inv_temperature > 0.f, "st_sample_rows: inv_temperature must be > 0");
+  ST_CHECK(top_k >= 0 && top_k <= 32 && top_k <= V, "st_sample_rows: need 0 <= top_k <= min(32, V) (got %d)", top_k);
+  ST_CHECK(t >= 0 && t < out_stride && u_stride >= 0, "st_sample_rows: bad output column %d of %d", t, out_stride);
+  if (n <= 0) return 0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const bool vec = ldl % 4 == 0 && reinterpret_cast<uintptr_t>(logits) % 16 == 0;
+  const bool regs = vec && V <= kSampleThreads * kSampleRegs;       // the kernel's chunk = V / 256 rounded up to 4 fits kSampleRegs
+  if (regs)
+    hipLaunchKernelGGL(sample_rows_kernel<RowReg>, dim3(n), dim3(kSampleThreads), 0, st, logits, ldl, V, u, u_stride, inv_temperature, top_k, end_id,
+                       finished, ids_out, logp_out, out_stride, t, cur);
+  else if (vec)
+    hipLaunchKernelGGL(sample_rows_kernel<RowMem<true>>, dim3(n), dim3(kSampleThreads), 0, st, logits, ldl, V, u, u_stride, inv_temperature, top_k, end_id,
+                       finished, ids_out, logp_out, out_stride, t, cur);
+  else
+    hipLaunchKernelGGL(sample_rows_kernel<RowMem<false>>, dim3(n), dim3(kSampleThreads), 0, st, logits, ldl, V, u, u_stride, inv_temperature, top_k, end_id,
+                       finished, ids_out, logp_out, out_stride, t, cur);
+  ST_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- the plain decoders' sampling loop (rnn.py:37-58 with a draw in place of max(1)[1]) --------------------------------------
+namespace {
+struct SPlan { size_t h[2], c[2], x, logits, cur, fin, total; };
+SPlan make_splan(const st_rnn_params* p, int n) {
+  const size_t es = st_dtype_size(p->dtype);
+  SPlan q; size_t o = 0;
+  auto take = [&](size_t bytes) { size_t x = o; o += al(bytes); return x; };
+  const size_t hb = (size_t)p->L * n * p->H * es;
+  for (int i = 0; i < 2; ++i) { q.h[i] = take(hb); q.c[i] = take(p->cell == ST_CELL_LSTM ? hb : 0); }
+  q.x = take((size_t)n * p->E * es);
+  q.logits = take((size_t)n * up8(p->V) * sizeof(float));
+  q.cur = take((size_t)n * sizeof(long));
+  q.fin = take((size_t)n);
+  q.total = o;
+  return q;
+}
+}  // namespace
+
+extern "C" size_t st_rnn_sample_workspace_bytes(const st_rnn_params* p, int n) {
+  if (!p || n <= 0) return 0;
+  return make_splan(p, n).total;
+}
+
+extern "C" int st_rnn_sample(const st_rnn_params* p, const void* feat, int n, int steps, const float* u, float inv_temperature, int top_k,
+                             long end_id, void* workspace, size_t workspace_bytes, long* ids_out, float* logp_out, void* stream) {
+  ST_CHECK(p && feat && u && workspace && ids_out && logp_out, "st_rnn_sample: null pointer");
+  ST_CHECK(n > 0 && steps > 0, "st_rnn_sample: need n > 0 and steps > 0");
+  ST_CHECK(p->L >= 1 && p->L <= ST_MAX_LAYERS && p->in0 == p->E, "st_rnn_sample: bad decoder configuration");
+  ST_CHECK(p->emb && p->w_lin && p->b_lin, "st_rnn_sample: null weights");
+  const SPlan q = make_splan(p, n);
+  ST_CHECK(workspace_bytes >= q.total, "st_rnn_sample: workspace too small");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  char* ws = reinterpret_cast<char*>(workspace);
+  const bool lstm = p->cell == ST_CELL_LSTM;
+  const int Vp = up8(p->V);
+  float* logits = reinterpret_cast<float*>(ws + q.logits);
+  long* cur = reinterpret_cast<long*>(ws + q.cur);
+  uint8_t* fin = reinterpret_cast<uint8_t*>(ws + q.fin);
+  if (hipMemsetAsync(fin, 0, (size_t)n, st) != hipSuccess) { st_set_error("st_rnn_sample: memset failed"); return 1; }
+  int c = 0;
+  for (int t = 0; t < steps; ++t) {
+    const int nx = c ^ 1;
+    // step 0: the image feature from a zero state (rnn.py:44-47); later steps: the embedding of the row's last token (rnn.py:53)
+    if (st_rnn_step(p, t == 0 ? feat : ws + q.x, n, t == 0 ? nullptr : ws + q.h[c], (t == 0 || !lstm) ? nullptr : ws + q.c[c], ws + q.h[nx],
+                    lstm ? ws + q.c[nx] : nullptr, logits, Vp, stream)) return 1;
+    if (st_sample_rows(logits, Vp, n, p->V, u + t, steps, inv_temperature, top_k, end_id, fin, ids_out, logp_out, steps, t, cur, stream)) return 1;
+    if (t + 1 < steps && st_embedding_rows(p->emb, cur, ws + q.x, n, p->E, p->V, p->E, p->dtype, stream)) return 1;
+    c = nx;
+  }
+  return 0;
+}

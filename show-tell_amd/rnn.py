@@ -6,6 +6,7 @@ Same constructor, same attribute names (``embeddings``, ``unit``, ``linear``) an
 
     logits = rnn(cnn_feature, image_caption, caption_size)      # (N_tok, V), time-major packed rows
     ids    = rnn.sentence_index(cnn_feature, beam_size=0)       # Long(B, 25) (squeezed)
+    ids, logp, lengths = rnn.sample(cnn_feature, num_samples=5, temperature=0.8, top_k=20)   # (B, S, 25) draws (st_rnn_sample)
 
 ``nn.Embedding`` / ``nn.GRU`` / ``nn.Linear`` objects are parameter containers only; all
 arithmetic runs in libshowtell_hip (st_rnn_forward / st_rnn_backward / st_rnn_greedy /
@@ -59,6 +60,37 @@ def grad_buffer(p):
 
 def up8(v):
     return (v + 7) // 8 * 8
+
+
+def check_sample_args(vocab_size, batch, num_samples, temperature, top_k, max_length, uniforms):
+    """Argument errors of ``sample`` (both decoders), raised before anything touches the device."""
+    if not temperature > 0:
+        raise ValueError(f"temperature must be > 0 (got {temperature})")
+    if int(top_k) != top_k or not 0 <= top_k <= min(32, vocab_size):
+        raise ValueError(f"top_k must be 0 (the whole vocabulary) or 1..{min(32, vocab_size)} (got {top_k})")
+    if int(num_samples) != num_samples or num_samples < 1:
+        raise ValueError(f"num_samples must be >= 1 (got {num_samples})")
+    if int(max_length) != max_length or max_length < 1:
+        raise ValueError(f"max_length must be >= 1 (got {max_length})")
+    if uniforms is not None:
+        want = (batch, int(num_samples), int(max_length))
+        if not torch.is_tensor(uniforms) or tuple(uniforms.shape) != want or uniforms.dtype != torch.float32:
+            raise ValueError(f"uniforms must be a float32 tensor of shape {want} (images, samples, steps)")
+
+
+def sample_uniforms(uniforms, shape, device, generator):
+    """The (B, S, T) fp32 uniforms of a ``sample`` call on `device`: the caller's, or torch.rand from `generator`."""
+    if uniforms is not None:
+        return uniforms.detach().to(device).contiguous()
+    if generator is not None and generator.device.type != device.type:
+        return torch.rand(shape, generator=generator, dtype=torch.float32).to(device)
+    return torch.rand(shape, device=device, generator=generator, dtype=torch.float32)
+
+
+def sample_lengths(ids, end_id):
+    """Tokens up to and including the first <end> of every row; the row's width if it never drew <end>."""
+    before = ((ids == end_id).cumsum(-1) == 0).sum(-1)
+    return (before + 1).clamp(max=ids.shape[-1])
 
 
 class _DecoderFn(torch.autograd.Function):
@@ -212,6 +244,37 @@ class RNN(torch.nn.Module):
         """beam_search.py:45-97 over the whole batch (BASELINE config 5: beam_width=5, max_length=25)."""
         from .beam import beam_search
         return beam_search(self, cnn_feature, beam_width, num_hypotheses, max_length, start_id, end_id)
+
+    def sample(self, cnn_feature, num_samples=1, temperature=1.0, top_k=0, max_length=CAP_MAX, end_id=2, generator=None,
+               uniforms=None):
+        """The loop of rnn.py:37-58 with a draw in place of max(1)[1]: `num_samples` captions per image from
+        softmax(logits / temperature), restricted to the `top_k` most likely words when top_k > 0 (at most 32).  One
+        st_rnn_sample call for all B * num_samples rows (row b * S + s), no host round trip per token.  The randomness is
+        `uniforms` (B, S, T) fp32 in [0, 1) on the device, one per row and step, or torch.rand from `generator`.
+
+        Returns (ids (B, S, T) int64, 0 after <end>; logp (B, S, T) fp32, the log-probability of each token under the
+        distribution it was drawn from, 0 after <end>; lengths (B, S) int64 counting <end>, T if <end> was never drawn)."""
+        B, S, T = cnn_feature.shape[0], num_samples, max_length
+        check_sample_args(self.vocab_size, B, S, temperature, top_k, T, uniforms)
+        S, T = int(S), int(T)
+        with torch.no_grad():
+            prm, keep = self._c_params()
+            if not cnn_feature.is_cuda:
+                raise _lib.ShowTellHipError("cnn_feature must be on the HIP device (no CPU fallback)")
+            dt = self.compute_dtype
+            feat = cnn_feature.detach().contiguous()
+            feat = feat if feat.dtype == dt else ops.cast(feat.float(), dt)
+            if S > 1:
+                feat = feat.repeat_interleave(S, 0)
+            n, dev = B * S, feat.device
+            u = sample_uniforms(uniforms, (B, S, T), dev, generator)
+            nbytes = lib().st_rnn_sample_workspace_bytes(C.byref(prm), n)
+            ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+            ids = torch.empty(n, T, device=dev, dtype=torch.long)
+            logp = torch.empty(n, T, device=dev, dtype=torch.float32)
+            check(lib().st_rnn_sample(C.byref(prm), _cp(feat), n, T, _cp(u), 1.0 / float(temperature), int(top_k), int(end_id), _cp(ws),
+                                      nbytes, _cp(ids), _cp(logp), _stream()), "st_rnn_sample")
+            return ids.view(B, S, T), logp.view(B, S, T), sample_lengths(ids, end_id).view(B, S)
 
     def sentence_index(self, cnn_feature, beam_size=0, return_logits=False):
         """rnn.py:37-108: 25-step greedy decode (beam_size=0) or the bs=1 ranking loop (beam_size>0)."""

@@ -5,10 +5,11 @@ through the ``cell`` switch, ``Attention/rnn_attn_LSTM.py``.
     ids            = rnn.sentence_index(cnn_feature, vocab)           # Long(B, 25)
     ids, alphas    = rnn.sentence_index(cnn_feature, vocab, return_alphas=True)   # + (B, 25, P) attention maps
     hyps           = rnn.beam_search(cnn_feature, beam_width=5, return_alphas=True)   # per image [(tokens, cost, (len-1, P))]
+    ids, logp, lengths, alphas = rnn.sample(cnn_feature, num_samples=5, return_alphas=True)   # (B, S, 25) draws + (B, S, 25, P) maps
 
 Same constructor, attribute names (``embeddings, unit, linear, init_h, attn.{encoder_att, decoder_att,
 full_att}, embed`` [+ ``init_c``]) and ``state_dict`` keys as the reference; the sub-modules are parameter
-containers, the arithmetic runs in st_attn_forward / st_attn_backward / st_attn_greedy / st_attn_beam_search.
+containers, the arithmetic runs in st_attn_forward / st_attn_backward / st_attn_greedy / st_attn_beam_search / st_attn_sample.
 
 Reference quirks kept: the input token at step t is ``caption[:, t]`` (the same token
 that is the target of that step), the initial hidden state is replicated over all layers, attention is keyed
@@ -23,7 +24,7 @@ import torch.nn as nn
 
 from . import _lib, ops
 from ._lib import ST_BF16, ST_CELL_GRU, ST_CELL_LSTM, ST_F32, AttnGrads, AttnParams, check, lib
-from .rnn import CAP_MAX, _cp, _stream, grad_buffer, up8, working_copy
+from .rnn import CAP_MAX, _cp, _stream, check_sample_args, grad_buffer, sample_lengths, sample_uniforms, up8, working_copy
 from .seq import plan_for
 
 
@@ -228,6 +229,30 @@ class RNN_Attn(nn.Module):
             check(lib().st_attn_greedy(C.byref(prm), _cp(featc), B, self.cap_max_size, int(ind), _cp(ws), nbytes, _cp(ids), _stream()),
                   "st_attn_greedy")
         return ids.squeeze()                                                 # rnn_attn.py:143
+
+    def sample(self, cnn_feature, num_samples=1, temperature=1.0, top_k=0, max_length=CAP_MAX, start_id=1, end_id=2,
+               generator=None, uniforms=None, return_alphas=False):
+        """The loop of rnn_attn.py:120-145 (test branch 77-94) from `start_id` with a draw in place of the arg-max of
+        rnn_attn.py:141; arguments and results as RNN.sample (one st_attn_sample call for all B * num_samples rows).
+        With `return_alphas` also alphas (B, S, T, P) fp32 on the device: the attention map of every step."""
+        B, S, T = cnn_feature.shape[0], num_samples, max_length
+        check_sample_args(self.vocab_size, B, S, temperature, top_k, T, uniforms)
+        S, T = int(S), int(T)
+        with torch.no_grad():
+            prm, keep, featc, B, P = self._decode_inputs(cnn_feature)
+            if S > 1:
+                featc = featc.repeat_interleave(S, 0)
+            n, dev = B * S, featc.device
+            u = sample_uniforms(uniforms, (B, S, T), dev, generator)
+            nbytes = lib().st_attn_sample_workspace_bytes(C.byref(prm), n)
+            ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+            ids = torch.empty(n, T, device=dev, dtype=torch.long)
+            logp = torch.empty(n, T, device=dev, dtype=torch.float32)
+            alphas = torch.empty(n, T, P, device=dev, dtype=torch.float32) if return_alphas else None
+            check(lib().st_attn_sample(C.byref(prm), _cp(featc), n, T, int(start_id), _cp(u), 1.0 / float(temperature), int(top_k),
+                                       int(end_id), _cp(ws), nbytes, _cp(ids), _cp(logp), _cp(alphas), _stream()), "st_attn_sample")
+            out = (ids.view(B, S, T), logp.view(B, S, T), sample_lengths(ids, end_id).view(B, S))
+            return out + (alphas.view(B, S, T, P),) if return_alphas else out
 
     def beam_search(self, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50, start_id=1, end_id=2, return_alphas=False,
                     return_records=False):
