@@ -13,12 +13,16 @@
 // forward:  x0 = [feat ; emb(caption)] gathered straight into packed rows (no cat/pack copies)
 //           per diagonal one fused launch: x W_ih^T + h W_hh^T + gates for every cell -> st_rnn_forward
 //           logits = y_top W_lin^T + b
-// backward: dlogits -> dW_lin, db_lin, dy_top; per diagonal (reversed) one gate-gradient launch and one skinny-GEMM
-//           launch (dh_{t-1} += dgh_t W_hh and dx_t = dgx_t W_ih of every cell); then per layer two MFMA GEMMs
-//           (dW_ih, dW_hh) whose K-major operands come from transposes that also sum the bias gradients
+// backward: dlogits -> dW_lin, db_lin, dy_top; per diagonal (reversed) ONE fused launch in the pull form: cell (l, t) computes
+//           dh = [dy_top] + dgh_{l,t+1} W_hh_l + dgx_{l+1,t} W_ih_{l+1} + its dh z carry from what the diagonal above wrote and
+//           does its gate gradients in the epilogue (22 dependent launches, no fp32 dy round trip below the top layer);
+//           dx0 = dgx_0 W_ih_0 is one whole-sequence GEMM after the wavefront; then per layer two MFMA GEMMs (dW_ih, dW_hh)
+//           whose K-major operands come from transposes that also sum the bias gradients.  ST_BPTT_FUSED=0 keeps the
+//           earlier push route (a gate-gradient launch and a skinny-GEMM launch per diagonal)
 //           -> st_rnn_backward
 #include "common.h"
 #include "rnn_kernels.h"
+#include <stdlib.h>
 #include <string.h>
 #include <vector>
 
@@ -272,7 +276,42 @@ extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, co
     if (ni && st_transpose_batch(wx[1], wy[1], nullptr, ni, dt, GH, H, H, GH, nullptr, nullptr, stream)) return 1;
   }
   // reversed wavefront: the cells of a diagonal need only cells of the diagonal above
-  for (int d = T + L - 2; d >= 0; --d) {
+  const char* env = getenv("ST_BPTT_FUSED");       // read per call: ST_BPTT_FUSED=0 keeps the two-launch push route (A/B runs, tests)
+  const bool fused = !(env && env[0] == '0');
+  // pull form, one launch per diagonal: cell (l, t) takes dgh_{l,t+1} W_hh_l and dgx_{l+1,t} W_ih_{l+1} from what the diagonal
+  // above wrote, adds dy (top layer) and its own dh z carry, and does its gate gradients in the epilogue
+  for (int d = T + L - 2; fused && d >= 0; --d) {
+    RnnBwdFused fc[ST_MAX_LAYERS];
+    int nf = 0;
+    for (int l = d < T ? 0 : d - (T - 1); l <= d && l < L; ++l) {
+      const int t = d - l;
+      const int bt = s->batch_sizes_host[t];
+      char* yl = ws + q.y + (size_t)l * n * H * es;
+      char* gl = ws + q.gates + (size_t)l * n * 4 * H * es;
+      char* cl = ws + q.cst + (size_t)l * n * H * es;
+      RnnBwdFused& f = fc[nf++];
+      memset(&f, 0, sizeof(f));
+      RnnBwdCell& c = f.e;
+      c.dy = l == L - 1 ? dy + (size_t)off[t] * H : nullptr; c.dhc = dhcl(l); c.dcc = dccl(l);
+      c.cache = gl + (size_t)off[t] * 4 * H * es;
+      c.hprev = t > 0 ? yl + (size_t)off[t - 1] * H * es : nullptr;
+      c.cnew = cl + (size_t)off[t] * H * es;
+      c.cprev = t > 0 ? cl + (size_t)off[t - 1] * H * es : nullptr;
+      c.dgx = dgxl(l) + (size_t)off[t] * GH * es; c.dgh = dghl(l) + (size_t)off[t] * GH * es; c.Bt = bt;
+      RnnGemmArgs& a = f.g;
+      a.M = bt; a.N = H;
+      if (t + 1 < T) {                             // rows [B_{t+1}, B_t) end here: no recurrent term
+        a.A = dghl(l) + (size_t)off[t + 1] * GH * es; a.W = wThh(l); a.M2 = s->batch_sizes_host[t + 1]; a.K = GH; a.lda = GH; a.ldw = GH;
+      }
+      if (l + 1 < L) {
+        a.A2 = dgxl(l + 1) + (size_t)off[t] * GH * es; a.W2 = wTih(l + 1); a.K2 = GH; a.lda2 = GH; a.ldw2 = GH;
+      }
+    }
+    if (rnn_bwd_fused_launch_batch(fc, nf, p->cell, dt, st)) return 1;
+  }
+  // dx0 = dgx_0 W_ih_0 feeds only the embedding / feature gradients: one whole-sequence GEMM off the recurrence
+  if (fused && need_dx0 && gemm_nt(dgxl(0), GH, wTih(0), GH, dx0, p->in0, n, p->in0, GH, dt, ST_F32, nullptr, 0, stream)) return 1;
+  for (int d = T + L - 2; !fused && d >= 0; --d) {
     RnnBwdCell gc[ST_MAX_LAYERS];
     RnnGemmArgs mc[2 * ST_MAX_LAYERS];
     int ng = 0, nm = 0;

@@ -6,6 +6,7 @@ struct RnnGemmArgs {
   // acc[g][m][n] = sum_k A[m][k] W[g*gstride + n][k]  (+ second operand pair A2/W2 when HAS_X)
   const void* A; const void* W; int M, N, K, lda, ldw, gstride;
   const void* A2; const void* W2; int K2, lda2, ldw2;
+  int M2;                              // fused BPTT cell only: rows of the (A, W) pair (B_{t+1} <= M); the (A2, W2) pair has M
   // EPI 0
   float* out_f32; int ldo; int accumulate;
   // gate epilogues
@@ -39,6 +40,12 @@ struct RnnBwdCell {                    // BPTT gate gradients of one (layer, tim
   void* dgx; void* dgh; int Bt;
 };
 struct RnnBwdBatch { RnnBwdCell c[kRnnBatch]; };
+// BPTT cell (l, t) in the pull form: dh = [dy] + dgh_{l,t+1} W_hh_l (g.A, g.W: g.M2 rows) + dgx_{l+1,t} W_ih_{l+1} (g.A2, g.W2: g.M
+// rows) + dhc, then the gate gradients of e for the block's own rows and units.  Either pair may be absent (NULL A / A2); e.dy is
+// NULL below the top layer.  A diagonal holds at most one cell per layer.
+struct RnnBwdFused { RnnGemmArgs g; RnnBwdCell e; };
+struct RnnBwdFusedBatch { RnnBwdFused c[ST_MAX_LAYERS]; };
+static_assert(sizeof(RnnBwdFusedBatch) <= 4000, "kernel-argument segment is 4 KiB");
 
 // One GRU unit (torch.nn.GRU, gate order r, z, n; reference rnn.py:32 / rnn.py:49):  x* = W_i* x + b_i*, h* = W_h* h + b_h*,
 //   r = s(xr + hr), z = s(xz + hz), n = tanh(xn + r hn), h' = (1 - z) n + z h.
@@ -78,6 +85,7 @@ int vocab_ce_dlogits(const void* y, const void* w, const float* bias, const long
 int rnn_gemm_launch(const RnnGemmArgs& a, int dtype, int epi, int has_x, hipStream_t st);
 int rnn_gemm_launch_batch(const RnnGemmArgs* cells, int ncells, int dtype, int epi, int has_x, hipStream_t st);
 int rnn_bwd_gates_launch_batch(const RnnBwdCell* cells, int ncells, int H, int cell_kind, int dtype, hipStream_t st);
+int rnn_bwd_fused_launch_batch(const RnnBwdFused* cells, int ncells, int cell_kind, int dtype, hipStream_t st);
 int pack_inputs_launch(const void* feat, const void* emb, const long* cap, int Tcap, const int* rows_b, const int* rows_t,
                        void* x0, long* target, int ntok, int E, int V, int mode, int dtype, hipStream_t st);
 int embedding_bwd_launch(const float* dx0, const long* cap, int Tcap, const int* rows_b, const int* rows_t,

@@ -59,14 +59,24 @@ __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x))
 // ---------------------------------------------------------------------------------------
 // skinny GEMM  acc[g][m][n] = sum_k A[m][k] * W[g*gstride + n][k]   (+ optional second pair)
 // ---------------------------------------------------------------------------------------
-template <typename T, int NG, bool HAS_X, int MT>
+// BWD (fused BPTT cell): the NG "gates" are NG 16-unit tiles of ONE gate group (gstride = 16), so the unit bound is checked per
+// tile, and the (A, W) pair has its own row count M2 <= M.  Its K = 3H / 4H rows are long and every byte comes through the
+// CU's texture path, so the fragments are REQUESTED coalesced -- lane i asks for row i / 4, 16-byte piece i % 4 of the 16-row x
+// 64-byte fragment: four lanes = 64 contiguous bytes, 16 requests per wave-instruction instead of 64 -- and put into MFMA
+// order (lane q4 * 16 + r16 <- lane r16 * 4 + q4) in registers.
+__device__ __forceinline__ u32x4 lane_gather(const u32x4& v, int src4) {
+  return u32x4{(unsigned)__builtin_amdgcn_ds_bpermute(src4, (int)v[0]), (unsigned)__builtin_amdgcn_ds_bpermute(src4, (int)v[1]),
+               (unsigned)__builtin_amdgcn_ds_bpermute(src4, (int)v[2]), (unsigned)__builtin_amdgcn_ds_bpermute(src4, (int)v[3])};
+}
+template <typename T, int NG, bool HAS_X, int MT, bool BWD = false>
 __device__ __forceinline__ void skinny_mma(const RnnGemmArgs& a, int mbase, int n0, int r16, int q4, int kslice,
                                            f32x4 (&accH)[MT][NG], f32x4 (&accX)[MT][NG]) {
   constexpr int EPC = Mfma<T>::EPC;
   // K steps requested per round trip; the fused two-operand, two-row-tile form halves it to stay within 2 waves per SIMD
   // (260 -> ~170 VGPRs: two blocks per CU overlap instead of one)
-  constexpr int UNR = (HAS_X && MT == 2) ? 2 : 4;
-  const int n = n0 + r16;
+  constexpr int UNR = BWD ? (MT + NG <= 4 ? 4 : 2) : (HAS_X && MT == 2) ? 2 : 4;
+  const int lr = BWD ? q4 * 4 + (r16 >> 2) : r16, lq = BWD ? (r16 & 3) : q4;   // the row and the 16-byte piece this lane requests
+  const int n = n0 + lr;
   const bool nok = n < a.N;
   // The kernel is latency bound (every fragment comes from L2), so bytes in flight per wave are the lever: K is split
   // over the block's 4 waves and a group of UNR K-steps of BOTH operand pairs (h W_hh and, in the fused form, x W_ih)
@@ -78,11 +88,12 @@ __device__ __forceinline__ void skinny_mma(const RnnGemmArgs& a, int mbase, int 
   const long gsH = (long)a.gstride * a.ldw;
   const T* WX = reinterpret_cast<const T*>(a.W2) + (long)n * a.ldw2;
   const long gsX = (long)a.gstride * a.ldw2;
-  const T* AH[MT]; const T* AX[MT]; bool mok[MT];
+  const T* AH[MT]; const T* AX[MT]; bool mok[MT], mokH[MT];
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
-    const int m = mbase + t * 16 + r16;
+    const int m = mbase + t * 16 + lr;
     mok[t] = m < a.M;
+    mokH[t] = BWD ? m < a.M2 : mok[t];
     AH[t] = reinterpret_cast<const T*>(a.A) + (long)m * a.lda;
     if (!HAS_X && a.x_keys && a.A) {                   // split decode step: the A operand is the embedding row of the previous token
       int tok = 0;
@@ -113,20 +124,20 @@ __device__ __forceinline__ void skinny_mma(const RnnGemmArgs& a, int mbase, int 
     u32x4 fa[MT][UNR], fw[UNR][NG], xa[MT][UNR], xw[UNR][NG];
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
-      const int sH = begH + gi * UNR + u, kH = (sH * 4 + q4) * EPC;
+      const int sH = begH + gi * UNR + u, kH = (sH * 4 + lq) * EPC;
       const bool okH = sH < endH && kH < a.K;
 #pragma unroll
       for (int t = 0; t < MT; ++t) {
         fa[t][u] = u32x4{0u, 0u, 0u, 0u};
-        if (mok[t] && okH) fa[t][u] = *reinterpret_cast<const u32x4*>(AH[t] + kH);
+        if (mokH[t] && okH) fa[t][u] = *reinterpret_cast<const u32x4*>(AH[t] + kH);
       }
 #pragma unroll
       for (int g = 0; g < NG; ++g) {
         fw[u][g] = u32x4{0u, 0u, 0u, 0u};
-        if (nok && okH) fw[u][g] = *reinterpret_cast<const u32x4*>(WH + g * gsH + kH);
+        if ((BWD ? n + g * 16 < a.N : nok) && okH) fw[u][g] = *reinterpret_cast<const u32x4*>(WH + g * gsH + kH);
       }
       if (HAS_X) {
-        const int sX = begX + gi * UNR + u, kX = (sX * 4 + q4) * EPC;
+        const int sX = begX + gi * UNR + u, kX = (sX * 4 + lq) * EPC;
         const bool okX = sX < endX && kX < a.K2;
 #pragma unroll
         for (int t = 0; t < MT; ++t) {
@@ -136,8 +147,18 @@ __device__ __forceinline__ void skinny_mma(const RnnGemmArgs& a, int mbase, int 
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
           xw[u][g] = u32x4{0u, 0u, 0u, 0u};
-          if (nok && okX) xw[u][g] = *reinterpret_cast<const u32x4*>(WX + g * gsX + kX);
+          if ((BWD ? n + g * 16 < a.N : nok) && okX) xw[u][g] = *reinterpret_cast<const u32x4*>(WX + g * gsX + kX);
         }
+      }
+    }
+    if (BWD) {
+      const int src4 = (r16 * 4 + q4) * 4;
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+#pragma unroll
+        for (int t = 0; t < MT; ++t) { fa[t][u] = lane_gather(fa[t][u], src4); xa[t][u] = lane_gather(xa[t][u], src4); }
+#pragma unroll
+        for (int g = 0; g < NG; ++g) { fw[u][g] = lane_gather(fw[u][g], src4); xw[u][g] = lane_gather(xw[u][g], src4); }
       }
     }
 #pragma unroll
@@ -442,6 +463,125 @@ __global__ __launch_bounds__(256) void lstm_bwd_gates_kernel(RnnBwdBatch batch, 
   store4<float>(dhc + (long)b * H + j, zero);   // dh_{t-1} is entirely the GEMM term, accumulated next
 }
 
+
+// ---------------------------------------------------------------------------------------
+// fused BPTT cell (pull form): dh = [dy] + dgh_{l,t+1} W_hh_l + dgx_{l+1,t} W_ih_{l+1} + dhc, then the gate gradients of
+// gru_bwd_gates_kernel / lstm_bwd_gates_kernel (same expressions, same order) for the block's own rows and units.
+// Block = MT x 16 rows x NT x 16 units; K is split over the 4 waves as in rnn_gemm_kernel, the partial sums meet in LDS
+// and wave w runs the epilogue of the 16 x 16 tiles w, w + 4, ...  Every element of dhc / dcc is read and written by the
+// same lane of the same block, and the products read only what the previous diagonal's launch wrote.
+// ---------------------------------------------------------------------------------------
+template <typename T> struct Raw4;                       // 4 consecutive elements as loaded: unpacked only in the epilogue
+template <> struct Raw4<float> { typedef f32x4 type; };
+template <> struct Raw4<bf16_t> { typedef u32x2 type; };
+template <typename T> __device__ __forceinline__ void unpack4(const typename Raw4<T>::type& t, float* v);
+template <> __device__ __forceinline__ void unpack4<float>(const f32x4& t, float* v) { v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3]; }
+template <> __device__ __forceinline__ void unpack4<bf16_t>(const u32x2& t, float* v) {
+  v[0] = __uint_as_float(t[0] << 16); v[1] = __uint_as_float(t[0] & 0xffff0000u);
+  v[2] = __uint_as_float(t[1] << 16); v[3] = __uint_as_float(t[1] & 0xffff0000u);
+}
+
+template <typename T, bool LSTM, int MT, int NT>
+__global__ __launch_bounds__(256) void rnn_bwd_cell_kernel(RnnBwdFusedBatch batch) {
+  typedef typename Raw4<T>::type raw_t;
+  const RnnGemmArgs& a = batch.c[blockIdx.z].g;
+  const RnnBwdCell& c = batch.c[blockIdx.z].e;
+  constexpr int TILES = MT * NT, TPW = (TILES + 3) / 4;
+  __shared__ f32x4 red[4][TILES][64];
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r16 = lane & 15, q4 = lane >> 4;
+  const int n0 = blockIdx.x * 16 * NT, mbase = blockIdx.y * 16 * MT;
+  if (mbase >= a.M || n0 >= a.N) return;            // the grid is sized for the launch's largest cell
+  const int H = a.N;
+  f32x4 accH[MT][NT], accX[MT][NT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t)
+#pragma unroll
+    for (int g = 0; g < NT; ++g) { accH[t][g] = f32x4{0.f, 0.f, 0.f, 0.f}; accX[t][g] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  // the epilogue operands are requested BEFORE the fragment loads so that they arrive under the same round trip:
+  // tile i = wid + 4 j is row tile i / NT, unit tile i % NT; the lane owns row pm and units pn .. pn + 3 of it
+  bool ok[TPW]; int pm[TPW], pn[TPW];
+  f32x4 rdy[TPW], rdhc[TPW], rdcc[TPW]; raw_t rc[TPW][4], rp[TPW], rcn[TPW];
+  const T* cache = reinterpret_cast<const T*>(c.cache);
+#pragma unroll
+  for (int j = 0; j < TPW; ++j) {
+    const int i = wid + 4 * j;
+    pm[j] = mbase + (i / NT) * 16 + r16; pn[j] = n0 + (i % NT) * 16 + 4 * q4;
+    ok[j] = i < TILES && pm[j] < a.M && pn[j] < H;
+    rdy[j] = rdhc[j] = rdcc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    rp[j] = rcn[j] = raw_t{};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) rc[j][q] = raw_t{};
+    if (!ok[j]) continue;
+    const long o = (long)pm[j] * H + pn[j];
+    if (c.dy) rdy[j] = *reinterpret_cast<const f32x4*>(c.dy + o);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) rc[j][q] = *reinterpret_cast<const raw_t*>(cache + (long)pm[j] * 4 * H + q * H + pn[j]);
+    if (LSTM) {
+      rdcc[j] = *reinterpret_cast<const f32x4*>(c.dcc + o);
+      rcn[j] = *reinterpret_cast<const raw_t*>(reinterpret_cast<const T*>(c.cnew) + o);
+      if (c.cprev) rp[j] = *reinterpret_cast<const raw_t*>(reinterpret_cast<const T*>(c.cprev) + o);
+    } else {
+      rdhc[j] = *reinterpret_cast<const f32x4*>(c.dhc + o);
+      if (c.hprev) rp[j] = *reinterpret_cast<const raw_t*>(reinterpret_cast<const T*>(c.hprev) + o);
+    }
+  }
+  skinny_mma<T, NT, true, MT, true>(a, mbase, n0, r16, q4, wid, accH, accX);
+#pragma unroll
+  for (int t = 0; t < MT; ++t)
+#pragma unroll
+    for (int g = 0; g < NT; ++g) red[wid][t * NT + g][lane] = accH[t][g] + accX[t][g];
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < TPW; ++j) {
+    if (!ok[j]) continue;
+    const int i = wid + 4 * j;
+    const f32x4 s = ((red[0][i][lane] + red[1][i][lane]) + red[2][i][lane]) + red[3][i][lane];
+    const long o = (long)pm[j] * H + pn[j];
+    if (!LSTM) {
+      float r[4], z[4], n[4], hn[4], hp[4];
+      unpack4<T>(rc[j][0], r); unpack4<T>(rc[j][1], z); unpack4<T>(rc[j][2], n); unpack4<T>(rc[j][3], hn); unpack4<T>(rp[j], hp);
+      float drp[4], dzp[4], dnp[4], dnr[4], dhz[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float dh = (rdy[j][e] + rdhc[j][e]) + s[e];
+        const float dn = dh * (1.f - z[e]);
+        const float dz = dh * (hp[e] - n[e]);
+        dnp[e] = dn * (1.f - n[e] * n[e]);
+        drp[e] = dnp[e] * hn[e] * r[e] * (1.f - r[e]);
+        dzp[e] = dz * z[e] * (1.f - z[e]);
+        dnr[e] = dnp[e] * r[e];
+        dhz[e] = dh * z[e];
+      }
+      T* ox = reinterpret_cast<T*>(c.dgx) + (long)pm[j] * 3 * H + pn[j];
+      T* oh = reinterpret_cast<T*>(c.dgh) + (long)pm[j] * 3 * H + pn[j];
+      store4<T>(ox, drp); store4<T>(ox + H, dzp); store4<T>(ox + 2 * H, dnp);
+      store4<T>(oh, drp); store4<T>(oh + H, dzp); store4<T>(oh + 2 * H, dnr);
+      store4<float>(c.dhc + o, dhz);
+    } else {
+      float ig[4], fg[4], gg[4], og[4], cn[4], cp[4];
+      unpack4<T>(rc[j][0], ig); unpack4<T>(rc[j][1], fg); unpack4<T>(rc[j][2], gg); unpack4<T>(rc[j][3], og);
+      unpack4<T>(rcn[j], cn); unpack4<T>(rp[j], cp);
+      float di[4], df[4], dgg[4], dob[4], dcp[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float dh = rdy[j][e] + s[e];            // dh_t of the LSTM is entirely the two products (+ dy at the top)
+        const float tc = tanhf(cn[e]);
+        const float dc = rdcc[j][e] + dh * og[e] * (1.f - tc * tc);
+        dob[e] = dh * tc * og[e] * (1.f - og[e]);
+        di[e] = dc * gg[e] * ig[e] * (1.f - ig[e]);
+        df[e] = dc * cp[e] * fg[e] * (1.f - fg[e]);
+        dgg[e] = dc * ig[e] * (1.f - gg[e] * gg[e]);
+        dcp[e] = dc * fg[e];
+      }
+      T* og_ = reinterpret_cast<T*>(c.dgx) + (long)pm[j] * 4 * H + pn[j];
+      store4<T>(og_, di); store4<T>(og_ + H, df); store4<T>(og_ + 2 * H, dgg); store4<T>(og_ + 3 * H, dob);
+      store4<float>(c.dcc + o, dcp);
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------
 // cross entropy over rows (mean reduction):  loss += -log softmax(x)[t] / nrows
 // dlogits = (softmax - onehot) * gscale   written in TD (may alias the logits when TD == TL)
@@ -573,6 +713,44 @@ int rnn_bwd_gates_launch_batch(const RnnBwdCell* cells, int ncells, int H, int c
   } else {
     if (dtype == ST_BF16) hipLaunchKernelGGL(lstm_bwd_gates_kernel<bf16_t>, grid, dim3(256), 0, st, b, H);
     else hipLaunchKernelGGL(lstm_bwd_gates_kernel<float>, grid, dim3(256), 0, st, b, H);
+  }
+  ST_LAUNCH_CHECK();
+  return 0;
+}
+
+// One launch for the cells of a reversed diagonal.  Block shape: 32 rows x 32 units, the fastest of 32 x 16, 32 x 32, 32 x 64,
+// 64 x 32 and 64 x 64 at the bench shape (profiles/r05_bptt_tile_shapes.txt): larger blocks halve the operand bytes but leave
+// CUs without a block and lengthen the K chain of every wave.
+int rnn_bwd_fused_launch_batch(const RnnBwdFused* cells, int ncells, int cell_kind, int dtype, hipStream_t st) {
+  ST_CHECK(ncells >= 0 && ncells <= ST_MAX_LAYERS, "rnn_bwd_fused: %d cells in one launch (max %d)", ncells, ST_MAX_LAYERS);
+  RnnBwdFusedBatch b;
+  memset(&b, 0, sizeof(b));
+  const int epc = dtype == ST_BF16 ? 8 : 4;
+  int nc = 0, maxM = 0, maxN = 0;
+  for (int i = 0; i < ncells; ++i) {
+    const RnnGemmArgs& a = cells[i].g;
+    if (a.M <= 0) continue;
+    ST_CHECK(a.N % 8 == 0, "rnn_bwd_fused: H=%d must be a multiple of 8", a.N);
+    ST_CHECK(!a.A || (a.K % epc == 0 && a.lda % epc == 0 && a.ldw % epc == 0 && a.M2 >= 0 && a.M2 <= a.M),
+             "rnn_bwd_fused: bad recurrent operand pair");
+    ST_CHECK(!a.A2 || (a.K2 % epc == 0 && a.lda2 % epc == 0 && a.ldw2 % epc == 0), "rnn_bwd_fused: bad input operand pair");
+    b.c[nc] = cells[i];
+    b.c[nc].g.gstride = 16;                         // the "gates" of skinny_mma are the block's 16-unit tiles
+    if (!a.A) b.c[nc].g.M2 = 0;
+    ++nc;
+    if (a.M > maxM) maxM = a.M;
+    if (a.N > maxN) maxN = a.N;
+  }
+  if (nc == 0) return 0;
+  const bool lstm = cell_kind == ST_CELL_LSTM;
+  constexpr int MT = 2, NT = 2;
+  const dim3 grid((maxN + 16 * NT - 1) / (16 * NT), (maxM + 16 * MT - 1) / (16 * MT), nc), block(256);
+  if (dtype == ST_BF16) {
+    if (lstm) hipLaunchKernelGGL((rnn_bwd_cell_kernel<bf16_t, true, MT, NT>), grid, block, 0, st, b);
+    else hipLaunchKernelGGL((rnn_bwd_cell_kernel<bf16_t, false, MT, NT>), grid, block, 0, st, b);
+  } else {
+    if (lstm) hipLaunchKernelGGL((rnn_bwd_cell_kernel<float, true, MT, NT>), grid, block, 0, st, b);
+    else hipLaunchKernelGGL((rnn_bwd_cell_kernel<float, false, MT, NT>), grid, block, 0, st, b);
   }
   ST_LAUNCH_CHECK();
   return 0;

@@ -17,4 +17,4 @@ image, caption, lens = synthetic_batch(B, V, seed=1, device=dev)
 for k in range(int(sys.argv[1]) if len(sys.argv) > 1 else 8):
     trainer.step(image, caption, lens)
 trainer.flush(); torch.cuda.synchronize()
-print("T =", int(lens.max()), "sum(lens) =", int(lens.sum()))
+print("T =", int(max(lens)), "sum(lens) =", int(sum(lens)))
