@@ -13,22 +13,30 @@
 //   d alpha_p = dz . feat_p + reg_p ; de = alpha (d alpha - <alpha, d alpha>) ; du_p = de_p w_f lrelu'(u_p)
 //   d att2 = sum_p du_p ; d att1[b,p] += du_p ; dw_f += sum_p de_p lrelu(u_p) ; db_f += sum_p de_p
 //   dh_{t-1}[L-1] += d att2 W_d      (attention at step t is keyed on the PREVIOUS top-layer state)
-#include "common.h"
-#include "rnn_kernels.h"
+#include "decoder_host.h"
 #include "attn_kernels.h"
-#include <string.h>
-#include <vector>
 
 namespace {
 
-inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-inline int up8(int v) { return (v + 7) & ~7; }
 inline size_t mx(size_t a, size_t b) { return a > b ? a : b; }
 
-struct Plan {
+// what prepare() fills, at the head of every attention workspace: feat_pf [B*P][F], its mean over P, h0, c0, att1 [B*P][A]
+struct AttnPrep {
+  size_t feat, mean, h0, c0, att1;
+  void take_prep(Arena& ar, const st_attn_params* p, size_t B) {
+    const size_t es = st_dtype_size(p->rnn.dtype), H = p->rnn.H;
+    feat = ar.take(B * p->P * p->F * es);
+    mean = ar.take(B * p->F * es);
+    h0 = ar.take(B * H * es);
+    c0 = ar.take(B * H * es);
+    att1 = ar.take(B * p->P * p->A * es);
+  }
+};
+
+struct Plan : AttnPrep {
   int G, GH, Np, Vp, BP;
   size_t es;
-  size_t feat, mean, h0, c0, att1, xp, y, gates, cst, z, att2, tokT;
+  size_t xp, y, gates, cst, z, att2, tokT;
   size_t dytop, dxa, dxb, dhc, dcc, dgx, dgh, dez, datt2p, datt2, dz, datt1, dalpha, hprev, tA, tB, wThh, wTih, wTmisc, cast, total;
 };
 
@@ -38,80 +46,57 @@ Plan make_plan(const st_attn_params* p, const st_packed_seq* s) {
   q.G = r.cell == ST_CELL_GRU ? 3 : 4;
   q.GH = q.G * r.H;
   q.BP = s->B * p->P;
-  q.Np = up8(s->ntok > q.BP ? s->ntok : q.BP);
-  q.Vp = up8(r.V);
+  q.Np = st_up8(s->ntok > q.BP ? s->ntok : q.BP);
+  q.Vp = st_up8(r.V);
   q.es = st_dtype_size(r.dtype);
   const size_t n = s->ntok, L = r.L, H = r.H, E = r.E, B = s->B, es = q.es;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t x = o; o += al(bytes); return x; };
-  q.feat = take((size_t)q.BP * p->F * es);
-  q.mean = take(B * p->F * es);
-  q.h0 = take(B * H * es);
-  q.c0 = take(B * H * es);
-  q.att1 = take((size_t)q.BP * p->A * es);
-  q.xp = take(n * 2 * E * es);
-  q.y = take(L * n * H * es);
-  q.gates = take(L * n * 4 * H * es);
-  q.cst = take(r.cell == ST_CELL_LSTM ? L * n * H * es : 0);
-  q.z = take(n * p->F * es);
-  q.att2 = take(n * p->A * sizeof(float));
+  Arena ar;
+  q.take_prep(ar, p, B);
+  q.xp = ar.take(n * 2 * E * es);
+  q.y = ar.take(L * n * H * es);
+  q.gates = ar.take(L * n * 4 * H * es);
+  q.cst = ar.take(r.cell == ST_CELL_LSTM ? L * n * H * es : 0);
+  q.z = ar.take(n * p->F * es);
+  q.att2 = ar.take(n * p->A * sizeof(float));
   q.tokT = 0;
   // backward
-  q.dytop = take(n * H * sizeof(float));
+  q.dytop = ar.take(n * H * sizeof(float));
   const size_t wmax = mx(H, 2 * E);
-  q.dxa = take(B * wmax * sizeof(float));
-  q.dxb = take(B * wmax * sizeof(float));
-  q.dhc = take(L * B * H * sizeof(float));
-  q.dcc = take(L * B * H * sizeof(float));
-  q.dgx = take(L * n * q.GH * es);
-  q.dgh = take(r.cell == ST_CELL_GRU ? L * n * q.GH * es : 0);
-  q.dez = take(n * E * es);
-  q.datt2p = take(n * p->A * es);
-  q.datt2 = take(B * p->A * sizeof(float));
-  q.dz = take(B * p->F * sizeof(float));
-  q.datt1 = take((size_t)q.BP * p->A * sizeof(float));
-  q.dalpha = take((size_t)q.BP * sizeof(float));
-  q.hprev = take(n * H * es);
+  q.dxa = ar.take(B * wmax * sizeof(float));
+  q.dxb = ar.take(B * wmax * sizeof(float));
+  q.dhc = ar.take(L * B * H * sizeof(float));
+  q.dcc = ar.take(L * B * H * sizeof(float));
+  q.dgx = ar.take(L * n * q.GH * es);
+  q.dgh = ar.take(r.cell == ST_CELL_GRU ? L * n * q.GH * es : 0);
+  q.dez = ar.take(n * E * es);
+  q.datt2p = ar.take(n * p->A * es);
+  q.datt2 = ar.take(B * p->A * sizeof(float));
+  q.dz = ar.take(B * p->F * sizeof(float));
+  q.datt1 = ar.take((size_t)q.BP * p->A * sizeof(float));
+  q.dalpha = ar.take((size_t)q.BP * sizeof(float));
+  q.hprev = ar.take(n * H * es);
   const size_t ra = mx(mx((size_t)r.V, (size_t)q.GH), mx((size_t)p->A, mx(E, H)));
   const size_t rb = mx(mx((size_t)p->F, 2 * E), H);
-  q.tA = take(ra * q.Np * es);
-  q.tB = take(rb * q.Np * es);
-  q.wThh = take(L * H * q.GH * es);
-  q.wTih = take(L * wmax * q.GH * es);
-  q.wTmisc = take(mx(mx((size_t)H * q.Vp, (size_t)p->F * E), (size_t)H * p->A) * es);
-  q.cast = take(mx(mx((size_t)q.BP * p->A, B * H), (size_t)H * p->A) * es);
-  q.total = o;
+  q.tA = ar.take(ra * q.Np * es);
+  q.tB = ar.take(rb * q.Np * es);
+  q.wThh = ar.take(L * H * q.GH * es);
+  q.wTih = ar.take(L * wmax * q.GH * es);
+  q.wTmisc = ar.take(mx(mx((size_t)H * q.Vp, (size_t)p->F * E), (size_t)H * p->A) * es);
+  q.cast = ar.take(mx(mx((size_t)q.BP * p->A, B * H), (size_t)H * p->A) * es);
+  q.total = ar.o;
   return q;
 }
 
-int gemm_nt(const void* a, int lda, const void* w, int ldw, void* y, int ldy, int M, int N, int K, int dtype, int out_dtype,
-            const float* bias, int accumulate, void* stream) {
-  if (M <= 0 || N <= 0) return 0;
-  st_conv_desc d;
-  memset(&d, 0, sizeof(d));
-  d.x = a; d.w = w; d.y = y; d.bias = bias; d.dtype = dtype; d.out_dtype = out_dtype;
-  d.B = M; d.Hin = 1; d.Win = 1; d.Cin = K; d.Ho = 1; d.Wo = 1; d.N = N; d.KH = 1; d.KW = 1; d.stride = 1; d.pad = 0;
-  d.ldx = lda; d.ldw = ldw; d.ldy = ldy; d.accumulate = accumulate;
-  return st_conv(&d, stream);
-}
-
-// out_f32[M][ldo] (+)= A[M][K] W[N][K]^T (+bias): skinny MFMA product for the <= batch rows of one timestep
-int skinny(const void* A, int lda, const void* W, int ldw, float* out, int ldo, int M, int N, int K, const float* bias, int accumulate,
-           int dtype, hipStream_t st) {
+// A[M][K] W[N][K]^T (+bias) through the skinny MFMA kernel, for the <= batch rows of one timestep: out is fp32 [M][ldo], (+)=; or,
+// with to_storage, storage-dtype rows (the per-step context embedding, [B_t x F] x [F x E] with K = 2048: 4 output tiles of a
+// 128x128 MFMA tile walk K for ~37 us, 128 blocks of 16x16 with K split over 4 waves for ~10)
+int skinny(const void* A, int lda, const void* W, int ldw, void* out, int ldo, int M, int N, int K, const float* bias, int accumulate,
+           int dtype, hipStream_t st, bool to_storage = false) {
   RnnGemmArgs a;
   memset(&a, 0, sizeof(a));
-  a.A = A; a.W = W; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.gstride = 0;
-  a.out_f32 = out; a.ldo = ldo; a.accumulate = accumulate; a.bias_h = bias;
-  return rnn_gemm_launch(a, dtype, 0, 0, st);
-}
-
-// y[M][ldy] (storage dtype) = A W^T + bias through the skinny kernel: for the per-step context embedding ([B_t x F] x [F x E],
-// K = 2048): 4 output tiles of a 128x128 MFMA tile walk K for ~37 us, 128 blocks of 16x16 with K split over 4 waves for ~10
-int skinny_t(const void* A, int lda, const void* W, int ldw, void* y, int ldy, int M, int N, int K, const float* bias, int dtype, hipStream_t st) {
-  RnnGemmArgs a;
-  memset(&a, 0, sizeof(a));
-  a.A = A; a.W = W; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.gstride = 0;
-  a.hout = y; a.ldho = ldy; a.bias_h = bias;
+  a.A = A; a.W = W; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.gstride = 0; a.bias_h = bias;
+  if (to_storage) { a.hout = out; a.ldho = ldo; }
+  else { a.out_f32 = reinterpret_cast<float*>(out); a.ldo = ldo; a.accumulate = accumulate; }
   return rnn_gemm_launch(a, dtype, 0, 0, st);
 }
 
@@ -128,29 +113,23 @@ int check_common(const st_attn_params* p, const st_packed_seq* s, const char* wh
            "%s: null attention weights", who);
   ST_CHECK(r.cell == ST_CELL_GRU || (p->w_init_c && p->b_init_c), "%s: LSTM needs init_c", who);
   if (s) {
-    ST_CHECK(s->B > 0 && s->T > 0 && s->ntok > 0 && s->batch_sizes_host && s->rows_b && s->rows_t && s->prev_row, "%s: bad packed-sequence descriptor", who);
-    int sum = 0, prev = s->B;
-    for (int t = 0; t < s->T; ++t) {
-      const int b = s->batch_sizes_host[t];
-      ST_CHECK(b > 0 && b <= prev, "%s: batch_sizes must be positive and non-increasing", who);
-      prev = b; sum += b;
-    }
-    ST_CHECK(sum == s->ntok && s->batch_sizes_host[0] == s->B, "%s: batch_sizes do not add up", who);
+    if (st_check_packed_seq(s, who, false)) return 1;        // the captions come as caption_T, not through s->caption
     ST_CHECK(s->Tcap >= s->T, "%s: caption width %d smaller than the longest length %d", who, s->Tcap, s->T);
   }
   return 0;
 }
 
-// feat_pf, mean, h0 (c0), att1 -- shared by training and greedy
-int prepare(const st_attn_params* p, const float* cnn_feature, int B, char* feat, char* mean, char* h0, char* c0, char* att1, void* stream) {
+// feat_pf, mean, h0 (c0), att1 -- shared by training and the searches
+int prepare(const st_attn_params* p, const float* cnn_feature, int B, char* ws, const AttnPrep& q, void* stream) {
+  char *feat = ws + q.feat, *mean = ws + q.mean, *h0 = ws + q.h0, *c0 = ws + q.c0, *att1 = ws + q.att1;
   const st_rnn_params& r = p->rnn;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int dt = r.dtype, BP = B * p->P;
   if (ncp_to_pf_launch(cnn_feature, feat, B, p->F, p->P, dt, st)) return 1;
   if (st_global_avgpool(feat, mean, dt, dt, B, p->P, p->F, stream)) return 1;                        // cnn_feature.mean(dim=2), rnn_attn.py:62
-  if (gemm_nt(mean, p->F, p->w_init_h, p->F, h0, r.H, B, r.H, p->F, dt, dt, p->b_init_h, 0, stream)) return 1;
-  if (r.cell == ST_CELL_LSTM && gemm_nt(mean, p->F, p->w_init_c, p->F, c0, r.H, B, r.H, p->F, dt, dt, p->b_init_c, 0, stream)) return 1;
-  return gemm_nt(feat, p->F, p->w_enc, p->F, att1, p->A, BP, p->A, p->F, dt, dt, p->b_enc, 0, stream);   // hoisted encoder_att
+  if (st_gemm_nt(mean, p->F, p->w_init_h, p->F, h0, r.H, B, r.H, p->F, dt, dt, p->b_init_h, stream)) return 1;
+  if (r.cell == ST_CELL_LSTM && st_gemm_nt(mean, p->F, p->w_init_c, p->F, c0, r.H, B, r.H, p->F, dt, dt, p->b_init_c, stream)) return 1;
+  return st_gemm_nt(feat, p->F, p->w_enc, p->F, att1, p->A, BP, p->A, p->F, dt, dt, p->b_enc, stream);   // hoisted encoder_att
 }
 
 }  // namespace
@@ -173,10 +152,9 @@ extern "C" int st_attn_forward(const st_attn_params* p, const st_packed_seq* s, 
   const int dt = r.dtype, H = r.H, E = r.E, n = s->ntok, B = s->B, L = r.L, P = p->P, A = p->A, F = p->F;
   const size_t es = q.es;
   (void)save_for_backward;   // every saved tensor is also the forward's own scratch
-  std::vector<int> off(s->T + 1, 0);
-  for (int t = 0; t < s->T; ++t) off[t + 1] = off[t] + s->batch_sizes_host[t];
+  const std::vector<int> off = st_packed_offsets(s);
 
-  if (prepare(p, cnn_feature, B, ws + q.feat, ws + q.mean, ws + q.h0, ws + q.c0, ws + q.att1, stream)) return 1;
+  if (prepare(p, cnn_feature, B, ws, q, stream)) return 1;
 
   for (int t = 0; t < s->T; ++t) {
     const int bt = s->batch_sizes_host[t];
@@ -187,31 +165,21 @@ extern "C" int st_attn_forward(const st_attn_params* p, const st_packed_seq* s, 
     if (skinny(htop_prev, H, p->w_dec, H, att2, A, bt, A, H, p->b_dec, 0, dt, st)) return 1;
     if (attn_fwd_launch(ws + q.att1, att2, p->w_full, p->b_full, ws + q.feat, alphas + (size_t)t * P, (long)s->Tcap * P, zt, bt, P, A, F, dt, st)) return 1;
     if (st_embedding_rows(r.emb, caption_T + (size_t)t * B, xt, bt, E, r.V, 2 * E, dt, stream)) return 1;
-    if (skinny_t(zt, F, p->w_embed, F, xt + (size_t)E * es, 2 * E, bt, E, F, p->b_embed, dt, st)) return 1;
+    if (skinny(zt, F, p->w_embed, F, xt + (size_t)E * es, 2 * E, bt, E, F, p->b_embed, 0, dt, st, true)) return 1;
     for (int l = 0; l < L; ++l) {
       char* yl = ws + q.y + (size_t)l * n * H * es;
-      RnnGemmArgs a;
-      memset(&a, 0, sizeof(a));
-      a.M = bt; a.N = H; a.gstride = H;
-      a.A2 = l == 0 ? xt : ws + q.y + ((size_t)(l - 1) * n + off[t]) * H * es;
-      a.W2 = r.w_ih[l]; a.K2 = l == 0 ? 2 * E : H; a.lda2 = a.K2; a.ldw2 = a.K2;
-      a.A = t > 0 ? yl + (size_t)off[t - 1] * H * es : ws + q.h0;      // every layer starts from the same h0 (rnn_attn.py:62)
-      a.W = r.w_hh[l]; a.K = H; a.lda = H; a.ldw = H;
-      a.hprev = a.A; a.ldhp = H;
-      a.bias_h = r.b_hh[l]; a.bias_x = r.b_ih[l];
-      a.hout = yl + (size_t)off[t] * H * es; a.ldho = H;
-      a.cache = ws + q.gates + ((size_t)l * n + off[t]) * 4 * H * es; a.ldcache = 4 * H;
-      if (r.cell == ST_CELL_LSTM) {
-        char* cl = ws + q.cst + (size_t)l * n * H * es;
-        a.cprev = t > 0 ? cl + (size_t)off[t - 1] * H * es : ws + q.c0;
-        a.cout = cl + (size_t)off[t] * H * es;
-      }
-      if (rnn_gemm_launch(a, dt, r.cell == ST_CELL_GRU ? 1 : 2, 1, st)) return 1;
+      char* cl = ws + q.cst + (size_t)l * n * H * es;
+      // every layer starts from the same h0 (c0) (rnn_attn.py:62)
+      const RnnGemmArgs a = rnn_full_cell(&r, l, l == 0 ? xt : ws + q.y + ((size_t)(l - 1) * n + off[t]) * H * es, l == 0 ? 2 * E : H,
+                                          t > 0 ? yl + (size_t)off[t - 1] * H * es : ws + q.h0, t > 0 ? cl + (size_t)off[t - 1] * H * es : ws + q.c0,
+                                          yl + (size_t)off[t] * H * es, cl + (size_t)off[t] * H * es, bt,
+                                          ws + q.gates + ((size_t)l * n + off[t]) * 4 * H * es);
+      if (rnn_gemm_launch(a, dt, rnn_cell_epi(r.cell), 1, st)) return 1;
     }
   }
   if (logits) {
     ST_CHECK(r.w_lin && r.b_lin, "st_attn_forward: logits requested without the vocabulary projection");
-    if (gemm_nt(ws + q.y + (size_t)(L - 1) * n * H * es, H, r.w_lin, H, logits, ldl, n, r.V, H, dt, logits_dtype, r.b_lin, 0, stream)) return 1;
+    if (st_gemm_nt(ws + q.y + (size_t)(L - 1) * n * H * es, H, r.w_lin, H, logits, ldl, n, r.V, H, dt, logits_dtype, r.b_lin, stream)) return 1;
   }
   return 0;
 }
@@ -235,8 +203,7 @@ extern "C" int st_attn_backward(const st_attn_params* p, const st_attn_grads* g,
   const size_t es = q.es;
   ST_CHECK(ldd >= q.Vp && ldd % 8 == 0, "st_attn_backward: dlogits leading dimension must be a multiple of 8 and >= %d", q.Vp);
   ST_CHECK(Np >= n && Np >= BP, "st_attn_backward: plan Np=%d n=%d BP=%d P=%d B=%d T=%d", Np, n, BP, P, B, s->T);
-  std::vector<int> off(s->T + 1, 0);
-  for (int t = 0; t < s->T; ++t) off[t + 1] = off[t] + s->batch_sizes_host[t];
+  const std::vector<int> off = st_packed_offsets(s);
   const char* ytop = ws + q.y + (size_t)(L - 1) * n * H * es;
   float* dytop = reinterpret_cast<float*>(ws + q.dytop);
   float* dhc = reinterpret_cast<float*>(ws + q.dhc);
@@ -249,9 +216,9 @@ extern "C" int st_attn_backward(const st_attn_params* p, const st_attn_grads* g,
   // vocabulary projection
   if (st_transpose_colsum(dlogits, ws + q.tA, g->rnn.b_lin, dt, n, r.V, ldd, Np, stream)) return 1;
   if (st_transpose(ytop, ws + q.tB, dt, n, H, H, Np, stream)) return 1;
-  if (gemm_nt(ws + q.tA, Np, ws + q.tB, Np, g->rnn.w_lin, H, r.V, H, Np, dt, ST_F32, nullptr, 1, stream)) return 1;
+  if (st_gemm_nt(ws + q.tA, Np, ws + q.tB, Np, g->rnn.w_lin, H, r.V, H, Np, dt, ST_F32, nullptr, stream, 1)) return 1;
   if (st_transpose(r.w_lin, ws + q.wTmisc, dt, r.V, H, H, q.Vp, stream)) return 1;
-  if (gemm_nt(dlogits, ldd, ws + q.wTmisc, q.Vp, dytop, H, n, H, q.Vp, dt, ST_F32, nullptr, 0, stream)) return 1;
+  if (st_gemm_nt(dlogits, ldd, ws + q.wTmisc, q.Vp, dytop, H, n, H, q.Vp, dt, ST_F32, nullptr, stream)) return 1;
 
   // transposed operands used inside the time loop
   for (int l = 0; l < L; ++l) {
@@ -319,26 +286,26 @@ extern "C" int st_attn_backward(const st_attn_params* p, const st_attn_grads* g,
     if (r.cell != ST_CELL_GRU && colsum_launch(dgh, g->rnn.b_hh[l], n, GH, GH, dt, st)) return 1;   // LSTM: dgh == dgx
     if (st_transpose_colsum(dgx, ws + q.tA, g->rnn.b_ih[l], dt, n, GH, GH, Np, stream)) return 1;
     if (st_transpose(xl, ws + q.tB, dt, n, in, in, Np, stream)) return 1;
-    if (gemm_nt(ws + q.tA, Np, ws + q.tB, Np, g->rnn.w_ih[l], in, GH, in, Np, dt, ST_F32, nullptr, 1, stream)) return 1;
+    if (st_gemm_nt(ws + q.tA, Np, ws + q.tB, Np, g->rnn.w_ih[l], in, GH, in, Np, dt, ST_F32, nullptr, stream, 1)) return 1;
     if (gather_hprev_launch(ws + q.y + (size_t)l * n * H * es, s->rows_t, s->prev_row, ws + q.hprev, n, H, dt, st, ws + q.h0, s->rows_b)) return 1;
     if (r.cell == ST_CELL_GRU && st_transpose_colsum(dgh, ws + q.tA, g->rnn.b_hh[l], dt, n, GH, GH, Np, stream)) return 1;
     if (st_transpose(ws + q.hprev, ws + q.tB, dt, n, H, H, Np, stream)) return 1;
-    if (gemm_nt(ws + q.tA, Np, ws + q.tB, Np, g->rnn.w_hh[l], H, GH, H, Np, dt, ST_F32, nullptr, 1, stream)) return 1;
+    if (st_gemm_nt(ws + q.tA, Np, ws + q.tB, Np, g->rnn.w_hh[l], H, GH, H, Np, dt, ST_F32, nullptr, stream, 1)) return 1;
   }
   // decoder_att: d att2 rows x previous top state (hprev of the last layer is still in q.hprev / tB)
   if (st_transpose_colsum(ws + q.datt2p, ws + q.tA, g->b_dec, dt, n, A, A, Np, stream)) return 1;
-  if (gemm_nt(ws + q.tA, Np, ws + q.tB, Np, g->w_dec, H, A, H, Np, dt, ST_F32, nullptr, 1, stream)) return 1;
+  if (st_gemm_nt(ws + q.tA, Np, ws + q.tB, Np, g->w_dec, H, A, H, Np, dt, ST_F32, nullptr, stream, 1)) return 1;
   // embed: d ez rows x z rows
   if (st_transpose_colsum(ws + q.dez, ws + q.tA, g->b_embed, dt, n, E, E, Np, stream)) return 1;
   if (st_transpose(ws + q.z, ws + q.tB, dt, n, F, F, Np, stream)) return 1;
-  if (gemm_nt(ws + q.tA, Np, ws + q.tB, Np, g->w_embed, F, E, F, Np, dt, ST_F32, nullptr, 1, stream)) return 1;
+  if (st_gemm_nt(ws + q.tA, Np, ws + q.tB, Np, g->w_embed, F, E, F, Np, dt, ST_F32, nullptr, stream, 1)) return 1;
   // encoder_att: time-summed d att1 (B*P rows) x feat
   if (st_cast(datt1, ws + q.cast, ST_F32, dt, (long)BP * A, stream)) return 1;
   if (st_transpose_colsum(ws + q.cast, ws + q.tA, g->b_enc, dt, BP, A, A, Np, stream)) return 1;
   if (st_transpose(ws + q.feat, ws + q.tB, dt, BP, F, F, Np, stream)) return 1;
-  if (gemm_nt(ws + q.tA, Np, ws + q.tB, Np, g->w_enc, F, A, F, Np, dt, ST_F32, nullptr, 1, stream)) return 1;
+  if (st_gemm_nt(ws + q.tA, Np, ws + q.tB, Np, g->w_enc, F, A, F, Np, dt, ST_F32, nullptr, stream, 1)) return 1;
   // init_h (init_c): every layer started from the same h0, so its gradient is the sum over layers
-  const int Bp = up8(B);
+  const int Bp = st_up8(B);
   for (int pass = 0; pass < (r.cell == ST_CELL_LSTM ? 2 : 1); ++pass) {
     float* acc = pass == 0 ? dhc : dcc;
     for (int l = 1; l < L; ++l) if (add_rows_launch(acc, acc + (size_t)l * B * H, (long)B * H, st)) return 1;
@@ -347,28 +314,25 @@ extern "C" int st_attn_backward(const st_attn_params* p, const st_attn_grads* g,
     float* gb = pass == 0 ? g->b_init_h : g->b_init_c;
     if (st_transpose_colsum(ws + q.cast, ws + q.tA, gb, dt, B, H, H, Bp, stream)) return 1;
     if (st_transpose(ws + q.mean, ws + q.tB, dt, B, F, F, Bp, stream)) return 1;
-    if (gemm_nt(ws + q.tA, Bp, ws + q.tB, Bp, gw, F, H, F, Bp, dt, ST_F32, nullptr, 1, stream)) return 1;
+    if (st_gemm_nt(ws + q.tA, Bp, ws + q.tB, Bp, gw, F, H, F, Bp, dt, ST_F32, nullptr, stream, 1)) return 1;
   }
   return 0;
 }
 
 // ---- greedy decoding (rnn_attn.py:77-94,120-145) -----------------------------------------------------------
 namespace {
-struct GPlan { size_t feat, mean, h0, c0, att1, h[2], c[2], x, z, att2, logits, ids, total; };
+struct GPlan : AttnPrep { size_t h[2], c[2], x, z, att2, logits, ids, total; };
 GPlan make_gplan(const st_attn_params* p, int B) {
   const st_rnn_params& r = p->rnn;
   const size_t es = st_dtype_size(r.dtype);
-  GPlan q; size_t o = 0;
-  auto take = [&](size_t bytes) { size_t x = o; o += al(bytes); return x; };
-  q.feat = take((size_t)B * p->P * p->F * es); q.mean = take((size_t)B * p->F * es);
-  q.h0 = take((size_t)B * r.H * es); q.c0 = take((size_t)B * r.H * es);
-  q.att1 = take((size_t)B * p->P * p->A * es);
-  for (int i = 0; i < 2; ++i) { q.h[i] = take((size_t)r.L * B * r.H * es); q.c[i] = take((size_t)r.L * B * r.H * es); }
-  q.x = take((size_t)B * 2 * r.E * es); q.z = take((size_t)B * p->F * es);
-  q.att2 = take((size_t)B * p->A * sizeof(float));
-  q.logits = take((size_t)B * up8(r.V) * sizeof(float));
-  q.ids = take((size_t)B * sizeof(long) + (size_t)B * p->P * sizeof(float));
-  q.total = o;
+  GPlan q; Arena ar;
+  q.take_prep(ar, p, B);
+  for (int i = 0; i < 2; ++i) { q.h[i] = ar.take((size_t)r.L * B * r.H * es); q.c[i] = ar.take((size_t)r.L * B * r.H * es); }
+  q.x = ar.take((size_t)B * 2 * r.E * es); q.z = ar.take((size_t)B * p->F * es);
+  q.att2 = ar.take((size_t)B * p->A * sizeof(float));
+  q.logits = ar.take((size_t)B * st_up8(r.V) * sizeof(float));
+  q.ids = ar.take((size_t)B * sizeof(long) + (size_t)B * p->P * sizeof(float));
+  q.total = ar.o;
   return q;
 }
 
@@ -416,14 +380,14 @@ int attn_greedy_run(const st_attn_params* p, const float* cnn_feature, int B, in
   const st_rnn_params& r = p->rnn;
   ST_CHECK(r.w_lin && r.b_lin, "%s: null vocabulary projection", who);
   const GPlan q = make_gplan(p, B);
-  ST_CHECK(workspace_bytes >= q.total + (sp ? al((size_t)B) : 0), "%s: workspace too small", who);
+  ST_CHECK(workspace_bytes >= q.total + (sp ? st_al256((size_t)B) : 0), "%s: workspace too small", who);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   char* ws = reinterpret_cast<char*>(workspace);
   uint8_t* fin = reinterpret_cast<uint8_t*>(ws + q.total);
   if (sp && hipMemsetAsync(fin, 0, (size_t)B, st) != hipSuccess) { st_set_error("%s: memset failed", who); return 1; }
-  const int dt = r.dtype, H = r.H, E = r.E, L = r.L, P = p->P, A = p->A, F = p->F, Vp = up8(r.V);
+  const int dt = r.dtype, H = r.H, E = r.E, L = r.L, P = p->P, A = p->A, F = p->F, Vp = st_up8(r.V);
   const size_t es = st_dtype_size(dt);
-  if (prepare(p, cnn_feature, B, ws + q.feat, ws + q.mean, ws + q.h0, ws + q.c0, ws + q.att1, stream)) return 1;
+  if (prepare(p, cnn_feature, B, ws, q, stream)) return 1;
   if (replicate_rows_launch(ws + q.h0, ws + q.h[0], (long)B * H, L, dt, st)) return 1;            // h0 repeated over layers (rnn_attn.py:62)
   if (r.cell == ST_CELL_LSTM && replicate_rows_launch(ws + q.c0, ws + q.c[0], (long)B * H, L, dt, st)) return 1;
   long* cur = reinterpret_cast<long*>(ws + q.ids);
@@ -441,7 +405,7 @@ int attn_greedy_run(const st_attn_params* p, const float* cnn_feature, int B, in
     if (skinny(htop, H, p->w_dec, H, att2, A, B, A, H, p->b_dec, 0, dt, st)) return 1;
     if (attn_fwd_launch(ws + q.att1, att2, p->w_full, p->b_full, ws + q.feat, alpha_t, alpha_stride, ws + q.z, B, P, A, F, dt, st)) return 1;
     if (st_embedding_rows(r.emb, cur, ws + q.x, B, E, r.V, 2 * E, dt, stream)) return 1;
-    if (skinny_t(ws + q.z, F, p->w_embed, F, ws + q.x + (size_t)E * es, 2 * E, B, E, F, p->b_embed, dt, st)) return 1;
+    if (skinny(ws + q.z, F, p->w_embed, F, ws + q.x + (size_t)E * es, 2 * E, B, E, F, p->b_embed, 0, dt, st, true)) return 1;
     if (st_rnn_step(&r, ws + q.x, B, ws + q.h[c], ws + q.c[c], ws + q.h[nx], ws + q.c[nx], logits, Vp, stream)) return 1;
     if (sp) {
       if (st_sample_rows(logits, Vp, B, r.V, sp->u + t, steps, sp->inv_temperature, sp->top_k, sp->end_id, fin, ids_out, sp->logp_out, steps, t,
@@ -469,7 +433,7 @@ extern "C" int st_attn_greedy_alphas(const st_attn_params* p, const float* cnn_f
 
 extern "C" size_t st_attn_sample_workspace_bytes(const st_attn_params* p, int n) {
   if (!p || n <= 0) return 0;
-  return make_gplan(p, n).total + al((size_t)n);
+  return make_gplan(p, n).total + st_al256((size_t)n);
 }
 
 extern "C" int st_attn_sample(const st_attn_params* p, const float* cnn_feature, int n, int steps, long start_id, const float* u,
@@ -484,27 +448,24 @@ extern "C" int st_attn_sample(const st_attn_params* p, const float* cnn_feature,
 // Fixed (image, slot) rows b*W + w as in beam.py: every iteration is one set of launches over the B*W rows and the fringe
 // selection runs on the device (st_beam_select), so the caller reads the records back once and replays the Node bookkeeping.
 namespace {
-struct BPlan { int n, k; size_t feat, mean, h0, c0, att1, h[2], c[2], x, z, att2, logits, tp, ti, gidx, slot, done, alpha, total; };
+struct BPlan : AttnPrep { int n, k; size_t h[2], c[2], x, z, att2, logits, tp, ti, gidx, slot, done, alpha, total; };
 BPlan make_bplan(const st_attn_params* p, int B, int W) {
   const st_rnn_params& r = p->rnn;
   const size_t es = st_dtype_size(r.dtype);
-  BPlan q; size_t o = 0;
-  auto take = [&](size_t bytes) { size_t x = o; o += al(bytes); return x; };
+  BPlan q; Arena ar;
   const size_t n = (size_t)B * W;
   q.n = (int)n;
   q.k = W < r.V ? W : r.V;
-  q.feat = take((size_t)B * p->P * p->F * es); q.mean = take((size_t)B * p->F * es);
-  q.h0 = take((size_t)B * r.H * es); q.c0 = take((size_t)B * r.H * es);
-  q.att1 = take((size_t)B * p->P * p->A * es);
+  q.take_prep(ar, p, B);
   const size_t cs = r.cell == ST_CELL_LSTM ? (size_t)r.L * n * r.H * es : 0;
-  for (int i = 0; i < 2; ++i) { q.h[i] = take((size_t)r.L * n * r.H * es); q.c[i] = take(cs); }
-  q.x = take(n * 2 * r.E * es); q.z = take(n * p->F * es);
-  q.att2 = take(n * p->A * sizeof(float));
-  q.logits = take(n * up8(r.V) * sizeof(float));
-  q.tp = take(n * q.k * sizeof(float)); q.ti = take(n * q.k * sizeof(long));
-  q.gidx = take(n * sizeof(int)); q.slot = take(n * sizeof(int)); q.done = take((size_t)B);
-  q.alpha = take(n * p->P * sizeof(float));
-  q.total = o;
+  for (int i = 0; i < 2; ++i) { q.h[i] = ar.take((size_t)r.L * n * r.H * es); q.c[i] = ar.take(cs); }
+  q.x = ar.take(n * 2 * r.E * es); q.z = ar.take(n * p->F * es);
+  q.att2 = ar.take(n * p->A * sizeof(float));
+  q.logits = ar.take(n * st_up8(r.V) * sizeof(float));
+  q.tp = ar.take(n * q.k * sizeof(float)); q.ti = ar.take(n * q.k * sizeof(long));
+  q.gidx = ar.take(n * sizeof(int)); q.slot = ar.take(n * sizeof(int)); q.done = ar.take((size_t)B);
+  q.alpha = ar.take(n * p->P * sizeof(float));
+  q.total = ar.o;
   return q;
 }
 
@@ -541,7 +502,7 @@ extern "C" int st_attn_beam_search(const st_attn_params* p, const float* cnn_fea
   ST_CHECK(workspace_bytes >= q.total, "st_attn_beam_search: workspace too small (%zu < %zu)", workspace_bytes, q.total);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   char* ws = reinterpret_cast<char*>(workspace);
-  const int dt = r.dtype, H = r.H, E = r.E, L = r.L, P = p->P, A = p->A, F = p->F, Vp = up8(r.V), n = q.n, k = q.k;
+  const int dt = r.dtype, H = r.H, E = r.E, L = r.L, P = p->P, A = p->A, F = p->F, Vp = st_up8(r.V), n = q.n, k = q.k;
   const size_t es = st_dtype_size(dt);
   const bool lstm = r.cell == ST_CELL_LSTM;
   int* slot = reinterpret_cast<int*>(ws + q.slot);
@@ -552,7 +513,7 @@ extern "C" int st_attn_beam_search(const st_attn_params* p, const float* cnn_fea
   float* tp = reinterpret_cast<float*>(ws + q.tp);
   long* ti = reinterpret_cast<long*>(ws + q.ti);
 
-  if (prepare(p, cnn_feature, B, ws + q.feat, ws + q.mean, ws + q.h0, ws + q.c0, ws + q.att1, stream)) return 1;
+  if (prepare(p, cnn_feature, B, ws, q, stream)) return 1;
   hipLaunchKernelGGL(beam_seed_kernel, dim3((n + 255) / 256), dim3(256), 0, st, B, W, start_id, slot, rec_tok, rec_cost, rec_par, done);
   ST_LAUNCH_CHECK();
   // h0 (c0) repeated over the layers (rnn_attn.py:62), then scattered to the slots of its image
@@ -570,7 +531,7 @@ extern "C" int st_attn_beam_search(const st_attn_params* p, const float* cnn_fea
     if (st_embedding_rows(r.emb, tok, ws + q.x, n, E, r.V, 2 * E, dt, stream)) return 1;
     if (skinny(htop, H, p->w_dec, H, att2, A, n, A, H, p->b_dec, 0, dt, st)) return 1;
     if (attn_beam_fwd_launch(ws + q.att1, att2, p->w_full, p->b_full, ws + q.feat, alpha_t, ws + q.z, B, W, P, A, F, dt, st)) return 1;
-    if (skinny_t(ws + q.z, F, p->w_embed, F, ws + q.x + (size_t)E * es, 2 * E, n, E, F, p->b_embed, dt, st)) return 1;
+    if (skinny(ws + q.z, F, p->w_embed, F, ws + q.x + (size_t)E * es, 2 * E, n, E, F, p->b_embed, 0, dt, st, true)) return 1;
     if (st_rnn_step(&r, ws + q.x, n, ws + q.h[0], lstm ? ws + q.c[0] : nullptr, ws + q.h[1], lstm ? ws + q.c[1] : nullptr, logits, Vp, stream)) return 1;
     if (st_softmax_topk(logits, Vp, n, r.V, k, tp, ti, 0, stream)) return 1;
     if (st_beam_select(tok, cost, done, tp, ti, B, W, k, end_id, rec_tok + (size_t)(t + 1) * n, rec_cost + (size_t)(t + 1) * n,

@@ -4,15 +4,10 @@
 // Per step: one fused launch per layer (x W_ih^T and h W_hh^T accumulate in the same MFMA
 // kernel, gates in its epilogue), one MFMA GEMM for the vocabulary projection and one
 // arg-max + embedding-gather kernel.  Everything is issued from this one C call.
-#include "common.h"
+#include "decoder_host.h"
 #include <stdlib.h>
-#include "rnn_kernels.h"
-#include <string.h>
 
 namespace {
-
-inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-inline int up8(int v) { return (v + 7) & ~7; }
 
 // first-maximum rule of torch.max(1): among equal maxima the lowest index wins
 template <typename T>
@@ -551,16 +546,6 @@ __global__ __launch_bounds__(256) void keys_to_ids_embed_kernel(unsigned long lo
     *reinterpret_cast<u32x4*>(x + (long)row * E + c) = *reinterpret_cast<const u32x4*>(emb + (long)bi * E + c);
 }
 
-int gemm_nt(const void* a, int lda, const void* w, int ldw, void* y, int ldy, int M, int N, int K, int dtype, int out_dtype,
-            const float* bias, void* stream) {
-  st_conv_desc d;
-  memset(&d, 0, sizeof(d));
-  d.x = a; d.w = w; d.y = y; d.bias = bias; d.dtype = dtype; d.out_dtype = out_dtype;
-  d.B = M; d.Hin = 1; d.Win = 1; d.Cin = K; d.Ho = 1; d.Wo = 1; d.N = N; d.KH = 1; d.KW = 1; d.stride = 1; d.pad = 0;
-  d.ldx = lda; d.ldw = ldw; d.ldy = ldy;
-  return st_conv(&d, stream);
-}
-
 }  // namespace
 
 // Greedy decoding keeps one arg-max key row per step (no re-arming between steps) for up to kFusedSteps steps, so that
@@ -568,14 +553,28 @@ int gemm_nt(const void* a, int lda, const void* w, int ldw, void* y, int ldy, in
 constexpr int kFusedSteps = 64;
 constexpr int kPipeSteps = 32;     // the pipelined decoder's workspace is sized for up to this many steps (rnn.py:39: 25)
 
+namespace {
+struct GreedyPlan { size_t h[2], c[2], x, logits, keys, gh, pipe, pipe_bytes, total; };
+GreedyPlan make_greedy_plan(const st_rnn_params* p, int B) {
+  const size_t es = st_dtype_size(p->dtype);
+  const size_t hb = (size_t)p->L * B * p->H * es;
+  GreedyPlan q; Arena ar;
+  for (int i = 0; i < 2; ++i) q.h[i] = ar.take(hb);
+  for (int i = 0; i < 2; ++i) q.c[i] = ar.take(hb);
+  q.x = ar.take((size_t)B * p->E * es);
+  q.logits = ar.take((size_t)B * st_up8(p->V) * sizeof(float));   // not read by the loop (logits_out is the caller's buffer): part of the layout
+  q.keys = ar.take((size_t)B * kFusedSteps * sizeof(unsigned long long));
+  q.gh = ar.take((size_t)p->L * B * (p->cell == ST_CELL_GRU ? 3 : 4) * p->H * sizeof(float));   // recurrent halves of the split step
+  q.pipe_bytes = rnn_greedy_pipe_bytes(p, B, kPipeSteps);   // the pipelined decoder's buffers (0 when the configuration is not eligible)
+  q.pipe = ar.take(q.pipe_bytes);
+  q.total = ar.o;
+  return q;
+}
+}  // namespace
+
 extern "C" size_t st_rnn_greedy_workspace_bytes(const st_rnn_params* p, int B) {
   if (!p || B <= 0) return 0;
-  const size_t es = st_dtype_size(p->dtype);
-  const size_t hb = al((size_t)p->L * B * p->H * es);
-  const int ng = p->cell == ST_CELL_GRU ? 3 : 4;
-  return 4 * hb + al((size_t)B * p->E * es) + al((size_t)B * up8(p->V) * sizeof(float)) + al((size_t)B * kFusedSteps * sizeof(unsigned long long)) +
-         al((size_t)p->L * B * ng * p->H * sizeof(float)) +      // recurrent halves of the split step (gh)
-         rnn_greedy_pipe_bytes(p, B, kPipeSteps);                // the pipelined decoder's buffers (0 when the configuration is not eligible)
+  return make_greedy_plan(p, B).total;
 }
 
 static thread_local int g_greedy_route = 1;             // st_rnn_greedy_last_route (include/showtell_hip.h)
@@ -589,24 +588,22 @@ extern "C" int st_rnn_greedy(const st_rnn_params* p, const void* feat, int B, in
   ST_CHECK(p->L >= 1 && p->L <= ST_MAX_LAYERS && p->in0 == p->E, "st_rnn_greedy: bad decoder configuration");
   ST_CHECK(p->H % 8 == 0 && p->E % 8 == 0, "st_rnn_greedy: E=%d and H=%d must be multiples of 8", p->E, p->H);
   ST_CHECK(p->emb && p->w_lin && p->b_lin, "st_rnn_greedy: null weights");
-  ST_CHECK(workspace_bytes >= st_rnn_greedy_workspace_bytes(p, B), "st_rnn_greedy: workspace too small");
+  ST_CHECK(B > 0, "st_rnn_greedy: need B > 0");
+  const GreedyPlan q = make_greedy_plan(p, B);
+  ST_CHECK(workspace_bytes >= q.total, "st_rnn_greedy: workspace too small");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int dt = p->dtype, H = p->H, E = p->E, V = p->V, Vp = up8(V), L = p->L;
+  const int dt = p->dtype, H = p->H, E = p->E, V = p->V, Vp = st_up8(V), L = p->L;
   const size_t es = st_dtype_size(dt);
-  const size_t hb = al((size_t)L * B * H * es);
   char* ws = reinterpret_cast<char*>(workspace);
-  char* hbuf[2] = {ws, ws + hb};
-  char* cbuf[2] = {ws + 2 * hb, ws + 3 * hb};
-  char* xbuf = ws + 4 * hb;
-  float* logits = reinterpret_cast<float*>(xbuf + al((size_t)B * E * es));
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(logits) + al((size_t)B * Vp * sizeof(float)));
+  char* hbuf[2] = {ws + q.h[0], ws + q.h[1]};
+  char* cbuf[2] = {ws + q.c[0], ws + q.c[1]};
+  char* xbuf = ws + q.x;
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws + q.keys);
   // bf16 GRU at the BASELINE decoder shape: the whole loop as ONE persistent kernel, a layer per XCD (csrc/decode_pipe.hip); it gives
   // up (rc 2: the grid could not be made co-resident) or does not run (rc 3: not eligible) -- then the launch chain below runs
   if (!logits_out && steps <= kPipeSteps) {
-    const size_t pipe_bytes = rnn_greedy_pipe_bytes(p, B, kPipeSteps);
-    if (pipe_bytes) {
-      const size_t base = st_rnn_greedy_workspace_bytes(p, B) - pipe_bytes;
-      const int rc = rnn_greedy_pipe(p, feat, B, steps, ws + base, pipe_bytes, ids_out, st);
+    if (q.pipe_bytes) {
+      const int rc = rnn_greedy_pipe(p, feat, B, steps, ws + q.pipe, q.pipe_bytes, ids_out, st);
       g_greedy_route = rc == 0 ? 0 : rc == 2 ? 2 : 1;
       if (rc == 0) return 0;
       if (rc == 1) return 1;
@@ -622,7 +619,7 @@ extern "C" int st_rnn_greedy(const st_rnn_params* p, const void* feat, int B, in
   // chain multiply only the input half (x, W_ih): half the operand bytes and MFMAs per dependent launch.
   static const bool split_env = [] { const char* e = getenv("ST_DECODE_SPLIT"); return !e || atoi(e) != 0; }();
   const int NGc = p->cell == ST_CELL_GRU ? 3 : 4;
-  float* gh = reinterpret_cast<float*>(reinterpret_cast<char*>(keys) + al((size_t)B * kFusedSteps * sizeof(unsigned long long)));
+  float* gh = reinterpret_cast<float*>(ws + q.gh);
   const size_t gh_l = (size_t)B * NGc * H;
   const bool split = fused && split_env && L >= 2;
   auto gh_cell = [&](int l, const void* hsrc) {          // gh[l] = W_hh[l] hsrc + b_hh[l]  (hsrc == NULL: the bias alone, h = 0)
@@ -636,7 +633,7 @@ extern "C" int st_rnn_greedy(const st_rnn_params* p, const void* feat, int B, in
   if (split) {                                           // step 0: h(-1) = 0 -> gh = b_hh for every layer, one launch
     RnnGemmArgs cells[ST_MAX_LAYERS];
     for (int l = 0; l < L; ++l) cells[l] = gh_cell(l, nullptr);
-    if (rnn_gemm_launch_batch(cells, L, dt, p->cell == ST_CELL_GRU ? 1 : 2, 0, st)) return 1;
+    if (rnn_gemm_launch_batch(cells, L, dt, rnn_cell_epi(p->cell), 0, st)) return 1;
   }
   for (int t = 0; t < steps; ++t) {
     const int nxt = cur ^ 1;
@@ -664,29 +661,18 @@ extern "C" int st_rnn_greedy(const st_rnn_params* p, const void* feat, int B, in
         // riding along: the recurrent half some LATER cell needs, from a state that is already complete
         if (l == 0) { if (t > 0) c2[n++] = gh_cell(L - 1, hbuf[cur] + (size_t)(L - 1) * B * H * es); }   // h_{L-1}(t-1) -> cell L-1 of THIS step
         else if (t + 1 < steps) c2[n++] = gh_cell(l - 1, hbuf[nxt] + (size_t)(l - 2 + 1) * B * H * es);   // h_{l-1}(t) -> cell l-1 of step t+1
-        if (rnn_gemm_launch_batch(c2, n, dt, p->cell == ST_CELL_GRU ? 1 : 2, 0, st)) return 1;
+        if (rnn_gemm_launch_batch(c2, n, dt, rnn_cell_epi(p->cell), 0, st)) return 1;
       }
     } else
     for (int l = 0; l < L; ++l) {
-      RnnGemmArgs a;
-      memset(&a, 0, sizeof(a));
-      a.M = B; a.N = H; a.gstride = H;
-      a.A2 = l == 0 ? x : hbuf[nxt] + (size_t)(l - 1) * B * H * es;
-      a.W2 = p->w_ih[l]; a.K2 = l == 0 ? E : H; a.lda2 = a.K2; a.ldw2 = a.K2;
+      const size_t lo = (size_t)l * B * H * es;         // layer l's rows of a state buffer
+      RnnGemmArgs a = rnn_full_cell(p, l, l == 0 ? x : hbuf[nxt] + lo - (size_t)B * H * es, l == 0 ? E : H, t > 0 ? hbuf[cur] + lo : nullptr,
+                                    t > 0 ? cbuf[cur] + lo : nullptr, hbuf[nxt] + lo, cbuf[nxt] + lo, B);
       if (l == 0 && fused && t > 0) {                   // x = embedding rows of step t-1's tokens, gathered by the cell
         a.A2 = p->emb; a.x_keys = keys + (size_t)(t - 1) * B; a.x_V = V;
         a.ids_out = ids_out; a.ids_stride = steps; a.ids_t = t - 1;
       }
-      a.A = t > 0 ? hbuf[cur] + (size_t)l * B * H * es : nullptr;
-      a.W = p->w_hh[l]; a.K = H; a.lda = H; a.ldw = H;
-      a.hprev = a.A; a.ldhp = H;
-      a.bias_h = p->b_hh[l]; a.bias_x = p->b_ih[l];
-      a.hout = hbuf[nxt] + (size_t)l * B * H * es; a.ldho = H;
-      if (p->cell == ST_CELL_LSTM) {
-        a.cprev = t > 0 ? cbuf[cur] + (size_t)l * B * H * es : nullptr;
-        a.cout = cbuf[nxt] + (size_t)l * B * H * es;
-      }
-      if (rnn_gemm_launch(a, dt, p->cell == ST_CELL_GRU ? 1 : 2, 1, st)) return 1;
+      if (rnn_gemm_launch(a, dt, rnn_cell_epi(p->cell), 1, st)) return 1;
     }
     if (!logits_out) {
       // fast path: vocabulary projection with a fused running arg-max (the logits are never written)
@@ -734,7 +720,7 @@ extern "C" int st_rnn_greedy(const st_rnn_params* p, const void* feat, int B, in
       continue;
     }
     float* lg = logits_out + (size_t)t * B * Vp;
-    if (gemm_nt(hbuf[nxt] + (size_t)(L - 1) * B * H * es, H, p->w_lin, H, lg, Vp, B, V, H, dt, ST_F32, p->b_lin, stream)) return 1;
+    if (st_gemm_nt(hbuf[nxt] + (size_t)(L - 1) * B * H * es, H, p->w_lin, H, lg, Vp, B, V, H, dt, ST_F32, p->b_lin, stream)) return 1;
     if (dt == ST_BF16)
       hipLaunchKernelGGL(argmax_embed_kernel<bf16_t>, dim3(B), dim3(256), 0, st, lg, Vp, V, ids_out, steps, t, (const bf16_t*)p->emb, (bf16_t*)xbuf, E);
     else
@@ -865,26 +851,17 @@ extern "C" int st_rnn_step(const st_rnn_params* p, const void* x, int n, const v
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int dt = p->dtype, H = p->H;
   const size_t es = st_dtype_size(dt);
+  const char *hi = reinterpret_cast<const char*>(h_in), *ci = reinterpret_cast<const char*>(c_in);
+  char *ho = reinterpret_cast<char*>(h_out), *co = reinterpret_cast<char*>(c_out);
   for (int l = 0; l < p->L; ++l) {
-    RnnGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.M = n; a.N = H; a.gstride = H;
-    a.A2 = l == 0 ? x : reinterpret_cast<const char*>(h_out) + (size_t)(l - 1) * n * H * es;
-    a.W2 = p->w_ih[l]; a.K2 = l == 0 ? p->in0 : H; a.lda2 = a.K2; a.ldw2 = a.K2;
-    a.A = h_in ? reinterpret_cast<const char*>(h_in) + (size_t)l * n * H * es : nullptr;
-    a.W = p->w_hh[l]; a.K = H; a.lda = H; a.ldw = H;
-    a.hprev = a.A; a.ldhp = H;
-    a.bias_h = p->b_hh[l]; a.bias_x = p->b_ih[l];
-    a.hout = reinterpret_cast<char*>(h_out) + (size_t)l * n * H * es; a.ldho = H;
-    if (p->cell == ST_CELL_LSTM) {
-      a.cprev = c_in ? reinterpret_cast<const char*>(c_in) + (size_t)l * n * H * es : nullptr;
-      a.cout = reinterpret_cast<char*>(c_out) + (size_t)l * n * H * es;
-    }
-    if (rnn_gemm_launch(a, dt, p->cell == ST_CELL_GRU ? 1 : 2, 1, st)) return 1;
+    const size_t lo = (size_t)l * n * H * es;           // layer l's rows of a state buffer
+    const RnnGemmArgs a = rnn_full_cell(p, l, l == 0 ? x : ho + lo - (size_t)n * H * es, l == 0 ? p->in0 : H, hi ? hi + lo : nullptr,
+                                        ci ? ci + lo : nullptr, ho + lo, co ? co + lo : nullptr, n);
+    if (rnn_gemm_launch(a, dt, rnn_cell_epi(p->cell), 1, st)) return 1;
   }
   if (logits) {
     ST_CHECK(p->w_lin && p->b_lin && ldl % 4 == 0 && ldl >= p->V, "st_rnn_step: bad logits buffer");
-    if (gemm_nt(reinterpret_cast<const char*>(h_out) + (size_t)(p->L - 1) * n * H * es, H, p->w_lin, H, logits, ldl, n, p->V, H, dt, ST_F32,
+    if (st_gemm_nt(ho + (size_t)(p->L - 1) * n * H * es, H, p->w_lin, H, logits, ldl, n, p->V, H, dt, ST_F32,
                 p->b_lin, stream)) return 1;
   }
   return 0;

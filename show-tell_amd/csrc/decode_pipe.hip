@@ -18,8 +18,7 @@
 // function st_gru_unit, same arg-max keys): token ids are bit-identical to the split-step path of st_rnn_greedy (tests assert it).
 // Every spin is bounded; on a timeout or when the dispatcher did not deal 32 workgroups to every XCD the kernel raises a flag and the
 // host falls back to the launch chain.
-#include "common.h"
-#include "rnn_kernels.h"
+#include "decoder_host.h"
 #include <stdlib.h>
 
 namespace {
@@ -371,8 +370,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
 }
 
-inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 // bytes the pipelined decoder needs behind the launch chain's workspace (0: this configuration stays on the launch chain)
@@ -382,7 +379,7 @@ size_t rnn_greedy_pipe_bytes(const st_rnn_params* p, int B, int steps) {
   const int nvw = (8 - p->L) * 32, ntile = (p->V + 15) / 16, tpw = (ntile + nvw - 1) / nvw;
   if (tpw > 8) return 0;
   const int nch = (B + CR - 1) / CR;
-  return al256((size_t)steps * p->L * nch * CR * PH * 2) + al256((size_t)steps * nch * CR * 8) + al256((size_t)steps * (p->L + 1) * nch * 128) + 256;
+  return st_al256((size_t)steps * p->L * nch * CR * PH * 2) + st_al256((size_t)steps * nch * CR * 8) + st_al256((size_t)steps * (p->L + 1) * nch * 128) + 256;
 }
 
 // 0: ids_out holds the result; 1: error (st_last_error); 2: gave up; 3: not run (not eligible, or ST_DECODE_PIPE=0) -- on 2 and 3
@@ -408,10 +405,10 @@ int rnn_greedy_pipe(const st_rnn_params* p, const void* feat, int B, int steps, 
   const int nvw = (8 - p->L) * 32, ntile = (p->V + 15) / 16;
   a.tpw = (ntile + nvw - 1) / nvw;
   char* w = reinterpret_cast<char*>(ws);
-  a.act = reinterpret_cast<bf16_t*>(w); w += al256((size_t)steps * p->L * a.nch * CR * PH * 2);
+  a.act = reinterpret_cast<bf16_t*>(w); w += st_al256((size_t)steps * p->L * a.nch * CR * PH * 2);
   char* zero0 = w;
-  a.keys = reinterpret_cast<unsigned long long*>(w); w += al256((size_t)steps * a.nch * CR * 8);
-  a.cnt = reinterpret_cast<unsigned*>(w); w += al256((size_t)steps * (p->L + 1) * a.nch * 128);
+  a.keys = reinterpret_cast<unsigned long long*>(w); w += st_al256((size_t)steps * a.nch * CR * 8);
+  a.cnt = reinterpret_cast<unsigned*>(w); w += st_al256((size_t)steps * (p->L + 1) * a.nch * 128);
   a.ticket = reinterpret_cast<unsigned*>(w); w += 256;
   a.ids_out = ids_out;
   if (hipMemsetAsync(zero0, 0, (size_t)(w - zero0), st) != hipSuccess) { st_set_error("rnn_greedy_pipe: memset failed"); return 1; }

@@ -7,9 +7,7 @@
 // The optimizers are single multi-tensor launches over ONE flat fp32 parameter buffer
 // (HBM-bound: SGD 3 reads + 2 writes, Adam 4 reads + 3 writes per element, plus the bf16
 // shadow copy the MFMA kernels read), instead of torch's per-tensor loops.
-#include "common.h"
-#include "rnn_kernels.h"
-#include <string.h>
+#include "decoder_host.h"
 
 namespace {
 
@@ -138,26 +136,12 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
 }
 
-int gemm_nt_(const void* a, int lda, const void* w, int ldw, void* y, int ldy, int M, int N, int K, int dtype, int out_dtype,
-             const float* bias, int accumulate, void* stream, int split_k = 0) {
-  st_conv_desc d;
-  memset(&d, 0, sizeof(d));
-  d.split_k = split_k;
-  d.x = a; d.w = w; d.y = y; d.bias = bias; d.dtype = dtype; d.out_dtype = out_dtype;
-  d.B = M; d.Hin = 1; d.Win = 1; d.Cin = K; d.Ho = 1; d.Wo = 1; d.N = N; d.KH = 1; d.KW = 1; d.stride = 1; d.pad = 0;
-  d.ldx = lda; d.ldw = ldw; d.ldy = ldy; d.accumulate = accumulate;
-  return st_conv(&d, stream);
-}
-
-inline int up8(int v) { return (v + 7) & ~7; }
-inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" size_t st_head_workspace_bytes(int B, int F, int E, int dtype) {
   const size_t es = st_dtype_size(dtype);
-  const int Bp = up8(B);
-  return al((size_t)B * up8(E) * es) + al((size_t)E * Bp * es) + al((size_t)F * Bp * es);
+  const int Bp = st_up8(B);
+  return st_al256((size_t)B * st_up8(E) * es) + st_al256((size_t)E * Bp * es) + st_al256((size_t)F * Bp * es);
 }
 
 extern "C" int st_linear_bn1d_forward(const void* x, const void* w, const float* bias, const float* gamma, const float* beta,
@@ -172,7 +156,7 @@ extern "C" int st_linear_bn1d_forward(const void* x, const void* w, const float*
   // B x E output tiles are few (4 at B = 128, E = 512) and K = F is long: 8 K slices in one grouped launch
   const int bk = dtype == ST_BF16 ? 64 : 32;
   const int split = (F % (8 * bk) == 0 && (long)B * E <= 256 * 128 * 64) ? 8 : 0;
-  if (gemm_nt_(x, F, w, F, z_out, E, B, E, F, dtype, ST_F32, bias, 0, stream, split)) return 1;
+  if (st_gemm_nt(x, F, w, F, z_out, E, B, E, F, dtype, ST_F32, bias, stream, 0, split)) return 1;
   const dim3 grid((E + kBnTX - 1) / kBnTX), block(kBnTX, kBnTY);
   if (dtype == ST_BF16)
     hipLaunchKernelGGL(bn1d_fwd_kernel<bf16_t>, grid, block, 0, st, z_out, gamma, beta, running_mean, running_var, save_mean, save_rstd,
@@ -192,10 +176,10 @@ extern "C" int st_linear_bn1d_backward(const float* dy, const float* z, const vo
   ST_CHECK(workspace_bytes >= st_head_workspace_bytes(B, F, E, dtype), "st_linear_bn1d_backward: workspace too small");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const size_t es = st_dtype_size(dtype);
-  const int Bp = up8(B), Ep = up8(E);
+  const int Bp = st_up8(B), Ep = st_up8(E);
   char* ws = reinterpret_cast<char*>(workspace);
-  char* dz = ws; ws += al((size_t)B * Ep * es);
-  char* dzT = ws; ws += al((size_t)E * Bp * es);
+  char* dz = ws; ws += st_al256((size_t)B * Ep * es);
+  char* dzT = ws; ws += st_al256((size_t)E * Bp * es);
   char* xT = ws;
   const dim3 grid((E + kBnTX - 1) / kBnTX), block(kBnTX, kBnTY);
   if (dtype == ST_BF16)
@@ -206,7 +190,7 @@ extern "C" int st_linear_bn1d_backward(const float* dy, const float* z, const vo
   // db += colsum(dz) ; dW += dz^T x
   if (st_transpose_colsum(dz, dzT, dbias, dtype, B, E, Ep, Bp, stream)) return 1;
   if (st_transpose(x, xT, dtype, B, F, F, Bp, stream)) return 1;
-  return gemm_nt_(dzT, Bp, xT, Bp, dw, F, E, F, Bp, dtype, ST_F32, nullptr, 1, stream);
+  return st_gemm_nt(dzT, Bp, xT, Bp, dw, F, E, F, Bp, dtype, ST_F32, nullptr, stream, 1);
 }
 
 extern "C" int st_sgd_step(float* param, const float* grad, float* momentum_buf, void* bf16_shadow, long n,

@@ -20,16 +20,10 @@
 //           whose K-major operands come from transposes that also sum the bias gradients.  ST_BPTT_FUSED=0 keeps the
 //           earlier push route (a gate-gradient launch and a skinny-GEMM launch per diagonal)
 //           -> st_rnn_backward
-#include "common.h"
-#include "rnn_kernels.h"
+#include "decoder_host.h"
 #include <stdlib.h>
-#include <string.h>
-#include <vector>
 
 namespace {
-
-inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-inline int up8(int v) { return (v + 7) & ~7; }
 
 struct Plan {
   int G, GH, Np, Vp, maxw;
@@ -41,49 +35,36 @@ Plan make_plan(const st_rnn_params* p, const st_packed_seq* s) {
   Plan q;
   q.G = p->cell == ST_CELL_GRU ? 3 : 4;
   q.GH = q.G * p->H;
-  q.Np = up8(s->ntok);
+  q.Np = st_up8(s->ntok);
   q.Vp = st_rnn_vocab_ld(p->V);
   q.es = st_dtype_size(p->dtype);
   q.maxw = p->in0 > p->H ? p->in0 : p->H;
   const size_t n = s->ntok, L = p->L, H = p->H;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t r = o; o += al(bytes); return r; };
-  q.x0 = take(n * p->in0 * q.es);
-  q.y = take(L * n * H * q.es);
-  q.gates = take(L * n * 4 * H * q.es);
-  q.cst = take(p->cell == ST_CELL_LSTM ? L * n * H * q.es : 0);
-  q.dyl = take(L * n * H * sizeof(float));          // d loss / d y_l, one [ntok][H] fp32 matrix per layer
-  q.dx0 = take(n * p->in0 * sizeof(float));         // d loss / d x0
-  q.dgx = take(L * n * q.GH * q.es);                // gate gradients of every layer (operands of the dW GEMMs)
-  q.dgh = take(p->cell == ST_CELL_GRU ? L * n * q.GH * q.es : 0);
-  q.dhc = take(L * (size_t)s->B * H * sizeof(float));
-  q.dcc = take(L * (size_t)s->B * H * sizeof(float));
+  Arena ar;
+  q.x0 = ar.take(n * p->in0 * q.es);
+  q.y = ar.take(L * n * H * q.es);
+  q.gates = ar.take(L * n * 4 * H * q.es);
+  q.cst = ar.take(p->cell == ST_CELL_LSTM ? L * n * H * q.es : 0);
+  q.dyl = ar.take(L * n * H * sizeof(float));          // d loss / d y_l, one [ntok][H] fp32 matrix per layer
+  q.dx0 = ar.take(n * p->in0 * sizeof(float));         // d loss / d x0
+  q.dgx = ar.take(L * n * q.GH * q.es);                // gate gradients of every layer (operands of the dW GEMMs)
+  q.dgh = ar.take(p->cell == ST_CELL_GRU ? L * n * q.GH * q.es : 0);
+  q.dhc = ar.take(L * (size_t)s->B * H * sizeof(float));
+  q.dcc = ar.take(L * (size_t)s->B * H * sizeof(float));
   // transposed operands: tA <= max(V, GH) x Np ; tB <= max(H, in0) x Np ; wT <= max(H x Vp, maxw x GH)
   const size_t ra = (size_t)(p->V > q.GH ? p->V : q.GH);
-  q.tA = take(ra * q.Np * q.es);
-  q.tB = take((size_t)q.maxw * q.Np * q.es);
+  q.tA = ar.take(ra * q.Np * q.es);
+  q.tB = ar.take((size_t)q.maxw * q.Np * q.es);
   const size_t w1 = (size_t)H * q.Vp, w2 = (size_t)q.maxw * q.GH;
-  q.wT = take((w1 > w2 ? w1 : w2) * q.es);
-  q.wThh = take(L * H * q.GH * q.es);               // W_hh^T and W_ih^T of every layer: the backward wavefront needs them all
-  q.wTih = take(L * (size_t)q.maxw * q.GH * q.es);
+  q.wT = ar.take((w1 > w2 ? w1 : w2) * q.es);
+  q.wThh = ar.take(L * H * q.GH * q.es);               // W_hh^T and W_ih^T of every layer: the backward wavefront needs them all
+  q.wTih = ar.take(L * (size_t)q.maxw * q.GH * q.es);
   // K-major operands of the 2L weight-gradient GEMMs (dgx^T, x^T, dgh^T, hprev^T of every layer), alive together so that
   // the GEMMs can go out as one grouped launch
-  q.gA = take(2 * L * (size_t)q.GH * q.Np * q.es);
-  q.gB = take(2 * L * (size_t)q.maxw * q.Np * q.es);
-  q.total = o;
+  q.gA = ar.take(2 * L * (size_t)q.GH * q.Np * q.es);
+  q.gB = ar.take(2 * L * (size_t)q.maxw * q.Np * q.es);
+  q.total = ar.o;
   return q;
-}
-
-int gemm_nt(const void* a, int lda, const void* w, int ldw, void* y, int ldy, int M, int N, int K, int dtype, int out_dtype,
-            const float* bias, int accumulate, void* stream, int split_k = 0) {
-  if (M <= 0 || N <= 0) return 0;
-  st_conv_desc d;
-  memset(&d, 0, sizeof(d));
-  d.split_k = split_k;
-  d.x = a; d.w = w; d.y = y; d.bias = bias; d.dtype = dtype; d.out_dtype = out_dtype;
-  d.B = M; d.Hin = 1; d.Win = 1; d.Cin = K; d.Ho = 1; d.Wo = 1; d.N = N; d.KH = 1; d.KW = 1; d.stride = 1; d.pad = 0;
-  d.ldx = lda; d.ldw = ldw; d.ldy = ldy; d.accumulate = accumulate;
-  return st_conv(&d, stream);
 }
 
 int check_common(const st_rnn_params* p, const st_packed_seq* s, const char* who) {
@@ -93,15 +74,7 @@ int check_common(const st_rnn_params* p, const st_packed_seq* s, const char* who
   ST_CHECK(p->L >= 1 && p->L <= ST_MAX_LAYERS, "%s: num_layers=%d out of range [1,%d]", who, p->L, ST_MAX_LAYERS);
   ST_CHECK(p->H % 8 == 0 && p->in0 % 8 == 0 && p->E % 8 == 0, "%s: E=%d, in0=%d and H=%d must be multiples of 8", who, p->E, p->in0, p->H);
   ST_CHECK(p->V > 0, "%s: bad vocabulary size", who);
-  ST_CHECK(s->B > 0 && s->T > 0 && s->ntok > 0 && s->batch_sizes_host && s->rows_b && s->rows_t && s->prev_row && s->caption,
-           "%s: bad packed-sequence descriptor", who);
-  int sum = 0, prev = s->B;
-  for (int t = 0; t < s->T; ++t) {
-    const int b = s->batch_sizes_host[t];
-    ST_CHECK(b > 0 && b <= prev, "%s: batch_sizes must be positive and non-increasing (captions sorted by length, utils.py:66)", who);
-    prev = b; sum += b;
-  }
-  ST_CHECK(sum == s->ntok && s->batch_sizes_host[0] == s->B, "%s: batch_sizes do not add up to ntok", who);
+  if (st_check_packed_seq(s, who, true)) return 1;
   for (int l = 0; l < p->L; ++l)
     ST_CHECK(p->w_ih[l] && p->w_hh[l] && p->b_ih[l] && p->b_hh[l], "%s: null weights for layer %d", who, l);
   return 0;
@@ -111,7 +84,7 @@ int check_common(const st_rnn_params* p, const st_packed_seq* s, const char* who
 
 // Leading dimension to give logits / dlogits rows: V rounded up to 8 elements for small vocabularies, to 512 (8 K tiles of
 // 64) from 2048 entries on, so that the K = V product of the backward pass can be split evenly.
-extern "C" int st_rnn_vocab_ld(int V) { return V < 2048 ? up8(V) : (V + 511) / 512 * 512; }
+extern "C" int st_rnn_vocab_ld(int V) { return V < 2048 ? st_up8(V) : (V + 511) / 512 * 512; }
 
 extern "C" size_t st_rnn_workspace_bytes(const st_rnn_params* p, const st_packed_seq* s) {
   if (!p || !s) return 0;
@@ -136,8 +109,7 @@ extern "C" int st_rnn_forward(const st_rnn_params* p, const st_packed_seq* s, co
     if (pack_inputs_launch(feat, p->emb, s->caption, s->Tcap, s->rows_b, s->rows_t, ws + q.x0, targets, n, p->E, p->V, 0, dt, st)) return 1;
     x0 = ws + q.x0;
   }
-  std::vector<int> off(s->T + 1, 0);
-  for (int t = 0; t < s->T; ++t) off[t + 1] = off[t] + s->batch_sizes_host[t];
+  const std::vector<int> off = st_packed_offsets(s);
 
   const int L = p->L, T = s->T;
   for (int d = 0; d < T + L - 1; ++d) {
@@ -151,27 +123,16 @@ extern "C" int st_rnn_forward(const st_rnn_params* p, const st_packed_seq* s, co
       char* yl = ws + q.y + (size_t)l * n * H * es;
       char* gl = ws + q.gates + (size_t)l * n * 4 * H * es;
       char* cl = ws + q.cst + (size_t)l * n * H * es;
-      RnnGemmArgs& a = cells[nc++];
-      memset(&a, 0, sizeof(a));
-      a.M = bt; a.N = H; a.K = H; a.lda = H; a.ldw = H; a.gstride = H;
-      a.W = p->w_hh[l];
-      a.A = t > 0 ? yl + (size_t)off[t - 1] * H * es : nullptr;
-      a.hprev = a.A; a.ldhp = H;
-      a.bias_h = p->b_hh[l];
-      a.A2 = xl + (size_t)off[t] * in * es; a.K2 = in; a.lda2 = in; a.W2 = p->w_ih[l]; a.ldw2 = in; a.bias_x = p->b_ih[l];
-      a.hout = yl + (size_t)off[t] * H * es; a.ldho = H;
-      if (save_for_backward) { a.cache = gl + (size_t)off[t] * 4 * H * es; a.ldcache = 4 * H; }
-      if (p->cell == ST_CELL_LSTM) {
-        a.cprev = t > 0 ? cl + (size_t)off[t - 1] * H * es : nullptr;
-        a.cout = cl + (size_t)off[t] * H * es;
-      }
+      cells[nc++] = rnn_full_cell(p, l, xl + (size_t)off[t] * in * es, in, t > 0 ? yl + (size_t)off[t - 1] * H * es : nullptr,
+                                  t > 0 ? cl + (size_t)off[t - 1] * H * es : nullptr, yl + (size_t)off[t] * H * es, cl + (size_t)off[t] * H * es,
+                                  bt, save_for_backward ? gl + (size_t)off[t] * 4 * H * es : nullptr);
     }
-    if (rnn_gemm_launch_batch(cells, nc, dt, p->cell == ST_CELL_GRU ? 1 : 2, 1, st)) return 1;
+    if (rnn_gemm_launch_batch(cells, nc, dt, rnn_cell_epi(p->cell), 1, st)) return 1;
   }
   if (logits) {
     ST_CHECK(p->w_lin && p->b_lin, "st_rnn_forward: logits requested without the vocabulary projection");
     const char* ytop = ws + q.y + (size_t)(p->L - 1) * n * H * es;
-    if (gemm_nt(ytop, H, p->w_lin, H, logits, ldl, n, p->V, H, dt, logits_dtype, p->b_lin, 0, stream)) return 1;
+    if (st_gemm_nt(ytop, H, p->w_lin, H, logits, ldl, n, p->V, H, dt, logits_dtype, p->b_lin, stream)) return 1;
   }
   return 0;
 }
@@ -221,8 +182,7 @@ extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, co
   char* ws = reinterpret_cast<char*>(workspace);
   const int dt = p->dtype, H = p->H, n = s->ntok, Np = q.Np, GH = q.GH;
   const size_t es = q.es;
-  std::vector<int> off(s->T + 1, 0);
-  for (int t = 0; t < s->T; ++t) off[t + 1] = off[t] + s->batch_sizes_host[t];
+  const std::vector<int> off = st_packed_offsets(s);
   const int L = p->L, T = s->T;
   auto dyl = [&](int l) { return reinterpret_cast<float*>(ws + q.dyl) + (size_t)l * n * H; };   // d loss / d y_l
   float* dy = dyl(L - 1);
@@ -230,18 +190,18 @@ extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, co
 
   if (dlogits) {
     ST_CHECK(p->w_lin && g->w_lin && g->b_lin, "st_rnn_backward: vocabulary projection gradients requested without buffers");
-    ST_CHECK(ldd >= up8(p->V) && ldd % 8 == 0 && ldd <= q.Vp, "st_rnn_backward: dlogits leading dimension %d must be a multiple of 8 in [%d, %d]",
-             ldd, up8(p->V), q.Vp);
+    ST_CHECK(ldd >= st_up8(p->V) && ldd % 8 == 0 && ldd <= q.Vp, "st_rnn_backward: dlogits leading dimension %d must be a multiple of 8 in [%d, %d]",
+             ldd, st_up8(p->V), q.Vp);
     // db = colsum(dlogits);  dW_lin += dlogits^T y_top;  dy_top = dlogits W_lin
     if (st_transpose_colsum(dlogits, ws + q.tA, g->b_lin, dt, n, p->V, ldd, Np, stream)) return 1;
     if (st_transpose(ytop, ws + q.tB, dt, n, H, H, Np, stream)) return 1;
-    if (gemm_nt(ws + q.tA, Np, ws + q.tB, Np, g->w_lin, H, p->V, H, Np, dt, ST_F32, nullptr, 1, stream)) return 1;
+    if (st_gemm_nt(ws + q.tA, Np, ws + q.tB, Np, g->w_lin, H, p->V, H, Np, dt, ST_F32, nullptr, stream, 1)) return 1;
     // dy = dlogits W_lin is 15 x 4 output tiles over K = V: with the padded leading dimension (st_rnn_vocab_ld: a multiple
     // of 8 K tiles, pad columns zero on both sides) it runs as 8 K slices in one grouped launch
     if (st_transpose(p->w_lin, ws + q.wT, dt, p->V, H, H, ldd, stream)) return 1;
     const int bk = dt == ST_BF16 ? 64 : 32;
     const int split = (ldd % (8 * bk) == 0 && ldd >= 16 * bk) ? 8 : 0;
-    if (gemm_nt(dlogits, ldd, ws + q.wT, ldd, dy, H, n, H, ldd, dt, ST_F32, nullptr, 0, stream, split)) return 1;
+    if (st_gemm_nt(dlogits, ldd, ws + q.wT, ldd, dy, H, n, H, ldd, dt, ST_F32, nullptr, stream, 0, split)) return 1;
     if (dy_top_extra) { st_set_error("st_rnn_backward: dlogits and dy_top_extra are exclusive"); return 1; }
   } else {
     ST_CHECK(dy_top_extra, "st_rnn_backward: need dlogits or dy_top");
@@ -275,6 +235,20 @@ extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, co
     if (st_transpose_batch(wx[0], wy[0], nullptr, L, dt, GH, H, H, GH, nullptr, nullptr, stream)) return 1;
     if (ni && st_transpose_batch(wx[1], wy[1], nullptr, ni, dt, GH, H, H, GH, nullptr, nullptr, stream)) return 1;
   }
+  auto bwd_cell = [&](int l, int t, const float* dyrows) {   // gate gradients of cell (l, t); dyrows: d loss / d y_l from row 0 on, or NULL
+    const char* yl = ws + q.y + (size_t)l * n * H * es;
+    const char* gl = ws + q.gates + (size_t)l * n * 4 * H * es;
+    const char* cl = ws + q.cst + (size_t)l * n * H * es;
+    RnnBwdCell c;
+    memset(&c, 0, sizeof(c));
+    c.dy = dyrows ? dyrows + (size_t)off[t] * H : nullptr; c.dhc = dhcl(l); c.dcc = dccl(l);
+    c.cache = gl + (size_t)off[t] * 4 * H * es;
+    c.hprev = t > 0 ? yl + (size_t)off[t - 1] * H * es : nullptr;
+    c.cnew = cl + (size_t)off[t] * H * es;
+    c.cprev = t > 0 ? cl + (size_t)off[t - 1] * H * es : nullptr;
+    c.dgx = dgxl(l) + (size_t)off[t] * GH * es; c.dgh = dghl(l) + (size_t)off[t] * GH * es; c.Bt = s->batch_sizes_host[t];
+    return c;
+  };
   // reversed wavefront: the cells of a diagonal need only cells of the diagonal above
   const char* env = getenv("ST_BPTT_FUSED");       // read per call: ST_BPTT_FUSED=0 keeps the two-launch push route (A/B runs, tests)
   const bool fused = !(env && env[0] == '0');
@@ -285,21 +259,11 @@ extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, co
     int nf = 0;
     for (int l = d < T ? 0 : d - (T - 1); l <= d && l < L; ++l) {
       const int t = d - l;
-      const int bt = s->batch_sizes_host[t];
-      char* yl = ws + q.y + (size_t)l * n * H * es;
-      char* gl = ws + q.gates + (size_t)l * n * 4 * H * es;
-      char* cl = ws + q.cst + (size_t)l * n * H * es;
       RnnBwdFused& f = fc[nf++];
       memset(&f, 0, sizeof(f));
-      RnnBwdCell& c = f.e;
-      c.dy = l == L - 1 ? dy + (size_t)off[t] * H : nullptr; c.dhc = dhcl(l); c.dcc = dccl(l);
-      c.cache = gl + (size_t)off[t] * 4 * H * es;
-      c.hprev = t > 0 ? yl + (size_t)off[t - 1] * H * es : nullptr;
-      c.cnew = cl + (size_t)off[t] * H * es;
-      c.cprev = t > 0 ? cl + (size_t)off[t - 1] * H * es : nullptr;
-      c.dgx = dgxl(l) + (size_t)off[t] * GH * es; c.dgh = dghl(l) + (size_t)off[t] * GH * es; c.Bt = bt;
+      f.e = bwd_cell(l, t, l == L - 1 ? dy : nullptr);
       RnnGemmArgs& a = f.g;
-      a.M = bt; a.N = H;
+      a.M = f.e.Bt; a.N = H;
       if (t + 1 < T) {                             // rows [B_{t+1}, B_t) end here: no recurrent term
         a.A = dghl(l) + (size_t)off[t + 1] * GH * es; a.W = wThh(l); a.M2 = s->batch_sizes_host[t + 1]; a.K = GH; a.lda = GH; a.ldw = GH;
       }
@@ -310,7 +274,7 @@ extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, co
     if (rnn_bwd_fused_launch_batch(fc, nf, p->cell, dt, st)) return 1;
   }
   // dx0 = dgx_0 W_ih_0 feeds only the embedding / feature gradients: one whole-sequence GEMM off the recurrence
-  if (fused && need_dx0 && gemm_nt(dgxl(0), GH, wTih(0), GH, dx0, p->in0, n, p->in0, GH, dt, ST_F32, nullptr, 0, stream)) return 1;
+  if (fused && need_dx0 && st_gemm_nt(dgxl(0), GH, wTih(0), GH, dx0, p->in0, n, p->in0, GH, dt, ST_F32, nullptr, stream)) return 1;
   for (int d = T + L - 2; !fused && d >= 0; --d) {
     RnnBwdCell gc[ST_MAX_LAYERS];
     RnnGemmArgs mc[2 * ST_MAX_LAYERS];
@@ -319,17 +283,7 @@ extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, co
       const int t = d - l;
       const int bt = s->batch_sizes_host[t];
       const int in = l == 0 ? p->in0 : H;
-      char* yl = ws + q.y + (size_t)l * n * H * es;
-      char* gl = ws + q.gates + (size_t)l * n * 4 * H * es;
-      char* cl = ws + q.cst + (size_t)l * n * H * es;
-      RnnBwdCell& c = gc[ng++];
-      memset(&c, 0, sizeof(c));
-      c.dy = dyl(l) + (size_t)off[t] * H; c.dhc = dhcl(l); c.dcc = dccl(l);
-      c.cache = gl + (size_t)off[t] * 4 * H * es;
-      c.hprev = t > 0 ? yl + (size_t)off[t - 1] * H * es : nullptr;
-      c.cnew = cl + (size_t)off[t] * H * es;
-      c.cprev = t > 0 ? cl + (size_t)off[t - 1] * H * es : nullptr;
-      c.dgx = dgxl(l) + (size_t)off[t] * GH * es; c.dgh = dghl(l) + (size_t)off[t] * GH * es; c.Bt = bt;
+      gc[ng++] = bwd_cell(l, t, dyl(l));
       if (t > 0) {                                 // dh_{t-1} += dgh_t W_hh
         RnnGemmArgs& a = mc[nm++];
         memset(&a, 0, sizeof(a));
@@ -351,11 +305,7 @@ extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, co
   st_conv_desc gd[2 * ST_MAX_LAYERS];
   int ng = 0;
   auto wgrad = [&](const void* aT, const void* bT, float* dw, int rows, int cols) {   // dw[rows][cols] += aT[rows][Np] . bT[cols][Np]^T
-    st_conv_desc& d = gd[ng++];
-    memset(&d, 0, sizeof(d));
-    d.x = aT; d.w = bT; d.y = dw; d.dtype = dt; d.out_dtype = ST_F32;
-    d.B = rows; d.Hin = 1; d.Win = 1; d.Cin = Np; d.Ho = 1; d.Wo = 1; d.N = cols; d.KH = 1; d.KW = 1; d.stride = 1; d.pad = 0;
-    d.ldx = Np; d.ldw = Np; d.ldy = cols; d.accumulate = 1;
+    gd[ng++] = st_gemm_nt_desc(aT, Np, bT, Np, dw, cols, rows, cols, Np, dt, ST_F32, nullptr, 1);
   };
   const void* tx[4][ST_MAX_LAYERS]; void* ty[4][ST_MAX_LAYERS]; float* tc[4][ST_MAX_LAYERS];   // dgx, x, dgh, y(->hprev) of every layer
   int nx = 0;                                                                                   // layers whose input width is H
@@ -386,8 +336,8 @@ extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, co
   if (st_transpose_batch(tx[3], ty[3], nullptr, L, dt, n, H, H, Np, s->rows_t, s->prev_row, stream)) return 1;
   for (int l = 0; l < L; ++l) {          // layers with a different input width: their dW_ih on its own
     const int in = l == 0 ? p->in0 : H;
-    if (in != H && gemm_nt(ws + q.gA + (size_t)(2 * l) * GH * Np * es, Np, ws + q.gB + (size_t)(2 * l) * q.maxw * Np * es, Np,
-                           g->w_ih[l], in, GH, in, Np, dt, ST_F32, nullptr, 1, stream)) return 1;
+    if (in != H && st_gemm_nt(ws + q.gA + (size_t)(2 * l) * GH * Np * es, Np, ws + q.gB + (size_t)(2 * l) * q.maxw * Np * es, Np,
+                              g->w_ih[l], in, GH, in, Np, dt, ST_F32, nullptr, stream, 1)) return 1;
   }
   for (int i = 0; i < ng; i += 12) {
     if (st_conv_batch(gd + i, ng - i < 12 ? ng - i : 12, stream)) return 1;

@@ -14,12 +14,9 @@
 // No lane ever sums a whole row.  Rows of up to 256 x 40 entries (V = 10000) are read ONCE, with all of a thread's loads in
 // flight together, and stay in registers between the passes; longer or unaligned rows take the passes over memory.
 // A row needs at least one finite entry: with none (all -inf or NaN) the token is 0 and logp is NaN.
-#include "common.h"
+#include "decoder_host.h"
 
 namespace {
-
-inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-inline int up8(int v) { return (v + 7) & ~7; }
 
 constexpr int kSampleThreads = 256;
 constexpr int kSampleCap = 1024;      // candidate list; more elements >= T0 (rows of equal logits): exact selection by rounds
@@ -228,15 +225,14 @@ namespace {
 struct SPlan { size_t h[2], c[2], x, logits, cur, fin, total; };
 SPlan make_splan(const st_rnn_params* p, int n) {
   const size_t es = st_dtype_size(p->dtype);
-  SPlan q; size_t o = 0;
-  auto take = [&](size_t bytes) { size_t x = o; o += al(bytes); return x; };
+  SPlan q; Arena ar;
   const size_t hb = (size_t)p->L * n * p->H * es;
-  for (int i = 0; i < 2; ++i) { q.h[i] = take(hb); q.c[i] = take(p->cell == ST_CELL_LSTM ? hb : 0); }
-  q.x = take((size_t)n * p->E * es);
-  q.logits = take((size_t)n * up8(p->V) * sizeof(float));
-  q.cur = take((size_t)n * sizeof(long));
-  q.fin = take((size_t)n);
-  q.total = o;
+  for (int i = 0; i < 2; ++i) { q.h[i] = ar.take(hb); q.c[i] = ar.take(p->cell == ST_CELL_LSTM ? hb : 0); }
+  q.x = ar.take((size_t)n * p->E * es);
+  q.logits = ar.take((size_t)n * st_up8(p->V) * sizeof(float));
+  q.cur = ar.take((size_t)n * sizeof(long));
+  q.fin = ar.take((size_t)n);
+  q.total = ar.o;
   return q;
 }
 }  // namespace
@@ -257,7 +253,7 @@ extern "C" int st_rnn_sample(const st_rnn_params* p, const void* feat, int n, in
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   char* ws = reinterpret_cast<char*>(workspace);
   const bool lstm = p->cell == ST_CELL_LSTM;
-  const int Vp = up8(p->V);
+  const int Vp = st_up8(p->V);
   float* logits = reinterpret_cast<float*>(ws + q.logits);
   long* cur = reinterpret_cast<long*>(ws + q.cur);
   uint8_t* fin = reinterpret_cast<uint8_t*>(ws + q.fin);
