@@ -308,9 +308,12 @@ class ResNet(nn.Module):
         self._bb = _Backbone(self.model, resnet_version, dtype)
 
     def _apply(self, fn, *a, **k):
+        from .rnn import drop_moved_working_copies, storage_places
+        places = storage_places(self)
         out = super()._apply(fn, *a, **k)
         self._bb.flat = None      # .cuda()/.cpu()/.to() replaced the tensors: re-flatten lazily
         self._bb.packed = None
+        drop_moved_working_copies(self, places)     # the head Linear's bf16 working copy
         return out
 
     def backbone_features(self, x, undo=None):

@@ -73,15 +73,17 @@ class _FlatOptimizer:
             self._apply_state(sd)
 
     def _sync_shadow(self, initial=False):
-        if self.shadow is None:
-            return
-        if initial:
+        """The step kernels write the flat buffer through a raw pointer: bump every parameter's version so that whatever is
+        keyed on it (rnn.working_copy's per-parameter bf16 copy when this optimizer owns no shadow) sees the new values.  With
+        a shadow of its own, the kernels' working copies are then re-pointed at it (the step kernel has refreshed it)."""
+        if self.shadow is not None and initial:
             from . import ops
             ops.cast(self.flat, self.shadow.dtype, out=self.shadow)
         for p, o in zip(self.params, self.offsets):
             torch.autograd.graph.increment_version(p)
-            p._st_shadow = self.shadow[o:o + p.numel()].view(p.shape)
-            p._st_shadow_ver, p._st_shadow_ptr = p._version, p.data_ptr()
+            if self.shadow is not None:
+                p._st_shadow = self.shadow[o:o + p.numel()].view(p.shape)
+                p._st_shadow_ver, p._st_shadow_ptr = p._version, p.data_ptr()
 
     def zero_grad(self, set_to_none=False):
         """Gradients stay views of the flat buffer (the all-reduce target); `set_to_none` is accepted and ignored."""

@@ -17,6 +17,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import mark_modified
+
 BUCKET_ELEMS = 8 * 1024 * 1024   # 32 MB fp32 per message: large enough to run at link bandwidth
 
 
@@ -53,14 +55,10 @@ def broadcast_state(modules, optimizer=None, src=0):
                     t.data.copy_(v.reshape(()))
                 else:
                     dist.broadcast(t.data, src)
-                # the write went through `.data`: bump the version counter so that caches keyed on (version, data_ptr) -- the
-                # backbone's packed bf16 / fragment-major filter copies (cnn.py:pack_weights), the optimizer's bf16 shadows --
-                # see that the tensor changed even when a forward had already run on this rank's own initial weights
-                torch.autograd.graph.increment_version(t)
-            bb = getattr(m, "_bb", None)              # frozen backbone: drop the packed copies outright (re-packed on the next forward)
-            if bb is not None:
-                bb.packed = None
-                bb.packed_key = None
+            # the writes went through `.data`: bump the version counters so that caches keyed on (version, data_ptr) -- the
+            # backbone's packed bf16 / fragment-major filter copies (cnn.py:pack_weights), the bf16 working copies -- see
+            # that the tensors changed even when a forward had already run on this rank's own initial weights
+            mark_modified(m)
     if optimizer is not None:
         optimizer._sync_shadow(initial=True)         # the bf16 copies the kernels read
 

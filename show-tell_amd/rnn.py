@@ -52,6 +52,24 @@ def working_copy(p, dtype):
     return sh
 
 
+def storage_places(module):
+    """(device, address) of every parameter of `module`, to be taken before Module._apply"""
+    return [(p.device, p.data_ptr()) for p in module.parameters()]
+
+
+def drop_moved_working_copies(module, places):
+    """After Module._apply (.cuda() / .cpu() / .to()), with `places` = storage_places(module) from before it: forget the
+    working copy of every parameter whose storage moved.  working_copy alone cannot be relied on here: a round trip
+    .cpu() -> .cuda() leaves the version counter where it was and the caching allocator hands the block it freed back at
+    the same address, so weights written on the host in between (through `.data`, as the reference initialises its layers)
+    would be invisible.  Host-side, and only when a module is moved."""
+    for p, place in zip(module.parameters(), places):
+        if (p.device, p.data_ptr()) != place:
+            for attr in ("_st_shadow", "_st_shadow_ver", "_st_shadow_ptr"):
+                if hasattr(p, attr):
+                    delattr(p, attr)
+
+
 def grad_buffer(p):
     if p.grad is None:
         p.grad = torch.zeros_like(p.data, dtype=torch.float32)
@@ -196,6 +214,12 @@ class RNN(torch.nn.Module):
         self.linear = nn.Linear(num_hidden_units, vocab_size)
         self.embed_dim, self.hidden, self.vocab_size, self.num_layers = embed_dim, num_hidden_units, vocab_size, num_layers
         self.compute_dtype = dtype
+
+    def _apply(self, fn, *a, **k):
+        places = storage_places(self)
+        out = super()._apply(fn, *a, **k)
+        drop_moved_working_copies(self, places)     # .cuda() / .cpu() / .to() replaced the storage the bf16 copies were cast from
+        return out
 
     # ---- C descriptors ---------------------------------------------------------------
     def _layer_params(self):

@@ -24,7 +24,8 @@ import torch.nn as nn
 
 from . import _lib, ops
 from ._lib import ST_BF16, ST_CELL_GRU, ST_CELL_LSTM, ST_F32, AttnGrads, AttnParams, check, lib
-from .rnn import CAP_MAX, _cp, _stream, check_sample_args, grad_buffer, sample_lengths, sample_uniforms, up8, working_copy
+from .rnn import (CAP_MAX, _cp, _stream, check_sample_args, drop_moved_working_copies, grad_buffer, sample_lengths, sample_uniforms,
+                  storage_places, up8, working_copy)
 from .seq import plan_for
 
 
@@ -141,6 +142,12 @@ class RNN_Attn(nn.Module):
         self.embed = nn.Linear(nos_filters, embed_dim)
         self.embed_dim, self.hidden, self.attention_dim = embed_dim, num_hidden_units, attention_dim
         self.compute_dtype = dtype
+
+    def _apply(self, fn, *a, **k):
+        places = storage_places(self)
+        out = super()._apply(fn, *a, **k)
+        drop_moved_working_copies(self, places)     # .cuda() / .cpu() / .to() replaced the storage the bf16 copies were cast from
+        return out
 
     def num_pixels_checked(self, P):
         if P > 64:
