@@ -13,6 +13,9 @@ from oracle import restatement as R
 
 pytestmark = pytest.mark.gpu
 TOL = {torch.float32: 1e-3, torch.bfloat16: 6e-2}
+# test_resnet101_bf16_block_by_block_undamped: (max-rel, L2) of one block output at B = 4 (train) / B = 2 (eval)
+UNDAMPED_BLOCK = (2e-2, 1e-2)
+UNDAMPED_BLOCK0 = (3e-2, 2e-2)
 
 
 def _rel(got, ref):
@@ -195,5 +198,5 @@ def test_resnet101_bf16_block_by_block_undamped(train):
     for k, n, mx, l2 in errs:
         # block 0 is compared from the fp32 IMAGE: bf16 image, 7x7 stem, pool and the four convolutions of layer1.0 -- twice the
         # roundings of any other block
-        lim_mx, lim_l2 = (3e-2, 2e-2) if k == 0 else (2e-2, 1e-2)
+        lim_mx, lim_l2 = UNDAMPED_BLOCK0 if k == 0 else UNDAMPED_BLOCK
         assert mx < lim_mx and l2 < lim_l2, f"block {k} ({n}, train={train}): max {mx:.3e}, L2 {l2:.3e}"

@@ -32,6 +32,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import restatement as R
+from tests._encoder_walk import KEEP32, MOM32, _absorbed, _batch_stats, _bf16, _block_metrics, _nchw64, _params  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -73,33 +74,7 @@ PIPE_VAR = 1.5e-1       # 7.3e-2
 DROP_MEAN = 1.5e-2      # |d running_mean| / sqrt(running_var): 7.1e-3
 DROP_VAR = 1.3e-1       # |d running_var| / running_var: 6.5e-2 (modes)
 
-MOM32 = float(np.float32(0.1))                   # the kernel's momentum and 1 - momentum, in fp32
-KEEP32 = float(np.float32(1.0) - np.float32(0.1))
 BNS = [bn for *_, bn in R.resnet_conv_list(101)]
-
-
-def _bf16(t):
-    return t.bfloat16().float()
-
-
-def _params(seed):
-    """R.init_encoder_params(101, 512) with test_gpu_encoder._make(damp=False)'s BatchNorm randomisation; conv weights rounded
-    to bf16 so that the oracle and the kernels see the same filters"""
-    p = R.init_encoder_params(101, 512, seed=seed)
-    g = torch.Generator().manual_seed(seed + 100)
-    for k in p:
-        if k.endswith("running_mean"):
-            p[k] = torch.randn(p[k].shape, generator=g) * 0.1
-        elif k.endswith("running_var"):
-            p[k] = torch.rand(p[k].shape, generator=g) + 0.5
-        elif ".bn" in k or k.startswith("model.1.") or "downsample.1" in k:
-            if k.endswith(".weight"):
-                p[k] = torch.rand(p[k].shape, generator=g) * 0.5 + 0.75
-            elif k.endswith(".bias"):
-                p[k] = torch.randn(p[k].shape, generator=g) * 0.1
-        if p[k].dim() == 4:
-            p[k] = _bf16(p[k])
-    return p
 
 
 def _model(params, attn, train):
@@ -114,37 +89,6 @@ def _buffers(m):
     sd = m.state_dict()
     return {k: v.detach().cpu().clone() for k, v in sd.items() if k.startswith("model.") and
             k.endswith(("running_mean", "running_var", "num_batches_tracked"))}
-
-
-def _nchw64(tap):
-    """a (B, h, w, C) bf16 tap -> (B, C, h, w) float64, exact"""
-    out = torch.empty((tap.shape[0], tap.shape[3], tap.shape[1], tap.shape[2]), dtype=torch.float64)
-    out.copy_(tap.permute(0, 3, 1, 2))
-    return out
-
-
-def _block_metrics(got, ref, moments):
-    """A (and B if `moments`) of one block output; got, ref (B, C, h, w) float64"""
-    ra = ref.abs()
-    d = got - ref
-    l2 = (d.norm() / ref.norm()).item()
-    ad = d.abs_()
-    mx = (ad.amax() / ra.amax()).item()
-    img = ad.flatten(1).amax(1) / ra.flatten(1).amax(1)
-    b, c, y, x = np.unravel_index(int(ad.argmax()), ad.shape)
-    out = dict(max=mx, l2=l2, img=img.max().item(), img_at=int(img.argmax()), at=(int(b), int(y), int(x), int(c)))
-    if moments:
-        sr, mr = torch.std_mean(ref, dim=(0, 2, 3))
-        sg, mg = torch.std_mean(got, dim=(0, 2, 3))
-        em = (mg - mr).abs() / sr
-        es = (sg / sr - 1).abs()
-        out.update(mean=em.max().item(), mean_ch=int(em.argmax()), std=es.max().item(), std_ch=int(es.argmax()))
-    return out
-
-
-def _absorbed(after, before, keep=KEEP32, mom=MOM32):
-    """the batch statistic a momentum update absorbed: (after - keep * before) / mom, float64"""
-    return (after.double() - keep * before.double()) / mom
 
 
 def _run(name):
@@ -246,12 +190,6 @@ def check_channel_moments(run):
     bad = [f"block {b['k']} ({b['name']}): mean {b['mean']:.2e} (channel {b['mean_ch']}), std {b['std']:.2e} (channel {b['std_ch']})"
            for b in bl if not (b["mean"] < MOMENT_MEAN and b["std"] < MOMENT_STD)]
     assert not bad, f"{run['name']}:\n  " + "\n  ".join(bad)
-
-
-def _batch_stats(buffers, before, bn, keep=KEEP32, mom=MOM32):
-    """(mean, unbiased variance) a layer's running buffers absorbed from `before`"""
-    return (_absorbed(buffers[bn + ".running_mean"], before[bn + ".running_mean"], keep, mom),
-            _absorbed(buffers[bn + ".running_var"], before[bn + ".running_var"], keep, mom))
 
 
 def check_running_buffers(run):
