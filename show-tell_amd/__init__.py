@@ -15,7 +15,7 @@ __all__ = ["ShowTellHipError", "mark_modified"]
 def mark_modified(*modules_or_parameters):
     """Tell the kernels' cached weight copies that tensors were written behind PyTorch's back.
 
-    No bf16 kernel reads a parameter directly: each reads a derived copy (the bf16 working copies of rnn.working_copy and
+    No bf16 kernel reads a parameter directly: each reads a derived copy (the bf16 working copies of _weights.working_copy and
     of the optimizers, the backbone's packed filters) that is refreshed when the parameter's version counter or address
     changes.  An in-place write through ``.data`` (``p.data.copy_(..)``, ``p.data.normal_()``) or through a raw pointer
     moves neither, so after such writes to a model that has already run, call this on the modules or tensors written:
@@ -29,8 +29,7 @@ def mark_modified(*modules_or_parameters):
             for sub in obj.modules():
                 bb = getattr(sub, "_bb", None)
                 if bb is not None:
-                    bb.packed = None
-                    bb.packed_key = None
+                    bb.invalidate_packed()
             return list(obj.parameters()) + list(obj.buffers())
         if torch.is_tensor(obj):
             return [obj]

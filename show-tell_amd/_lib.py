@@ -5,6 +5,8 @@ There is no CPU fallback: if the HIP library is missing, every op raises.
 import ctypes as C
 import os
 
+import torch  # before the library: it then binds to torch's libamdhip64 (two runtimes in one process leave it no device)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libshowtell_hip.so")
 
@@ -127,6 +129,8 @@ _SIGS = {
     "st_conv1x1_kfuse8": ([C.POINTER(Conv1x1KfuseDesc), c_p], c_i),
     "st_conv_b2b": ([C.POINTER(ConvB2bDesc), c_p], c_i),
     "st_conv_b2b_supported": ([c_i, c_i, c_i], c_i),
+    "st_conv_c3c1": ([C.POINTER(ConvC3c1Desc), c_p], c_i),
+    "st_conv_c3c1_supported": ([c_i, c_i, c_i], c_i),
     "st_conv1x1_astat_supported": ([c_i, c_i], c_i),
     "st_conv1x1_astat": ([C.POINTER(Conv1x1WregDesc), c_p], c_i),
     "st_conv1x1_kstream_supported": ([c_i, c_i], c_i),
@@ -206,11 +210,31 @@ _SIGS = {
     "st_resnet_plan": ([c_p, c_i, c_i, c_i, c_i, C.c_char_p, C.c_size_t], c_i),
 }
 
-_lib = None
+_EXPERIMENTAL = ("st_conv1x1_kfuse8",)     # measured, not routed: absent from the product build
+
+_DTYPE_CODES = {torch.float32: ST_F32, torch.bfloat16: ST_BF16}
 
 
 class ShowTellHipError(RuntimeError):
     pass
+
+
+def ptr(t):
+    """A tensor's device address as the C ABI takes it; None (NULL) for None."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream():
+    """The current torch stream as the `void* stream` every entry point ends with."""
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def dtype_code(dtype):
+    """ST_F32 / ST_BF16 for a torch dtype; anything else is an error (no kernel takes it)."""
+    try:
+        return _DTYPE_CODES[dtype]
+    except KeyError:
+        raise ShowTellHipError(f"unsupported dtype {dtype}") from None
 
 
 def declared_symbols():
@@ -218,7 +242,28 @@ def declared_symbols():
     return sorted([k for k in _SIGS if k not in _EXPERIMENTAL] + ["st_last_error"])
 
 
-_EXPERIMENTAL = ("st_conv1x1_kfuse8",)     # measured, not routed: absent from the product build
+class _Bound:
+    """The entry points of _SIGS (and st_last_error) with their argument and return types set, as plain instance
+    attributes.  Nothing else: a symbol the library exports but _SIGS does not describe would be called with ctypes'
+    default conversions, so asking for one is an error (__getattr__ runs only when the attribute is missing)."""
+
+    def __init__(self, cdll):
+        self.st_last_error = cdll.st_last_error
+        self.st_last_error.argtypes, self.st_last_error.restype = [], C.c_char_p
+        for name, (args, res) in _SIGS.items():
+            if name in _EXPERIMENTAL and not hasattr(cdll, name):
+                continue                            # `make EXPERIMENTAL=1` builds only (csrc/Makefile)
+            fn = getattr(cdll, name)
+            fn.argtypes, fn.restype = args, res
+            setattr(self, name, fn)
+
+    def __getattr__(self, name):
+        if name in _SIGS:
+            raise AttributeError(f"{name} is not in this build of the library (`make EXPERIMENTAL=1`)")
+        raise AttributeError(f"{name} has no entry in _lib._SIGS: describe its signature there before calling it")
+
+
+_lib = None
 
 
 def has_symbol(name):
@@ -232,18 +277,7 @@ def lib():
             raise ShowTellHipError(
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(there is no CPU fallback for the HIP path)")
-        # torch must load ITS HIP runtime first: the library then binds to the same libamdhip64 instance
-        # (loading /opt/rocm's copy before torch's leaves the process with two runtimes and no device).
-        import torch  # noqa: F401
-        L = C.CDLL(LIB_PATH)
-        L.st_last_error.restype = C.c_char_p
-        L.st_last_error.argtypes = []
-        for name, (args, res) in _SIGS.items():
-            if name in _EXPERIMENTAL and not hasattr(L, name):
-                continue                            # `make EXPERIMENTAL=1` builds only (csrc/Makefile)
-            fn = getattr(L, name)
-            fn.argtypes, fn.restype = args, res
-        _lib = L
+        _lib = _Bound(C.CDLL(LIB_PATH))
     return _lib
 
 

@@ -17,13 +17,9 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import ops
-from ._lib import ST_BF16, ST_F32, check, lib
-from .rnn import CAP_MAX, _cp, _stream, up8
-
-
-def _dtc(dt):
-    return ST_F32 if dt == torch.float32 else ST_BF16
+from ._lib import check, dtype_code as _dtc, lib
+from ._lib import ptr as _cp, stream as _stream
+from .rnn import CAP_MAX, up8
 
 
 class _Stepper:
@@ -75,8 +71,7 @@ class _Stepper:
 
 
 def _feat(rnn, cnn_feature):
-    f = cnn_feature.detach().contiguous()
-    return f if f.dtype == rnn.compute_dtype else ops.cast(f.float(), rnn.compute_dtype)
+    return rnn._feature(cnn_feature)
 
 
 def quirky_beam(rnn, cnn_feature, beam_size, steps=CAP_MAX):

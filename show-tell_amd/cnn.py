@@ -19,13 +19,13 @@ cnn.py:23-31).  There is no network here; weights are random (torchvision's
 Kaiming fan-out init) until ``load_state_dict`` supplies real ones.
 """
 import ctypes as C
-import math
 
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
-from ._lib import ST_BF16, ST_F32, check, lib
+from . import _lib
+from ._lib import check, dtype_code, lib, ptr as _p
+from ._weights import FollowsMoves
 
 _SPECS = {18: ("basic", [2, 2, 2, 2]), 34: ("basic", [3, 4, 6, 3]), 50: ("bottleneck", [3, 4, 6, 3]),
           101: ("bottleneck", [3, 4, 23, 3]), 152: ("bottleneck", [3, 8, 36, 3])}
@@ -108,7 +108,7 @@ class _Backbone:
     def _ensure_handle(self):
         if self.handle is None:
             h = C.c_void_p()
-            rc = lib().st_resnet_create(self.version, ST_BF16 if self.dtype == torch.bfloat16 else ST_F32, C.byref(h))
+            rc = lib().st_resnet_create(self.version, dtype_code(self.dtype), C.byref(h))
             if rc == 2:
                 raise ValueError(lib().st_last_error().decode())
             check(rc, "st_resnet_create")
@@ -155,6 +155,11 @@ class _Backbone:
         o = self.info[-1]["bnoff"]
         return bn.weight.data_ptr() == self.flat["gamma"][o:].data_ptr()
 
+    def invalidate_packed(self):
+        """The conv weights were moved, or written without a version bump (mark_modified): pack them again on the next forward."""
+        self.packed = None
+        self.packed_key = None
+
     def pack_weights(self, device):
         key = (device, tuple(c.weight._version for c, _ in self.pairs), tuple(c.weight.data_ptr() for c, _ in self.pairs))
         if self.packed is not None and key == self.packed_key:
@@ -163,17 +168,17 @@ class _Backbone:
         n = lib().st_resnet_weight_elems(self.handle)
         self.packed = torch.empty(n, device=device, dtype=self.dtype)
         es = self.packed.element_size()
-        dt = ST_BF16 if self.dtype == torch.bfloat16 else ST_F32
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        dt = dtype_code(self.dtype)
+        st = _lib.stream()
         for i, (conv, _) in enumerate(self.pairs):
             inf = self.info[i]
             w = conv.weight.data
             assert w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
-            check(lib().st_pack_conv_weight(C.c_void_p(w.data_ptr()), C.c_void_p(self.packed.data_ptr() + inf["woff"] * es),
+            check(lib().st_pack_conv_weight(_p(w), C.c_void_p(self.packed.data_ptr() + inf["woff"] * es),
                                             dt, inf["cout"], inf["cin"], inf["k"], inf["k"], inf["cin_p"], inf["korder"], st),
                   "st_pack_conv_weight")
             if inf["ntw"] > 0:      # second, fragment-major copy for the image-resident 3x3 kernel (st_conv3x3_img)
-                check(lib().st_pack_conv_weight_frag(C.c_void_p(w.data_ptr()), C.c_void_p(self.packed.data_ptr() + inf["woff_frag"] * es),
+                check(lib().st_pack_conv_weight_frag(_p(w), C.c_void_p(self.packed.data_ptr() + inf["woff_frag"] * es),
                                                      inf["cout"], inf["cin"], inf["k"], inf["k"], inf["ntw"], st), "st_pack_conv_weight_frag")
         self.packed_key = key
 
@@ -195,7 +200,7 @@ class _Backbone:
                 shapes.append((B, h, w, planes * exp))
         n = sum(a * b * c * d for a, b, c, d in shapes)
         buf = torch.empty(n, device=x.device, dtype=self.dtype)
-        check(lib().st_resnet_set_taps(self.handle, C.c_void_p(buf.data_ptr()), buf.numel() * buf.element_size()), "st_resnet_set_taps")
+        check(lib().st_resnet_set_taps(self.handle, _p(buf), buf.numel() * buf.element_size()), "st_resnet_set_taps")
         try:
             pooled, ncp = self.forward(x, train, True, want_ncp)
             torch.cuda.synchronize()
@@ -260,11 +265,10 @@ class _Backbone:
             ho, wo = (ho - 1) // 2 + 1, (wo - 1) // 2 + 1
         pooled = torch.empty(B, F, device=dev, dtype=pooled_dtype) if want_pooled else None
         ncp = torch.empty(B, F, ho * wo, device=dev, dtype=torch.float32) if want_ncp else None
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         fl = self.flat
-        check(lib().st_resnet_forward(self.handle, p(x), B, H, W, p(self.packed), p(fl["gamma"]), p(fl["beta"]),
-                                      p(fl["rm"]), p(fl["rv"]), 2 if train else 0, 0.1, 1e-5, p(ws), ws.numel(),
-                                      None, p(pooled), ST_BF16 if pooled_dtype == torch.bfloat16 else ST_F32, p(ncp),
+        check(lib().st_resnet_forward(self.handle, _p(x), B, H, W, _p(self.packed), _p(fl["gamma"]), _p(fl["beta"]),
+                                      _p(fl["rm"]), _p(fl["rv"]), 2 if train else 0, 0.1, 1e-5, _p(ws), ws.numel(),
+                                      None, _p(pooled), dtype_code(pooled_dtype), _p(ncp),
                                       C.c_void_p(cur.cuda_stream)), "st_resnet_forward")
         if train:
             # the momentum updates of the running buffers (and num_batches_tracked) are applied in minibatch order even when
@@ -273,7 +277,7 @@ class _Backbone:
                 cur.wait_event(self._upd_event)
             if undo is not None:    # the running means / vars as this update finds them, for restore_running
                 undo[:] = [self.running.clone()]
-            check(lib().st_resnet_update_running(self.handle, p(ws), p(fl["rm"]), p(fl["rv"]), 0.1, C.c_void_p(cur.cuda_stream)),
+            check(lib().st_resnet_update_running(self.handle, _p(ws), _p(fl["rm"]), _p(fl["rv"]), 0.1, C.c_void_p(cur.cuda_stream)),
                   "st_resnet_update_running")
             self.nbt.add_(1)
             self._upd_event = torch.cuda.Event()
@@ -288,7 +292,7 @@ class _Backbone:
             pass
 
 
-class ResNet(nn.Module):
+class ResNet(FollowsMoves, nn.Module):
     '''
     Encoding via ResNet (reference cnn.py:9-51); `dtype` selects the kernels' storage type
     (torch.float32 = parity mode, torch.bfloat16 = performance mode, fp32 accumulation).
@@ -308,12 +312,9 @@ class ResNet(nn.Module):
         self._bb = _Backbone(self.model, resnet_version, dtype)
 
     def _apply(self, fn, *a, **k):
-        from .rnn import drop_moved_working_copies, storage_places
-        places = storage_places(self)
-        out = super()._apply(fn, *a, **k)
+        out = super()._apply(fn, *a, **k)      # FollowsMoves: the head Linear's bf16 working copy
         self._bb.flat = None      # .cuda()/.cpu()/.to() replaced the tensors: re-flatten lazily
-        self._bb.packed = None
-        drop_moved_working_copies(self, places)     # the head Linear's bf16 working copy
+        self._bb.invalidate_packed()
         return out
 
     def backbone_features(self, x, undo=None):

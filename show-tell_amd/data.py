@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import check, lib, ptr as _p, stream
 
 MEAN = (0.485, 0.456, 0.406)   # utils.py:88
 STD = (0.229, 0.224, 0.225)
@@ -101,10 +101,10 @@ class DeviceTransform:
             tmp = torch.empty(B * max_h * ow * 3, dtype=torch.uint8, device=dev)
             out = torch.empty(B, 3, oh, ow, dtype=torch.float32, device=dev)
             u8 = torch.empty(B, oh, ow, 3, dtype=torch.uint8, device=dev) if return_u8 else None
-            p = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
-            d = _lib.ImageBatchDesc(p(src), src.numel(), p(d_off), p(d_meta[0]), p(d_meta[1]), p(d_meta[2]), B, max_h, max_w, oh, ow,
-                                    p(self._lut), p(tmp), p(out), p(u8))
-            check(lib().st_image_transform(C.byref(d), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "st_image_transform")
+            d = _lib.ImageBatchDesc(src=_p(src), src_bytes=src.numel(), offset=_p(d_off), height=_p(d_meta[0]), width=_p(d_meta[1]),
+                                    flip=_p(d_meta[2]), batch=B, max_height=max_h, max_width=max_w, out_h=oh, out_w=ow,
+                                    lut=_p(self._lut), tmp=_p(tmp), out=_p(out), out_u8=_p(u8))
+            check(lib().st_image_transform(C.byref(d), stream()), "st_image_transform")
         return (out, u8) if return_u8 else out
 
 

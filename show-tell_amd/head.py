@@ -3,13 +3,12 @@
 ``x`` is the detached backbone output (cnn.py:47), so only the four head tensors receive
 gradients; they are accumulated straight into ``param.grad`` by st_linear_bn1d_backward.
 """
-import ctypes as C
-
 import torch
 
 from . import ops
-from ._lib import ST_BF16, ST_F32, check, lib
-from .rnn import _cp, _stream, grad_buffer, working_copy
+from ._lib import check, dtype_code, lib
+from ._lib import ptr as _cp, stream as _stream
+from ._weights import grad_buffer, working_copy
 
 
 class _HeadFn(torch.autograd.Function):
@@ -18,7 +17,7 @@ class _HeadFn(torch.autograd.Function):
         dev = x.device
         B, F = x.shape
         E = linear.out_features
-        dtc = ST_F32 if dtype == torch.float32 else ST_BF16
+        dtc = dtype_code(dtype)
         xd = x if x.dtype == dtype else ops.cast(x.contiguous(), dtype)
         w = working_copy(linear.weight, dtype)
         z = torch.empty(B, E, device=dev, dtype=torch.float32)
@@ -39,7 +38,7 @@ class _HeadFn(torch.autograd.Function):
         xd, z, mean, rstd, linear, bn, train, dtype = ctx.saved
         B, F = xd.shape
         E = linear.out_features
-        dtc = ST_F32 if dtype == torch.float32 else ST_BF16
+        dtc = dtype_code(dtype)
         nbytes = lib().st_head_workspace_bytes(B, F, E, dtc)
         ws = torch.empty(nbytes, device=dy.device, dtype=torch.uint8)
         check(lib().st_linear_bn1d_backward(_cp(dy.contiguous().float()), _cp(z), _cp(xd), _cp(bn.weight.data), _cp(mean), _cp(rstd),

@@ -8,24 +8,15 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import (ST_BF16, ST_F32, BnActDesc, ConvB2bDesc, Conv1x1KfuseDesc, Conv1x1WregDesc, Conv3x3ImgDesc, ConvDesc, StemConvPoolDesc,
-                   check, lib)
+from ._lib import (BnActDesc, ConvB2bDesc, ConvC3c1Desc, Conv1x1KfuseDesc, Conv1x1WregDesc, Conv3x3ImgDesc, ConvDesc, StemConvPoolDesc,
+                   check, dtype_code, lib)
+from ._lib import ptr as _p, stream as _stream  # noqa: F401  (the names this module has always used; tools import them)
 
-_DT = {torch.float32: ST_F32, torch.bfloat16: ST_BF16}
+_DT = _lib._DTYPE_CODES
 
 
 def dt_code(t):
-    if t.dtype not in _DT:
-        raise _lib.ShowTellHipError(f"unsupported dtype {t.dtype}")
-    return _DT[t.dtype]
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return dtype_code(t.dtype)
 
 
 def _dev(*ts):
@@ -34,6 +25,22 @@ def _dev(*ts):
             raise _lib.ShowTellHipError("tensor is not on the GPU (the HIP path has no CPU fallback)")
         if t is not None and not t.is_contiguous():
             raise _lib.ShowTellHipError("tensor must be contiguous")
+
+
+def _set_bn(d, prefix, bn, count=False, replicas=None):
+    """Describe the batch norm `bn` = dict(stats, gamma, beta[, count, eps, replicas]) in the fields `prefix`_stats / _gamma /
+    _beta of descriptor `d`; count: also `prefix`_count / _eps; replicas: the name of d's replica-count field for these
+    statistics, where it has one.  bn None: the fields stay NULL / 0."""
+    if bn is None:
+        return
+    _dev(bn["stats"], bn["gamma"], bn["beta"])
+    for f in ("stats", "gamma", "beta"):
+        setattr(d, f"{prefix}_{f}", bn[f].data_ptr())
+    if count:
+        setattr(d, prefix + "_count", float(bn["count"]))
+        setattr(d, prefix + "_eps", float(bn.get("eps", 1e-5)))
+    if replicas:
+        setattr(d, replicas, int(bn.get("replicas", 0)))
 
 
 def conv_nhwc(x, w, KH, KW, stride, pad, out_dtype=None, bias=None, scale=None, shift=None,
@@ -52,31 +59,59 @@ def conv_nhwc(x, w, KH, KW, stride, pad, out_dtype=None, bias=None, scale=None, 
     if out is None:
         out = torch.empty(B, Ho, Wo, N, device=x.device, dtype=out_dtype)
     assert out.shape == (B, Ho, Wo, N) and out.dtype == out_dtype
-    d = ConvDesc(_p(x), _p(w), _p(out), _p(bias), _p(scale), _p(shift), _p(residual), _p(stats),
-                 dt_code(x), _DT[out_dtype], B, Hin, Win, Cin, Ho, Wo, N, KH, KW, stride, pad,
-                 Cin, w.shape[1], N, int(relu), int(accumulate), 0, int(k_order), int(stats_replicas))
-    if in_bn is not None:
-        _dev(in_bn["stats"], in_bn["gamma"], in_bn["beta"])
-        d.in_stats, d.in_gamma, d.in_beta = in_bn["stats"].data_ptr(), in_bn["gamma"].data_ptr(), in_bn["beta"].data_ptr()
-        d.in_count, d.in_eps = float(in_bn["count"]), float(in_bn.get("eps", 1e-5))
+    d = ConvDesc(x=_p(x), w=_p(w), y=_p(out), bias=_p(bias), scale=_p(scale), shift=_p(shift), residual=_p(residual), stats=_p(stats),
+                 dtype=dtype_code(x.dtype), out_dtype=_DT[out_dtype], B=B, Hin=Hin, Win=Win, Cin=Cin, Ho=Ho, Wo=Wo, N=N,
+                 KH=KH, KW=KW, stride=stride, pad=pad, ldx=Cin, ldw=w.shape[1], ldy=N, relu=int(relu), accumulate=int(accumulate),
+                 k_order=int(k_order), stats_replicas=int(stats_replicas))
+    _set_bn(d, "in", in_bn, count=True)
     check(lib().st_conv(C.byref(d), _stream()), "st_conv")
     return out
+
+
+def _s2d_images(images, dtype):
+    """(B,3,H,W) fp32 -> the stem's space-to-depth input (B, H/2+3, W/2+3, 16) (st_nchw_to_s2d16)."""
+    B, Cc, H, W = images.shape
+    assert Cc == 3 and images.dtype == torch.float32
+    xs = torch.empty(B, H // 2 + 3, W // 2 + 3, 16, device=images.device, dtype=dtype)
+    check(lib().st_nchw_to_s2d16(_p(images), _p(xs), _DT[dtype], B, H, W, _stream()), "st_nchw_to_s2d16")
+    return xs
+
+
+def stem_weight_s2d(w_packed, cpad, dtype):
+    """The (64, 7*7*cpad) k_order-0 stem filters as the (64, 256) operand of the space-to-depth route (st_stem_weight_s2d)."""
+    _dev(w_packed)
+    ws = torch.empty(64, 256, device=w_packed.device, dtype=dtype)
+    check(lib().st_stem_weight_s2d(_p(w_packed), _p(ws), _DT[dtype], cpad, _stream()), "st_stem_weight_s2d")
+    return ws
+
+
+def stem_weight_frag_from_s2d(ws):
+    """stem_weight_s2d's bf16 result in st_stem_conv_pool's fragment order (st_stem_weight_frag)."""
+    _dev(ws)
+    wf = torch.empty(64 * 256, device=ws.device, dtype=torch.bfloat16)
+    check(lib().st_stem_weight_frag(_p(ws), _p(wf), _stream()), "st_stem_weight_frag")
+    return wf
+
+
+def stem_weight_frag(w_packed, cpad):
+    """The same operand in one launch from the bf16 (64, 7*7*cpad) filters (st_stem_weight_frag_packed, as st_resnet_forward packs)."""
+    _dev(w_packed)
+    wf = torch.empty(64 * 256, device=w_packed.device, dtype=torch.bfloat16)
+    check(lib().st_stem_weight_frag_packed(_p(w_packed), int(cpad), _p(wf), _stream()), "st_stem_weight_frag_packed")
+    return wf
 
 
 def stem_conv_s2d(images, w_packed, cpad, dtype, stats=None, scale=None, shift=None, relu=False):
     """torchvision stem (7x7 s2 p3 over RGB, cnn.py:46) through the space-to-depth route: images (B,3,H,W) fp32 with
     even H, W; w_packed the usual (64, 7*7*cpad) k_order-0 weights.  Returns (B,H/2,W/2,64)."""
     _dev(images, w_packed, stats, scale, shift)
-    B, Cc, H, W = images.shape
-    assert Cc == 3 and images.dtype == torch.float32
-    xs = torch.empty(B, H // 2 + 3, W // 2 + 3, 16, device=images.device, dtype=dtype)
-    check(lib().st_nchw_to_s2d16(_p(images), _p(xs), _DT[dtype], B, H, W, _stream()), "st_nchw_to_s2d16")
-    ws = torch.empty(64, 256, device=images.device, dtype=dtype)
-    check(lib().st_stem_weight_s2d(_p(w_packed), _p(ws), _DT[dtype], cpad, _stream()), "st_stem_weight_s2d")
+    B, _, H, W = images.shape
+    xs = _s2d_images(images, dtype)
+    ws = stem_weight_s2d(w_packed, cpad, dtype)
     out = torch.empty(B, H // 2, W // 2, 64, device=images.device, dtype=dtype)
-    d = ConvDesc(_p(xs), _p(ws), _p(out), None, _p(scale), _p(shift), None, _p(stats),
-                 _DT[dtype], _DT[dtype], B, H // 2 + 3, W // 2 + 3, 64, H // 2, W // 2, 64, 4, 1, 1, 0,
-                 16, 256, 64, int(relu), 0, 36, 0, 0)
+    d = ConvDesc(x=_p(xs), w=_p(ws), y=_p(out), scale=_p(scale), shift=_p(shift), stats=_p(stats), dtype=_DT[dtype], out_dtype=_DT[dtype],
+                 B=B, Hin=H // 2 + 3, Win=W // 2 + 3, Cin=64, Ho=H // 2, Wo=W // 2, N=64, KH=4, KW=1, stride=1, pad=0,
+                 ldx=16, ldw=256, ldy=64, relu=int(relu), Cin_logical=36)
     check(lib().st_conv(C.byref(d), _stream()), "st_conv(s2d stem)")
     return out, xs, ws
 
@@ -86,43 +121,30 @@ def stem_conv_pool(images, w_packed, cpad, stats=None, stats_replicas=0, gamma=N
     w_packed the usual (64, 7*7*cpad) bf16 k_order-0 weights.  Train (gamma, stats): the pooled RAW output (max / min by sign(gamma));
     eval (scale, shift): maxpool(relu(conv * scale + shift)).  Returns (B, PH, PW, 64) bf16."""
     _dev(images, w_packed, stats, gamma, scale, shift)
-    B, Cc, H, W = images.shape
-    assert Cc == 3 and images.dtype == torch.float32
-    dt = torch.bfloat16
-    xs = torch.empty(B, H // 2 + 3, W // 2 + 3, 16, device=images.device, dtype=dt)
-    check(lib().st_nchw_to_s2d16(_p(images), _p(xs), _DT[dt], B, H, W, _stream()), "st_nchw_to_s2d16")
-    ws = torch.empty(64, 256, device=images.device, dtype=dt)
-    check(lib().st_stem_weight_s2d(_p(w_packed), _p(ws), _DT[dt], cpad, _stream()), "st_stem_weight_s2d")
-    wf = torch.empty(64 * 256, device=images.device, dtype=dt)
-    check(lib().st_stem_weight_frag(_p(ws), _p(wf), _stream()), "st_stem_weight_frag")
-    wf1 = torch.empty_like(wf)                     # the one-launch form st_resnet_forward uses: must be the same operands
-    check(lib().st_stem_weight_frag_packed(_p(w_packed), int(cpad), _p(wf1), _stream()), "st_stem_weight_frag_packed")
-    if not torch.equal(wf, wf1):
-        raise _lib.ShowTellHipError("st_stem_weight_frag_packed differs from st_stem_weight_frag(st_stem_weight_s2d(.))")
+    B, _, H, W = images.shape
+    xs = _s2d_images(images, torch.bfloat16)
+    wf = stem_weight_frag(w_packed, cpad)
     PH, PW = (H // 2 - 1) // 2 + 1, (W // 2 - 1) // 2 + 1
-    out = torch.empty(B, PH, PW, 64, device=images.device, dtype=dt)
-    d = StemConvPoolDesc(_p(xs), _p(wf), _p(out), _p(stats), int(stats_replicas), _p(gamma), _p(scale), _p(shift), B, H, W)
+    out = torch.empty(B, PH, PW, 64, device=images.device, dtype=torch.bfloat16)
+    d = StemConvPoolDesc(x_s2d=_p(xs), w_frag=_p(wf), y=_p(out), stats=_p(stats), stats_replicas=int(stats_replicas), gamma=_p(gamma),
+                         scale=_p(scale), shift=_p(shift), B=B, H=H, W=W)
     check(lib().st_stem_conv_pool(C.byref(d), _stream()), "st_stem_conv_pool")
     return out
+
+
+def _gemm_desc(a, w, out, K, lda, ldw, **fields):
+    return ConvDesc(x=_p(a), w=_p(w), y=_p(out), dtype=dtype_code(a.dtype), out_dtype=_DT[out.dtype], B=a.shape[0], Hin=1, Win=1, Cin=K,
+                    Ho=1, Wo=1, N=w.shape[0], KH=1, KW=1, stride=1, pad=0, ldx=lda, ldw=ldw, ldy=out.stride(0), **fields)
 
 
 def gemm_nt(a, w, out_dtype=None, bias=None, out=None, accumulate=False, stats=None, relu=False,
             lda=None, ldw=None, K=None, split_k=0):
     """y[M,N] = a[M,K] @ w[N,K]^T (+bias).  a, w may carry padded leading dimensions."""
     _dev(a, w, bias, out, stats)
-    M = a.shape[0]
-    N = w.shape[0]
-    lda = lda or a.stride(0)
-    ldw = ldw or w.stride(0)
-    K = K or a.shape[1]
-    out_dtype = out_dtype or a.dtype
     if out is None:
-        out = torch.empty(M, N, device=a.device, dtype=out_dtype)
-    ldy = out.stride(0)
-    d = ConvDesc(_p(a), _p(w), _p(out), _p(bias), None, None, None, _p(stats),
-                 dt_code(a), _DT[out.dtype], M, 1, 1, K, 1, 1, N, 1, 1, 1, 0,
-                 lda, ldw, ldy, int(relu), int(accumulate), 0, 0)
-    d.split_k = int(split_k)
+        out = torch.empty(a.shape[0], w.shape[0], device=a.device, dtype=out_dtype or a.dtype)
+    d = _gemm_desc(a, w, out, K or a.shape[1], lda or a.stride(0), ldw or w.stride(0), bias=_p(bias), stats=_p(stats),
+                   relu=int(relu), accumulate=int(accumulate), split_k=int(split_k))
     check(lib().st_conv(C.byref(d), _stream()), "st_conv(gemm)")
     return out
 
@@ -133,10 +155,7 @@ def gemm_nt_batch(As, Ws, outs, accumulate=False):
     arr = (ConvDesc * n)()
     for i, (a, w, o) in enumerate(zip(As, Ws, outs)):
         _dev(a, w, o)
-        M, K = a.shape
-        N = w.shape[0]
-        arr[i] = ConvDesc(_p(a), _p(w), _p(o), None, None, None, None, None, dt_code(a), _DT[o.dtype], M, 1, 1, K, 1, 1, N, 1, 1, 1, 0,
-                          a.stride(0), w.stride(0), o.stride(0), 0, int(accumulate), 0, 0, 0)
+        arr[i] = _gemm_desc(a, w, o, a.shape[1], a.stride(0), w.stride(0), accumulate=int(accumulate))
     check(lib().st_conv_batch(arr, n, _stream()), "st_conv_batch")
     return outs
 
@@ -152,10 +171,11 @@ def bn_act(x, gamma, beta, stats=None, running=None, count=1.0, eps=1e-5, relu=T
     rm, rv = running if running is not None else (None, None)
     rb = res_bn or {}
     rrm, rrv = rb.get("running", (None, None))
-    d = BnActDesc(_p(x), _p(out), _p(res), _p(stats), _p(gamma), _p(beta), _p(rm), _p(rv),
-                  _p(rb.get("stats")), _p(rb.get("gamma")), _p(rb.get("beta")), _p(rrm), _p(rrv),
-                  int(res_bn is not None), dt_code(x), rows, Cc, float(count), float(eps), int(relu),
-                  int(stats_replicas), int(rb.get("stats_replicas", 0)))
+    d = BnActDesc(x=_p(x), y=_p(out), res=_p(res), stats=_p(stats), gamma=_p(gamma), beta=_p(beta), running_mean=_p(rm), running_var=_p(rv),
+                  res_stats=_p(rb.get("stats")), res_gamma=_p(rb.get("gamma")), res_beta=_p(rb.get("beta")),
+                  res_running_mean=_p(rrm), res_running_var=_p(rrv), res_bn=int(res_bn is not None), dtype=dtype_code(x.dtype),
+                  rows=rows, C=Cc, count=float(count), eps=float(eps), relu=int(relu),
+                  stats_replicas=int(stats_replicas), res_stats_replicas=int(rb.get("stats_replicas", 0)))
     check(lib().st_bn_act(C.byref(d), _stream()), "st_bn_act")
     return out
 
@@ -179,7 +199,7 @@ def nhwc_to_ncp_f32(x):
     _dev(x)
     B, H, W, Cc = x.shape
     y = torch.empty(B, Cc, H * W, device=x.device, dtype=torch.float32)
-    check(lib().st_nhwc_to_ncp_f32(_p(x), _p(y), dt_code(x), B, H * W, Cc, _stream()), "st_nhwc_to_ncp_f32")
+    check(lib().st_nhwc_to_ncp_f32(_p(x), _p(y), dtype_code(x.dtype), B, H * W, Cc, _stream()), "st_nhwc_to_ncp_f32")
     return y
 
 
@@ -188,7 +208,7 @@ def maxpool3x3s2(x):
     B, H, W, Cc = x.shape
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     y = torch.empty(B, Ho, Wo, Cc, device=x.device, dtype=x.dtype)
-    check(lib().st_maxpool3x3s2(_p(x), _p(y), dt_code(x), B, H, W, Cc, _stream()), "st_maxpool3x3s2")
+    check(lib().st_maxpool3x3s2(_p(x), _p(y), dtype_code(x.dtype), B, H, W, Cc, _stream()), "st_maxpool3x3s2")
     return y
 
 
@@ -199,7 +219,7 @@ def maxpool3x3s2_bn(x, gamma, beta, stats=None, running=None, count=1.0, eps=1e-
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     y = torch.empty(B, Ho, Wo, Cc, device=x.device, dtype=x.dtype)
     rm, rv = running if running is not None else (None, None)
-    check(lib().st_maxpool3x3s2_bn(_p(x), _p(y), dt_code(x), B, H, W, Cc, _p(stats), _p(gamma), _p(beta), _p(rm), _p(rv),
+    check(lib().st_maxpool3x3s2_bn(_p(x), _p(y), dtype_code(x.dtype), B, H, W, Cc, _p(stats), _p(gamma), _p(beta), _p(rm), _p(rv),
                                    float(count), float(eps), _stream()), "st_maxpool3x3s2_bn")
     return y
 
@@ -209,7 +229,7 @@ def global_avgpool(x, out_dtype=None):
     B, H, W, Cc = x.shape
     out_dtype = out_dtype or x.dtype
     y = torch.empty(B, Cc, device=x.device, dtype=out_dtype)
-    check(lib().st_global_avgpool(_p(x), _p(y), dt_code(x), _DT[out_dtype], B, H * W, Cc, _stream()), "st_global_avgpool")
+    check(lib().st_global_avgpool(_p(x), _p(y), dtype_code(x.dtype), _DT[out_dtype], B, H * W, Cc, _stream()), "st_global_avgpool")
     return y
 
 
@@ -217,7 +237,7 @@ def cast(x, dtype, out=None):
     _dev(x, out)
     if out is None:
         out = torch.empty(x.shape, device=x.device, dtype=dtype)
-    check(lib().st_cast(_p(x), _p(out), dt_code(x), _DT[dtype], x.numel(), _stream()), "st_cast")
+    check(lib().st_cast(_p(x), _p(out), dtype_code(x.dtype), _DT[dtype], x.numel(), _stream()), "st_cast")
     return out
 
 
@@ -228,7 +248,7 @@ def transpose(x, ldy=None, out=None, colsum=None):
     ldy = ldy or rows
     if out is None:
         out = torch.empty(cols, ldy, device=x.device, dtype=x.dtype)
-    check(lib().st_transpose_colsum(_p(x), _p(out), _p(colsum), dt_code(x), rows, cols, x.stride(0), ldy, _stream()),
+    check(lib().st_transpose_colsum(_p(x), _p(out), _p(colsum), dtype_code(x.dtype), rows, cols, x.stride(0), ldy, _stream()),
           "st_transpose_colsum")
     return out
 
@@ -246,23 +266,25 @@ def conv3x3_img_supported(H, W, C, N):
     return int(lib().st_conv3x3_img_supported(H, W, C, N))
 
 
-def conv3x3_img(x, w_frag, N, stats=None, stats_replicas=0, scale=None, shift=None, relu=False, in_bn=None, out=None):
-    """Image-resident 3x3 s1 p1 conv (st_conv3x3_img): x (B,H,W,C) bf16 NHWC, w_frag from pack_conv_weight_frag."""
+def _conv3x3(entry, name, out_hw, x, w_frag, N, stats, stats_replicas, scale, shift, relu, in_bn, out):
+    """conv3x3_img and conv3x3_s2: one descriptor type, `entry` and the output's (Ho, Wo) differ."""
     _dev(x, w_frag, stats, scale, shift, out)
     B, H, W, Cc = x.shape
     if x.dtype != torch.bfloat16:
-        raise _lib.ShowTellHipError("conv3x3_img is a bf16 kernel")
+        raise _lib.ShowTellHipError(f"{name} is a bf16 kernel")
     if out is None:
-        out = torch.empty(B, H, W, N, device=x.device, dtype=torch.bfloat16)
-    d = Conv3x3ImgDesc(_p(x), _p(w_frag), _p(out), _p(stats), int(stats_replicas), _p(scale), _p(shift), int(relu),
-                       None, None, None, 0.0, 0.0, B, H, W, Cc, N, 0)
-    if in_bn is not None:
-        _dev(in_bn["stats"], in_bn["gamma"], in_bn["beta"])
-        d.in_stats, d.in_gamma, d.in_beta = in_bn["stats"].data_ptr(), in_bn["gamma"].data_ptr(), in_bn["beta"].data_ptr()
-        d.in_count, d.in_eps = float(in_bn["count"]), float(in_bn.get("eps", 1e-5))
-        d.in_stats_replicas = int(in_bn.get("replicas", 0))
-    check(lib().st_conv3x3_img(C.byref(d), _stream()), "st_conv3x3_img")
+        out = torch.empty(B, *out_hw(H, W), N, device=x.device, dtype=torch.bfloat16)
+    d = Conv3x3ImgDesc(x=_p(x), w_frag=_p(w_frag), y=_p(out), stats=_p(stats), stats_replicas=int(stats_replicas), scale=_p(scale),
+                       shift=_p(shift), relu=int(relu), B=B, H=H, W=W, C=Cc, N=N)
+    _set_bn(d, "in", in_bn, count=True, replicas="in_stats_replicas")
+    check(entry(C.byref(d), _stream()), "st_" + name)
     return out
+
+
+def conv3x3_img(x, w_frag, N, stats=None, stats_replicas=0, scale=None, shift=None, relu=False, in_bn=None, out=None):
+    """Image-resident 3x3 s1 p1 conv (st_conv3x3_img): x (B,H,W,C) bf16 NHWC, w_frag from pack_conv_weight_frag."""
+    return _conv3x3(lib().st_conv3x3_img, "conv3x3_img", lambda H, W: (H, W),
+                    x, w_frag, N, stats, stats_replicas, scale, shift, relu, in_bn, out)
 
 
 def conv3x3_s2_supported(Cin, N):
@@ -271,20 +293,24 @@ def conv3x3_s2_supported(Cin, N):
 
 def conv3x3_s2(x, w_frag, N, stats=None, stats_replicas=0, scale=None, shift=None, relu=False, in_bn=None, out=None):
     """K-streaming 3x3 stride-2 pad-1 conv (st_conv3x3_s2): x (B,H,W,C) bf16 NHWC, w_frag = pack_conv_weight_frag(w, conv3x3_s2_supported(C, N))."""
-    _dev(x, w_frag, stats, scale, shift, out)
+    return _conv3x3(lib().st_conv3x3_s2, "conv3x3_s2", lambda H, W: ((H - 1) // 2 + 1, (W - 1) // 2 + 1),
+                    x, w_frag, N, stats, stats_replicas, scale, shift, relu, in_bn, out)
+
+
+def _conv1x1(entry, name, x, w_frag, N, stride, stats, stats_replicas, scale, shift, relu, out, residual=None, in_bn=None,
+             stats_only=False):
+    """conv1x1_wreg, conv1x1_astat and conv1x1_kstream: one descriptor type, `entry` and the optional arguments each takes differ.
+    stats_only: y == NULL -- only the [sum | sumsq] statistics of the output are produced (returns None)."""
+    _dev(x, w_frag, stats, scale, shift, residual, out)
     B, H, W, Cc = x.shape
     if x.dtype != torch.bfloat16:
-        raise _lib.ShowTellHipError("conv3x3_s2 is a bf16 kernel")
-    if out is None:
-        out = torch.empty(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, N, device=x.device, dtype=torch.bfloat16)
-    d = Conv3x3ImgDesc(_p(x), _p(w_frag), _p(out), _p(stats), int(stats_replicas), _p(scale), _p(shift), int(relu),
-                       None, None, None, 0.0, 0.0, B, H, W, Cc, N, 0)
-    if in_bn is not None:
-        _dev(in_bn["stats"], in_bn["gamma"], in_bn["beta"])
-        d.in_stats, d.in_gamma, d.in_beta = in_bn["stats"].data_ptr(), in_bn["gamma"].data_ptr(), in_bn["beta"].data_ptr()
-        d.in_count, d.in_eps = float(in_bn["count"]), float(in_bn.get("eps", 1e-5))
-        d.in_stats_replicas = int(in_bn.get("replicas", 0))
-    check(lib().st_conv3x3_s2(C.byref(d), _stream()), "st_conv3x3_s2")
+        raise _lib.ShowTellHipError(f"{name} is a bf16 kernel")
+    if out is None and not stats_only:
+        out = torch.empty(B, (H - 1) // stride + 1, (W - 1) // stride + 1, N, device=x.device, dtype=torch.bfloat16)
+    d = Conv1x1WregDesc(x=_p(x), w_frag=_p(w_frag), y=_p(out), residual=_p(residual), stats=_p(stats), stats_replicas=int(stats_replicas),
+                        scale=_p(scale), shift=_p(shift), relu=int(relu), B=B, Hin=H, Win=W, C=Cc, N=N, stride=int(stride))
+    _set_bn(d, "in", in_bn, count=True, replicas="in_stats_replicas")
+    check(entry(C.byref(d), _stream()), "st_" + name)
     return out
 
 
@@ -296,22 +322,8 @@ def conv1x1_wreg(x, w_frag, N, stride=1, stats=None, stats_replicas=0, scale=Non
                  stats_only=False):
     """Register-resident-filter 1x1 conv (st_conv1x1_wreg): x (B,H,W,C) bf16 NHWC, w_frag from pack_conv_weight_frag(w (N,C,1,1)).
     stats_only: y == NULL -- only the [sum | sumsq] statistics of the output are produced (returns None)."""
-    _dev(x, w_frag, stats, scale, shift, residual, out)
-    B, H, W, Cc = x.shape
-    if x.dtype != torch.bfloat16:
-        raise _lib.ShowTellHipError("conv1x1_wreg is a bf16 kernel")
-    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    if out is None and not stats_only:
-        out = torch.empty(B, Ho, Wo, N, device=x.device, dtype=torch.bfloat16)
-    d = Conv1x1WregDesc(_p(x), _p(w_frag), _p(out), _p(residual), _p(stats), int(stats_replicas), _p(scale), _p(shift), int(relu),
-                        None, None, None, 0.0, 0.0, 0, B, H, W, Cc, N, int(stride))
-    if in_bn is not None:
-        _dev(in_bn["stats"], in_bn["gamma"], in_bn["beta"])
-        d.in_stats, d.in_gamma, d.in_beta = in_bn["stats"].data_ptr(), in_bn["gamma"].data_ptr(), in_bn["beta"].data_ptr()
-        d.in_count, d.in_eps = float(in_bn["count"]), float(in_bn.get("eps", 1e-5))
-        d.in_stats_replicas = int(in_bn.get("replicas", 0))
-    check(lib().st_conv1x1_wreg(C.byref(d), _stream()), "st_conv1x1_wreg")
-    return out
+    return _conv1x1(lib().st_conv1x1_wreg, "conv1x1_wreg", x, w_frag, N, stride, stats, stats_replicas, scale, shift, relu, out,
+                    residual, in_bn, stats_only)
 
 
 def conv1x1_kfuse_supported(Cin, N):
@@ -321,19 +333,16 @@ def conv1x1_kfuse_supported(Cin, N):
 def conv1x1_kfuse(raw, identity, w_frag, bn, N=256, id_bn=None, stats=None, stats_replicas=0, x_out=None, out=None, eight_waves=False):
     """st_conv1x1_kfuse: x = relu(bn(raw) + identity) (written to x_out; identity normalised with id_bn first when given),
     y = conv1x1(x) (C -> N).  bn / id_bn = dict(stats, gamma, beta[, count, eps, replicas]).  Returns (x_out, y)."""
-    _dev(raw, identity, w_frag, stats, x_out, out, bn["stats"], bn["gamma"], bn["beta"])
+    _dev(raw, identity, w_frag, stats, x_out, out)
     rows = raw.numel() // raw.shape[-1]
     if x_out is None:
         x_out = torch.empty_like(raw)
     if out is None:
         out = torch.empty(*raw.shape[:-1], N, device=raw.device, dtype=torch.bfloat16)
-    d = Conv1x1KfuseDesc(_p(raw), _p(identity), _p(x_out), _p(w_frag), _p(out), _p(stats), int(stats_replicas), _p(bn["stats"]), _p(bn["gamma"]),
-                         _p(bn["beta"]), float(bn["count"]), float(bn.get("eps", 1e-5)), int(bn.get("replicas", 0)), rows, raw.shape[-1], N,
-                         None, None, None, 0)
-    if id_bn is not None:
-        _dev(id_bn["stats"], id_bn["gamma"], id_bn["beta"])
-        d.id_stats, d.id_gamma, d.id_beta = id_bn["stats"].data_ptr(), id_bn["gamma"].data_ptr(), id_bn["beta"].data_ptr()
-        d.id_stats_replicas = int(id_bn.get("replicas", 0))
+    d = Conv1x1KfuseDesc(raw=_p(raw), identity=_p(identity), x_out=_p(x_out), w_frag=_p(w_frag), y=_p(out), stats=_p(stats),
+                         stats_replicas=int(stats_replicas), rows=rows, C=raw.shape[-1], N=N)
+    _set_bn(d, "f", bn, count=True, replicas="f_stats_replicas")
+    _set_bn(d, "id", id_bn, replicas="id_stats_replicas")
     if eight_waves:
         check(lib().st_conv1x1_kfuse8(C.byref(d), _stream()), "st_conv1x1_kfuse8")
     else:
@@ -346,17 +355,15 @@ def conv_b2b(raw2, w3_frag, identity, w1_frag, N, bn2, bn3, count, id_bn=None, e
     bn2 / bn3 / id_bn = dict(stats, gamma, beta[, replicas]).  Returns (x_out, y)."""
     _dev(raw2, w3_frag, identity, w1_frag, stats, x_out, out)
     rows = raw2.numel() // raw2.shape[-1]
-    C1, C2 = raw2.shape[-1], identity.shape[-1]
     if x_out is None:
         x_out = torch.empty_like(identity)
     if out is None and N > 0:
         out = torch.empty(*raw2.shape[:-1], N, device=raw2.device, dtype=torch.bfloat16)
-    ib = id_bn or {}
-    d = ConvB2bDesc(_p(raw2), _p(w3_frag), _p(identity), _p(x_out), _p(w1_frag), _p(out), _p(stats), int(stats_replicas),
-                    _p(bn2["stats"]), _p(bn2["gamma"]), _p(bn2["beta"]), int(bn2.get("replicas", 0)),
-                    _p(bn3["stats"]), _p(bn3["gamma"]), _p(bn3["beta"]), int(bn3.get("replicas", 0)),
-                    _p(ib.get("stats")), _p(ib.get("gamma")), _p(ib.get("beta")), int(ib.get("replicas", 0)),
-                    float(count), float(eps), rows, C1, C2, N)
+    d = ConvB2bDesc(raw2=_p(raw2), w3_frag=_p(w3_frag), identity=_p(identity), x_out=_p(x_out), w1_frag=_p(w1_frag), y=_p(out),
+                    stats=_p(stats), stats_replicas=int(stats_replicas), count=float(count), eps=float(eps),
+                    rows=rows, C1=raw2.shape[-1], C2=identity.shape[-1], N=N)
+    for prefix, bn in (("bn2", bn2), ("bn3", bn3), ("id", id_bn)):
+        _set_bn(d, prefix, bn, replicas=prefix + "_replicas")
     check(lib().st_conv_b2b(C.byref(d), _stream()), "st_conv_b2b")
     return x_out, out
 
@@ -366,27 +373,18 @@ def conv_c3c1(x2, w3_frag, identity, w1_frag, bn2=None, bn3=None, count=None, ep
     """st_conv_c3c1: x = relu(bn3(conv3(a2)) + identity) (-> x_out), y = conv1_next(x) for the 14 x 14 Bottlenecks (256 -> 1024 -> 256)
     and the 28 x 28 ones (128 -> 512 -> 128).
     train: bn3 = dict(stats, gamma, beta[, replicas]) (+ bn2 for a raw x2), count; eval: scale3 / shift3 / scale1 / shift1.  Returns (x_out, y)."""
-    from ._lib import ConvC3c1Desc
     _dev(x2, w3_frag, identity, w1_frag, stats, x_out, out, scale3, shift3, scale1, shift1)
     rows = x2.numel() // x2.shape[-1]
     if x_out is None:
         x_out = torch.empty_like(identity)
     if out is None:
         out = torch.empty(*x2.shape[:-1], x2.shape[-1], device=x2.device, dtype=torch.bfloat16)
-    d = ConvC3c1Desc()
-    d.x2, d.w3_frag, d.identity, d.x_out, d.w1_frag, d.y = x2.data_ptr(), w3_frag.data_ptr(), identity.data_ptr(), x_out.data_ptr(), w1_frag.data_ptr(), out.data_ptr()
-    d.stats, d.stats_replicas = (stats.data_ptr() if stats is not None else None), int(stats_replicas)
-    for nm, bn in (("bn2", bn2), ("bn3", bn3), ("id", id_bn)):
-        if bn is not None:
-            _dev(bn["stats"], bn["gamma"], bn["beta"])
-            setattr(d, nm + "_stats", bn["stats"].data_ptr()); setattr(d, nm + "_gamma", bn["gamma"].data_ptr()); setattr(d, nm + "_beta", bn["beta"].data_ptr())
-            setattr(d, nm + "_replicas", int(bn.get("replicas", 0)))
-    d.count, d.eps = float(count or 0.0), float(eps)
-    for nm, t in (("scale3", scale3), ("shift3", shift3), ("scale1", scale1), ("shift1", shift1)):
-        if t is not None:
-            setattr(d, nm, t.data_ptr())
-    d.relu1 = int(relu1)
-    d.rows, d.C1, d.C2, d.N = rows, x2.shape[-1], identity.shape[-1], out.shape[-1]
+    d = ConvC3c1Desc(x2=_p(x2), w3_frag=_p(w3_frag), identity=_p(identity), x_out=_p(x_out), w1_frag=_p(w1_frag), y=_p(out),
+                     stats=_p(stats), stats_replicas=int(stats_replicas), count=float(count or 0.0), eps=float(eps),
+                     scale3=_p(scale3), shift3=_p(shift3), scale1=_p(scale1), shift1=_p(shift1), relu1=int(relu1),
+                     rows=rows, C1=x2.shape[-1], C2=identity.shape[-1], N=out.shape[-1])
+    for prefix, bn in (("bn2", bn2), ("bn3", bn3), ("id", id_bn)):
+        _set_bn(d, prefix, bn, replicas=prefix + "_replicas")
     check(lib().st_conv_c3c1(C.byref(d), _stream()), "st_conv_c3c1")
     return x_out, out
 
@@ -399,20 +397,8 @@ def conv1x1_astat(x, w_frag, N, stride=1, stats=None, stats_replicas=0, scale=No
                   stats_only=False):
     """Activation-stationary 1x1 conv (st_conv1x1_astat): stride 1 with (C, N) in {(256, 1024), (512, 2048)}, stride 2 with (256, 512) /
     (512, 1024); w_frag = pack_conv_weight_frag(w, conv1x1_astat_supported(C, N))."""
-    _dev(x, w_frag, stats, scale, shift, out, residual)
-    B, H, W, Cc = x.shape
-    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    if out is None and not stats_only:                  # stats_only: y == NULL, only the [sum | sumsq] statistics are produced
-        out = torch.empty(B, Ho, Wo, N, device=x.device, dtype=torch.bfloat16)
-    d = Conv1x1WregDesc(_p(x), _p(w_frag), _p(out), _p(residual), _p(stats), int(stats_replicas), _p(scale), _p(shift), int(relu),
-                        None, None, None, 0.0, 0.0, 0, B, H, W, Cc, N, int(stride))
-    if in_bn is not None:
-        _dev(in_bn["stats"], in_bn["gamma"], in_bn["beta"])
-        d.in_stats, d.in_gamma, d.in_beta = in_bn["stats"].data_ptr(), in_bn["gamma"].data_ptr(), in_bn["beta"].data_ptr()
-        d.in_count, d.in_eps = float(in_bn["count"]), float(in_bn.get("eps", 1e-5))
-        d.in_stats_replicas = int(in_bn.get("replicas", 0))
-    check(lib().st_conv1x1_astat(C.byref(d), _stream()), "st_conv1x1_astat")
-    return out
+    return _conv1x1(lib().st_conv1x1_astat, "conv1x1_astat", x, w_frag, N, stride, stats, stats_replicas, scale, shift, relu, out,
+                    residual, in_bn, stats_only)
 
 
 def conv1x1_kstream_supported(Cin, N):
@@ -421,15 +407,7 @@ def conv1x1_kstream_supported(Cin, N):
 
 def conv1x1_kstream(x, w_frag, N, stride=1, stats=None, stats_replicas=0, scale=None, shift=None, relu=False, out=None):
     """Long-K 1x1 conv (st_conv1x1_kstream): x (B,H,W,C) bf16 NHWC with C in {1024, 2048}, w_frag = pack_conv_weight_frag(w, 4)."""
-    _dev(x, w_frag, stats, scale, shift, out)
-    B, H, W, Cc = x.shape
-    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    if out is None:
-        out = torch.empty(B, Ho, Wo, N, device=x.device, dtype=torch.bfloat16)
-    d = Conv1x1WregDesc(_p(x), _p(w_frag), _p(out), None, _p(stats), int(stats_replicas), _p(scale), _p(shift), int(relu),
-                        None, None, None, 0.0, 0.0, 0, B, H, W, Cc, N, int(stride))
-    check(lib().st_conv1x1_kstream(C.byref(d), _stream()), "st_conv1x1_kstream")
-    return out
+    return _conv1x1(lib().st_conv1x1_kstream, "conv1x1_kstream", x, w_frag, N, stride, stats, stats_replicas, scale, shift, relu, out)
 
 
 def pack_conv_weight(w, dtype, cpad=None, k_order=0):

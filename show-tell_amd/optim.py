@@ -6,13 +6,11 @@ All parameters handed to the optimizer are moved into one flat fp32 buffer (each
 also refreshes the bf16 shadow copies the MFMA kernels read, and a data-parallel job can
 all-reduce the flat gradient in a few large messages (see parallel.py).
 """
-import ctypes as C
-import math
-
 import torch
 
 from ._lib import check, lib
-from .rnn import _cp, _stream
+from ._lib import ptr as _cp, stream as _stream
+from ._weights import adopt_working_copy
 
 
 class _FlatOptimizer:
@@ -74,7 +72,7 @@ class _FlatOptimizer:
 
     def _sync_shadow(self, initial=False):
         """The step kernels write the flat buffer through a raw pointer: bump every parameter's version so that whatever is
-        keyed on it (rnn.working_copy's per-parameter bf16 copy when this optimizer owns no shadow) sees the new values.  With
+        keyed on it (_weights.working_copy's per-parameter bf16 copy when this optimizer owns no shadow) sees the new values.  With
         a shadow of its own, the kernels' working copies are then re-pointed at it (the step kernel has refreshed it)."""
         if self.shadow is not None and initial:
             from . import ops
@@ -82,8 +80,7 @@ class _FlatOptimizer:
         for p, o in zip(self.params, self.offsets):
             torch.autograd.graph.increment_version(p)
             if self.shadow is not None:
-                p._st_shadow = self.shadow[o:o + p.numel()].view(p.shape)
-                p._st_shadow_ver, p._st_shadow_ptr = p._version, p.data_ptr()
+                adopt_working_copy(p, self.shadow[o:o + p.numel()].view(p.shape))
 
     def zero_grad(self, set_to_none=False):
         """Gradients stay views of the flat buffer (the all-reduce target); `set_to_none` is accepted and ignored."""

@@ -23,57 +23,14 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from ._lib import ST_BF16, ST_CELL_GRU, ST_CELL_LSTM, ST_F32, RnnGrads, RnnParams, check, lib
+from ._lib import ST_CELL_GRU, ST_CELL_LSTM, ST_F32, RnnGrads, RnnParams, check, dtype_code, lib
+from ._lib import ptr as _cp, stream as _stream  # noqa: F401  (tests and tools import these names from here)
+from ._weights import FollowsMoves, grad_buffer, working_copy  # noqa: F401  (rnn.working_copy stays importable)
 from .seq import plan_for
 
 CAP_MAX = 25  # rnn.py:39
 
-
-def _cp(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def working_copy(p, dtype):
-    """The tensor the kernels read for parameter `p`: itself in fp32 mode, a cached bf16
-    shadow otherwise (refreshed when the parameter was modified or moved)."""
-    if dtype == torch.float32:
-        return p.data
-    sh = getattr(p, "_st_shadow", None)
-    if (sh is None or sh.device != p.device or getattr(p, "_st_shadow_ver", -1) != p._version
-            or getattr(p, "_st_shadow_ptr", 0) != p.data_ptr()):
-        if sh is None or sh.device != p.device or sh.shape != p.shape:
-            sh = torch.empty(p.shape, device=p.device, dtype=dtype)
-        ops.cast(p.data.contiguous(), dtype, out=sh)
-        p._st_shadow, p._st_shadow_ver, p._st_shadow_ptr = sh, p._version, p.data_ptr()
-    return sh
-
-
-def storage_places(module):
-    """(device, address) of every parameter of `module`, to be taken before Module._apply"""
-    return [(p.device, p.data_ptr()) for p in module.parameters()]
-
-
-def drop_moved_working_copies(module, places):
-    """After Module._apply (.cuda() / .cpu() / .to()), with `places` = storage_places(module) from before it: forget the
-    working copy of every parameter whose storage moved.  working_copy alone cannot be relied on here: a round trip
-    .cpu() -> .cuda() leaves the version counter where it was and the caching allocator hands the block it freed back at
-    the same address, so weights written on the host in between (through `.data`, as the reference initialises its layers)
-    would be invisible.  Host-side, and only when a module is moved."""
-    for p, place in zip(module.parameters(), places):
-        if (p.device, p.data_ptr()) != place:
-            for attr in ("_st_shadow", "_st_shadow_ver", "_st_shadow_ptr"):
-                if hasattr(p, attr):
-                    delattr(p, attr)
-
-
-def grad_buffer(p):
-    if p.grad is None:
-        p.grad = torch.zeros_like(p.data, dtype=torch.float32)
-    return p.grad
+_LAYER_NAMES = [tuple(f"{n}_l{l}" for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")) for l in range(_lib.ST_MAX_LAYERS)]
 
 
 def up8(v):
@@ -111,6 +68,33 @@ def sample_lengths(ids, end_id):
     return (before + 1).clamp(max=ids.shape[-1])
 
 
+def ce_loss(logits, dt, targets, n, V, Vp, loss):
+    """loss += mean cross entropy of the (n, Vp) logits rows (V valid columns) against `targets`."""
+    check(lib().st_cross_entropy(_cp(logits), dtype_code(dt), _cp(targets), n, V, Vp, _cp(loss), None, 0, Vp, 1.0, None, _stream()),
+          "st_cross_entropy")
+
+
+def ce_loss_backward(logits, dt, targets, n, V, Vp, gout):
+    """The saved logits of ce_loss, overwritten in place by (softmax - onehot) * dLoss / N_tok.  Returns (dlogits, dLoss as the
+    fp32 device scalar the kernel read)."""
+    gsc = gout.detach().float().contiguous()
+    dtc = dtype_code(dt)
+    check(lib().st_cross_entropy(_cp(logits), dtc, _cp(targets), n, V, Vp, None, _cp(logits), dtc, Vp, 1.0, _cp(gsc), _stream()),
+          "st_cross_entropy(bwd)")
+    return logits, gsc
+
+
+def logits_grad(gout, dt, n, V, Vp, alloc):
+    """mode 'logits' backward: the caller's (n, V) gradient as the (n, Vp) `dt` rows the backward GEMMs read (st_cast2d);
+    `alloc` (torch.zeros / torch.empty) makes them."""
+    g = gout if gout.dtype == torch.float32 else gout.float()
+    if g.stride(1) != 1:
+        g = g.contiguous()
+    dlog = alloc(n, Vp, device=g.device, dtype=dt)
+    check(lib().st_cast2d(_cp(g), _cp(dlog), ST_F32, dtype_code(dt), n, V, g.stride(0), Vp, _stream()), "st_cast2d")
+    return dlog
+
+
 class _DecoderFn(torch.autograd.Function):
     """mode 'logits': returns fp32 logits rows; mode 'loss': returns the mean cross entropy."""
 
@@ -125,8 +109,7 @@ class _DecoderFn(torch.autograd.Function):
         seq = plan.c_struct(caption)
         prm, keep = m._c_params()
         dt = m.compute_dtype
-        featd = feat.detach().contiguous()
-        featd = featd if featd.dtype == dt else ops.cast(featd.float(), dt)
+        featd = m._feature(feat)
         nbytes = lib().st_rnn_workspace_bytes(C.byref(prm), C.byref(seq))
         ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
         V, Vp, n = m.vocab_size, lib().st_rnn_vocab_ld(m.vocab_size), plan.ntok
@@ -134,10 +117,10 @@ class _DecoderFn(torch.autograd.Function):
         # mode 'loss' in bf16: the vocabulary projection and the cross entropy run tile by tile without a logits tensor (csrc/vocab_ce.hip);
         # ST_FUSED_CE=0 keeps st_rnn_forward's logits + st_cross_entropy
         fused = mode == "loss" and os.environ.get("ST_FUSED_CE", "1") != "0" and bool(lib().st_rnn_fused_loss_supported(C.byref(prm)))
-        logits = None if fused else torch.empty(n, Vp, device=dev, dtype=torch.float32 if mode == "logits" else dt)
-        check(lib().st_rnn_forward(C.byref(prm), C.byref(seq), None, _cp(featd), _cp(ws), nbytes, _cp(logits),
-                                   ST_F32 if (logits is not None and logits.dtype == torch.float32) else ST_BF16, Vp, _cp(targets),
-                                   int(need_grad), _stream()), "st_rnn_forward")
+        ldt = torch.float32 if mode == "logits" else dt
+        logits = None if fused else torch.empty(n, Vp, device=dev, dtype=ldt)
+        check(lib().st_rnn_forward(C.byref(prm), C.byref(seq), None, _cp(featd), _cp(ws), nbytes, _cp(logits), dtype_code(ldt), Vp,
+                                   _cp(targets), int(need_grad), _stream()), "st_rnn_forward")
         ctx.m, ctx.plan, ctx.caption, ctx.ws, ctx.mode, ctx.keep = m, plan, caption, ws, mode, keep
         ctx.feat_dtype = feat.dtype
         ctx.fused = fused
@@ -151,8 +134,7 @@ class _DecoderFn(torch.autograd.Function):
                   "st_rnn_fused_loss")
             ctx.logits, ctx.targets, ctx.scratch = None, targets, scratch
             return loss
-        check(lib().st_cross_entropy(_cp(logits), ST_F32 if dt == torch.float32 else ST_BF16, _cp(targets), n, V, Vp,
-                                     _cp(loss), None, 0, Vp, 1.0, None, _stream()), "st_cross_entropy")
+        ce_loss(logits, dt, targets, n, V, Vp, loss)
         ctx.logits, ctx.targets = logits, targets
         return loss
 
@@ -161,30 +143,19 @@ class _DecoderFn(torch.autograd.Function):
         m, plan = ctx.m, ctx.plan
         dev = gout.device
         dt = m.compute_dtype
-        dtc = ST_F32 if dt == torch.float32 else ST_BF16
         V, Vp, n = m.vocab_size, lib().st_rnn_vocab_ld(m.vocab_size), plan.ntok
+        prm, keep = m._c_params()
+        seq = plan.c_struct(ctx.caption)
         if ctx.mode == "logits":
-            g = gout if gout.dtype == torch.float32 else gout.float()
-            dlog = torch.zeros(n, Vp, device=dev, dtype=dt)   # pad columns feed the backward GEMM as K: must be zero
-            gs = g.stride(0) if g.stride(1) == 1 else None
-            if gs is None:
-                g = g.contiguous(); gs = g.stride(0)
-            check(lib().st_cast2d(_cp(g), _cp(dlog), ST_F32, dtc, n, V, gs, Vp, _stream()), "st_cast2d")
+            dlog = logits_grad(gout, dt, n, V, Vp, torch.zeros)   # pad columns feed the backward GEMM as K: must be zero
         elif ctx.fused:
             gsc = gout.detach().float().contiguous()
             dlog = torch.empty(n, Vp, device=dev, dtype=dt)
-            prm_, keep_ = m._c_params()
-            seq_ = plan.c_struct(ctx.caption)
-            check(lib().st_rnn_fused_dlogits(C.byref(prm_), C.byref(seq_), _cp(ctx.ws), ctx.ws.numel(), _cp(ctx.targets), _cp(ctx.scratch),
+            check(lib().st_rnn_fused_dlogits(C.byref(prm), C.byref(seq), _cp(ctx.ws), ctx.ws.numel(), _cp(ctx.targets), _cp(ctx.scratch),
                                              _cp(gsc), _cp(dlog), Vp, _stream()), "st_rnn_fused_dlogits")
         else:
-            dlog = ctx.logits   # overwritten in place by (softmax - onehot) * dLoss / N_tok
-            gsc = gout.detach().float().contiguous()
-            check(lib().st_cross_entropy(_cp(ctx.logits), dtc, _cp(ctx.targets), n, V, Vp, None, _cp(dlog), dtc, Vp, 1.0,
-                                         _cp(gsc), _stream()), "st_cross_entropy(bwd)")
-        prm, keep = m._c_params()
+            dlog, gsc = ce_loss_backward(ctx.logits, dt, ctx.targets, n, V, Vp, gout)
         grads, keep2 = m._c_grads()
-        seq = plan.c_struct(ctx.caption)
         dfeat = torch.empty(plan.B, m.embed_dim, device=dev, dtype=torch.float32)
         check(lib().st_rnn_backward(C.byref(prm), C.byref(grads), C.byref(seq), None, _cp(dlog), Vp, None, _cp(ctx.ws),
                                     ctx.ws.numel(), _cp(dfeat), None, _stream()), "st_rnn_backward")
@@ -192,9 +163,66 @@ class _DecoderFn(torch.autograd.Function):
         return dfeat.to(ctx.feat_dtype), None, None, None, None, None, None
 
 
-class RNN(torch.nn.Module):
+class Decoder(FollowsMoves, nn.Module):
+    """What RNN and RNN_Attn share: the recurrent stack's part of the C descriptors and the set-up of ``sample``.
+    A subclass has ``embeddings``, ``unit``, ``linear``, ``embed_dim``, ``hidden``, ``vocab_size``, ``num_layers`` and
+    ``compute_dtype``."""
 
     cell = "gru"
+
+    def _layer_params(self):
+        u = self.unit
+        return [(getattr(u, wi), getattr(u, wh), getattr(u, bi), getattr(u, bh)) for wi, wh, bi, bh in _LAYER_NAMES[:self.num_layers]]
+
+    def _rnn_params(self, r, in0, keep):
+        """Fill the st_rnn_params `r` (layer 0 reads `in0` inputs); the working copies it points at go to `keep`.  Returns the
+        function that did that for one parameter (for the weights a subclass adds)."""
+        dt = self.compute_dtype
+
+        def wc(prm):
+            t = working_copy(prm, dt); keep.append(t); return t.data_ptr()
+        r.cell = ST_CELL_GRU if self.cell == "gru" else ST_CELL_LSTM
+        r.dtype = dtype_code(dt)
+        r.L, r.in0, r.H, r.V, r.E = self.num_layers, in0, self.hidden, self.vocab_size, self.embed_dim
+        r.emb = wc(self.embeddings.weight)
+        for l, (wi, wh, bi, bh) in enumerate(self._layer_params()):
+            r.w_ih[l], r.w_hh[l], r.b_ih[l], r.b_hh[l] = wc(wi), wc(wh), bi.data.data_ptr(), bh.data.data_ptr()
+        r.w_lin, r.b_lin = wc(self.linear.weight), self.linear.bias.data.data_ptr()
+        return wc
+
+    def _rnn_grads(self, g, keep):
+        """The same for the st_rnn_grads `g` and the fp32 gradient buffers (created on first use)."""
+        def gb(prm):
+            t = grad_buffer(prm); keep.append(t); return t.data_ptr()
+        g.emb = gb(self.embeddings.weight)
+        for l, (wi, wh, bi, bh) in enumerate(self._layer_params()):
+            g.w_ih[l], g.w_hh[l], g.b_ih[l], g.b_hh[l] = gb(wi), gb(wh), gb(bi), gb(bh)
+        g.w_lin, g.b_lin = gb(self.linear.weight), gb(self.linear.bias)
+        return gb
+
+    def _feature(self, cnn_feature):
+        """The (B, E) image features as the recurrent kernels read them: detached, contiguous, in the compute dtype."""
+        f = cnn_feature.detach().contiguous()
+        return f if f.dtype == self.compute_dtype else ops.cast(f.float(), self.compute_dtype)
+
+    def _sample_shape(self, cnn_feature, num_samples, temperature, top_k, max_length, uniforms):
+        """(B, S, T) of a ``sample`` call, its arguments checked before anything touches the device."""
+        B = cnn_feature.shape[0]
+        check_sample_args(self.vocab_size, B, num_samples, temperature, top_k, max_length, uniforms)
+        return B, int(num_samples), int(max_length)
+
+    @staticmethod
+    def _sample_buffers(feat, B, S, T, uniforms, generator):
+        """`feat` repeated for the S draws of every image (row b * S + s), n = B * S, and the per-row buffers of a ``sample``
+        call: the uniforms (n * T), ids and logp (n, T)."""
+        if S > 1:
+            feat = feat.repeat_interleave(S, 0)
+        n, dev = B * S, feat.device
+        u = sample_uniforms(uniforms, (B, S, T), dev, generator)
+        return feat, n, u, torch.empty(n, T, device=dev, dtype=torch.long), torch.empty(n, T, device=dev, dtype=torch.float32)
+
+
+class RNN(Decoder):
 
     def __init__(self, embed_dim, num_hidden_units, vocab_size, num_layers, dtype=torch.float32):
         '''
@@ -215,44 +243,17 @@ class RNN(torch.nn.Module):
         self.embed_dim, self.hidden, self.vocab_size, self.num_layers = embed_dim, num_hidden_units, vocab_size, num_layers
         self.compute_dtype = dtype
 
-    def _apply(self, fn, *a, **k):
-        places = storage_places(self)
-        out = super()._apply(fn, *a, **k)
-        drop_moved_working_copies(self, places)     # .cuda() / .cpu() / .to() replaced the storage the bf16 copies were cast from
-        return out
-
     # ---- C descriptors ---------------------------------------------------------------
-    def _layer_params(self):
-        return [(getattr(self.unit, f"weight_ih_l{l}"), getattr(self.unit, f"weight_hh_l{l}"),
-                 getattr(self.unit, f"bias_ih_l{l}"), getattr(self.unit, f"bias_hh_l{l}")) for l in range(self.num_layers)]
-
     def _c_params(self):
-        dt = self.compute_dtype
         if not self.linear.weight.is_cuda:
             raise _lib.ShowTellHipError("the decoder must live on a HIP device (no CPU fallback in the MI355X build)")
-        p = RnnParams()
-        p.cell = ST_CELL_GRU if self.cell == "gru" else ST_CELL_LSTM
-        p.dtype = ST_F32 if dt == torch.float32 else ST_BF16
-        p.L, p.in0, p.H, p.V, p.E = self.num_layers, self.embed_dim, self.hidden, self.vocab_size, self.embed_dim
-        keep = []
-        e = working_copy(self.embeddings.weight, dt); keep.append(e); p.emb = e.data_ptr()
-        for l, (wi, wh, bi, bh) in enumerate(self._layer_params()):
-            a, b = working_copy(wi, dt), working_copy(wh, dt)
-            keep += [a, b]
-            p.w_ih[l], p.w_hh[l], p.b_ih[l], p.b_hh[l] = a.data_ptr(), b.data_ptr(), bi.data.data_ptr(), bh.data.data_ptr()
-        w = working_copy(self.linear.weight, dt); keep.append(w)
-        p.w_lin, p.b_lin = w.data_ptr(), self.linear.bias.data.data_ptr()
+        p, keep = RnnParams(), []
+        self._rnn_params(p, self.embed_dim, keep)
         return p, keep
 
     def _c_grads(self):
-        g = RnnGrads()
-        keep = []
-        def gb(prm):
-            t = grad_buffer(prm); keep.append(t); return t.data_ptr()
-        g.emb = gb(self.embeddings.weight)
-        for l, (wi, wh, bi, bh) in enumerate(self._layer_params()):
-            g.w_ih[l], g.w_hh[l], g.b_ih[l], g.b_hh[l] = gb(wi), gb(wh), gb(bi), gb(bh)
-        g.w_lin, g.b_lin = gb(self.linear.weight), gb(self.linear.bias)
+        g, keep = RnnGrads(), []
+        self._rnn_grads(g, keep)
         return g, keep
 
     # ---- reference surface -------------------------------------------------------------
@@ -278,24 +279,14 @@ class RNN(torch.nn.Module):
 
         Returns (ids (B, S, T) int64, 0 after <end>; logp (B, S, T) fp32, the log-probability of each token under the
         distribution it was drawn from, 0 after <end>; lengths (B, S) int64 counting <end>, T if <end> was never drawn)."""
-        B, S, T = cnn_feature.shape[0], num_samples, max_length
-        check_sample_args(self.vocab_size, B, S, temperature, top_k, T, uniforms)
-        S, T = int(S), int(T)
+        B, S, T = self._sample_shape(cnn_feature, num_samples, temperature, top_k, max_length, uniforms)
         with torch.no_grad():
             prm, keep = self._c_params()
             if not cnn_feature.is_cuda:
                 raise _lib.ShowTellHipError("cnn_feature must be on the HIP device (no CPU fallback)")
-            dt = self.compute_dtype
-            feat = cnn_feature.detach().contiguous()
-            feat = feat if feat.dtype == dt else ops.cast(feat.float(), dt)
-            if S > 1:
-                feat = feat.repeat_interleave(S, 0)
-            n, dev = B * S, feat.device
-            u = sample_uniforms(uniforms, (B, S, T), dev, generator)
+            feat, n, u, ids, logp = self._sample_buffers(self._feature(cnn_feature), B, S, T, uniforms, generator)
             nbytes = lib().st_rnn_sample_workspace_bytes(C.byref(prm), n)
-            ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-            ids = torch.empty(n, T, device=dev, dtype=torch.long)
-            logp = torch.empty(n, T, device=dev, dtype=torch.float32)
+            ws = torch.empty(nbytes, device=feat.device, dtype=torch.uint8)
             check(lib().st_rnn_sample(C.byref(prm), _cp(feat), n, T, _cp(u), 1.0 / float(temperature), int(top_k), int(end_id), _cp(ws),
                                       nbytes, _cp(ids), _cp(logp), _stream()), "st_rnn_sample")
             return ids.view(B, S, T), logp.view(B, S, T), sample_lengths(ids, end_id).view(B, S)
@@ -307,9 +298,7 @@ class RNN(torch.nn.Module):
             return quirky_beam(self, cnn_feature, beam_size)
         with torch.no_grad():
             prm, keep = self._c_params()
-            dt = self.compute_dtype
-            feat = cnn_feature.detach().contiguous()
-            feat = feat if feat.dtype == dt else ops.cast(feat.float(), dt)
+            feat = self._feature(cnn_feature)
             B = feat.shape[0]
             nbytes = lib().st_rnn_greedy_workspace_bytes(C.byref(prm), B)
             ws = torch.empty(nbytes, device=feat.device, dtype=torch.uint8)

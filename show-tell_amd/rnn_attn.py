@@ -22,10 +22,10 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
-from ._lib import ST_BF16, ST_CELL_GRU, ST_CELL_LSTM, ST_F32, AttnGrads, AttnParams, check, lib
-from .rnn import (CAP_MAX, _cp, _stream, check_sample_args, drop_moved_working_copies, grad_buffer, sample_lengths, sample_uniforms,
-                  storage_places, up8, working_copy)
+from . import _lib
+from ._lib import AttnGrads, AttnParams, check, dtype_code, lib
+from ._lib import ptr as _cp, stream as _stream
+from .rnn import CAP_MAX, Decoder, ce_loss, ce_loss_backward, logits_grad, sample_lengths, up8
 from .seq import plan_for
 
 
@@ -57,7 +57,6 @@ class _AttnFn(torch.autograd.Function):
         cap_T = caption.t().contiguous()
         prm, keep = m._c_params()
         dt = m.compute_dtype
-        dtc = ST_F32 if dt == torch.float32 else ST_BF16
         B, Fd, P = feat.shape
         if Fd != m.nos_filters or P != m.num_pixels_checked(P):
             raise _lib.ShowTellHipError(f"cnn_feature must be (B, {m.nos_filters}, P), got {tuple(feat.shape)}")
@@ -69,8 +68,7 @@ class _AttnFn(torch.autograd.Function):
         alphas = torch.zeros(B, T, P, device=dev, dtype=torch.float32)        # rnn_attn.py:65
         logits = torch.empty(n, Vp, device=dev, dtype=torch.float32 if mode == "logits" else dt)
         check(lib().st_attn_forward(C.byref(prm), C.byref(seq), _cp(featc), _cp(cap_T), _cp(ws), nbytes, _cp(logits),
-                                    ST_F32 if logits.dtype == torch.float32 else ST_BF16, Vp, _cp(alphas), int(need_grad), _stream()),
-              "st_attn_forward")
+                                    dtype_code(logits.dtype), Vp, _cp(alphas), int(need_grad), _stream()), "st_attn_forward")
         # st_attn_forward steps over plan.T columns; alphas has T (padded) columns: strides must agree
         ctx.m, ctx.plan, ctx.caption, ctx.cap_T, ctx.ws, ctx.mode, ctx.P = m, plan, caption, cap_T, ws, mode, P
         ctx.alphas, ctx.alpha_c, ctx.keep = alphas, alpha_c, keep
@@ -78,7 +76,7 @@ class _AttnFn(torch.autograd.Function):
             return logits[:, :V], alphas
         targets = torch.nn.utils.rnn.pack_padded_sequence(caption, lens, batch_first=True)[0].contiguous()   # main_attn.py:126
         loss = torch.zeros((), device=dev, dtype=torch.float32)
-        check(lib().st_cross_entropy(_cp(logits), dtc, _cp(targets), n, V, Vp, _cp(loss), None, 0, Vp, 1.0, None, _stream()), "st_cross_entropy")
+        ce_loss(logits, dt, targets, n, V, Vp, loss)
         check(lib().st_attn_reg_loss(_cp(alphas), B, T, P, float(alpha_c), _cp(loss), _stream()), "st_attn_reg_loss")
         ctx.logits, ctx.targets = logits, targets
         return loss, alphas
@@ -86,25 +84,16 @@ class _AttnFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g0, galphas):
         m, plan = ctx.m, ctx.plan
-        dev = g0.device
         dt = m.compute_dtype
-        dtc = ST_F32 if dt == torch.float32 else ST_BF16
         V, Vp, n = m.vocab_size, up8(m.vocab_size), plan.ntok
         gs = None
         dal = None
         if ctx.mode == "logits":
-            g = g0 if g0.dtype == torch.float32 else g0.float()
-            if g.stride(1) != 1:
-                g = g.contiguous()
-            dlog = torch.empty(n, Vp, device=dev, dtype=dt)
-            check(lib().st_cast2d(_cp(g), _cp(dlog), ST_F32, dtc, n, V, g.stride(0), Vp, _stream()), "st_cast2d")
+            dlog = logits_grad(g0, dt, n, V, Vp, torch.empty)
             dal = (galphas if galphas is not None else torch.zeros_like(ctx.alphas)).float().contiguous()
             alpha_c = 0.0
         else:
-            dlog = ctx.logits
-            gs = g0.detach().float().contiguous()
-            check(lib().st_cross_entropy(_cp(ctx.logits), dtc, _cp(ctx.targets), n, V, Vp, None, _cp(dlog), dtc, Vp, 1.0, _cp(gs), _stream()),
-                  "st_cross_entropy(bwd)")
+            dlog, gs = ce_loss_backward(ctx.logits, dt, ctx.targets, n, V, Vp, g0)
             alpha_c = ctx.alpha_c
         prm, keep = m._c_params()
         prm.P = ctx.P
@@ -116,9 +105,7 @@ class _AttnFn(torch.autograd.Function):
         return None, None, None, None, None, None, None, None
 
 
-class RNN_Attn(nn.Module):
-
-    cell = "gru"
+class RNN_Attn(Decoder):
 
     def __init__(self, embed_dim, nos_filters, attention_dim, num_hidden_units, vocab_size, num_layers, dtype=torch.float32):
         '''
@@ -143,35 +130,14 @@ class RNN_Attn(nn.Module):
         self.embed_dim, self.hidden, self.attention_dim = embed_dim, num_hidden_units, attention_dim
         self.compute_dtype = dtype
 
-    def _apply(self, fn, *a, **k):
-        places = storage_places(self)
-        out = super()._apply(fn, *a, **k)
-        drop_moved_working_copies(self, places)     # .cuda() / .cpu() / .to() replaced the storage the bf16 copies were cast from
-        return out
-
     def num_pixels_checked(self, P):
         if P > 64:
             raise _lib.ShowTellHipError(f"at most 64 feature-map pixels are supported (got {P})")
         return P
 
-    def _layer_params(self):
-        return [(getattr(self.unit, f"weight_ih_l{l}"), getattr(self.unit, f"weight_hh_l{l}"),
-                 getattr(self.unit, f"bias_ih_l{l}"), getattr(self.unit, f"bias_hh_l{l}")) for l in range(self.num_layers)]
-
     def _c_params(self):
-        dt = self.compute_dtype
-        p = AttnParams()
-        r = p.rnn
-        r.cell = ST_CELL_GRU if self.cell == "gru" else ST_CELL_LSTM
-        r.dtype = ST_F32 if dt == torch.float32 else ST_BF16
-        r.L, r.in0, r.H, r.V, r.E = self.num_layers, 2 * self.embed_dim, self.hidden, self.vocab_size, self.embed_dim
-        keep = []
-        def wc(prm):
-            t = working_copy(prm, dt); keep.append(t); return t.data_ptr()
-        r.emb = wc(self.embeddings.weight)
-        for l, (wi, wh, bi, bh) in enumerate(self._layer_params()):
-            r.w_ih[l], r.w_hh[l], r.b_ih[l], r.b_hh[l] = wc(wi), wc(wh), bi.data.data_ptr(), bh.data.data_ptr()
-        r.w_lin, r.b_lin = wc(self.linear.weight), self.linear.bias.data.data_ptr()
+        p, keep = AttnParams(), []
+        wc = self._rnn_params(p.rnn, 2 * self.embed_dim, keep)
         p.F, p.A, p.P = self.nos_filters, self.attention_dim, 49
         a = self.attn
         p.w_enc, p.b_enc = wc(a.encoder_att.weight), a.encoder_att.bias.data.data_ptr()
@@ -184,14 +150,8 @@ class RNN_Attn(nn.Module):
         return p, keep
 
     def _c_grads(self):
-        g = AttnGrads()
-        keep = []
-        def gb(prm):
-            t = grad_buffer(prm); keep.append(t); return t.data_ptr()
-        g.rnn.emb = gb(self.embeddings.weight)
-        for l, (wi, wh, bi, bh) in enumerate(self._layer_params()):
-            g.rnn.w_ih[l], g.rnn.w_hh[l], g.rnn.b_ih[l], g.rnn.b_hh[l] = gb(wi), gb(wh), gb(bi), gb(bh)
-        g.rnn.w_lin, g.rnn.b_lin = gb(self.linear.weight), gb(self.linear.bias)
+        g, keep = AttnGrads(), []
+        gb = self._rnn_grads(g.rnn, keep)
         a = self.attn
         g.w_enc, g.b_enc = gb(a.encoder_att.weight), gb(a.encoder_att.bias)
         g.w_dec, g.b_dec = gb(a.decoder_att.weight), gb(a.decoder_att.bias)
@@ -242,19 +202,13 @@ class RNN_Attn(nn.Module):
         """The loop of rnn_attn.py:120-145 (test branch 77-94) from `start_id` with a draw in place of the arg-max of
         rnn_attn.py:141; arguments and results as RNN.sample (one st_attn_sample call for all B * num_samples rows).
         With `return_alphas` also alphas (B, S, T, P) fp32 on the device: the attention map of every step."""
-        B, S, T = cnn_feature.shape[0], num_samples, max_length
-        check_sample_args(self.vocab_size, B, S, temperature, top_k, T, uniforms)
-        S, T = int(S), int(T)
+        B, S, T = self._sample_shape(cnn_feature, num_samples, temperature, top_k, max_length, uniforms)
         with torch.no_grad():
             prm, keep, featc, B, P = self._decode_inputs(cnn_feature)
-            if S > 1:
-                featc = featc.repeat_interleave(S, 0)
-            n, dev = B * S, featc.device
-            u = sample_uniforms(uniforms, (B, S, T), dev, generator)
+            featc, n, u, ids, logp = self._sample_buffers(featc, B, S, T, uniforms, generator)
+            dev = featc.device
             nbytes = lib().st_attn_sample_workspace_bytes(C.byref(prm), n)
             ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-            ids = torch.empty(n, T, device=dev, dtype=torch.long)
-            logp = torch.empty(n, T, device=dev, dtype=torch.float32)
             alphas = torch.empty(n, T, P, device=dev, dtype=torch.float32) if return_alphas else None
             check(lib().st_attn_sample(C.byref(prm), _cp(featc), n, T, int(start_id), _cp(u), 1.0 / float(temperature), int(top_k),
                                        int(end_id), _cp(ws), nbytes, _cp(ids), _cp(logp), _cp(alphas), _stream()), "st_attn_sample")

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import PackedSeq, ShowTellHipError
+from ._lib import PackedSeq, ShowTellHipError, ptr
 
 _CACHE = {}
 
@@ -43,9 +43,8 @@ class SeqPlan:
             raise ShowTellHipError("image_caption must be a contiguous LongTensor (utils.py:70)")
         if caption.shape[0] != self.B or caption.shape[1] < self.T:
             raise ShowTellHipError(f"caption shape {tuple(caption.shape)} does not match caption_size (B={self.B}, T={self.T})")
-        return PackedSeq(self.B, self.T, self.ntok, caption.shape[1], self._bs_c,
-                         C.c_void_p(self.rows_b.data_ptr()), C.c_void_p(self.rows_t.data_ptr()),
-                         C.c_void_p(self.prev_row.data_ptr()), C.c_void_p(caption.data_ptr()))
+        return PackedSeq(B=self.B, T=self.T, ntok=self.ntok, Tcap=caption.shape[1], batch_sizes_host=self._bs_c,
+                         rows_b=ptr(self.rows_b), rows_t=ptr(self.rows_t), prev_row=ptr(self.prev_row), caption=ptr(caption))
 
 
 def plan_for(lens, device):

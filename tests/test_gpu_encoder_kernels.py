@@ -458,3 +458,15 @@ def test_stem_conv_pool_one_kernel_matches_conv_bn_relu_maxpool(B, H, W):
     assert torch.equal(y_e, ops.maxpool3x3s2(raw_e))
     ref_e = F.max_pool2d(F.relu(conv * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1)), 3, 2, 1).permute(0, 2, 3, 1)
     assert (y_e.float().cpu() - ref_e).abs().max().item() <= 3e-2 * ref_e.abs().max().item()
+
+
+def test_stem_weight_frag_packed_equals_the_two_step_form():
+    """st_stem_weight_frag_packed (one launch, what st_resnet_forward and ops.stem_conv_pool use) yields the operands of
+    st_stem_weight_frag(st_stem_weight_s2d(.)) bit for bit, for random bf16 (64, 7*7*8) filters (pad channels random too)."""
+    ops = _ops()
+    w = torch.randn(64, 7 * 7 * 8, generator=torch.Generator().manual_seed(11)).bfloat16().cuda()
+    one = ops.stem_weight_frag(w, 8)
+    two = ops.stem_weight_frag_from_s2d(ops.stem_weight_s2d(w, 8, torch.bfloat16))
+    assert one.shape == two.shape == (64 * 256,) and one.dtype == two.dtype == torch.bfloat16
+    assert one.float().abs().sum().item() > 0
+    assert torch.equal(one, two)
