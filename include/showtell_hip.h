@@ -446,6 +446,17 @@ int st_rnn_fused_loss(const st_rnn_params* p, const st_packed_seq* s, const void
                       const long* targets, float* scratch, size_t scratch_bytes, float* loss_accum, void* stream);
 int st_rnn_fused_dlogits(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
                          const long* targets, const float* scratch, const float* grad_scale_dev, void* dlogits, int ldd, void* stream);
+/* The same with a per-row weight and the per-row losses (reward-weighted training, scoring of given captions).  row_weight[ntok] and
+ * nll_out[ntok] are fp32 device buffers of the caller in packed-row order; either may be NULL, and with both NULL these are the calls above:
+ *   st_rnn_fused_loss_w:    nll_out[r] = logsumexp(x_r) - x_r[target_r] (unweighted);  *loss_accum += sum_r row_weight[r] * nll_r / ntok
+ *                           (the divisor stays ntok: row_weight = 1 is the mean); loss_accum may be NULL when nll_out is given;
+ *   st_rnn_fused_dlogits_w: row r of dlogits is also multiplied by row_weight[r] (a constant of the loss: it gets no gradient). */
+int st_rnn_fused_loss_w(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
+                        const long* targets, float* scratch, size_t scratch_bytes, const float* row_weight, float* nll_out,
+                        float* loss_accum, void* stream);
+int st_rnn_fused_dlogits_w(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
+                           const long* targets, const float* scratch, const float* grad_scale_dev, const float* row_weight,
+                           void* dlogits, int ldd, void* stream);
 
 /* nn.CrossEntropyLoss() (mean) forward + backward (main.py:94,149):
  *   *loss_accum += mean_r( logsumexp(x_r) - x_r[target_r] );  dlogits = (softmax - onehot) * grad_scale / rows
@@ -453,6 +464,11 @@ int st_rnn_fused_dlogits(const st_rnn_params* p, const st_packed_seq* s, const v
 int st_cross_entropy(const void* logits, int logits_dtype, const long* target, int rows, int V, int ldl,
                      float* loss_accum, void* dlogits, int dlogits_dtype, int ldd, float grad_scale,
                      const float* grad_scale_dev /* optional device scalar multiplied in */, void* stream);
+/* ... with a per-row weight and the per-row losses (fp32 device buffers of `rows` entries, either may be NULL; both NULL: the call above):
+ *   nll_out[r] = logsumexp(x_r) - x_r[target_r];  *loss_accum += sum_r row_weight[r] * nll_r / rows;  dlogits row r times row_weight[r] */
+int st_cross_entropy_w(const void* logits, int logits_dtype, const long* target, int rows, int V, int ldl,
+                       const float* row_weight, float* nll_out, float* loss_accum, void* dlogits, int dlogits_dtype, int ldd,
+                       float grad_scale, const float* grad_scale_dev, void* stream);
 
 /* Encoder head: y = BatchNorm1d(x W^T + b) (cnn.py:37-38,49; momentum 0.01) and its backward
  * (dx is not needed: the backbone output is detached, cnn.py:47).  Gradients are accumulated. */

@@ -146,29 +146,43 @@ extern "C" size_t st_rnn_fused_loss_bytes(const st_rnn_params* p, const st_packe
   if (!p || !s) return 0;
   return ((size_t)s->ntok * (2 + 2 * (size_t)vocab_ce_tiles(p->V))) * sizeof(float);
 }
-extern "C" int st_rnn_fused_loss(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
-                                 const long* targets, float* scratch, size_t scratch_bytes, float* loss_accum, void* stream) {
+// row_weight / nll_out [ntok] (fp32, packed rows, caller-owned, either may be NULL): *loss_accum += sum_r row_weight[r] * nll_r / ntok,
+// nll_out[r] = nll_r (unweighted).  loss_accum may be NULL when nll_out is given (scoring only)
+extern "C" int st_rnn_fused_loss_w(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
+                                   const long* targets, float* scratch, size_t scratch_bytes, const float* row_weight, float* nll_out,
+                                   float* loss_accum, void* stream) {
   if (check_common(p, s, "st_rnn_fused_loss")) return 1;
-  ST_CHECK(workspace && targets && scratch && loss_accum, "st_rnn_fused_loss: null pointer");
+  ST_CHECK(workspace && targets && scratch && (loss_accum || nll_out), "st_rnn_fused_loss: null pointer");
   ST_CHECK(st_rnn_fused_loss_supported(p), "st_rnn_fused_loss: needs bf16, H = 512 and the vocabulary projection (use st_rnn_forward's logits + st_cross_entropy)");
   const Plan q = make_plan(p, s);
   ST_CHECK(workspace_bytes >= q.total && scratch_bytes >= st_rnn_fused_loss_bytes(p, s), "st_rnn_fused_loss: workspace / scratch too small");
   const char* ytop = reinterpret_cast<const char*>(workspace) + q.y + (size_t)(p->L - 1) * s->ntok * p->H * q.es;
   const int n = s->ntok;
   return vocab_ce_forward(ytop, p->w_lin, p->b_lin, targets, n, p->V, scratch + 2 * (size_t)n, scratch + n, scratch, loss_accum,
-                          reinterpret_cast<hipStream_t>(stream));
+                          row_weight, nll_out, reinterpret_cast<hipStream_t>(stream));
+}
+extern "C" int st_rnn_fused_loss(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
+                                 const long* targets, float* scratch, size_t scratch_bytes, float* loss_accum, void* stream) {
+  ST_CHECK(loss_accum, "st_rnn_fused_loss: null pointer");
+  return st_rnn_fused_loss_w(p, s, workspace, workspace_bytes, targets, scratch, scratch_bytes, nullptr, nullptr, loss_accum, stream);
 }
 // dlogits[ntok][ldd] (bf16) = (softmax - onehot) / ntok * *grad_scale_dev, from the same tile products; pad columns [V, ldd) zero
-extern "C" int st_rnn_fused_dlogits(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
-                                    const long* targets, const float* scratch, const float* grad_scale_dev, void* dlogits, int ldd, void* stream) {
+// (_w: row r also times row_weight[r]; NULL: 1)
+extern "C" int st_rnn_fused_dlogits_w(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
+                                      const long* targets, const float* scratch, const float* grad_scale_dev, const float* row_weight,
+                                      void* dlogits, int ldd, void* stream) {
   if (check_common(p, s, "st_rnn_fused_dlogits")) return 1;
   ST_CHECK(workspace && targets && scratch && dlogits, "st_rnn_fused_dlogits: null pointer");
   ST_CHECK(st_rnn_fused_loss_supported(p), "st_rnn_fused_dlogits: unsupported configuration");
   const Plan q = make_plan(p, s);
   ST_CHECK(workspace_bytes >= q.total, "st_rnn_fused_dlogits: workspace too small");
   const char* ytop = reinterpret_cast<const char*>(workspace) + q.y + (size_t)(p->L - 1) * s->ntok * p->H * q.es;
-  return vocab_ce_dlogits(ytop, p->w_lin, p->b_lin, targets, scratch, s->ntok, p->V, dlogits, ldd, 1.0f, grad_scale_dev,
+  return vocab_ce_dlogits(ytop, p->w_lin, p->b_lin, targets, scratch, s->ntok, p->V, dlogits, ldd, 1.0f, grad_scale_dev, row_weight,
                           reinterpret_cast<hipStream_t>(stream));
+}
+extern "C" int st_rnn_fused_dlogits(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
+                                    const long* targets, const float* scratch, const float* grad_scale_dev, void* dlogits, int ldd, void* stream) {
+  return st_rnn_fused_dlogits_w(p, s, workspace, workspace_bytes, targets, scratch, grad_scale_dev, nullptr, dlogits, ldd, stream);
 }
 
 extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,

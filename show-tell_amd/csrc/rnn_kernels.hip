@@ -586,11 +586,14 @@ __global__ __launch_bounds__(256) void rnn_bwd_cell_kernel(RnnBwdFusedBatch batc
 // cross entropy over rows (mean reduction):  loss += -log softmax(x)[t] / nrows
 // dlogits = (softmax - onehot) * gscale   written in TD (may alias the logits when TD == TL)
 // one block per row; the row is read twice from L2 (max+sum online, then gradient)
+// WGT: the row's loss term and gradient are also times row_w[row] (NULL: 1; the divisor stays nrows) and its unweighted
+// -log softmax(x)[t] goes to nll[row] (NULL: not stored); without WGT the kernel is the code it was
 // ---------------------------------------------------------------------------------------
-template <typename TL, typename TD>
+template <typename TL, typename TD, bool WGT>
 __global__ __launch_bounds__(256) void ce_kernel(const TL* __restrict__ logits, const long* __restrict__ target,
                                                  float* __restrict__ loss, TD* __restrict__ dlogits,
-                                                 int V, int ldl, int ldd, float inv_rows, float gscale, const float* __restrict__ gscale_dev) {
+                                                 int V, int ldl, int ldd, float inv_rows, float gscale, const float* __restrict__ gscale_dev,
+                                                 const float* __restrict__ row_w, float* __restrict__ nll) {
   __shared__ float sm[8], ss[8];
   const int row = blockIdx.x;
   const TL* x = logits + (long)row * ldl;
@@ -623,7 +626,14 @@ __global__ __launch_bounds__(256) void ce_kernel(const TL* __restrict__ logits, 
   const float lse = M + __logf(S);
   const float xt = to_f32<TL>(x[t]);
   __syncthreads();   // dlogits may alias the logits: every read of x[t] happens before any write
-  if (threadIdx.x == 0 && loss) atomicAdd(loss, (lse - xt) * inv_rows);
+  if constexpr (WGT) {
+    const float wr = row_w ? row_w[row] : 1.f;
+    if (threadIdx.x == 0 && nll) nll[row] = lse - xt;
+    if (threadIdx.x == 0 && loss) atomicAdd(loss, wr * (lse - xt) * inv_rows);
+    gscale *= wr;
+  } else {
+    if (threadIdx.x == 0 && loss) atomicAdd(loss, (lse - xt) * inv_rows);
+  }
   if (dlogits) {
     if (gscale_dev) gscale *= *gscale_dev;
     TD* d = dlogits + (long)row * ldd;
@@ -819,23 +829,41 @@ int colsum_launch(const void* x, float* out, int rows, int cols, int ldx, int dt
   return 0;
 }
 
-extern "C" int st_cross_entropy(const void* logits, int logits_dtype, const long* target, int rows, int V, int ldl,
-                                float* loss_accum, void* dlogits, int dlogits_dtype, int ldd, float grad_scale,
-                                const float* grad_scale_dev, void* stream) {
+namespace {
+template <bool WGT>
+void ce_launch(const void* logits, int logits_dtype, const long* target, int rows, int V, int ldl, float* loss_accum, void* dlogits,
+               int dlogits_dtype, int ldd, float inv, float gs, const float* grad_scale_dev, const float* row_w, float* nll, hipStream_t st) {
+  const dim3 grid(rows), block(256);
+  if (logits_dtype == ST_F32 && (dlogits_dtype == ST_F32 || !dlogits))
+    hipLaunchKernelGGL((ce_kernel<float, float, WGT>), grid, block, 0, st, (const float*)logits, target, loss_accum, (float*)dlogits, V, ldl, ldd, inv, gs, grad_scale_dev, row_w, nll);
+  else if (logits_dtype == ST_F32)
+    hipLaunchKernelGGL((ce_kernel<float, bf16_t, WGT>), grid, block, 0, st, (const float*)logits, target, loss_accum, (bf16_t*)dlogits, V, ldl, ldd, inv, gs, grad_scale_dev, row_w, nll);
+  else if (dlogits_dtype == ST_BF16 || !dlogits)
+    hipLaunchKernelGGL((ce_kernel<bf16_t, bf16_t, WGT>), grid, block, 0, st, (const bf16_t*)logits, target, loss_accum, (bf16_t*)dlogits, V, ldl, ldd, inv, gs, grad_scale_dev, row_w, nll);
+  else
+    hipLaunchKernelGGL((ce_kernel<bf16_t, float, WGT>), grid, block, 0, st, (const bf16_t*)logits, target, loss_accum, (float*)dlogits, V, ldl, ldd, inv, gs, grad_scale_dev, row_w, nll);
+}
+}  // namespace
+
+extern "C" int st_cross_entropy_w(const void* logits, int logits_dtype, const long* target, int rows, int V, int ldl,
+                                  const float* row_weight, float* nll_out, float* loss_accum, void* dlogits, int dlogits_dtype, int ldd,
+                                  float grad_scale, const float* grad_scale_dev, void* stream) {
   ST_CHECK(logits && target, "st_cross_entropy: null pointer");
   ST_CHECK(rows >= 0 && V > 0 && ldl >= V, "st_cross_entropy: bad shape");
   if (rows == 0) return 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const float inv = 1.0f / rows, gs = grad_scale / rows;
-  const dim3 grid(rows), block(256);
-  if (logits_dtype == ST_F32 && (dlogits_dtype == ST_F32 || !dlogits))
-    hipLaunchKernelGGL((ce_kernel<float, float>), grid, block, 0, st, (const float*)logits, target, loss_accum, (float*)dlogits, V, ldl, ldd, inv, gs, grad_scale_dev);
-  else if (logits_dtype == ST_F32)
-    hipLaunchKernelGGL((ce_kernel<float, bf16_t>), grid, block, 0, st, (const float*)logits, target, loss_accum, (bf16_t*)dlogits, V, ldl, ldd, inv, gs, grad_scale_dev);
-  else if (dlogits_dtype == ST_BF16 || !dlogits)
-    hipLaunchKernelGGL((ce_kernel<bf16_t, bf16_t>), grid, block, 0, st, (const bf16_t*)logits, target, loss_accum, (bf16_t*)dlogits, V, ldl, ldd, inv, gs, grad_scale_dev);
+  if (row_weight || nll_out)
+    ce_launch<true>(logits, logits_dtype, target, rows, V, ldl, loss_accum, dlogits, dlogits_dtype, ldd, inv, gs, grad_scale_dev, row_weight, nll_out, st);
   else
-    hipLaunchKernelGGL((ce_kernel<bf16_t, float>), grid, block, 0, st, (const bf16_t*)logits, target, loss_accum, (float*)dlogits, V, ldl, ldd, inv, gs, grad_scale_dev);
+    ce_launch<false>(logits, logits_dtype, target, rows, V, ldl, loss_accum, dlogits, dlogits_dtype, ldd, inv, gs, grad_scale_dev, nullptr, nullptr, st);
   ST_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int st_cross_entropy(const void* logits, int logits_dtype, const long* target, int rows, int V, int ldl,
+                                float* loss_accum, void* dlogits, int dlogits_dtype, int ldd, float grad_scale,
+                                const float* grad_scale_dev, void* stream) {
+  return st_cross_entropy_w(logits, logits_dtype, target, rows, V, ldl, nullptr, nullptr, loss_accum, dlogits, dlogits_dtype, ldd,
+                            grad_scale, grad_scale_dev, stream);
 }

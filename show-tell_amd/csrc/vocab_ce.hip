@@ -31,6 +31,7 @@ struct VceArgs {
   float* partial;         // MODE 0: [ntile][n][2]
   float* tgt_logit;       // MODE 0: [n]
   const float* lse;       // MODE 1: [n]
+  const float* row_w;     // MODE 1, WGT: [n] per-row weight of the loss (a constant: no gradient flows into it)
   bf16_t* dlogits;        // MODE 1: [n][ldd]
   const float* gscale_dev; float gscale;   // MODE 1: dlogits = (p - onehot) * gscale * (*gscale_dev)
   int n, V, ntile, ldd, nsplit;
@@ -46,7 +47,10 @@ __device__ __forceinline__ f32x4 vmfma(const u32x4& a, const u32x4& b, const f32
 // 128 MFMAs per wave cannot cover; the other workgroup's can.  Measured before: weight rows streamed per (64 x 256) tile: 43 us per pass (17 of
 // them waiting for the rows, 19 staging and launching 1000 workgroups; 64 x 128 / 128 x 256 tiles, deeper rings, line-paired rows: the same);
 // this form with a double-buffered tile at one workgroup per CU: 49 us.
-template <int MODE>
+// WGT (MODE 1 only): the row's gradient is scaled by row_w[token], loaded beside lse -- one more live register in the epilogue, where the
+// 128 weight registers and the accumulators leave room for it (the register tables are in DESIGN.md section 7); the unweighted
+// instantiations are the code they were.
+template <int MODE, bool WGT = false>
 __global__ __launch_bounds__(256, 2) void vocab_ce_kernel(VceArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* xch = reinterpret_cast<float*>(smem + VTILE);               // [4 waves][64 tokens][2]
@@ -161,6 +165,8 @@ __global__ __launch_bounds__(256, 2) void vocab_ce_kernel(VceArgs a) {
         long t = a.target[mc];
         t = t < 0 ? 0 : (t >= a.V ? a.V - 1 : t);
         const float l = a.lse[mc];
+        float gw = gs;
+        if constexpr (WGT) gw *= a.row_w[mc];
 #pragma unroll
         for (int j = 0; j < VNT; ++j) {
           float d[4];
@@ -168,7 +174,7 @@ __global__ __launch_bounds__(256, 2) void vocab_ce_kernel(VceArgs a) {
           for (int e = 0; e < 4; ++e) {
             const int v = n0 + wid * 32 + 16 * j + 4 * q4 + e;
             const float p = vok[j][e] ? __expf(acc[i][j][e] + bz[j][e] - l) : 0.f;
-            d[e] = vok[j][e] ? (p - ((long)v == t ? 1.f : 0.f)) * gs : 0.f;   // pad entries (V .. ldd) are zero: they feed GEMMs as K
+            d[e] = vok[j][e] ? (p - ((long)v == t ? 1.f : 0.f)) * gw : 0.f;   // pad entries (V .. ldd) are zero: they feed GEMMs as K
           }
           if (i == 0 && j == 0) __syncthreads();                      // (uniform) every wave has read its last operands: the tile area is free
           *reinterpret_cast<u32x2*>(stage + (16 * i + r16) * VSROW + (wid * 32 + 16 * j + 4 * q4) * 2) = u32x2{pack_bf16x2(d[0], d[1]), pack_bf16x2(d[2], d[3])};
@@ -189,10 +195,13 @@ __global__ __launch_bounds__(256, 2) void vocab_ce_kernel(VceArgs a) {
   }
 }
 
-// lse[m] = log sum_v exp(x[m][v]) from the tiles' partials; loss += (lse - x[m][target]) / n.  A block = 64 tokens x 4 tile groups (group g
+// lse[m] = log sum_v exp(x[m][v]) from the tiles' partials; loss += (lse - x[m][target]) / n.  WGT: the row's term is weighted by row_w[m]
+// (NULL: 1; the divisor stays n) and its unweighted lse - x[m][target] goes to nll[m] (NULL: not stored).  A block = 64 tokens x 4 tile groups (group g
 // merges tiles g, g + 4, .. in order, the groups meet in LDS in group order): the merge is a chain of dependent exponentials per token.
+template <bool WGT>
 __global__ __launch_bounds__(256) void vocab_ce_reduce_kernel(const float* __restrict__ partial, const float* __restrict__ tgt_logit,
-                                                              float* __restrict__ lse, float* __restrict__ loss, int n, int ntile, float inv_rows) {
+                                                              float* __restrict__ lse, float* __restrict__ loss, int n, int ntile, float inv_rows,
+                                                              const float* __restrict__ row_w, float* __restrict__ nll) {
   __shared__ float gm[4][64], gsum[4][64];
   const int tk = threadIdx.x & 63, g = threadIdx.x >> 6;
   const int m = blockIdx.x * 64 + tk, mc = m < n ? m : n - 1;
@@ -226,7 +235,13 @@ __global__ __launch_bounds__(256) void vocab_ce_reduce_kernel(const float* __res
     if (m < n) {
       const float l = M + __logf(S);
       lse[m] = l;
-      term = (l - tgt_logit[m]) * inv_rows;
+      if constexpr (WGT) {
+        const float nl = l - tgt_logit[m];
+        if (nll) nll[m] = nl;
+        term = (row_w ? row_w[m] * nl : nl) * inv_rows;
+      } else {
+        term = (l - tgt_logit[m]) * inv_rows;
+      }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) term += __shfl_xor(term, o, 64);
@@ -249,6 +264,7 @@ int vce_launch_attr() {
   if (dev >= 0 && dev < 64 && !attr_set[dev]) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vocab_ce_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, VLDS);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vocab_ce_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, VLDS);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vocab_ce_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, VLDS);
     attr_set[dev] = 1;
   }
   return 0;
@@ -260,9 +276,10 @@ int vce_launch_attr() {
 int vocab_ce_supported(int dtype, int H) { return dtype == ST_BF16 && H == VH ? 1 : 0; }
 int vocab_ce_tiles(int V) { return (V + VBN - 1) / VBN; }
 
-// forward: y [n][512] bf16, w [V][512] bf16 -> lse[n], *loss += mean NLL.  partial: n * vocab_ce_tiles(V) * 2 floats; tgt: n floats
+// forward: y [n][512] bf16, w [V][512] bf16 -> lse[n], *loss += sum_r row_w[r] * NLL_r / n (row_w NULL: the mean NLL), nll[r] = NLL_r
+// where asked for (loss may be NULL then).  partial: n * vocab_ce_tiles(V) * 2 floats; tgt: n floats
 int vocab_ce_forward(const void* y, const void* w, const float* bias, const long* target, int n, int V, float* partial, float* tgt,
-                     float* lse, float* loss, hipStream_t st) {
+                     float* lse, float* loss, const float* row_w, float* nll, hipStream_t st) {
   if (n <= 0) return 0;
   vce_launch_attr();
   VceArgs a{};
@@ -270,23 +287,27 @@ int vocab_ce_forward(const void* y, const void* w, const float* bias, const long
   a.partial = partial; a.tgt_logit = tgt; a.n = n; a.V = V; a.ntile = vocab_ce_tiles(V);
   a.nsplit = vce_splits(a.ntile, (n + VBM - 1) / VBM);
   hipLaunchKernelGGL(vocab_ce_kernel<0>, dim3(a.ntile * a.nsplit), dim3(256), VLDS, st, a);
-  hipLaunchKernelGGL(vocab_ce_reduce_kernel, dim3((n + 63) / 64), dim3(256), 0, st, partial, tgt, lse, loss, n, a.ntile, 1.0f / n);
+  if (row_w || nll)
+    hipLaunchKernelGGL(vocab_ce_reduce_kernel<true>, dim3((n + 63) / 64), dim3(256), 0, st, partial, tgt, lse, loss, n, a.ntile, 1.0f / n, row_w, nll);
+  else
+    hipLaunchKernelGGL(vocab_ce_reduce_kernel<false>, dim3((n + 63) / 64), dim3(256), 0, st, partial, tgt, lse, loss, n, a.ntile, 1.0f / n, nullptr, nullptr);
   ST_LAUNCH_CHECK();
   return 0;
 }
 
-// backward: dlogits[n][ldd] bf16 = (softmax - onehot) * gscale / n (* *gscale_dev); columns V .. ldd are written as zeros
+// backward: dlogits[n][ldd] bf16 = (softmax - onehot) * gscale / n (* *gscale_dev) (* row_w[row]); columns V .. ldd are written as zeros
 int vocab_ce_dlogits(const void* y, const void* w, const float* bias, const long* target, const float* lse, int n, int V,
-                     void* dlogits, int ldd, float gscale, const float* gscale_dev, hipStream_t st) {
+                     void* dlogits, int ldd, float gscale, const float* gscale_dev, const float* row_w, hipStream_t st) {
   if (n <= 0) return 0;
   ST_CHECK(ldd % 8 == 0 && ldd >= V, "vocab_ce_dlogits: ldd=%d must be a multiple of 8 and >= V", ldd);
   vce_launch_attr();
   VceArgs a{};
   a.y = reinterpret_cast<const bf16_t*>(y); a.w = reinterpret_cast<const bf16_t*>(w); a.bias = bias; a.target = target;
-  a.lse = lse; a.dlogits = reinterpret_cast<bf16_t*>(dlogits); a.gscale = gscale / n; a.gscale_dev = gscale_dev;
+  a.lse = lse; a.row_w = row_w; a.dlogits = reinterpret_cast<bf16_t*>(dlogits); a.gscale = gscale / n; a.gscale_dev = gscale_dev;
   a.n = n; a.V = V; a.ldd = ldd; a.ntile = (ldd + VBN - 1) / VBN;     // the tiles also cover the pad columns
   a.nsplit = vce_splits(a.ntile, (n + VBM - 1) / VBM);
-  hipLaunchKernelGGL(vocab_ce_kernel<1>, dim3(a.ntile * a.nsplit), dim3(256), VLDS, st, a);
+  if (row_w) hipLaunchKernelGGL((vocab_ce_kernel<1, true>), dim3(a.ntile * a.nsplit), dim3(256), VLDS, st, a);
+  else hipLaunchKernelGGL(vocab_ce_kernel<1>, dim3(a.ntile * a.nsplit), dim3(256), VLDS, st, a);
   ST_LAUNCH_CHECK();
   return 0;
 }

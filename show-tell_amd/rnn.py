@@ -7,6 +7,8 @@ Same constructor, same attribute names (``embeddings``, ``unit``, ``linear``) an
     logits = rnn(cnn_feature, image_caption, caption_size)      # (N_tok, V), time-major packed rows
     ids    = rnn.sentence_index(cnn_feature, beam_size=0)       # Long(B, 25) (squeezed)
     ids, logp, lengths = rnn.sample(cnn_feature, num_samples=5, temperature=0.8, top_k=20)   # (B, S, 25) draws (st_rnn_sample)
+    loss   = rnn.loss(cnn_feature, image_caption, caption_size, sequence_weight=advantage)   # sum w * nll / N_tok (reward-weighted)
+    logp   = rnn.token_logp(cnn_feature, image_caption, caption_size)                        # (B, T) log p of every given token
 
 ``nn.Embedding`` / ``nn.GRU`` / ``nn.Linear`` objects are parameter containers only; all
 arithmetic runs in libshowtell_hip (st_rnn_forward / st_rnn_backward / st_rnn_greedy /
@@ -68,19 +70,70 @@ def sample_lengths(ids, end_id):
     return (before + 1).clamp(max=ids.shape[-1])
 
 
-def ce_loss(logits, dt, targets, n, V, Vp, loss):
-    """loss += mean cross entropy of the (n, Vp) logits rows (V valid columns) against `targets`."""
-    check(lib().st_cross_entropy(_cp(logits), dtype_code(dt), _cp(targets), n, V, Vp, _cp(loss), None, 0, Vp, 1.0, None, _stream()),
-          "st_cross_entropy")
+def check_weight_args(batch, width, sequence_weight, token_weight):
+    """Argument errors of the loss weights (both decoders), raised before anything touches the device: `sequence_weight` is a
+    (batch,) and `token_weight` a (batch, width) floating-point tensor, width that of the caption tensor."""
+    for name, w, want in (("sequence_weight", sequence_weight, (batch,)), ("token_weight", token_weight, (batch, width))):
+        if w is None:
+            continue
+        if not torch.is_tensor(w) or not w.dtype.is_floating_point or tuple(w.shape) != want:
+            raise ValueError(f"{name} must be a floating-point tensor of shape {want}"
+                             + (f" (got {w.dtype}, {tuple(w.shape)})" if torch.is_tensor(w) else f" (got {type(w).__name__})"))
 
 
-def ce_loss_backward(logits, dt, targets, n, V, Vp, gout):
-    """The saved logits of ce_loss, overwritten in place by (softmax - onehot) * dLoss / N_tok.  Returns (dlogits, dLoss as the
-    fp32 device scalar the kernel read)."""
+def check_caption_args(caption, lens):
+    """Argument errors of a (caption, caption_size) pair, before anything touches the device."""
+    if not torch.is_tensor(caption) or caption.dim() != 2 or caption.dtype != torch.int64:
+        raise ValueError("image_caption must be a (B, T) LongTensor")
+    if len(lens) != caption.shape[0] or max(int(l) for l in lens) > caption.shape[1]:
+        raise ValueError(f"caption_size must hold {caption.shape[0]} lengths of at most {caption.shape[1]}")
+
+
+def pack_row_weights(plan, sequence_weight, token_weight, device):
+    """The weight of every packed row (t, b) as the kernels read it: sequence_weight[b] * token_weight[b, t], fp32 (ntok,) on
+    `device`, gathered there with the plan's row map; None when neither is given.  Constants of the loss: detached."""
+    if sequence_weight is None and token_weight is None:
+        return None
+    rb, rt = plan.row_index(device)
+    w = None
+    if sequence_weight is not None:
+        w = sequence_weight.detach().to(device=device, dtype=torch.float32)[rb]
+    if token_weight is not None:
+        tw = token_weight.detach().to(device=device, dtype=torch.float32)[rb, rt]
+        w = tw if w is None else w * tw
+    return w.contiguous()
+
+
+def unpack_rows(plan, rows, width, device):
+    """(B, width) from packed rows: out[b, t] = rows[row(t, b)], 0 past each length."""
+    rb, rt = plan.row_index(device)
+    out = torch.zeros(plan.B, width, device=device, dtype=rows.dtype)
+    out[rb, rt] = rows
+    return out
+
+
+def ce_loss(logits, dt, targets, n, V, Vp, loss, roww=None, nll=None):
+    """loss += mean cross entropy of the (n, Vp) logits rows (V valid columns) against `targets`; with `roww` (n,) every row's
+    term times its weight (the divisor stays n); `nll` (n,) receives the rows' unweighted terms (`loss` may then be None)."""
+    if roww is None and nll is None:
+        check(lib().st_cross_entropy(_cp(logits), dtype_code(dt), _cp(targets), n, V, Vp, _cp(loss), None, 0, Vp, 1.0, None, _stream()),
+              "st_cross_entropy")
+    else:
+        check(lib().st_cross_entropy_w(_cp(logits), dtype_code(dt), _cp(targets), n, V, Vp, _cp(roww), _cp(nll), _cp(loss), None, 0, Vp,
+                                       1.0, None, _stream()), "st_cross_entropy_w")
+
+
+def ce_loss_backward(logits, dt, targets, n, V, Vp, gout, roww=None):
+    """The saved logits of ce_loss, overwritten in place by (softmax - onehot) * dLoss / N_tok (row r times roww[r]).  Returns
+    (dlogits, dLoss as the fp32 device scalar the kernel read)."""
     gsc = gout.detach().float().contiguous()
     dtc = dtype_code(dt)
-    check(lib().st_cross_entropy(_cp(logits), dtc, _cp(targets), n, V, Vp, None, _cp(logits), dtc, Vp, 1.0, _cp(gsc), _stream()),
-          "st_cross_entropy(bwd)")
+    if roww is None:
+        check(lib().st_cross_entropy(_cp(logits), dtc, _cp(targets), n, V, Vp, None, _cp(logits), dtc, Vp, 1.0, _cp(gsc), _stream()),
+              "st_cross_entropy(bwd)")
+    else:
+        check(lib().st_cross_entropy_w(_cp(logits), dtc, _cp(targets), n, V, Vp, _cp(roww), None, None, _cp(logits), dtc, Vp, 1.0,
+                                       _cp(gsc), _stream()), "st_cross_entropy_w(bwd)")
     return logits, gsc
 
 
@@ -96,10 +149,11 @@ def logits_grad(gout, dt, n, V, Vp, alloc):
 
 
 class _DecoderFn(torch.autograd.Function):
-    """mode 'logits': returns fp32 logits rows; mode 'loss': returns the mean cross entropy."""
+    """mode 'logits': returns fp32 logits rows; mode 'loss': returns the mean cross entropy, every row's term times
+    sequence_weight[b] * token_weight[b, t] where given; mode 'nll': returns the packed rows' -log p(target) (no gradient)."""
 
     @staticmethod
-    def forward(ctx, feat, _anchor, module, caption, lens, mode, need_grad):
+    def forward(ctx, feat, _anchor, module, caption, lens, mode, need_grad, sequence_weight, token_weight):
         m = module
         dev = feat.device
         if not feat.is_cuda or not m.linear.weight.is_cuda:
@@ -110,32 +164,41 @@ class _DecoderFn(torch.autograd.Function):
         prm, keep = m._c_params()
         dt = m.compute_dtype
         featd = m._feature(feat)
+        roww = pack_row_weights(plan, sequence_weight, token_weight, dev)
         nbytes = lib().st_rnn_workspace_bytes(C.byref(prm), C.byref(seq))
         ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
         V, Vp, n = m.vocab_size, lib().st_rnn_vocab_ld(m.vocab_size), plan.ntok
         targets = torch.empty(n, device=dev, dtype=torch.long)
         # mode 'loss' in bf16: the vocabulary projection and the cross entropy run tile by tile without a logits tensor (csrc/vocab_ce.hip);
         # ST_FUSED_CE=0 keeps st_rnn_forward's logits + st_cross_entropy
-        fused = mode == "loss" and os.environ.get("ST_FUSED_CE", "1") != "0" and bool(lib().st_rnn_fused_loss_supported(C.byref(prm)))
-        ldt = torch.float32 if mode == "logits" else dt
+        fused = mode != "logits" and os.environ.get("ST_FUSED_CE", "1") != "0" and bool(lib().st_rnn_fused_loss_supported(C.byref(prm)))
+        ldt = dt if mode == "loss" else torch.float32
         logits = None if fused else torch.empty(n, Vp, device=dev, dtype=ldt)
         check(lib().st_rnn_forward(C.byref(prm), C.byref(seq), None, _cp(featd), _cp(ws), nbytes, _cp(logits), dtype_code(ldt), Vp,
                                    _cp(targets), int(need_grad), _stream()), "st_rnn_forward")
         ctx.m, ctx.plan, ctx.caption, ctx.ws, ctx.mode, ctx.keep = m, plan, caption, ws, mode, keep
         ctx.feat_dtype = feat.dtype
-        ctx.fused = fused
+        ctx.fused, ctx.roww = fused, roww
         if mode == "logits":
             return logits[:, :V]
-        loss = torch.zeros((), device=dev, dtype=torch.float32)
+        loss = torch.zeros((), device=dev, dtype=torch.float32) if mode == "loss" else None
+        nll = torch.empty(n, device=dev, dtype=torch.float32) if mode == "nll" else None
         if fused:
             sb = lib().st_rnn_fused_loss_bytes(C.byref(prm), C.byref(seq))
             scratch = torch.empty(sb // 4, device=dev, dtype=torch.float32)
-            check(lib().st_rnn_fused_loss(C.byref(prm), C.byref(seq), _cp(ws), nbytes, _cp(targets), _cp(scratch), sb, _cp(loss), _stream()),
-                  "st_rnn_fused_loss")
+            if roww is None and nll is None:
+                check(lib().st_rnn_fused_loss(C.byref(prm), C.byref(seq), _cp(ws), nbytes, _cp(targets), _cp(scratch), sb, _cp(loss),
+                                              _stream()), "st_rnn_fused_loss")
+            else:
+                check(lib().st_rnn_fused_loss_w(C.byref(prm), C.byref(seq), _cp(ws), nbytes, _cp(targets), _cp(scratch), sb, _cp(roww),
+                                                _cp(nll), _cp(loss), _stream()), "st_rnn_fused_loss_w")
             ctx.logits, ctx.targets, ctx.scratch = None, targets, scratch
-            return loss
-        ce_loss(logits, dt, targets, n, V, Vp, loss)
-        ctx.logits, ctx.targets = logits, targets
+        else:
+            ce_loss(logits, ldt, targets, n, V, Vp, loss, roww, nll)
+            ctx.logits, ctx.targets = logits, targets
+        if mode == "nll":
+            ctx.mark_non_differentiable(nll)
+            return nll
         return loss
 
     @staticmethod
@@ -148,19 +211,26 @@ class _DecoderFn(torch.autograd.Function):
         seq = plan.c_struct(ctx.caption)
         if ctx.mode == "logits":
             dlog = logits_grad(gout, dt, n, V, Vp, torch.zeros)   # pad columns feed the backward GEMM as K: must be zero
+        elif ctx.mode != "loss":
+            raise _lib.ShowTellHipError("token_logp has no gradient")
         elif ctx.fused:
             gsc = gout.detach().float().contiguous()
             dlog = torch.empty(n, Vp, device=dev, dtype=dt)
-            check(lib().st_rnn_fused_dlogits(C.byref(prm), C.byref(seq), _cp(ctx.ws), ctx.ws.numel(), _cp(ctx.targets), _cp(ctx.scratch),
-                                             _cp(gsc), _cp(dlog), Vp, _stream()), "st_rnn_fused_dlogits")
+            if ctx.roww is None:
+                check(lib().st_rnn_fused_dlogits(C.byref(prm), C.byref(seq), _cp(ctx.ws), ctx.ws.numel(), _cp(ctx.targets), _cp(ctx.scratch),
+                                                 _cp(gsc), _cp(dlog), Vp, _stream()), "st_rnn_fused_dlogits")
+            else:
+                check(lib().st_rnn_fused_dlogits_w(C.byref(prm), C.byref(seq), _cp(ctx.ws), ctx.ws.numel(), _cp(ctx.targets),
+                                                   _cp(ctx.scratch), _cp(gsc), _cp(ctx.roww), _cp(dlog), Vp, _stream()),
+                      "st_rnn_fused_dlogits_w")
         else:
-            dlog, gsc = ce_loss_backward(ctx.logits, dt, ctx.targets, n, V, Vp, gout)
+            dlog, gsc = ce_loss_backward(ctx.logits, dt, ctx.targets, n, V, Vp, gout, ctx.roww)
         grads, keep2 = m._c_grads()
         dfeat = torch.empty(plan.B, m.embed_dim, device=dev, dtype=torch.float32)
         check(lib().st_rnn_backward(C.byref(prm), C.byref(grads), C.byref(seq), None, _cp(dlog), Vp, None, _cp(ctx.ws),
                                     ctx.ws.numel(), _cp(dfeat), None, _stream()), "st_rnn_backward")
         ctx.ws = None
-        return dfeat.to(ctx.feat_dtype), None, None, None, None, None, None
+        return dfeat.to(ctx.feat_dtype), None, None, None, None, None, None, None, None
 
 
 class Decoder(FollowsMoves, nn.Module):
@@ -259,11 +329,32 @@ class RNN(Decoder):
     # ---- reference surface -------------------------------------------------------------
     def forward(self, cnn_feature, image_caption, caption_size):
         """rnn.py:27-35: teacher-forced logits over the packed sequence, (N_tok, V) fp32."""
-        return _DecoderFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "logits", torch.is_grad_enabled())
+        return _DecoderFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "logits", torch.is_grad_enabled(), None, None)
 
-    def loss(self, cnn_feature, image_caption, caption_size):
-        """main.py:145-149 fused: CrossEntropyLoss()(rnn(feat, cap, lens), packed(cap)) as one scalar."""
-        return _DecoderFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "loss", torch.is_grad_enabled())
+    def loss(self, cnn_feature, image_caption, caption_size, sequence_weight=None, token_weight=None):
+        """main.py:145-149 fused: CrossEntropyLoss()(rnn(feat, cap, lens), packed(cap)) as one scalar.
+
+        With `sequence_weight` (B,) and / or `token_weight` (B, T) (float tensors, signed, T the caption tensor's width; both:
+        their product) the scalar is sum_{b,t} w[b, t] * nll[b, t] / N_tok -- reward-weighted training (REINFORCE, self-critical
+        sequence training).  The divisor stays N_tok, so weights of one give the plain loss; the weights are constants (no
+        gradient flows into them) and apply inside the loss kernels: no logits tensor appears on the fused route."""
+        if sequence_weight is None and token_weight is None:
+            return _DecoderFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "loss", torch.is_grad_enabled(),
+                                    None, None)
+        check_caption_args(image_caption, caption_size)
+        check_weight_args(image_caption.shape[0], image_caption.shape[1], sequence_weight, token_weight)
+        return _DecoderFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "loss", torch.is_grad_enabled(),
+                                sequence_weight, token_weight)
+
+    def token_logp(self, cnn_feature, image_caption, caption_size):
+        """log p(image_caption[b, t] | image b, image_caption[b, :t]) for every token of the given captions: (B, T) fp32, T the
+        caption tensor's width, 0 past caption_size[b].  No gradient.  -token_logp.sum() / N_tok is loss(); with the output of
+        ``sample`` as captions it scores what that call's `logp` scored (at temperature 1, top_k 0; the two passes round differently).  On the fused route (bf16,
+        H = 512) the vocabulary projection runs tile by tile: there is no logits tensor."""
+        check_caption_args(image_caption, caption_size)
+        with torch.no_grad():
+            nll = _DecoderFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "nll", False, None, None)
+            return unpack_rows(plan_for(caption_size, nll.device), -nll, image_caption.shape[1], nll.device)
 
     def beam_search(self, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50, start_id=1, end_id=2):
         """beam_search.py:45-97 over the whole batch (BASELINE config 5: beam_width=5, max_length=25)."""

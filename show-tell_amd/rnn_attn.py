@@ -25,7 +25,8 @@ import torch.nn as nn
 from . import _lib
 from ._lib import AttnGrads, AttnParams, check, dtype_code, lib
 from ._lib import ptr as _cp, stream as _stream
-from .rnn import CAP_MAX, Decoder, ce_loss, ce_loss_backward, logits_grad, sample_lengths, up8
+from .rnn import (CAP_MAX, Decoder, ce_loss, ce_loss_backward, check_caption_args, check_weight_args, logits_grad, pack_row_weights,
+                  sample_lengths, unpack_rows, up8)
 from .seq import plan_for
 
 
@@ -46,7 +47,7 @@ class Attention_Net(nn.Module):
 
 class _AttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feat, _anchor, module, caption, lens, mode, alpha_c, need_grad):
+    def forward(ctx, feat, _anchor, module, caption, lens, mode, alpha_c, need_grad, sequence_weight, token_weight):
         m = module
         dev = feat.device
         if not feat.is_cuda or not m.linear.weight.is_cuda:
@@ -66,17 +67,23 @@ class _AttnFn(torch.autograd.Function):
         ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
         V, Vp, n, T = m.vocab_size, up8(m.vocab_size), plan.ntok, caption.shape[1]
         alphas = torch.zeros(B, T, P, device=dev, dtype=torch.float32)        # rnn_attn.py:65
-        logits = torch.empty(n, Vp, device=dev, dtype=torch.float32 if mode == "logits" else dt)
+        roww = pack_row_weights(plan, sequence_weight, token_weight, dev)
+        logits = torch.empty(n, Vp, device=dev, dtype=dt if mode == "loss" else torch.float32)
         check(lib().st_attn_forward(C.byref(prm), C.byref(seq), _cp(featc), _cp(cap_T), _cp(ws), nbytes, _cp(logits),
                                     dtype_code(logits.dtype), Vp, _cp(alphas), int(need_grad), _stream()), "st_attn_forward")
         # st_attn_forward steps over plan.T columns; alphas has T (padded) columns: strides must agree
         ctx.m, ctx.plan, ctx.caption, ctx.cap_T, ctx.ws, ctx.mode, ctx.P = m, plan, caption, cap_T, ws, mode, P
-        ctx.alphas, ctx.alpha_c, ctx.keep = alphas, alpha_c, keep
+        ctx.alphas, ctx.alpha_c, ctx.keep, ctx.roww = alphas, alpha_c, keep, roww
         if mode == "logits":
             return logits[:, :V], alphas
         targets = torch.nn.utils.rnn.pack_padded_sequence(caption, lens, batch_first=True)[0].contiguous()   # main_attn.py:126
+        if mode == "nll":
+            nll = torch.empty(n, device=dev, dtype=torch.float32)
+            ce_loss(logits, logits.dtype, targets, n, V, Vp, None, None, nll)
+            ctx.mark_non_differentiable(nll, alphas)
+            return nll, alphas
         loss = torch.zeros((), device=dev, dtype=torch.float32)
-        ce_loss(logits, dt, targets, n, V, Vp, loss)
+        ce_loss(logits, dt, targets, n, V, Vp, loss, roww)     # the doubly-stochastic term below stays unweighted
         check(lib().st_attn_reg_loss(_cp(alphas), B, T, P, float(alpha_c), _cp(loss), _stream()), "st_attn_reg_loss")
         ctx.logits, ctx.targets = logits, targets
         return loss, alphas
@@ -92,8 +99,10 @@ class _AttnFn(torch.autograd.Function):
             dlog = logits_grad(g0, dt, n, V, Vp, torch.empty)
             dal = (galphas if galphas is not None else torch.zeros_like(ctx.alphas)).float().contiguous()
             alpha_c = 0.0
+        elif ctx.mode != "loss":
+            raise _lib.ShowTellHipError("token_logp has no gradient")
         else:
-            dlog, gs = ce_loss_backward(ctx.logits, dt, ctx.targets, n, V, Vp, g0)
+            dlog, gs = ce_loss_backward(ctx.logits, dt, ctx.targets, n, V, Vp, g0, ctx.roww)
             alpha_c = ctx.alpha_c
         prm, keep = m._c_params()
         prm.P = ctx.P
@@ -102,7 +111,7 @@ class _AttnFn(torch.autograd.Function):
         check(lib().st_attn_backward(C.byref(prm), C.byref(grads), C.byref(seq), _cp(ctx.cap_T), _cp(dlog), Vp, _cp(ctx.alphas), _cp(dal),
                                      float(alpha_c), _cp(gs), _cp(ctx.ws), ctx.ws.numel(), _stream()), "st_attn_backward")
         ctx.ws = None
-        return None, None, None, None, None, None, None, None
+        return None, None, None, None, None, None, None, None, None, None
 
 
 class RNN_Attn(Decoder):
@@ -164,12 +173,26 @@ class RNN_Attn(Decoder):
 
     def forward(self, cnn_feature, image_caption, caption_size):
         """rnn_attn.py:98-118: (packed logits (N_tok,V) fp32, alphas (B,T,P))."""
-        return _AttnFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "logits", 0.0, torch.is_grad_enabled())
+        return _AttnFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "logits", 0.0, torch.is_grad_enabled(), None, None)
 
-    def loss(self, cnn_feature, image_caption, caption_size, alpha_c=1.0):
-        """main_attn.py:126-131 fused: CE(packed logits, packed caption) + alpha_c * mean((1 - sum_t alpha)^2)."""
-        out, _ = _AttnFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "loss", float(alpha_c), torch.is_grad_enabled())
+    def loss(self, cnn_feature, image_caption, caption_size, alpha_c=1.0, sequence_weight=None, token_weight=None):
+        """main_attn.py:126-131 fused: CE(packed logits, packed caption) + alpha_c * mean((1 - sum_t alpha)^2).
+        `sequence_weight` (B,) / `token_weight` (B, T) weight the cross-entropy terms as in RNN.loss (the divisor stays N_tok, no
+        gradient into the weights); the doubly-stochastic term stays unweighted."""
+        if sequence_weight is not None or token_weight is not None:
+            check_caption_args(image_caption, caption_size)
+            check_weight_args(image_caption.shape[0], image_caption.shape[1], sequence_weight, token_weight)
+        out, _ = _AttnFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "loss", float(alpha_c), torch.is_grad_enabled(),
+                               sequence_weight, token_weight)
         return out
+
+    def token_logp(self, cnn_feature, image_caption, caption_size):
+        """log p(image_caption[b, t]) at every step of the teacher-forced pass (rnn_attn.py:98-118): (B, T) fp32, 0 past
+        caption_size[b]; no gradient.  -token_logp.sum() / N_tok is the cross-entropy part of loss()."""
+        check_caption_args(image_caption, caption_size)
+        with torch.no_grad():
+            nll, _ = _AttnFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "nll", 0.0, False, None, None)
+            return unpack_rows(plan_for(caption_size, nll.device), -nll, image_caption.shape[1], nll.device)
 
     def _decode_inputs(self, cnn_feature):
         if not cnn_feature.is_cuda:

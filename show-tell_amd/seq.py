@@ -35,6 +35,14 @@ class SeqPlan:
         self.rows_t = torch.from_numpy(rows_t).to(device)
         self.prev_row = torch.from_numpy(prev).to(device)
         self._bs_c = (C.c_int * self.T)(*[int(v) for v in bs])
+        self._row_index = {}
+
+    def row_index(self, device):
+        """(rows_b, rows_t) as int64 index tensors on `device`: x[rows_b, rows_t] gathers a (B, T) tensor to packed rows."""
+        key = str(device)
+        if key not in self._row_index:
+            self._row_index[key] = (self.rows_b.to(device=device, dtype=torch.long), self.rows_t.to(device=device, dtype=torch.long))
+        return self._row_index[key]
 
     def c_struct(self, caption):
         if not caption.is_cuda:

@@ -24,6 +24,7 @@ import torch
 
 from .head import linear_bn1d
 from .parallel import GradAllReducer, broadcast_state
+from .rnn import sample_lengths
 
 
 def synthetic_batch(B, V, seed=1, device="cuda", image_size=224, mean=12.5, std=2.5, lo=6, hi=25):
@@ -41,6 +42,36 @@ def synthetic_batch(B, V, seed=1, device="cuda", image_size=224, mean=12.5, std=
     g = torch.Generator(device="cpu").manual_seed(seed)
     images = torch.randn(B, 3, image_size, image_size, generator=g)
     return images.to(device), torch.from_numpy(cap).to(device), [int(l) for l in lens]
+
+
+def self_critical_advantage(reward, baseline, greedy_reward=None):
+    """reward (B, S) -> advantage (B, S).  'greedy': reward - the greedy caption's reward (B,) of the same image (self-critical
+    sequence training); 'mean': reward - the mean reward of the image's OTHER samples (needs S >= 2).  Computed in float64 and
+    returned as float32: equal rewards give an advantage of exactly 0."""
+    reward = torch.as_tensor(reward).double()
+    if reward.dim() != 2:
+        raise ValueError(f"reward_fn must return (B, S) rewards (got shape {tuple(reward.shape)})")
+    if baseline == "greedy":
+        g = torch.as_tensor(greedy_reward).double().reshape(-1)
+        if g.shape[0] != reward.shape[0]:
+            raise ValueError(f"reward_fn must return one reward per greedy caption (got {g.shape[0]} for {reward.shape[0]} images)")
+        return (reward - g[:, None]).float()
+    if baseline == "mean":
+        S = reward.shape[1]
+        if S < 2:
+            raise ValueError("baseline='mean' needs num_samples >= 2")
+        return (reward - (reward.sum(1, keepdim=True) - reward) / (S - 1)).float()
+    raise ValueError(f"baseline must be 'greedy' or 'mean' (got {baseline!r})")
+
+
+def sample_caption_batch(ids, lengths):
+    """The B * S sampled rows of ``sample`` as a caption batch: ids (B, S, T), lengths (B, S) -> (order, captions (B * S, T),
+    lens list), rows sorted by length, descending and stable (what pack_padded_sequence asks for).  order[k] = b * S + s is the
+    sample behind sorted row k: its image is order[k] // S, and a per-sample value v (B, S) goes along as v.reshape(-1)[order]."""
+    B, S, T = ids.shape
+    flat_len = lengths.reshape(B * S)
+    order = torch.sort(flat_len, descending=True, stable=True)[1]
+    return order, ids.reshape(B * S, T)[order].contiguous(), [int(l) for l in flat_len[order].tolist()]
 
 
 class Trainer:
@@ -102,9 +133,10 @@ class Trainer:
             ev.record(side)
         self._pre.append((image, pooled, ev, undo))
 
-    def step(self, image, caption, caption_len, upcoming=()):
-        """One training step.  `upcoming`: the images of the next minibatches, in order (at most `depth` are used)."""
-        cnn, rnn = self.cnn, self.rnn
+    def _features(self, image, upcoming):
+        """What every kind of step starts with: the frozen backbone (taken from or issued to the side streams), the previous
+        step's deferred optimizer update, zero_grad, and the trainable head.  Returns the (B, E) image features."""
+        cnn = self.cnn
         pooled = self._backbone(image)                 # frozen, detached (cnn.py:46-47): overlaps the all-reduce
         # keep up to `depth` later minibatches' frozen backbones in flight, beside this step's trainable part and each other
         upcoming = [im for im in list(upcoming)[:self.depth] if im is not None]
@@ -117,12 +149,53 @@ class Trainer:
                 self._prefetch(im)
         self._apply_pending()                          # previous step's optimizer.step() (main.py:152)
         self.opt.zero_grad()                           # main.py:146
-        feat = linear_bn1d(pooled, cnn.linear_secondlast_layer, cnn.last_layer, cnn.training, cnn.compute_dtype)
-        loss = rnn.loss(feat, caption, caption_len)    # main.py:148-149
+        return linear_bn1d(pooled, cnn.linear_secondlast_layer, cnn.last_layer, cnn.training, cnn.compute_dtype)
+
+    def step(self, image, caption, caption_len, upcoming=()):
+        """One training step.  `upcoming`: the images of the next minibatches, in order (at most `depth` are used)."""
+        feat = self._features(image, upcoming)
+        loss = self.rnn.loss(feat, caption, caption_len)    # main.py:148-149
         loss.backward()                                # main.py:151
         self.reducer.start(self.opt.flat_grad)
         self.pending = True
         return loss
+
+    def step_self_critical(self, image, reward_fn, num_samples=5, baseline="greedy", upcoming=(), generator=None, uniforms=None,
+                           end_id=2):
+        """One reward-weighted step on the model's own samples (REINFORCE with a baseline; baseline='greedy' is self-critical
+        sequence training): `num_samples` captions per image are drawn on the device (temperature 1, whole vocabulary),
+        `reward_fn(ids (B, S, T) int64, lengths (B, S) int64) -> (B, S)` scores them on the host (CPU tensors; e.g.
+        ``evaluation.cider_reward``), and the loss is sum over the sampled tokens of (reward - baseline) * -log p(token) / N_tok:
+        ``rnn.loss`` with ``sequence_weight`` on the samples as a caption batch, the image features repeated.  The baseline is
+        the reward of the greedy caption of the same image ('greedy') or the mean reward of the image's other samples ('mean').
+        Backward and the deferred all-reduce / optimizer schedule are those of `step`.  Returns (loss, mean reward of the samples).
+        `generator` / `uniforms` fix the draws as in ``RNN.sample``."""
+        if baseline not in ("greedy", "mean"):
+            raise ValueError(f"baseline must be 'greedy' or 'mean' (got {baseline!r})")
+        if baseline == "mean" and num_samples < 2:
+            raise ValueError("baseline='mean' needs num_samples >= 2")
+        rnn = self.rnn
+        feat = self._features(image, upcoming)
+        B, S = feat.shape[0], int(num_samples)
+        with torch.no_grad():
+            ids, _, lengths = rnn.sample(feat, S, temperature=1.0, top_k=0, end_id=end_id, generator=generator, uniforms=uniforms)
+            greedy = None
+            if baseline == "greedy":
+                gids = rnn.sentence_index(feat).reshape(B, 1, -1)
+                greedy = reward_fn(gids.cpu(), sample_lengths(gids, end_id).cpu())
+            ids_cpu, len_cpu = ids.cpu(), lengths.cpu()
+        reward = torch.as_tensor(reward_fn(ids_cpu, len_cpu), dtype=torch.float32)
+        if tuple(reward.shape) != (B, S):
+            raise ValueError(f"reward_fn must return {(B, S)} rewards (got shape {tuple(reward.shape)})")
+        advantage = self_critical_advantage(reward, baseline, greedy)
+        order, cap, lens = sample_caption_batch(ids_cpu, len_cpu)
+        dev = feat.device
+        feat_rep = feat[(order // S).to(dev)]          # the image behind every sorted row
+        loss = rnn.loss(feat_rep, cap.to(dev), lens, sequence_weight=advantage.reshape(-1)[order])
+        loss.backward()
+        self.reducer.start(self.opt.flat_grad)
+        self.pending = True
+        return loss, reward.mean()
 
     def flush(self):
         self._apply_pending()
