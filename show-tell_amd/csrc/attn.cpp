@@ -336,29 +336,6 @@ GPlan make_gplan(const st_attn_params* p, int B) {
   return q;
 }
 
-// arg-max over the vocabulary (first maximum, like torch.max) -> ids column t and the running token buffer
-__global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ logits, int ldl, int V, long* __restrict__ ids,
-                                                     int ids_stride, int t, long* __restrict__ cur) {
-  __shared__ float sv[4]; __shared__ int si[4];
-  const int row = blockIdx.x;
-  const float* l = logits + (long)row * ldl;
-  float best = -INFINITY; int bi = 0x7fffffff;
-  for (int i = threadIdx.x; i < V; i += blockDim.x) { const float v = l[i]; if (v > best || (v == best && i < bi)) { best = v; bi = i; } }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
-  if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    best = sv[0]; bi = si[0];
-    for (int w = 1; w < 4; ++w) if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
-    if (bi >= V) bi = 0;
-    ids[(long)row * ids_stride + t] = bi;
-    cur[row] = bi;
-  }
-}
 __global__ void fill_ids_kernel(long* cur, int n, long v) { const int i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) cur[i] = v; }
 }  // namespace
 
@@ -410,10 +387,7 @@ int attn_greedy_run(const st_attn_params* p, const float* cnn_feature, int B, in
     if (sp) {
       if (st_sample_rows(logits, Vp, B, r.V, sp->u + t, steps, sp->inv_temperature, sp->top_k, sp->end_id, fin, ids_out, sp->logp_out, steps, t,
                          cur, stream)) return 1;
-    } else {
-      hipLaunchKernelGGL(argmax_kernel, dim3(B), dim3(256), 0, st, logits, Vp, r.V, ids_out, steps, t, cur);
-      ST_LAUNCH_CHECK();
-    }
+    } else if (argmax_rows_launch(logits, Vp, B, r.V, ids_out, steps, t, cur, st)) return 1;   // first maximum, like torch.max (rnn_attn.py:141)
     c = nx;
   }
   return 0;

@@ -5,36 +5,29 @@
 // kernel, gates in its epilogue), one MFMA GEMM for the vocabulary projection and one
 // arg-max + embedding-gather kernel.  Everything is issued from this one C call.
 #include "decoder_host.h"
+#include "select.h"
 #include <stdlib.h>
 
 namespace {
 
-// first-maximum rule of torch.max(1): among equal maxima the lowest index wins
+// Whole-row arg-max (first maximum, like torch.max(1)) -> ids column t; optionally the running token buffer cur[row] (the
+// attention decoders) and the winner's embedding row x[row] (the plain decoder's next input).
 template <typename T>
 __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restrict__ logits, int ldl, int V,
-                                                           long* __restrict__ ids, int ids_stride, int t,
+                                                           long* __restrict__ ids, int ids_stride, int t, long* __restrict__ cur,
                                                            const T* __restrict__ emb, T* __restrict__ x, int E) {
   __shared__ float sv[4];
   __shared__ int si[4];
   const int row = blockIdx.x;
   const float* l = logits + (long)row * ldl;
-  float best = -INFINITY; int bi = 0x7fffffff;
+  float best = -INFINITY; int bi = kNoIndex;
   for (int i = threadIdx.x; i < V; i += blockDim.x) {
     const float v = l[i];
-    if (v > best || (v == best && i < bi)) { best = v; bi = i; }
+    if (ranks_before(v, i, best, bi)) { best = v; bi = i; }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { sv[wid] = best; si[wid] = bi; }
-  __syncthreads();
-  best = sv[0]; bi = si[0];
-  for (int w = 1; w < 4; ++w) if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
+  block_first(best, bi, sv, si);
   if (bi >= V) bi = 0;   // all-NaN row: keep the index in range
-  if (threadIdx.x == 0) ids[(long)row * ids_stride + t] = bi;
+  if (threadIdx.x == 0) { ids[(long)row * ids_stride + t] = bi; if (cur) cur[row] = bi; }
   if (x) {
     constexpr int N = 16 / (int)sizeof(T);
     for (int c = threadIdx.x * N; c < E; c += blockDim.x * N)
@@ -94,23 +87,14 @@ __global__ __launch_bounds__(256) void softmax_topk_kernel(const float* __restri
   __syncthreads();
   S = ssum[0] + ssum[1] + ssum[2] + ssum[3];
   for (int j = 0; j < k; ++j) {
-    float best = -INFINITY; int bi = 0x7fffffff;
+    float best = -INFINITY; int bi = kNoIndex;
     for (int i = threadIdx.x; i < V; i += blockDim.x) {
       bool used = false;
       for (int q = 0; q < j; ++q) used |= (chosen[q] == i);
       const float v = l[i];
-      if (!used && (v > best || (v == best && i < bi))) { best = v; bi = i; }
+      if (!used && ranks_before(v, i, best, bi)) { best = v; bi = i; }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
-      if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-    __syncthreads();
-    if (lane == 0) { sv[wid] = best; si[wid] = bi; }
-    __syncthreads();
-    best = sv[0]; bi = si[0];
-    for (int w = 1; w < 4; ++w) if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
+    block_first(best, bi, sv, si);
     if (bi >= V) bi = 0;
     if (threadIdx.x == 0) {
       chosen[j] = bi;
@@ -121,88 +105,9 @@ __global__ __launch_bounds__(256) void softmax_topk_kernel(const float* __restri
   }
 }
 
-
-// The same result for k <= 8 in TWO passes over the row instead of 2 + k: pass 1 keeps, per thread, the maximum and a sorted
-// list of its k best (value descending, index ascending: a thread meets its indices in increasing order, so strict '>' on
-// insertion keeps first-index-wins); pass 2 is the sum of exponentials in exactly the order of softmax_topk_kernel (the
-// probabilities are bit-identical); then k rounds of a block-wide arg-max over the threads' list heads pick the winners.
-template <int KMAX>
-__global__ __launch_bounds__(256) void softmax_topk_fast_kernel(const float* __restrict__ logits, int ldl, int V, int k,
-                                                                float* __restrict__ top_p, long* __restrict__ top_id, int raw) {
-  __shared__ float sv[4]; __shared__ int si[4]; __shared__ float ssum[4];
-  const int row = blockIdx.x, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const float* l = logits + (long)row * ldl;
-  float lv[KMAX]; int li[KMAX];
-#pragma unroll
-  for (int q = 0; q < KMAX; ++q) { lv[q] = -INFINITY; li[q] = 0x7fffffff; }
-  float M = -INFINITY;
-  constexpr int UN = 8;                                      // loads in flight per thread: the passes are L2-latency bound
-  for (int i0 = threadIdx.x; i0 < V; i0 += UN * 256) {
-    float vv[UN];
-#pragma unroll
-    for (int u = 0; u < UN; ++u) vv[u] = i0 + u * 256 < V ? l[i0 + u * 256] : -INFINITY;
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      const int i = i0 + u * 256;
-      const float v = vv[u];
-      if (i >= V) continue;
-      M = fmaxf(M, v);
-      if (v > lv[KMAX - 1] || li[KMAX - 1] == 0x7fffffff) {  // enters the list (an empty slot takes anything)
-        float cv = v; int cidx = i;
-#pragma unroll
-        for (int q = 0; q < KMAX; ++q) {
-          const bool before = cv > lv[q] || (li[q] == 0x7fffffff && cidx != 0x7fffffff);
-          if (before) { const float tv = lv[q]; const int ti = li[q]; lv[q] = cv; li[q] = cidx; cv = tv; cidx = ti; }
-        }
-      }
-    }
-  }
-  M = wave_max(M);
-  if (lane == 0) sv[wid] = M;
-  __syncthreads();
-  M = fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3]));
-  float S = 0.f;
-  if (!raw) {
-    for (int i0 = threadIdx.x; i0 < V; i0 += UN * 256) {     // same order of additions as softmax_topk_kernel
-      float vv[UN];
-#pragma unroll
-      for (int u = 0; u < UN; ++u) vv[u] = i0 + u * 256 < V ? l[i0 + u * 256] : 0.f;
-#pragma unroll
-      for (int u = 0; u < UN; ++u) if (i0 + u * 256 < V) S += expf(vv[u] - M);
-    }
-    S = wave_sum(S);
-    if (lane == 0) ssum[wid] = S;
-  }
-  __syncthreads();
-  if (!raw) S = ssum[0] + ssum[1] + ssum[2] + ssum[3];
-  for (int j = 0; j < k; ++j) {
-    float best = lv[0]; int bi = li[0];                      // this thread's best remaining candidate
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
-      if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-    __syncthreads();
-    if (lane == 0) { sv[wid] = best; si[wid] = bi; }
-    __syncthreads();
-    best = sv[0]; bi = si[0];
-    for (int w = 1; w < 4; ++w) if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
-    if (li[0] == bi && bi != 0x7fffffff) {                   // the winner's owner moves on to its next candidate
-#pragma unroll
-      for (int q = 0; q + 1 < KMAX; ++q) { lv[q] = lv[q + 1]; li[q] = li[q + 1]; }
-      lv[KMAX - 1] = -INFINITY; li[KMAX - 1] = 0x7fffffff;
-    }
-    if (bi >= V) bi = 0;
-    if (threadIdx.x == 0) {
-      top_id[(long)row * k + j] = bi;
-      top_p[(long)row * k + j] = raw ? best : expf(best - M) / S;
-    }
-  }
-}
-
-
-// The same result again, without the per-thread sorted lists (their insertion code ran for nearly every element: with 64 lanes some
-// lane always had a new list entry, 47 us for 1280 x 10000 logits against 8.5 us of HBM time):
+// The same result for k <= 8 in two passes over the row instead of 2 + k, without per-thread sorted lists (their insertion code ran
+// for nearly every element: with 64 lanes some lane always had a new list entry, 47 us for 1280 x 10000 logits against 8.5 us of
+// HBM time):
 //   pass 1: every thread keeps only its MAXIMUM; the block's k-th largest thread maximum T is a lower bound of the row's k-th largest
 //           element (k threads hold an element >= T), so the row's top k are among the elements >= T;
 //   pass 2: the sum of exponentials in the order of softmax_topk_kernel (probabilities bit-identical) -- and the elements >= T are
@@ -244,16 +149,7 @@ __global__ __launch_bounds__(256) void softmax_topk_thr_kernel(const float* __re
   float T = -INFINITY, mine = tm;
   for (int j = 0; j < k; ++j) {
     float best = mine; int bi = (int)threadIdx.x;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
-      if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-    __syncthreads();
-    if (lane == 0) { sv[wid] = best; si[wid] = bi; }
-    __syncthreads();
-    best = sv[0]; bi = si[0];
-    for (int w = 1; w < 4; ++w) if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
+    block_first(best, bi, sv, si);
     if ((int)threadIdx.x == bi) mine = -INFINITY;
     T = best;
   }
@@ -285,18 +181,14 @@ __global__ __launch_bounds__(256) void softmax_topk_thr_kernel(const float* __re
     if (wid == 0) {
       int chosen[32];
       for (int j = 0; j < k; ++j) {
-        float best = -INFINITY; int bi = 0x7fffffff;
+        float best = -INFINITY; int bi = kNoIndex;
         for (int i = lane; i < V; i += 64) {
           bool used = false;
           for (int q = 0; q < j; ++q) used |= (chosen[q] == i);
           const float v = l[i];
-          if (!used && (v > best || (v == best && i < bi))) { best = v; bi = i; }
+          if (!used && ranks_before(v, i, best, bi)) { best = v; bi = i; }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
-          if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-        }
+        wave_first(best, bi);
         if (bi >= V) bi = 0;
         chosen[j] = bi;
         if (lane == 0) { top_id[(long)row * k + j] = bi; top_p[(long)row * k + j] = raw ? best : expf(best - M) / S; }
@@ -305,20 +197,11 @@ __global__ __launch_bounds__(256) void softmax_topk_thr_kernel(const float* __re
     return;
   }
   float myv = (int)threadIdx.x < n ? cv[threadIdx.x] : -INFINITY;
-  int myi = (int)threadIdx.x < n ? ci[threadIdx.x] : 0x7fffffff;
+  int myi = (int)threadIdx.x < n ? ci[threadIdx.x] : kNoIndex;
   for (int j = 0; j < k; ++j) {
     float best = myv; int bi = myi;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
-      if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-    __syncthreads();
-    if (lane == 0) { sv[wid] = best; si[wid] = bi; }
-    __syncthreads();
-    best = sv[0]; bi = si[0];
-    for (int w = 1; w < 4; ++w) if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
-    if (myi == bi && bi != 0x7fffffff) { myv = -INFINITY; myi = 0x7fffffff; }
+    block_first(best, bi, sv, si);
+    if (myi == bi && bi != kNoIndex) { myv = -INFINITY; myi = kNoIndex; }
     if (bi >= V) bi = 0;
     if (threadIdx.x == 0) {
       top_id[(long)row * k + j] = bi;
@@ -361,7 +244,7 @@ __global__ __launch_bounds__(256) void vocab_argmax_kernel(const T* __restrict__
   const bool mok = m < M;
   const T* Ar = A + (long)m * lda;
   const int nsteps = (K + 4 * EPC - 1) / (4 * EPC);
-  float best = -INFINITY; int bi = 0x7fffffff;
+  float best = -INFINITY; int bi = kNoIndex;
   for (int tt = 0; tt < 2; ++tt) {
     const int n0 = ((nslice * 4 + wid) * 2 + tt) * 16;
     if (n0 >= N) break;
@@ -387,20 +270,12 @@ __global__ __launch_bounds__(256) void vocab_argmax_kernel(const T* __restrict__
     for (int e = 0; e < 4; ++e) {
       if (n + e < N) {
         const float v = acc[e] + bias[n + e];
-        if (v > best || (v == best && n + e < bi)) { best = v; bi = n + e; }
+        if (ranks_before(v, n + e, best, bi)) { best = v; bi = n + e; }
       }
     }
   }
-#pragma unroll
-  for (int o = 16; o < 64; o <<= 1) {
-    const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
-  if (q4 == 0 && mok && bi != 0x7fffffff) {
-    unsigned u = __float_as_uint(best);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    atomicMax(keys + m, ((unsigned long long)u << 32) | (unsigned long long)(0xffffffffu - (unsigned)bi));
-  }
+  quad_first(best, bi);
+  if (q4 == 0 && mok && bi != kNoIndex) atomicMax(keys + m, argmax_key(best, bi));   // (an empty key is 0, a no-op for the maximum: no atomic for it)
 }
 
 // Same product, LDS-staged form for the shapes that fit (rows*K*sizeof(T) <= 128 KiB per pass, K <= 16 MFMA steps):
@@ -463,7 +338,7 @@ __global__ __launch_bounds__(256) void vocab_argmax_lds_kernel(const T* __restri
     const int ntile = (rows + 15) / 16;
     // per row tile: (value, first index) over this wave's 16 entries -> wbest
     auto finish = [&](const f32x4& acc, int mt) {
-      float best = -INFINITY; int bi = 0x7fffffff;
+      float best = -INFINITY; int bi = kNoIndex;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         if (n + e < N) {
@@ -471,6 +346,9 @@ __global__ __launch_bounds__(256) void vocab_argmax_lds_kernel(const T* __restri
           if (v > best || (v == best && n + e < bi)) { best = v; bi = n + e; }
         }
       }
+      // Written out by hand, NOT through select.h's ranks_before / quad_first / argmax_key (the same rule, the same key): with
+      // the calls the compiler turns this epilogue's branches into selects and re-schedules the tile loop around it, and the
+      // bf16 launch chain at B = 128, V = 10000 ran 0.3 us per step slower (profiles/select_refactor_ab.txt)
 #pragma unroll
       for (int o = 16; o < 64; o <<= 1) {
         const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
@@ -478,7 +356,7 @@ __global__ __launch_bounds__(256) void vocab_argmax_lds_kernel(const T* __restri
       }
       if (q4 == 0) {
         unsigned long long key = 0ull;                  // 0 = nothing (real keys have a non-zero index half)
-        if (bi != 0x7fffffff) {
+        if (bi != kNoIndex) {
           unsigned u = __float_as_uint(best);
           u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
           key = ((unsigned long long)u << 32) | (unsigned long long)(0xffffffffu - (unsigned)bi);
@@ -536,9 +414,7 @@ __global__ __launch_bounds__(256) void keys_to_ids_embed_kernel(unsigned long lo
                                                                 int ids_stride, int t, const T* __restrict__ emb, T* __restrict__ x,
                                                                 int E, int V) {
   const int row = blockIdx.x;
-  const unsigned long long key = keys[row];
-  int bi = (int)(0xffffffffu - (unsigned)(key & 0xffffffffull));
-  if (bi < 0 || bi >= V) bi = 0;
+  const int bi = key_token(keys[row], V);
   __syncthreads();
   if (threadIdx.x == 0) { ids[(long)row * ids_stride + t] = bi; keys[row] = 0ull; }
   constexpr int N = 16 / (int)sizeof(T);
@@ -571,6 +447,51 @@ GreedyPlan make_greedy_plan(const st_rnn_params* p, int B) {
   return q;
 }
 }  // namespace
+
+// The greedy fast path's vocabulary stage: keys[m] = max over n of the packed (h[m] . W_lin[n] + b_lin[n], first n); the logits
+// are never written.  htop = the top layer's B state rows.
+static int vocab_argmax_launch(const st_rnn_params* p, const void* htop, int B, unsigned long long* keys, hipStream_t st) {
+  const int dt = p->dtype, H = p->H, V = p->V;
+  const size_t es = st_dtype_size(dt);
+  const int epc = dt == ST_BF16 ? 8 : 4;
+  int rpp = (int)((128 * 1024) / ((size_t)H * es)) & ~15;
+  if (rpp > ((B + 15) & ~15)) rpp = (B + 15) & ~15;
+  int ysplit = 1;                                       // V/64 blocks alone fill 157 of 256 CUs at V = 10000: split the rows too
+  while ((V + 63) / 64 * ysplit < 256 && rpp >= 32 && rpp % 32 == 0 && ysplit < 4) { ysplit *= 2; rpp /= 2; }
+  if (H <= 64 * epc && H % (8 * epc) == 0 && rpp >= 16) {
+    // LDS-staged form: activations once per block, projection matrix once chip-wide
+    const size_t lds = (size_t)rpp * H * es + (size_t)4 * rpp * sizeof(unsigned long long);
+    static bool attr_set[64] = {};                      // the attribute belongs to the (function, device) pair
+    int dev_ = 0;
+    (void)hipGetDevice(&dev_);
+    if (dev_ >= 0 && dev_ < 64 && !attr_set[dev_]) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vocab_argmax_lds_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vocab_argmax_lds_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      attr_set[dev_] = true;
+    }
+    const dim3 vgrid(((V + 63) / 64 + 7) / 8 * 8 * ysplit);
+    if (dt == ST_BF16)
+      hipLaunchKernelGGL(vocab_argmax_lds_kernel<bf16_t>, vgrid, dim3(256), lds, st, (const bf16_t*)htop, H, (const bf16_t*)p->w_lin, H, p->b_lin, B, V, H, keys, rpp, ysplit);
+    else
+      hipLaunchKernelGGL(vocab_argmax_lds_kernel<float>, vgrid, dim3(256), lds, st, (const float*)htop, H, (const float*)p->w_lin, H, p->b_lin, B, V, H, keys, rpp, ysplit);
+  } else {
+    const int nsl = (V + 127) / 128, nmt = (B + 15) / 16;
+    const dim3 vgrid(((nsl + 7) / 8) * 8 * nmt);
+    if (dt == ST_BF16)
+      hipLaunchKernelGGL(vocab_argmax_kernel<bf16_t>, vgrid, dim3(256), 0, st, (const bf16_t*)htop, H, (const bf16_t*)p->w_lin, H, p->b_lin, B, V, H, keys);
+    else
+      hipLaunchKernelGGL(vocab_argmax_kernel<float>, vgrid, dim3(256), 0, st, (const float*)htop, H, (const float*)p->w_lin, H, p->b_lin, B, V, H, keys);
+  }
+  ST_LAUNCH_CHECK();
+  return 0;
+}
+
+// whole-row arg-max of fp32 logits -> ids column t and cur (declared in decoder_host.h: the attention decoders' greedy step)
+int argmax_rows_launch(const float* logits, int ldl, int n, int V, long* ids, int ids_stride, int t, long* cur, hipStream_t st) {
+  hipLaunchKernelGGL(argmax_embed_kernel<float>, dim3(n), dim3(256), 0, st, logits, ldl, V, ids, ids_stride, t, cur, (const float*)nullptr, (float*)nullptr, 0);
+  ST_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" size_t st_rnn_greedy_workspace_bytes(const st_rnn_params* p, int B) {
   if (!p || B <= 0) return 0;
@@ -674,40 +595,10 @@ extern "C" int st_rnn_greedy(const st_rnn_params* p, const void* feat, int B, in
       }
       if (rnn_gemm_launch(a, dt, rnn_cell_epi(p->cell), 1, st)) return 1;
     }
+    const char* htop = hbuf[nxt] + (size_t)(L - 1) * B * H * es;
     if (!logits_out) {
-      // fast path: vocabulary projection with a fused running arg-max (the logits are never written)
-      const char* htop = hbuf[nxt] + (size_t)(L - 1) * B * H * es;
       unsigned long long* kt = fused ? keys + (size_t)t * B : keys;
-      const int epc = dt == ST_BF16 ? 8 : 4;
-      int rpp = (int)((128 * 1024) / ((size_t)H * es)) & ~15;
-      if (rpp > ((B + 15) & ~15)) rpp = (B + 15) & ~15;
-      int ysplit = 1;                                   // V/64 blocks alone fill 157 of 256 CUs at V = 10000: split the rows too
-      while ((V + 63) / 64 * ysplit < 256 && rpp >= 32 && rpp % 32 == 0 && ysplit < 4) { ysplit *= 2; rpp /= 2; }
-      if (H <= 64 * epc && H % (8 * epc) == 0 && rpp >= 16) {
-        // LDS-staged form: activations once per block, projection matrix once chip-wide
-        const size_t lds = (size_t)rpp * H * es + (size_t)4 * rpp * sizeof(unsigned long long);
-        static bool attr_set[64] = {};                  // the attribute belongs to the (function, device) pair
-        int dev_ = 0;
-        (void)hipGetDevice(&dev_);
-        if (dev_ >= 0 && dev_ < 64 && !attr_set[dev_]) {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vocab_argmax_lds_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vocab_argmax_lds_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-          attr_set[dev_] = true;
-        }
-        const dim3 vgrid(((V + 63) / 64 + 7) / 8 * 8 * ysplit);
-        if (dt == ST_BF16)
-          hipLaunchKernelGGL(vocab_argmax_lds_kernel<bf16_t>, vgrid, dim3(256), lds, st, (const bf16_t*)htop, H, (const bf16_t*)p->w_lin, H, p->b_lin, B, V, H, kt, rpp, ysplit);
-        else
-          hipLaunchKernelGGL(vocab_argmax_lds_kernel<float>, vgrid, dim3(256), lds, st, (const float*)htop, H, (const float*)p->w_lin, H, p->b_lin, B, V, H, kt, rpp, ysplit);
-      } else {
-        const int nsl = (V + 127) / 128, nmt = (B + 15) / 16;
-        const dim3 vgrid(((nsl + 7) / 8) * 8 * nmt);
-        if (dt == ST_BF16)
-          hipLaunchKernelGGL(vocab_argmax_kernel<bf16_t>, vgrid, dim3(256), 0, st, (const bf16_t*)htop, H, (const bf16_t*)p->w_lin, H, p->b_lin, B, V, H, kt);
-        else
-          hipLaunchKernelGGL(vocab_argmax_kernel<float>, vgrid, dim3(256), 0, st, (const float*)htop, H, (const float*)p->w_lin, H, p->b_lin, B, V, H, kt);
-      }
-      ST_LAUNCH_CHECK();
+      if (vocab_argmax_launch(p, htop, B, kt, st)) return 1;
       if (!fused || t == steps - 1) {                   // fused: only the last step's ids are left to write
         if (dt == ST_BF16)
           hipLaunchKernelGGL(keys_to_ids_embed_kernel<bf16_t>, dim3(B), dim3(64), 0, st, kt, ids_out, steps, t, (const bf16_t*)p->emb, (bf16_t*)xbuf, E, V);
@@ -720,11 +611,11 @@ extern "C" int st_rnn_greedy(const st_rnn_params* p, const void* feat, int B, in
       continue;
     }
     float* lg = logits_out + (size_t)t * B * Vp;
-    if (st_gemm_nt(hbuf[nxt] + (size_t)(L - 1) * B * H * es, H, p->w_lin, H, lg, Vp, B, V, H, dt, ST_F32, p->b_lin, stream)) return 1;
+    if (st_gemm_nt(htop, H, p->w_lin, H, lg, Vp, B, V, H, dt, ST_F32, p->b_lin, stream)) return 1;
     if (dt == ST_BF16)
-      hipLaunchKernelGGL(argmax_embed_kernel<bf16_t>, dim3(B), dim3(256), 0, st, lg, Vp, V, ids_out, steps, t, (const bf16_t*)p->emb, (bf16_t*)xbuf, E);
+      hipLaunchKernelGGL(argmax_embed_kernel<bf16_t>, dim3(B), dim3(256), 0, st, lg, Vp, V, ids_out, steps, t, (long*)nullptr, (const bf16_t*)p->emb, (bf16_t*)xbuf, E);
     else
-      hipLaunchKernelGGL(argmax_embed_kernel<float>, dim3(B), dim3(256), 0, st, lg, Vp, V, ids_out, steps, t, (const float*)p->emb, (float*)xbuf, E);
+      hipLaunchKernelGGL(argmax_embed_kernel<float>, dim3(B), dim3(256), 0, st, lg, Vp, V, ids_out, steps, t, (long*)nullptr, (const float*)p->emb, (float*)xbuf, E);
     ST_LAUNCH_CHECK();
     x = xbuf;
     cur = nxt;
@@ -762,17 +653,12 @@ extern "C" int st_softmax_topk(const float* logits, int ldl, int n, int V, int k
   ST_CHECK(logits && top_p && top_id, "st_softmax_topk: null pointer");
   ST_CHECK(k >= 1 && k <= 32 && k <= V && ldl >= V, "st_softmax_topk: need 1 <= k <= min(32, V)");
   if (n <= 0) return 0;
-  // k <= 8 (every beam width in use): two passes over the row; the 2 + k pass form stays as the general case and as the
-  // cross-check (ST_TOPK_SLOW=1)
+  // k <= 8 (every beam width in use) and a row of at least k * 256 entries: two passes over the row; the 2 + k pass form stays as
+  // the general case and as the cross-check (ST_TOPK_SLOW=1)
   static int slow = -1;
   if (slow < 0) { const char* e = getenv("ST_TOPK_SLOW"); slow = e ? atoi(e) : 0; }
-  static const bool thr = [] { const char* e = getenv("ST_TOPK_THR"); return !e || atoi(e) != 0; }();   // A/B switch: 0 = the sorted-list form
-  if (k <= 8 && !slow && thr && (long)k * 256 <= V)
+  if (k <= 8 && !slow && (long)k * 256 <= V)
     hipLaunchKernelGGL(softmax_topk_thr_kernel, dim3(n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), logits, ldl, V, k, top_p, top_id, raw);
-  else if (k <= 5 && !slow && (long)k * 256 <= V)
-    hipLaunchKernelGGL(softmax_topk_fast_kernel<5>, dim3(n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), logits, ldl, V, k, top_p, top_id, raw);
-  else if (k <= 8 && !slow && (long)k * 256 <= V)
-    hipLaunchKernelGGL(softmax_topk_fast_kernel<8>, dim3(n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), logits, ldl, V, k, top_p, top_id, raw);
   else
     hipLaunchKernelGGL(softmax_topk_kernel, dim3(n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), logits, ldl, V, k, top_p, top_id, raw);
   ST_LAUNCH_CHECK();

@@ -19,6 +19,7 @@
 // Every spin is bounded; on a timeout or when the dispatcher did not deal 32 workgroups to every XCD the kernel raises a flag and the
 // host falls back to the launch chain.
 #include "decoder_host.h"
+#include "select.h"
 #include <stdlib.h>
 
 namespace {
@@ -192,8 +193,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
               for (int i = 0; i < 8; ++i) {        // token of step t-1 -> embedding row (the keys were merged by memory-side atomics)
                 const int row = (tid >> 6) + 4 * i;
                 const unsigned long long key = __hip_atomic_load(&a.keys[(size_t)(t - 1) * nch * CR + r0 + row], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                int tok = (int)(0xffffffffu - (unsigned)(key & 0xffffffffull));
-                if (tok < 0 || tok >= a.V) tok = 0;
+                const int tok = key_token(key, a.V);
                 if (li == 0 && (tid & 63) == 0 && r0 + row < a.B) a.ids_out[(long)(r0 + row) * a.steps + t - 1] = tok;
                 rowp[i] = a.emb + (size_t)tok * PH;
               }
@@ -273,9 +273,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         if (!wait_count(cnt_of(a.steps - 1, L, c), (unsigned)nvw, err, wid, lane, abort_flag)) return;
         if (tid < CR && c * CR + tid < a.B) {
           const unsigned long long key = __hip_atomic_load(&a.keys[(size_t)(a.steps - 1) * nch * CR + c * CR + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          int tok = (int)(0xffffffffu - (unsigned)(key & 0xffffffffull));
-          if (tok < 0 || tok >= a.V) tok = 0;
-          a.ids_out[(long)(c * CR + tid) * a.steps + a.steps - 1] = tok;
+          a.ids_out[(long)(c * CR + tid) * a.steps + a.steps - 1] = key_token(key, a.V);
         }
       }
     }
@@ -316,7 +314,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       }
       __syncthreads();
       // (value, first index) over this wave's entries, per row of the chain's two 16-row tiles
-      float best[2] = {-INFINITY, -INFINITY}; int bidx[2] = {0x7fffffff, 0x7fffffff};
+      float best[2] = {-INFINITY, -INFINITY}; int bidx[2] = {kNoIndex, kNoIndex};
 #pragma unroll
       for (int jj = 0; jj < 2; ++jj) {
         if (n0[jj] >= 0) {
@@ -333,7 +331,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             for (int e = 0; e < 4; ++e) {
               if (n + e < a.V) {
                 const float v = acc[e] + bz[jj][e];
-                if (v > best[i] || (v == best[i] && n + e < bidx[i])) { best[i] = v; bidx[i] = n + e; }
+                if (ranks_before(v, n + e, best[i], bidx[i])) { best[i] = v; bidx[i] = n + e; }
               }
             }
           }
@@ -341,20 +339,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-#pragma unroll
-        for (int o = 16; o < 64; o <<= 1) {
-          const float ov = __shfl_xor(best[i], o, 64); const int oi = __shfl_xor(bidx[i], o, 64);
-          if (ov > best[i] || (ov == best[i] && oi < bidx[i])) { best[i] = ov; bidx[i] = oi; }
-        }
-        if (q4 == 0) {
-          unsigned long long key = 0ull;
-          if (bidx[i] != 0x7fffffff) {
-            unsigned u = __float_as_uint(best[i]);
-            u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-            key = ((unsigned long long)u << 32) | (unsigned long long)(0xffffffffu - (unsigned)bidx[i]);
-          }
-          wbest[wid * CR + i * 16 + r16] = key;
-        }
+        quad_first(best[i], bidx[i]);
+        if (q4 == 0) wbest[wid * CR + i * 16 + r16] = argmax_key(best[i], bidx[i]);
       }
       __syncthreads();
       if (tid < CR) {

@@ -57,6 +57,10 @@ inline std::vector<int> st_packed_offsets(const st_packed_seq* s) {
   return off;
 }
 
+// Whole-row arg-max (first maximum, like torch.max(1)) of n rows of fp32 logits -> ids[row * ids_stride + t] and, when cur is
+// given, cur[row]: csrc/decode.hip, argmax_embed_kernel without its embedding gather.
+int argmax_rows_launch(const float* logits, int ldl, int n, int V, long* ids, int ids_stride, int t, long* cur, hipStream_t st);
+
 inline int rnn_cell_epi(int cell) { return cell == ST_CELL_GRU ? 1 : 2; }   // gate epilogue of rnn_gemm_launch*
 
 // RnnGemmArgs of one full (has_x = 1) cell of layer l over M rows: gates from x W_ih^T + b_ih and hprev W_hh^T + b_hh.  x rows are

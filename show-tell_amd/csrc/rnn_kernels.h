@@ -2,7 +2,10 @@
 #pragma once
 #include "common.h"
 
-struct RnnGemmArgs {
+// alignas(16): a launch carries up to kRnnBatch of these back to back in the kernel-argument segment, and a size that is no
+// multiple of 16 puts every second cell's pointer pairs across a 16-byte boundary -- the kernels' scalar loads of them split, and the
+// bf16 greedy launch chain (two cells per launch) ran 0.8 us per step slower (profiles/select_refactor_ab.txt)
+struct alignas(16) RnnGemmArgs {
   // acc[g][m][n] = sum_k A[m][k] W[g*gstride + n][k]  (+ second operand pair A2/W2 when HAS_X)
   const void* A; const void* W; int M, N, K, lda, ldw, gstride;
   const void* A2; const void* W2; int K2, lda2, ldw2;
@@ -16,7 +19,6 @@ struct RnnGemmArgs {
   void* hout; void* cout; int ldho;
   void* hout2; int ldho2;              // optional second copy of h' (decode: running state + layer output)
   void* cache; int ldcache;            // saved gates for BPTT (NULL at inference)
-  unsigned long long* argmax_keys;     // EPI 3: per-row packed (value, index) maxima
   // greedy decode, layer 0: row m of the x operand is A2 + token(x_keys[m]) * lda2 (A2 = the embedding table), i.e. the
   // embedding gather of the previous step's arg-max happens inside the cell; block column 0 also writes the token ids
   const unsigned long long* x_keys; int x_V;
@@ -28,6 +30,7 @@ struct RnnGemmArgs {
   // No new fields (16 cells must fit the 4 KiB kernel-argument segment): in these forms `accumulate` carries the mode
   // (kCellRawOut / kCellSplit) and (gx, ldgx) point at the fp32 gh rows.
 };
+static_assert(sizeof(RnnGemmArgs) % 16 == 0, "cells sit back to back in the kernel-argument segment: keep each one 16-byte aligned");
 constexpr int kCellRawOut = 1, kCellSplit = 2;
 
 // Up to kRnnBatch independent cells in ONE launch (blockIdx.z picks the cell): the (layer, time) wavefront of the

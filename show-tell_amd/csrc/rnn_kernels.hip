@@ -14,6 +14,7 @@
 // and the whole gate nonlinearity runs in the epilogue so a timestep is ONE launch.
 #include "common.h"
 #include "rnn_kernels.h"
+#include "select.h"
 #include <string.h>
 
 namespace {
@@ -95,24 +96,15 @@ __device__ __forceinline__ void skinny_mma(const RnnGemmArgs& a, int mbase, int 
     mok[t] = m < a.M;
     mokH[t] = BWD ? m < a.M2 : mok[t];
     AH[t] = reinterpret_cast<const T*>(a.A) + (long)m * a.lda;
-    if (!HAS_X && a.x_keys && a.A) {                   // split decode step: the A operand is the embedding row of the previous token
-      int tok = 0;
-      if (mok[t]) {
-        tok = (int)(0xffffffffu - (unsigned)(a.x_keys[m] & 0xffffffffull));
-        if (tok < 0 || tok >= a.x_V) tok = 0;
-        if (a.ids_out && n0 == 0 && kslice == 0 && q4 == 0) a.ids_out[(long)m * a.ids_stride + a.ids_t] = tok;
-      }
-      AH[t] = reinterpret_cast<const T*>(a.A) + (long)tok * a.lda;
-    }
     long xrow = m;
-    if (HAS_X && a.x_keys) {                           // token of the previous step -> embedding row
+    if (a.x_keys && (HAS_X || a.A)) {                  // greedy decode: the token of the previous step picks an embedding row
       int tok = 0;
       if (mok[t]) {
-        tok = (int)(0xffffffffu - (unsigned)(a.x_keys[m] & 0xffffffffull));
-        if (tok < 0 || tok >= a.x_V) tok = 0;
+        tok = key_token(a.x_keys[m], a.x_V);
         if (a.ids_out && n0 == 0 && kslice == 0 && q4 == 0) a.ids_out[(long)m * a.ids_stride + a.ids_t] = tok;
       }
-      xrow = tok;
+      if (HAS_X) xrow = tok;                           // fused cell: the x operand
+      else AH[t] = reinterpret_cast<const T*>(a.A) + (long)tok * a.lda;   // split step: the A operand is the input half
     }
     AX[t] = reinterpret_cast<const T*>(a.A2) + xrow * a.lda2;
   }
@@ -197,7 +189,7 @@ __global__ __launch_bounds__(256) void rnn_gemm_kernel(RnnGemmBatch batch) {
   // the epilogue operands (biases, precomputed x-projection, previous state) are requested BEFORE the fragment loads
   // so that they arrive under the same round trip
   const int pm = m0 + r16, pn = n0 + 4 * q4;
-  const bool epi_ok = wid < MT && pm < a.M && pn < a.N && EPI != 3;
+  const bool epi_ok = wid < MT && pm < a.M && pn < a.N;
   float ex[NG][4], eb[NG][4], es[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int g = 0; g < NG; ++g)
@@ -240,31 +232,8 @@ __global__ __launch_bounds__(256) void rnn_gemm_kernel(RnnGemmBatch batch) {
 
   // lane owns row m = m0 + r16 and units n = n0 + 4*q4 + {0..3}
   const int m = m0 + r16, n = n0 + 4 * q4;
-  if (EPI != 3 && (m >= a.M || n >= a.N)) return;
+  if (m >= a.M || n >= a.N) return;
   const int H = a.N;
-  if (EPI == 3) {
-    // greedy decoding: the logits are never written; (value, first index) per row by 64-bit atomic max
-    float best = -INFINITY; int bi = 0x7fffffff;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (n + e < a.N) {
-        const float v = sumH[0][e] + (a.bias_h ? a.bias_h[n + e] : 0.f);
-        if (v > best) { best = v; bi = n + e; }
-      }
-    }
-#pragma unroll
-    for (int o = 16; o < 64; o <<= 1) {
-      const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
-      if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-    if (q4 == 0 && bi != 0x7fffffff && m < a.M) {   // rows past M took part in the shuffles only
-      unsigned u = __float_as_uint(best);
-      u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-      const unsigned long long key = ((unsigned long long)u << 32) | (unsigned long long)(0xffffffffu - (unsigned)bi);
-      atomicMax(a.argmax_keys + m, key);
-    }
-    return;
-  }
   if (EPI == 0) {
     float v[4];
 #pragma unroll
@@ -670,7 +639,7 @@ int rnn_gemm_launch_batch(const RnnGemmArgs* cells, int ncells, int dtype, int e
   for (int i = 0; i < ncells; ++i) {
     const RnnGemmArgs& a = cells[i];
     if (a.M <= 0) continue;
-    ST_CHECK(epi == 3 || a.N % 4 == 0, "rnn_gemm: N=%d must be a multiple of 4", a.N);
+    ST_CHECK(a.N % 4 == 0, "rnn_gemm: N=%d must be a multiple of 4", a.N);
     ST_CHECK(a.K % epc == 0 && a.lda % epc == 0 && a.ldw % epc == 0, "rnn_gemm: K/lda/ldw must be multiples of %d", epc);
     if (has_x) ST_CHECK(a.K2 % epc == 0 && a.lda2 % epc == 0 && a.ldw2 % epc == 0, "rnn_gemm: K2/lda2/ldw2 must be multiples of %d", epc);
     b.c[nc++] = a;
@@ -681,18 +650,16 @@ int rnn_gemm_launch_batch(const RnnGemmArgs* cells, int ncells, int dtype, int e
   const dim3 grid((maxN + 15) / 16, (maxM + 15) / 16, nc), block(256);
   // many cells in one launch: the weights are most of the L2 traffic -> two row tiles per block share them
   // ... and so do the 16-row tiles of one tall cell (beam search steps 1280 rows at a time: 80 row tiles re-read the weights)
-  const bool mt2 = (nc >= 2 || maxM >= 512) && maxM > 16 && epi != 3;
+  const bool mt2 = (nc >= 2 || maxM >= 512) && maxM > 16;
   const dim3 grid2((maxN + 15) / 16, (maxM + 31) / 32, nc);
 #define RG(T, NG, EPI, HX) do { if (mt2) hipLaunchKernelGGL((rnn_gemm_kernel<T, NG, EPI, HX, 2>), grid2, block, 0, st, b); \
                                else hipLaunchKernelGGL((rnn_gemm_kernel<T, NG, EPI, HX, 1>), grid, block, 0, st, b); } while (0)
   if (dtype == ST_BF16) {
     if (epi == 0) RG(bf16_t, 1, 0, false);
-    else if (epi == 3) RG(bf16_t, 1, 3, false);
     else if (epi == 1) { if (has_x) RG(bf16_t, 3, 1, true); else RG(bf16_t, 3, 1, false); }
     else { if (has_x) RG(bf16_t, 4, 2, true); else RG(bf16_t, 4, 2, false); }
   } else {
     if (epi == 0) RG(float, 1, 0, false);
-    else if (epi == 3) RG(float, 1, 3, false);
     else if (epi == 1) { if (has_x) RG(float, 3, 1, true); else RG(float, 3, 1, false); }
     else { if (has_x) RG(float, 4, 2, true); else RG(float, 4, 2, false); }
   }

@@ -15,14 +15,12 @@
 // flight together, and stay in registers between the passes; longer or unaligned rows take the passes over memory.
 // A row needs at least one finite entry: with none (all -inf or NaN) the token is 0 and logp is NaN.
 #include "decoder_host.h"
+#include "select.h"
 
 namespace {
 
 constexpr int kSampleThreads = 256;
 constexpr int kSampleCap = 1024;      // candidate list; more elements >= T0 (rows of equal logits): exact selection by rounds
-
-// a ranks before b in st_softmax_topk's order: value descending, index ascending
-__device__ __forceinline__ bool ranks_before(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
 
 // f(value, index) for every index of [lo, hi) in increasing order; lo is a multiple of 4 (16-byte loads when VEC: the row
 // is padded to a multiple of 4 entries, so the last load stays inside the row)
@@ -66,20 +64,6 @@ struct RowReg {
   }
 };
 
-// block-wide first element in st_softmax_topk's order (4 waves); every thread returns the winner
-__device__ __forceinline__ void block_first(float& v, int& i, float* sv, int* si) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(v, o, 64); const int oi = __shfl_xor(i, o, 64);
-    if (ranks_before(ov, oi, v, i)) { v = ov; i = oi; }
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = v; si[threadIdx.x >> 6] = i; }
-  __syncthreads();
-  v = sv[0]; i = si[0];
-  for (int w = 1; w < 4; ++w) if (ranks_before(sv[w], si[w], v, i)) { v = sv[w]; i = si[w]; }
-}
-
 template <typename Row>
 __global__ __launch_bounds__(kSampleThreads) void sample_rows_kernel(const float* __restrict__ logits, int ldl, int V, const float* __restrict__ u,
                                                                      int u_stride, float inv_t, int top_k, long end_id, uint8_t* __restrict__ finished,
@@ -109,7 +93,7 @@ __global__ __launch_bounds__(kSampleThreads) void sample_rows_kernel(const float
   if (tid == 0) s_cnt = 0;
   __syncthreads();
   M = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
-  float T = -INFINITY; int Ti = 0x7fffffff;                  // top_k == 0 (or V): everything is kept
+  float T = -INFINITY; int Ti = kNoIndex;                    // top_k == 0 (or V): everything is kept
   if (top_k > 0 && top_k < V) {
     int rank = 0;                                            // of this thread's maximum among the 256 (a total order: one thread per rank)
     for (int o = 0; o < kSampleThreads; ++o) rank += ranks_before(s_tm[o], o, tm, tid) ? 1 : 0;
@@ -131,7 +115,7 @@ __global__ __launch_bounds__(kSampleThreads) void sample_rows_kernel(const float
     } else {                                                 // (block-uniform) round j picks the first element after round j-1's
       float pv = INFINITY; int pi = -1;
       for (int j = 0; j < top_k; ++j) {
-        float bv = -INFINITY; int bi = 0x7fffffff;
+        float bv = -INFINITY; int bi = kNoIndex;
         row_part.each([&](float v, int i) {
           if (ranks_before(pv, pi, v, i) && ranks_before(v, i, bv, bi)) { bv = v; bi = i; }
         });

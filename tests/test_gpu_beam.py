@@ -121,15 +121,18 @@ def test_bf16_greedy_bleu4_vs_fp32_oracle():
     assert R.bleu_corpus(gts, res, 4)[3] >= 0.9
 
 
+@pytest.mark.parametrize("V,ldl", [(5003, 5008), (2048, 2048), (2047, 2048), (37, 40)])
 @pytest.mark.parametrize("k", [1, 5, 8, 12])
-def test_softmax_topk_kernels_against_torch(k):
-    """st_softmax_topk: the two-pass form (k <= 8) and the general form (k = 12) against torch -- indices exact including
-    ties (first index wins, as torch.sort(stable) on the negated row), probabilities to float32 rounding; raw mode returns logits."""
+def test_softmax_topk_kernels_against_torch(k, V, ldl):
+    """st_softmax_topk: the threshold form (k <= 8 and k * 256 <= V) and the general form (k = 12, or a shorter row) against
+    torch -- indices exact including ties (first index wins, as torch.sort(stable) on the negated row), probabilities to float32
+    rounding; raw mode returns logits.  V = 2048 with k = 8 is the first row length on the threshold kernel (exactly k * 256),
+    2047 falls to the general kernel, and at V = 37 most threads hold no element, so the empty index takes part in every merge."""
     import ctypes as C
     from showtell_amd._lib import check, lib
     from showtell_amd.rnn import _cp, _stream
     torch.manual_seed(3)
-    n, V, ldl = 37, 5003, 5008
+    n = 37
     x = torch.randn(n, ldl, device="cuda")
     x[:, ::7] = x[:, 3:4]                                # many exact ties, some of them at the top
     x[5, :V] = 0.25                                      # a constant row: indices 0 .. k-1
