@@ -489,6 +489,33 @@ int st_sgd_step(float* param, const float* grad, float* momentum_buf, void* bf16
 int st_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* bf16_shadow, long n,
                  float lr, float beta1, float beta2, float eps, int step, float grad_scale, void* stream);
 
+/* Global-norm gradient clipping, weight decay and a non-finite guard for the two optimizers, with nothing read back by the host.
+ * st_grad_sumsq writes one partial sum of squares of grad[0..n) per workgroup into `partials` (device, room for
+ * st_grad_sumsq_max_parts() floats) and the number written into *nparts_out (host); the grid depends on n only and no float
+ * atomics are used, so the same input gives the same bits.  The _ex steps, launched after it on the same stream, add the
+ * partials up in every workgroup (fixed order) and derive
+ *     norm = grad_scale * sqrt(sum)                       (flat_grad holds the sum over ranks, grad_scale = 1 / world)
+ *     coef = grad_scale * min(1, max_norm / (norm + 1e-6))    (torch.nn.utils.clip_grad_norm_; max_norm <= 0: coef = grad_scale)
+ * then  g' = coef * g + weight_decay * p  (SGD; Adam with decoupled = 0, as torch.optim.Adam(weight_decay=)), or
+ * p *= 1 - lr * weight_decay and the moments from coef * g  (decoupled = 1, torch.optim.AdamW).
+ * skip_nonfinite: a launch whose sum is not finite leaves param, the state and the shadow untouched and counts as skipped;
+ * Adam's bias correction (and SGD's "first step") then follow the count of APPLIED steps kept in `status` instead of
+ * `step` / `first_step`.  Without it a non-finite norm propagates as torch's does.
+ * status: ST_OPTIM_STATUS_WORDS 32-bit words of device memory owned by the caller, zeroed (or set to a restored step count in
+ * words 2, 4, 5) before the first call:  [0] float last norm, [1] float last coef, [2] int applied steps, [3] int skipped steps,
+ * [4], [5] int the applied count as two slots.  A launch reads slot `parity` and writes slot `parity ^ 1`: the caller passes
+ * 0, 1, 0, 1, .. on consecutive _ex calls that share a status block. */
+#define ST_OPTIM_STATUS_WORDS 8
+int st_grad_sumsq_max_parts(void);
+int st_grad_sumsq(const float* grad, long n, float* partials, int* nparts_out, void* stream);
+int st_sgd_step_ex(float* param, const float* grad, float* momentum_buf, void* bf16_shadow, long n,
+                   float lr, float momentum, int first_step, float grad_scale, const float* partials, int nparts,
+                   float max_norm, float weight_decay, int skip_nonfinite, int parity, void* status, void* stream);
+int st_adam_step_ex(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* bf16_shadow, long n,
+                    float lr, float beta1, float beta2, float eps, int step, float grad_scale, const float* partials,
+                    int nparts, float max_norm, float weight_decay, int decoupled, int skip_nonfinite, int parity,
+                    void* status, void* stream);
+
 /* Greedy decoding, exactly `steps` iterations with no early stop (rnn.py:37-58, rnn_lstm.py:35-57):
  * ids_out[B][steps] int64 (first-maximum tie rule of torch.max).  logits_out (optional, tests):
  * [steps][B][Vp] fp32 with Vp = V rounded up to 8. */

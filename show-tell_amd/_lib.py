@@ -198,6 +198,10 @@ _SIGS = {
     "st_linear_bn1d_backward": ([c_p] * 6 + [c_i, c_i, c_i, c_i, c_i] + [c_p] * 5 + [C.c_size_t, c_p], c_i),
     "st_sgd_step": ([c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_i, c_f, c_p], c_i),
     "st_adam_step": ([c_p, c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_i, c_f, c_p], c_i),
+    "st_grad_sumsq_max_parts": ([], c_i),
+    "st_grad_sumsq": ([c_p, c_l, c_p, C.POINTER(c_i), c_p], c_i),
+    "st_sgd_step_ex": ([c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_i, c_f, c_p, c_i, c_f, c_f, c_i, c_i, c_p, c_p], c_i),
+    "st_adam_step_ex": ([c_p, c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_i, c_f, c_p, c_i, c_f, c_f, c_i, c_i, c_i, c_p, c_p], c_i),
     "st_resnet_create": ([c_i, c_i, C.POINTER(c_p)], c_i),
     "st_resnet_destroy": ([c_p], None),
     "st_resnet_num_convs": ([c_p], c_i),

@@ -151,8 +151,18 @@ class Trainer:
         self.opt.zero_grad()                           # main.py:146
         return linear_bn1d(pooled, cnn.linear_secondlast_layer, cnn.last_layer, cnn.training, cnn.compute_dtype)
 
+    @property
+    def grad_norm(self):
+        """The optimizer's ``last_grad_norm``: a 0-d device tensor holding the global norm of the (rank-averaged) gradient that
+        the last APPLIED optimizer step saw -- the deferred one runs inside the next `step` or `flush` -- or None for an
+        optimizer without one.  Reading its value synchronises; the training loop itself never does."""
+        return getattr(self.opt, "last_grad_norm", None)
+
     def step(self, image, caption, caption_len, upcoming=()):
-        """One training step.  `upcoming`: the images of the next minibatches, in order (at most `depth` are used)."""
+        """One training step.  `upcoming`: the images of the next minibatches, in order (at most `depth` are used).
+        Gradient clipping, weight decay and the non-finite guard are the optimizer's keywords (``max_grad_norm``,
+        ``weight_decay``, ``skip_nonfinite``, optim.py): they act inside the deferred optimizer step, after the all-reduce, on
+        the device, and need nothing here."""
         feat = self._features(image, upcoming)
         loss = self.rnn.loss(feat, caption, caption_len)    # main.py:148-149
         loss.backward()                                # main.py:151
@@ -169,6 +179,7 @@ class Trainer:
         ``rnn.loss`` with ``sequence_weight`` on the samples as a caption batch, the image features repeated.  The baseline is
         the reward of the greedy caption of the same image ('greedy') or the mean reward of the image's other samples ('mean').
         Backward and the deferred all-reduce / optimizer schedule are those of `step`.  Returns (loss, mean reward of the samples).
+        Signed, reward-scaled losses are where an optimizer built with ``max_grad_norm`` (and ``skip_nonfinite``) earns its keep.
         `generator` / `uniforms` fix the draws as in ``RNN.sample``."""
         if baseline not in ("greedy", "mean"):
             raise ValueError(f"baseline must be 'greedy' or 'mean' (got {baseline!r})")
