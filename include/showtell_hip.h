@@ -457,6 +457,23 @@ int st_rnn_fused_loss_w(const st_rnn_params* p, const st_packed_seq* s, const vo
 int st_rnn_fused_dlogits_w(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
                            const long* targets, const float* scratch, const float* grad_scale_dev, const float* row_weight,
                            void* dlogits, int ldd, void* stream);
+/* The same with label smoothing, torch's nn.CrossEntropyLoss(label_smoothing = eps), 0 <= eps < 1 (checked; NaN is refused):
+ *   u_r = logsumexp(x_r) - (1 / V) * sum_{v < V} x_r[v]   (cross entropy against the uniform distribution)
+ *   st_rnn_fused_loss_ls:    *loss_accum += sum_r row_weight[r] * ((1 - eps) * nll_r + eps * u_r) / ntok;  smooth_out[r] = u_r;  nll_out[r]
+ *                            stays the unsmoothed nll_r.  row_weight / nll_out / smooth_out follow the NULL conventions of _w.  The rows'
+ *                            mean logit is formed tile by tile: `tile_sums` (st_rnn_fused_loss_ls_bytes, fp32, the caller's, dead after the
+ *                            call) receives each 128-entry tile's sum per token and is added in a fixed order, so u_r is bit-reproducible.
+ *                            st_rnn_fused_loss_bytes and the workspace are those of the calls above.
+ *   st_rnn_fused_dlogits_ls: dlogits = (softmax - (1 - eps) * onehot - eps / V) / ntok * *grad_scale_dev (* row_weight[r]); pad columns
+ *                            [V, ldd) exact zeros.  With eps = 0 both compute what the _w calls compute, bit for bit. */
+size_t st_rnn_fused_loss_ls_bytes(const st_rnn_params* p, const st_packed_seq* s);
+int st_rnn_fused_loss_ls(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
+                         const long* targets, float* scratch, size_t scratch_bytes, const float* row_weight, float* nll_out,
+                         float* smooth_out, float label_smoothing, float* tile_sums, size_t tile_sums_bytes, float* loss_accum,
+                         void* stream);
+int st_rnn_fused_dlogits_ls(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
+                            const long* targets, const float* scratch, const float* grad_scale_dev, const float* row_weight,
+                            float label_smoothing, void* dlogits, int ldd, void* stream);
 
 /* nn.CrossEntropyLoss() (mean) forward + backward (main.py:94,149):
  *   *loss_accum += mean_r( logsumexp(x_r) - x_r[target_r] );  dlogits = (softmax - onehot) * grad_scale / rows
@@ -469,6 +486,12 @@ int st_cross_entropy(const void* logits, int logits_dtype, const long* target, i
 int st_cross_entropy_w(const void* logits, int logits_dtype, const long* target, int rows, int V, int ldl,
                        const float* row_weight, float* nll_out, float* loss_accum, void* dlogits, int dlogits_dtype, int ldd,
                        float grad_scale, const float* grad_scale_dev, void* stream);
+/* ... with label smoothing eps in [0, 1) (checked): smooth_out[r] = logsumexp(x_r) - mean_{v < V} x_r[v] (NULL: not stored);
+ *   *loss_accum += sum_r row_weight[r] * ((1 - eps) * nll_r + eps * smooth_r) / rows;  dlogits = (softmax - (1 - eps) * onehot - eps / V)
+ *   * row_weight[r] * grad_scale / rows; nll_out stays unsmoothed.  dlogits may alias logits as above. */
+int st_cross_entropy_ls(const void* logits, int logits_dtype, const long* target, int rows, int V, int ldl,
+                        const float* row_weight, float* nll_out, float* smooth_out, float label_smoothing, float* loss_accum,
+                        void* dlogits, int dlogits_dtype, int ldd, float grad_scale, const float* grad_scale_dev, void* stream);
 
 /* Encoder head: y = BatchNorm1d(x W^T + b) (cnn.py:37-38,49; momentum 0.01) and its backward
  * (dx is not needed: the backbone output is detached, cnn.py:47).  Gradients are accumulated. */

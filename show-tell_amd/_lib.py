@@ -167,6 +167,10 @@ _SIGS = {
     "st_rnn_fused_dlogits": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_i, c_p], c_i),
     "st_rnn_fused_loss_w": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, C.c_size_t, c_p, c_p, C.c_size_t, c_p, c_p, c_p, c_p], c_i),
     "st_rnn_fused_dlogits_w": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p, c_i, c_p], c_i),
+    "st_rnn_fused_loss_ls_bytes": ([C.POINTER(RnnParams), C.POINTER(PackedSeq)], C.c_size_t),
+    "st_rnn_fused_loss_ls": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, C.c_size_t, c_p, c_p, C.c_size_t, c_p, c_p, c_p, c_f, c_p,
+                             C.c_size_t, c_p, c_p], c_i),
+    "st_rnn_fused_dlogits_ls": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_f, c_p, c_i, c_p], c_i),
     "st_rnn_backward": ([C.POINTER(RnnParams), C.POINTER(RnnGrads), C.POINTER(PackedSeq), c_p, c_p, c_i, c_p, c_p, C.c_size_t,
                          c_p, c_p, c_p], c_i),
     "st_rnn_greedy_workspace_bytes": ([C.POINTER(RnnParams), c_i], C.c_size_t),
@@ -193,6 +197,7 @@ _SIGS = {
     "st_attn_beam_search": ([c_p, c_p, c_i, c_i, c_i, c_l, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p, c_p], c_i),
     "st_cross_entropy": ([c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_f, c_p, c_p], c_i),
     "st_cross_entropy_w": ([c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_p, c_p], c_i),
+    "st_cross_entropy_ls": ([c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_i, c_i, c_f, c_p, c_p], c_i),
     "st_head_workspace_bytes": ([c_i, c_i, c_i, c_i], C.c_size_t),
     "st_linear_bn1d_forward": ([c_p] * 7 + [c_i, c_i, c_i, c_i, c_i, c_f, c_f] + [c_p] * 6, c_i),
     "st_linear_bn1d_backward": ([c_p] * 6 + [c_i, c_i, c_i, c_i, c_i] + [c_p] * 5 + [C.c_size_t, c_p], c_i),

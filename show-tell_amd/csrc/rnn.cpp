@@ -185,6 +185,44 @@ extern "C" int st_rnn_fused_dlogits(const st_rnn_params* p, const st_packed_seq*
   return st_rnn_fused_dlogits_w(p, s, workspace, workspace_bytes, targets, scratch, grad_scale_dev, nullptr, dlogits, ldd, stream);
 }
 
+// ---- the same with label smoothing (torch's CrossEntropyLoss(label_smoothing = eps)): the LS kernels of csrc/vocab_ce.hip --------------
+// tile_sums (floats): [tiles][ntok] sums of each tile's valid logits, caller-owned so that st_rnn_fused_loss_bytes stays what it was
+extern "C" size_t st_rnn_fused_loss_ls_bytes(const st_rnn_params* p, const st_packed_seq* s) {
+  if (!p || !s) return 0;
+  return (size_t)s->ntok * (size_t)vocab_ce_tiles(p->V) * sizeof(float);
+}
+extern "C" int st_rnn_fused_loss_ls(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
+                                    const long* targets, float* scratch, size_t scratch_bytes, const float* row_weight, float* nll_out,
+                                    float* smooth_out, float label_smoothing, float* tile_sums, size_t tile_sums_bytes, float* loss_accum,
+                                    void* stream) {
+  if (check_common(p, s, "st_rnn_fused_loss_ls")) return 1;
+  ST_CHECK(workspace && targets && scratch && tile_sums && (loss_accum || nll_out || smooth_out), "st_rnn_fused_loss_ls: null pointer");
+  ST_CHECK(label_smoothing >= 0.f && label_smoothing < 1.f, "st_rnn_fused_loss_ls: label_smoothing=%g outside [0, 1)", (double)label_smoothing);
+  ST_CHECK(st_rnn_fused_loss_supported(p), "st_rnn_fused_loss_ls: needs bf16, H = 512 and the vocabulary projection (use st_rnn_forward's logits + st_cross_entropy_ls)");
+  const Plan q = make_plan(p, s);
+  ST_CHECK(workspace_bytes >= q.total && scratch_bytes >= st_rnn_fused_loss_bytes(p, s), "st_rnn_fused_loss_ls: workspace / scratch too small");
+  ST_CHECK(tile_sums_bytes >= st_rnn_fused_loss_ls_bytes(p, s), "st_rnn_fused_loss_ls: tile_sums too small (%zu < %zu)", tile_sums_bytes,
+           st_rnn_fused_loss_ls_bytes(p, s));
+  const char* ytop = reinterpret_cast<const char*>(workspace) + q.y + (size_t)(p->L - 1) * s->ntok * p->H * q.es;
+  const int n = s->ntok;
+  return vocab_ce_forward(ytop, p->w_lin, p->b_lin, targets, n, p->V, scratch + 2 * (size_t)n, scratch + n, scratch, loss_accum,
+                          row_weight, nll_out, reinterpret_cast<hipStream_t>(stream), tile_sums, smooth_out, label_smoothing);
+}
+// dlogits = (softmax - (1 - eps) * onehot - eps / V) / ntok * *grad_scale_dev (* row_weight[r]); pad columns [V, ldd) zero
+extern "C" int st_rnn_fused_dlogits_ls(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
+                                       const long* targets, const float* scratch, const float* grad_scale_dev, const float* row_weight,
+                                       float label_smoothing, void* dlogits, int ldd, void* stream) {
+  if (check_common(p, s, "st_rnn_fused_dlogits_ls")) return 1;
+  ST_CHECK(workspace && targets && scratch && dlogits, "st_rnn_fused_dlogits_ls: null pointer");
+  ST_CHECK(label_smoothing >= 0.f && label_smoothing < 1.f, "st_rnn_fused_dlogits_ls: label_smoothing=%g outside [0, 1)", (double)label_smoothing);
+  ST_CHECK(st_rnn_fused_loss_supported(p), "st_rnn_fused_dlogits_ls: unsupported configuration");
+  const Plan q = make_plan(p, s);
+  ST_CHECK(workspace_bytes >= q.total, "st_rnn_fused_dlogits_ls: workspace too small");
+  const char* ytop = reinterpret_cast<const char*>(workspace) + q.y + (size_t)(p->L - 1) * s->ntok * p->H * q.es;
+  return vocab_ce_dlogits(ytop, p->w_lin, p->b_lin, targets, scratch, s->ntok, p->V, dlogits, ldd, 1.0f, grad_scale_dev, row_weight,
+                          reinterpret_cast<hipStream_t>(stream), true, label_smoothing);
+}
+
 extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,
                                const void* x0_override, const void* dlogits, int ldd, const float* dy_top_extra,
                                void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, void* stream) {

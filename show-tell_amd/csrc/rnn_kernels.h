@@ -81,10 +81,13 @@ int rnn_greedy_pipe(const st_rnn_params* p, const void* feat, int B, int steps, 
 int vocab_ce_supported(int dtype, int H);
 int vocab_ce_tiles(int V);
 // (row_w: optional per-row loss weight; nll: optional per-row lse - x[target] output; both [n] fp32 on the device)
+// (tile_sums [vocab_ce_tiles(V)][n] / smoothed: label smoothing eps through the LS kernels, smooth: optional per-row lse - mean(x) output)
 int vocab_ce_forward(const void* y, const void* w, const float* bias, const long* target, int n, int V, float* partial, float* tgt,
-                     float* lse, float* loss, const float* row_w, float* nll, hipStream_t st);
+                     float* lse, float* loss, const float* row_w, float* nll, hipStream_t st, float* tile_sums = nullptr,
+                     float* smooth = nullptr, float eps = 0.f);
 int vocab_ce_dlogits(const void* y, const void* w, const float* bias, const long* target, const float* lse, int n, int V,
-                     void* dlogits, int ldd, float gscale, const float* gscale_dev, const float* row_w, hipStream_t st);
+                     void* dlogits, int ldd, float gscale, const float* gscale_dev, const float* row_w, hipStream_t st,
+                     bool smoothed = false, float eps = 0.f);
 
 int rnn_gemm_launch(const RnnGemmArgs& a, int dtype, int epi, int has_x, hipStream_t st);
 int rnn_gemm_launch_batch(const RnnGemmArgs* cells, int ncells, int dtype, int epi, int has_x, hipStream_t st);

@@ -557,20 +557,33 @@ __global__ __launch_bounds__(256) void rnn_bwd_cell_kernel(RnnBwdFusedBatch batc
 // one block per row; the row is read twice from L2 (max+sum online, then gradient)
 // WGT: the row's loss term and gradient are also times row_w[row] (NULL: 1; the divisor stays nrows) and its unweighted
 // -log softmax(x)[t] goes to nll[row] (NULL: not stored); without WGT the kernel is the code it was
+// LS (label smoothing, with WGT): the first pass also carries sum x beside (m, s); u = lse - sum / V goes to smooth[row] (NULL: not
+// stored), the row's term is (1 - eps) * nll + eps * u and dlogits = (softmax - (1 - eps) * onehot - eps / V) * gscale; every read of
+// the row that the loss needs still happens before the first write.  The other instantiations are the code they were
 // ---------------------------------------------------------------------------------------
-template <typename TL, typename TD, bool WGT>
+struct CeSmooth {
+  float* smooth;   // [rows] or NULL
+  float eps, inv_v;
+};
+template <typename TL, typename TD, bool WGT, bool LS = false>
 __global__ __launch_bounds__(256) void ce_kernel(const TL* __restrict__ logits, const long* __restrict__ target,
                                                  float* __restrict__ loss, TD* __restrict__ dlogits,
                                                  int V, int ldl, int ldd, float inv_rows, float gscale, const float* __restrict__ gscale_dev,
-                                                 const float* __restrict__ row_w, float* __restrict__ nll) {
+                                                 const float* __restrict__ row_w, float* __restrict__ nll, CeSmooth ls) {
   __shared__ float sm[8], ss[8];
+  __shared__ float sx[LS ? 8 : 1];
   const int row = blockIdx.x;
   const TL* x = logits + (long)row * ldl;
-  float m = -INFINITY, s = 0.f;
+  float m = -INFINITY, s = 0.f, xs = 0.f;
   for (int i = threadIdx.x; i < V; i += blockDim.x) {
     const float v = to_f32<TL>(x[i]);
     const float nm = fmaxf(m, v);
-    s = s * __expf(m - nm) + __expf(v - nm);
+    if constexpr (LS) {   // the fused multiply-add spelled out: beside `xs += v` the compiler pairs the two additions instead of contracting
+      s = __fmaf_rn(s, __expf(m - nm), __expf(v - nm));   // this one, and lse would differ from the other instantiations' in its last bit
+      xs += v;
+    } else {
+      s = s * __expf(m - nm) + __expf(v - nm);
+    }
     m = nm;
   }
   // combine (m, s) pairs across the wave, then across waves
@@ -580,9 +593,11 @@ __global__ __launch_bounds__(256) void ce_kernel(const TL* __restrict__ logits, 
     const float nm = fmaxf(m, om);
     s = (m == -INFINITY ? 0.f : s * __expf(m - nm)) + (om == -INFINITY ? 0.f : os * __expf(om - nm));
     m = nm;
+    if constexpr (LS) xs += __shfl_xor(xs, o, 64);
   }
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   if (lane == 0) { sm[wid] = m; ss[wid] = s; }
+  if constexpr (LS) { if (lane == 0) sx[wid] = xs; }
   __syncthreads();
   float M = sm[0], S = ss[0];
   for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
@@ -590,12 +605,23 @@ __global__ __launch_bounds__(256) void ce_kernel(const TL* __restrict__ logits, 
     S = S * __expf(M - nm) + ss[w] * __expf(sm[w] - nm);
     M = nm;
   }
+  float X = 0.f;
+  if constexpr (LS) { for (int w = 0; w < (int)(blockDim.x >> 6); ++w) X += sx[w]; }
   long t = target[row];
   t = t < 0 ? 0 : (t >= V ? V - 1 : t);
   const float lse = M + __logf(S);
   const float xt = to_f32<TL>(x[t]);
   __syncthreads();   // dlogits may alias the logits: every read of x[t] happens before any write
-  if constexpr (WGT) {
+  float keep = 1.f, unif = 0.f;
+  if constexpr (LS) {
+    const float wr = row_w ? row_w[row] : 1.f;
+    const float nl = lse - xt, u = lse - X * ls.inv_v;
+    keep = 1.f - ls.eps; unif = ls.eps * ls.inv_v;
+    if (threadIdx.x == 0 && nll) nll[row] = nl;
+    if (threadIdx.x == 0 && ls.smooth) ls.smooth[row] = u;
+    if (threadIdx.x == 0 && loss) atomicAdd(loss, wr * (keep * nl + ls.eps * u) * inv_rows);
+    gscale *= wr;
+  } else if constexpr (WGT) {
     const float wr = row_w ? row_w[row] : 1.f;
     if (threadIdx.x == 0 && nll) nll[row] = lse - xt;
     if (threadIdx.x == 0 && loss) atomicAdd(loss, wr * (lse - xt) * inv_rows);
@@ -608,7 +634,8 @@ __global__ __launch_bounds__(256) void ce_kernel(const TL* __restrict__ logits, 
     TD* d = dlogits + (long)row * ldd;
     for (int i = threadIdx.x; i < V; i += blockDim.x) {
       const float p = __expf(to_f32<TL>(x[i]) - lse);
-      d[i] = from_f32<TD>((p - (i == t ? 1.f : 0.f)) * gscale);
+      if constexpr (LS) d[i] = from_f32<TD>((p - ((i == t ? keep : 0.f) + unif)) * gscale);
+      else d[i] = from_f32<TD>((p - (i == t ? 1.f : 0.f)) * gscale);
     }
     for (int i = V + threadIdx.x; i < ldd; i += blockDim.x) d[i] = from_f32<TD>(0.f);   // pad columns feed GEMMs as K
   }
@@ -797,18 +824,19 @@ int colsum_launch(const void* x, float* out, int rows, int cols, int ldx, int dt
 }
 
 namespace {
-template <bool WGT>
+template <bool WGT, bool LS = false>
 void ce_launch(const void* logits, int logits_dtype, const long* target, int rows, int V, int ldl, float* loss_accum, void* dlogits,
-               int dlogits_dtype, int ldd, float inv, float gs, const float* grad_scale_dev, const float* row_w, float* nll, hipStream_t st) {
+               int dlogits_dtype, int ldd, float inv, float gs, const float* grad_scale_dev, const float* row_w, float* nll, hipStream_t st,
+               CeSmooth ls = CeSmooth{}) {
   const dim3 grid(rows), block(256);
   if (logits_dtype == ST_F32 && (dlogits_dtype == ST_F32 || !dlogits))
-    hipLaunchKernelGGL((ce_kernel<float, float, WGT>), grid, block, 0, st, (const float*)logits, target, loss_accum, (float*)dlogits, V, ldl, ldd, inv, gs, grad_scale_dev, row_w, nll);
+    hipLaunchKernelGGL((ce_kernel<float, float, WGT, LS>), grid, block, 0, st, (const float*)logits, target, loss_accum, (float*)dlogits, V, ldl, ldd, inv, gs, grad_scale_dev, row_w, nll, ls);
   else if (logits_dtype == ST_F32)
-    hipLaunchKernelGGL((ce_kernel<float, bf16_t, WGT>), grid, block, 0, st, (const float*)logits, target, loss_accum, (bf16_t*)dlogits, V, ldl, ldd, inv, gs, grad_scale_dev, row_w, nll);
+    hipLaunchKernelGGL((ce_kernel<float, bf16_t, WGT, LS>), grid, block, 0, st, (const float*)logits, target, loss_accum, (bf16_t*)dlogits, V, ldl, ldd, inv, gs, grad_scale_dev, row_w, nll, ls);
   else if (dlogits_dtype == ST_BF16 || !dlogits)
-    hipLaunchKernelGGL((ce_kernel<bf16_t, bf16_t, WGT>), grid, block, 0, st, (const bf16_t*)logits, target, loss_accum, (bf16_t*)dlogits, V, ldl, ldd, inv, gs, grad_scale_dev, row_w, nll);
+    hipLaunchKernelGGL((ce_kernel<bf16_t, bf16_t, WGT, LS>), grid, block, 0, st, (const bf16_t*)logits, target, loss_accum, (bf16_t*)dlogits, V, ldl, ldd, inv, gs, grad_scale_dev, row_w, nll, ls);
   else
-    hipLaunchKernelGGL((ce_kernel<bf16_t, float, WGT>), grid, block, 0, st, (const bf16_t*)logits, target, loss_accum, (float*)dlogits, V, ldl, ldd, inv, gs, grad_scale_dev, row_w, nll);
+    hipLaunchKernelGGL((ce_kernel<bf16_t, float, WGT, LS>), grid, block, 0, st, (const bf16_t*)logits, target, loss_accum, (float*)dlogits, V, ldl, ldd, inv, gs, grad_scale_dev, row_w, nll, ls);
 }
 }  // namespace
 
@@ -824,6 +852,20 @@ extern "C" int st_cross_entropy_w(const void* logits, int logits_dtype, const lo
     ce_launch<true>(logits, logits_dtype, target, rows, V, ldl, loss_accum, dlogits, dlogits_dtype, ldd, inv, gs, grad_scale_dev, row_weight, nll_out, st);
   else
     ce_launch<false>(logits, logits_dtype, target, rows, V, ldl, loss_accum, dlogits, dlogits_dtype, ldd, inv, gs, grad_scale_dev, nullptr, nullptr, st);
+  ST_LAUNCH_CHECK();
+  return 0;
+}
+
+// label smoothing: the LS instantiation whatever row_weight / nll_out / smooth_out are (NULL conventions of st_cross_entropy_w)
+extern "C" int st_cross_entropy_ls(const void* logits, int logits_dtype, const long* target, int rows, int V, int ldl,
+                                   const float* row_weight, float* nll_out, float* smooth_out, float label_smoothing, float* loss_accum,
+                                   void* dlogits, int dlogits_dtype, int ldd, float grad_scale, const float* grad_scale_dev, void* stream) {
+  ST_CHECK(logits && target, "st_cross_entropy_ls: null pointer");
+  ST_CHECK(rows >= 0 && V > 0 && ldl >= V, "st_cross_entropy_ls: bad shape");
+  ST_CHECK(label_smoothing >= 0.f && label_smoothing < 1.f, "st_cross_entropy_ls: label_smoothing=%g outside [0, 1)", (double)label_smoothing);
+  if (rows == 0) return 0;
+  ce_launch<true, true>(logits, logits_dtype, target, rows, V, ldl, loss_accum, dlogits, dlogits_dtype, ldd, 1.0f / rows, grad_scale / rows,
+                        grad_scale_dev, row_weight, nll_out, reinterpret_cast<hipStream_t>(stream), CeSmooth{smooth_out, label_smoothing, 1.0f / V});
   ST_LAUNCH_CHECK();
   return 0;
 }

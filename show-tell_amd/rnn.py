@@ -8,6 +8,7 @@ Same constructor, same attribute names (``embeddings``, ``unit``, ``linear``) an
     ids    = rnn.sentence_index(cnn_feature, beam_size=0)       # Long(B, 25) (squeezed)
     ids, logp, lengths = rnn.sample(cnn_feature, num_samples=5, temperature=0.8, top_k=20)   # (B, S, 25) draws (st_rnn_sample)
     loss   = rnn.loss(cnn_feature, image_caption, caption_size, sequence_weight=advantage)   # sum w * nll / N_tok (reward-weighted)
+    loss   = rnn.loss(cnn_feature, image_caption, caption_size, label_smoothing=0.1)         # CrossEntropyLoss(label_smoothing=0.1)
     logp   = rnn.token_logp(cnn_feature, image_caption, caption_size)                        # (B, T) log p of every given token
 
 ``nn.Embedding`` / ``nn.GRU`` / ``nn.Linear`` objects are parameter containers only; all
@@ -81,6 +82,18 @@ def check_weight_args(batch, width, sequence_weight, token_weight):
                              + (f" (got {w.dtype}, {tuple(w.shape)})" if torch.is_tensor(w) else f" (got {type(w).__name__})"))
 
 
+def check_label_smoothing(label_smoothing):
+    """Argument error of `label_smoothing` (both decoders and the Trainer), raised before anything touches the device: a number in
+    [0, 1), as torch's CrossEntropyLoss takes it (1.0 and NaN are refused).  Returns it as a float."""
+    try:
+        eps = float(label_smoothing)
+    except (TypeError, ValueError):
+        raise ValueError(f"label_smoothing must be a number in [0, 1) (got {label_smoothing!r})") from None
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1) (got {label_smoothing!r})")
+    return eps
+
+
 def check_caption_args(caption, lens):
     """Argument errors of a (caption, caption_size) pair, before anything touches the device."""
     if not torch.is_tensor(caption) or caption.dim() != 2 or caption.dtype != torch.int64:
@@ -112,10 +125,14 @@ def unpack_rows(plan, rows, width, device):
     return out
 
 
-def ce_loss(logits, dt, targets, n, V, Vp, loss, roww=None, nll=None):
+def ce_loss(logits, dt, targets, n, V, Vp, loss, roww=None, nll=None, eps=0.0):
     """loss += mean cross entropy of the (n, Vp) logits rows (V valid columns) against `targets`; with `roww` (n,) every row's
-    term times its weight (the divisor stays n); `nll` (n,) receives the rows' unweighted terms (`loss` may then be None)."""
-    if roww is None and nll is None:
+    term times its weight (the divisor stays n); `nll` (n,) receives the rows' unweighted terms (`loss` may then be None).
+    eps > 0: label smoothing, the row's term is (1 - eps) * nll + eps * (logsumexp - mean logit) (st_cross_entropy_ls)."""
+    if eps:
+        check(lib().st_cross_entropy_ls(_cp(logits), dtype_code(dt), _cp(targets), n, V, Vp, _cp(roww), _cp(nll), None, eps, _cp(loss),
+                                        None, 0, Vp, 1.0, None, _stream()), "st_cross_entropy_ls")
+    elif roww is None and nll is None:
         check(lib().st_cross_entropy(_cp(logits), dtype_code(dt), _cp(targets), n, V, Vp, _cp(loss), None, 0, Vp, 1.0, None, _stream()),
               "st_cross_entropy")
     else:
@@ -123,12 +140,15 @@ def ce_loss(logits, dt, targets, n, V, Vp, loss, roww=None, nll=None):
                                        1.0, None, _stream()), "st_cross_entropy_w")
 
 
-def ce_loss_backward(logits, dt, targets, n, V, Vp, gout, roww=None):
-    """The saved logits of ce_loss, overwritten in place by (softmax - onehot) * dLoss / N_tok (row r times roww[r]).  Returns
-    (dlogits, dLoss as the fp32 device scalar the kernel read)."""
+def ce_loss_backward(logits, dt, targets, n, V, Vp, gout, roww=None, eps=0.0):
+    """The saved logits of ce_loss, overwritten in place by (softmax - onehot) * dLoss / N_tok (row r times roww[r]; eps > 0:
+    softmax - (1 - eps) * onehot - eps / V).  Returns (dlogits, dLoss as the fp32 device scalar the kernel read)."""
     gsc = gout.detach().float().contiguous()
     dtc = dtype_code(dt)
-    if roww is None:
+    if eps:
+        check(lib().st_cross_entropy_ls(_cp(logits), dtc, _cp(targets), n, V, Vp, _cp(roww), None, None, eps, None, _cp(logits), dtc, Vp,
+                                        1.0, _cp(gsc), _stream()), "st_cross_entropy_ls(bwd)")
+    elif roww is None:
         check(lib().st_cross_entropy(_cp(logits), dtc, _cp(targets), n, V, Vp, None, _cp(logits), dtc, Vp, 1.0, _cp(gsc), _stream()),
               "st_cross_entropy(bwd)")
     else:
@@ -150,10 +170,11 @@ def logits_grad(gout, dt, n, V, Vp, alloc):
 
 class _DecoderFn(torch.autograd.Function):
     """mode 'logits': returns fp32 logits rows; mode 'loss': returns the mean cross entropy, every row's term times
-    sequence_weight[b] * token_weight[b, t] where given; mode 'nll': returns the packed rows' -log p(target) (no gradient)."""
+    sequence_weight[b] * token_weight[b, t] where given and smoothed by `eps` where that is not 0; mode 'nll': returns the packed
+    rows' -log p(target) (no gradient)."""
 
     @staticmethod
-    def forward(ctx, feat, _anchor, module, caption, lens, mode, need_grad, sequence_weight, token_weight):
+    def forward(ctx, feat, _anchor, module, caption, lens, mode, need_grad, sequence_weight, token_weight, eps=0.0):
         m = module
         dev = feat.device
         if not feat.is_cuda or not m.linear.weight.is_cuda:
@@ -178,7 +199,7 @@ class _DecoderFn(torch.autograd.Function):
                                    _cp(targets), int(need_grad), _stream()), "st_rnn_forward")
         ctx.m, ctx.plan, ctx.caption, ctx.ws, ctx.mode, ctx.keep = m, plan, caption, ws, mode, keep
         ctx.feat_dtype = feat.dtype
-        ctx.fused, ctx.roww = fused, roww
+        ctx.fused, ctx.roww, ctx.eps = fused, roww, eps
         if mode == "logits":
             return logits[:, :V]
         loss = torch.zeros((), device=dev, dtype=torch.float32) if mode == "loss" else None
@@ -186,7 +207,12 @@ class _DecoderFn(torch.autograd.Function):
         if fused:
             sb = lib().st_rnn_fused_loss_bytes(C.byref(prm), C.byref(seq))
             scratch = torch.empty(sb // 4, device=dev, dtype=torch.float32)
-            if roww is None and nll is None:
+            if eps:       # label smoothing: the tile sums of the rows' logits live in a buffer of this call only
+                tb = lib().st_rnn_fused_loss_ls_bytes(C.byref(prm), C.byref(seq))
+                tsum = torch.empty(tb // 4, device=dev, dtype=torch.float32)
+                check(lib().st_rnn_fused_loss_ls(C.byref(prm), C.byref(seq), _cp(ws), nbytes, _cp(targets), _cp(scratch), sb, _cp(roww),
+                                                 _cp(nll), None, eps, _cp(tsum), tb, _cp(loss), _stream()), "st_rnn_fused_loss_ls")
+            elif roww is None and nll is None:
                 check(lib().st_rnn_fused_loss(C.byref(prm), C.byref(seq), _cp(ws), nbytes, _cp(targets), _cp(scratch), sb, _cp(loss),
                                               _stream()), "st_rnn_fused_loss")
             else:
@@ -194,7 +220,7 @@ class _DecoderFn(torch.autograd.Function):
                                                 _cp(nll), _cp(loss), _stream()), "st_rnn_fused_loss_w")
             ctx.logits, ctx.targets, ctx.scratch = None, targets, scratch
         else:
-            ce_loss(logits, ldt, targets, n, V, Vp, loss, roww, nll)
+            ce_loss(logits, ldt, targets, n, V, Vp, loss, roww, nll, eps)
             ctx.logits, ctx.targets = logits, targets
         if mode == "nll":
             ctx.mark_non_differentiable(nll)
@@ -216,7 +242,11 @@ class _DecoderFn(torch.autograd.Function):
         elif ctx.fused:
             gsc = gout.detach().float().contiguous()
             dlog = torch.empty(n, Vp, device=dev, dtype=dt)
-            if ctx.roww is None:
+            if ctx.eps:
+                check(lib().st_rnn_fused_dlogits_ls(C.byref(prm), C.byref(seq), _cp(ctx.ws), ctx.ws.numel(), _cp(ctx.targets),
+                                                    _cp(ctx.scratch), _cp(gsc), _cp(ctx.roww), ctx.eps, _cp(dlog), Vp, _stream()),
+                      "st_rnn_fused_dlogits_ls")
+            elif ctx.roww is None:
                 check(lib().st_rnn_fused_dlogits(C.byref(prm), C.byref(seq), _cp(ctx.ws), ctx.ws.numel(), _cp(ctx.targets), _cp(ctx.scratch),
                                                  _cp(gsc), _cp(dlog), Vp, _stream()), "st_rnn_fused_dlogits")
             else:
@@ -224,13 +254,13 @@ class _DecoderFn(torch.autograd.Function):
                                                    _cp(ctx.scratch), _cp(gsc), _cp(ctx.roww), _cp(dlog), Vp, _stream()),
                       "st_rnn_fused_dlogits_w")
         else:
-            dlog, gsc = ce_loss_backward(ctx.logits, dt, ctx.targets, n, V, Vp, gout, ctx.roww)
+            dlog, gsc = ce_loss_backward(ctx.logits, dt, ctx.targets, n, V, Vp, gout, ctx.roww, ctx.eps)
         grads, keep2 = m._c_grads()
         dfeat = torch.empty(plan.B, m.embed_dim, device=dev, dtype=torch.float32)
         check(lib().st_rnn_backward(C.byref(prm), C.byref(grads), C.byref(seq), None, _cp(dlog), Vp, None, _cp(ctx.ws),
                                     ctx.ws.numel(), _cp(dfeat), None, _stream()), "st_rnn_backward")
         ctx.ws = None
-        return dfeat.to(ctx.feat_dtype), None, None, None, None, None, None, None, None
+        return dfeat.to(ctx.feat_dtype), None, None, None, None, None, None, None, None, None
 
 
 class Decoder(FollowsMoves, nn.Module):
@@ -331,20 +361,25 @@ class RNN(Decoder):
         """rnn.py:27-35: teacher-forced logits over the packed sequence, (N_tok, V) fp32."""
         return _DecoderFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "logits", torch.is_grad_enabled(), None, None)
 
-    def loss(self, cnn_feature, image_caption, caption_size, sequence_weight=None, token_weight=None):
+    def loss(self, cnn_feature, image_caption, caption_size, sequence_weight=None, token_weight=None, label_smoothing=0.0):
         """main.py:145-149 fused: CrossEntropyLoss()(rnn(feat, cap, lens), packed(cap)) as one scalar.
 
         With `sequence_weight` (B,) and / or `token_weight` (B, T) (float tensors, signed, T the caption tensor's width; both:
         their product) the scalar is sum_{b,t} w[b, t] * nll[b, t] / N_tok -- reward-weighted training (REINFORCE, self-critical
         sequence training).  The divisor stays N_tok, so weights of one give the plain loss; the weights are constants (no
-        gradient flows into them) and apply inside the loss kernels: no logits tensor appears on the fused route."""
-        if sequence_weight is None and token_weight is None:
+        gradient flows into them) and apply inside the loss kernels: no logits tensor appears on the fused route.
+
+        `label_smoothing` = eps in [0, 1) is CrossEntropyLoss(label_smoothing=eps): every row's term becomes
+        (1 - eps) * nll + eps * (logsumexp(x) - mean(x)), times its weight where weights are given (the divisor stays N_tok).  The
+        rows' mean logit is formed inside the loss kernels too; with eps = 0 the call is the one it was."""
+        eps = check_label_smoothing(label_smoothing)
+        if sequence_weight is None and token_weight is None and not eps:
             return _DecoderFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "loss", torch.is_grad_enabled(),
                                     None, None)
         check_caption_args(image_caption, caption_size)
         check_weight_args(image_caption.shape[0], image_caption.shape[1], sequence_weight, token_weight)
         return _DecoderFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "loss", torch.is_grad_enabled(),
-                                sequence_weight, token_weight)
+                                sequence_weight, token_weight, eps)
 
     def token_logp(self, cnn_feature, image_caption, caption_size):
         """log p(image_caption[b, t] | image b, image_caption[b, :t]) for every token of the given captions: (B, T) fp32, T the

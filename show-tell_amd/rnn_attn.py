@@ -25,8 +25,8 @@ import torch.nn as nn
 from . import _lib
 from ._lib import AttnGrads, AttnParams, check, dtype_code, lib
 from ._lib import ptr as _cp, stream as _stream
-from .rnn import (CAP_MAX, Decoder, ce_loss, ce_loss_backward, check_caption_args, check_weight_args, logits_grad, pack_row_weights,
-                  sample_lengths, unpack_rows, up8)
+from .rnn import (CAP_MAX, Decoder, ce_loss, ce_loss_backward, check_caption_args, check_label_smoothing, check_weight_args, logits_grad,
+                  pack_row_weights, sample_lengths, unpack_rows, up8)
 from .seq import plan_for
 
 
@@ -47,7 +47,7 @@ class Attention_Net(nn.Module):
 
 class _AttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feat, _anchor, module, caption, lens, mode, alpha_c, need_grad, sequence_weight, token_weight):
+    def forward(ctx, feat, _anchor, module, caption, lens, mode, alpha_c, need_grad, sequence_weight, token_weight, eps=0.0):
         m = module
         dev = feat.device
         if not feat.is_cuda or not m.linear.weight.is_cuda:
@@ -73,7 +73,7 @@ class _AttnFn(torch.autograd.Function):
                                     dtype_code(logits.dtype), Vp, _cp(alphas), int(need_grad), _stream()), "st_attn_forward")
         # st_attn_forward steps over plan.T columns; alphas has T (padded) columns: strides must agree
         ctx.m, ctx.plan, ctx.caption, ctx.cap_T, ctx.ws, ctx.mode, ctx.P = m, plan, caption, cap_T, ws, mode, P
-        ctx.alphas, ctx.alpha_c, ctx.keep, ctx.roww = alphas, alpha_c, keep, roww
+        ctx.alphas, ctx.alpha_c, ctx.keep, ctx.roww, ctx.eps = alphas, alpha_c, keep, roww, eps
         if mode == "logits":
             return logits[:, :V], alphas
         targets = torch.nn.utils.rnn.pack_padded_sequence(caption, lens, batch_first=True)[0].contiguous()   # main_attn.py:126
@@ -83,7 +83,7 @@ class _AttnFn(torch.autograd.Function):
             ctx.mark_non_differentiable(nll, alphas)
             return nll, alphas
         loss = torch.zeros((), device=dev, dtype=torch.float32)
-        ce_loss(logits, dt, targets, n, V, Vp, loss, roww)     # the doubly-stochastic term below stays unweighted
+        ce_loss(logits, dt, targets, n, V, Vp, loss, roww, None, eps)     # the doubly-stochastic term below stays unweighted and unsmoothed
         check(lib().st_attn_reg_loss(_cp(alphas), B, T, P, float(alpha_c), _cp(loss), _stream()), "st_attn_reg_loss")
         ctx.logits, ctx.targets = logits, targets
         return loss, alphas
@@ -102,7 +102,7 @@ class _AttnFn(torch.autograd.Function):
         elif ctx.mode != "loss":
             raise _lib.ShowTellHipError("token_logp has no gradient")
         else:
-            dlog, gs = ce_loss_backward(ctx.logits, dt, ctx.targets, n, V, Vp, g0, ctx.roww)
+            dlog, gs = ce_loss_backward(ctx.logits, dt, ctx.targets, n, V, Vp, g0, ctx.roww, ctx.eps)
             alpha_c = ctx.alpha_c
         prm, keep = m._c_params()
         prm.P = ctx.P
@@ -111,7 +111,7 @@ class _AttnFn(torch.autograd.Function):
         check(lib().st_attn_backward(C.byref(prm), C.byref(grads), C.byref(seq), _cp(ctx.cap_T), _cp(dlog), Vp, _cp(ctx.alphas), _cp(dal),
                                      float(alpha_c), _cp(gs), _cp(ctx.ws), ctx.ws.numel(), _stream()), "st_attn_backward")
         ctx.ws = None
-        return None, None, None, None, None, None, None, None, None, None
+        return None, None, None, None, None, None, None, None, None, None, None
 
 
 class RNN_Attn(Decoder):
@@ -175,15 +175,17 @@ class RNN_Attn(Decoder):
         """rnn_attn.py:98-118: (packed logits (N_tok,V) fp32, alphas (B,T,P))."""
         return _AttnFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "logits", 0.0, torch.is_grad_enabled(), None, None)
 
-    def loss(self, cnn_feature, image_caption, caption_size, alpha_c=1.0, sequence_weight=None, token_weight=None):
+    def loss(self, cnn_feature, image_caption, caption_size, alpha_c=1.0, sequence_weight=None, token_weight=None, label_smoothing=0.0):
         """main_attn.py:126-131 fused: CE(packed logits, packed caption) + alpha_c * mean((1 - sum_t alpha)^2).
         `sequence_weight` (B,) / `token_weight` (B, T) weight the cross-entropy terms as in RNN.loss (the divisor stays N_tok, no
-        gradient into the weights); the doubly-stochastic term stays unweighted."""
+        gradient into the weights); `label_smoothing` in [0, 1) smooths them as CrossEntropyLoss(label_smoothing=) does (0: the
+        call it was); the doubly-stochastic term stays unweighted and unsmoothed."""
+        eps = check_label_smoothing(label_smoothing)
         if sequence_weight is not None or token_weight is not None:
             check_caption_args(image_caption, caption_size)
             check_weight_args(image_caption.shape[0], image_caption.shape[1], sequence_weight, token_weight)
         out, _ = _AttnFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "loss", float(alpha_c), torch.is_grad_enabled(),
-                               sequence_weight, token_weight)
+                               sequence_weight, token_weight, eps)
         return out
 
     def token_logp(self, cnn_feature, image_caption, caption_size):

@@ -24,7 +24,7 @@ import torch
 
 from .head import linear_bn1d
 from .parallel import GradAllReducer, broadcast_state
-from .rnn import sample_lengths
+from .rnn import check_label_smoothing, sample_lengths
 
 
 def synthetic_batch(B, V, seed=1, device="cuda", image_size=224, mean=12.5, std=2.5, lo=6, hi=25):
@@ -75,7 +75,10 @@ def sample_caption_batch(ids, lengths):
 
 
 class Trainer:
-    def __init__(self, cnn, rnn, optimizer, world_size=1):
+    def __init__(self, cnn, rnn, optimizer, world_size=1, label_smoothing=0.0):
+        """`label_smoothing` in [0, 1): `step` trains on CrossEntropyLoss(label_smoothing=..) (``rnn.loss(.., label_smoothing=)``);
+        0 is the reference's plain cross entropy."""
+        self.label_smoothing = check_label_smoothing(label_smoothing)
         self.cnn, self.rnn, self.opt = cnn, rnn, optimizer
         self.reducer = GradAllReducer(world_size)
         if world_size > 1:
@@ -164,7 +167,10 @@ class Trainer:
         ``weight_decay``, ``skip_nonfinite``, optim.py): they act inside the deferred optimizer step, after the all-reduce, on
         the device, and need nothing here."""
         feat = self._features(image, upcoming)
-        loss = self.rnn.loss(feat, caption, caption_len)    # main.py:148-149
+        if self.label_smoothing:
+            loss = self.rnn.loss(feat, caption, caption_len, label_smoothing=self.label_smoothing)
+        else:
+            loss = self.rnn.loss(feat, caption, caption_len)    # main.py:148-149
         loss.backward()                                # main.py:151
         self.reducer.start(self.opt.flat_grad)
         self.pending = True
@@ -180,7 +186,9 @@ class Trainer:
         the reward of the greedy caption of the same image ('greedy') or the mean reward of the image's other samples ('mean').
         Backward and the deferred all-reduce / optimizer schedule are those of `step`.  Returns (loss, mean reward of the samples).
         Signed, reward-scaled losses are where an optimizer built with ``max_grad_norm`` (and ``skip_nonfinite``) earns its keep.
-        `generator` / `uniforms` fix the draws as in ``RNN.sample``."""
+        `generator` / `uniforms` fix the draws as in ``RNN.sample``.
+        The Trainer's `label_smoothing` does not apply here: a reward-weighted log-likelihood of the model's own samples is not a
+        target distribution to be smoothed, so this step stays unsmoothed."""
         if baseline not in ("greedy", "mean"):
             raise ValueError(f"baseline must be 'greedy' or 'mean' (got {baseline!r})")
         if baseline == "mean" and num_samples < 2:
