@@ -475,6 +475,56 @@ int st_rnn_fused_dlogits_ls(const st_rnn_params* p, const st_packed_seq* s, cons
                             const long* targets, const float* scratch, const float* grad_scale_dev, const float* row_weight,
                             float label_smoothing, void* dlogits, int ldd, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Dropout for the teacher-forced decoders: nn.GRU(dropout = p) between layers, nn.Dropout in front of `linear` and on the layer-0
+ * input rows.  The kernels hold no generator state.  The mask is a pure function of (seed, step, site, packed row, column)
+ * (csrc/dropout.h):  words = Philox4x32-10(counter = (column / 4, packed row, site, step), key = (seed low 32, seed high 32)), word e
+ * belongs to column 4 * (column / 4) + e;  an element is kept iff word >= (uint32) floor(p * 2^32);  a kept element is
+ * T(float(x) * float(1 / (1 - p))), a dropped one +0.  The packed row is row(t, b) of st_packed_seq, so the mask depends on no launch
+ * geometry or route.  Sites: l = the output of recurrent layer l (L - 1: the rows `linear` reads), 255 = the layer-0 input rows.
+ *   st_dropout_rows: y[r][c] = masked x[r][c] for r < rows, c < cols (cols, ldx, ldy multiples of 4; fp32 or bf16; y == x allowed);
+ *                    row0 is the packed row of x's first row.
+ * st_dropout describes one training step's dropout.  Each p is in [0, 1), 0 = that site off.  p_layer applies to the output of every
+ * layer but the last (nothing for L = 1).  `buf` (st_rnn_dropout_bytes / st_attn_dropout_bytes; the caller's, needed when p_layer or
+ * p_out is on) receives the dropped copies, L matrices [ntok][H] in the compute dtype, and carries them from the forward call to the
+ * loss and backward calls of the same step, which take the same descriptor.  The workspaces stay what they are.
+ * The _drop forms with a NULL descriptor (or every p = 0) are the plain calls, launch for launch:
+ *   st_rnn_forward_drop:       x0 is masked in place (p_in; not with x0_override); with p_layer the wavefront's cells write h' for
+ *                              their recurrence and the dropped h' for the layer above, in the same launches; with p_out the
+ *                              projection reads the dropped copy of y_top;
+ *   st_rnn_fused_loss_drop /   the fused loss and its dlogits over the dropped y_top: one form for row weights and label smoothing
+ *   st_rnn_fused_dlogits_drop: (NULL / 0 conventions of the _w and _ls calls; tile_sums is needed when label_smoothing > 0 or
+ *                              smooth_out is given);
+ *   st_rnn_backward_drop:      dy_top and dx0 are masked (fp32, in place), the fused BPTT cell masks the product it takes from the
+ *                              layer above in registers (with p_layer the call is the fused route whatever ST_BPTT_FUSED says),
+ *                              dW_ih_{l+1} and dW_lin contract with the dropped copies, dW_hh_l with the plain rows;
+ *   st_attn_forward_drop /     p_out only (p_in, p_layer must be 0): the recurrence and the next step's attention read the plain top
+ *   st_attn_backward_drop:     state; the projection and dW_lin the dropped copy; dy_top is masked before the step loop.
+ * ---------------------------------------------------------------------------------- */
+typedef struct {
+  double p_in, p_layer, p_out;
+  long seed;                                         /* 64 bits, both halves key the generator */
+  int step;                                          /* >= 0: one per training step            */
+  void* buf; size_t buf_bytes;
+} st_dropout;
+
+int st_dropout_rows(const void* x, void* y, int dtype, int rows, int cols, int ldx, int ldy, double p, long seed, int step,
+                    int site, int row0, void* stream);
+size_t st_rnn_dropout_bytes(const st_rnn_params* p, const st_packed_seq* s);
+int st_rnn_forward_drop(const st_rnn_params* p, const st_packed_seq* s, const void* x0_override, const void* feat,
+                        void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
+                        long* targets, int save_for_backward, const st_dropout* drop, void* stream);
+int st_rnn_fused_loss_drop(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
+                           const long* targets, float* scratch, size_t scratch_bytes, const float* row_weight, float* nll_out,
+                           float* smooth_out, float label_smoothing, float* tile_sums, size_t tile_sums_bytes, float* loss_accum,
+                           const st_dropout* drop, void* stream);
+int st_rnn_fused_dlogits_drop(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
+                              const long* targets, const float* scratch, const float* grad_scale_dev, const float* row_weight,
+                              float label_smoothing, void* dlogits, int ldd, const st_dropout* drop, void* stream);
+int st_rnn_backward_drop(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,
+                         const void* x0_override, const void* dlogits, int ldd, const float* dy_top,
+                         void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, const st_dropout* drop, void* stream);
+
 /* nn.CrossEntropyLoss() (mean) forward + backward (main.py:94,149):
  *   *loss_accum += mean_r( logsumexp(x_r) - x_r[target_r] );  dlogits = (softmax - onehot) * grad_scale / rows
  * dlogits may alias logits when the dtypes match; pad columns [V, ldd) are zero-filled. */
@@ -628,6 +678,14 @@ int st_attn_backward(const st_attn_params* p, const st_attn_grads* g, const st_p
                      const float* dalphas /* (B,T,P) gradient w.r.t. alphas from the caller, or NULL: use alpha_c */,
                      float alpha_c, const float* grad_scale_dev, void* workspace, size_t workspace_bytes, void* stream);
 int st_attn_reg_loss(const float* alphas, int B, int T, int P, float alpha_c, float* loss_accum, void* stream);
+/* ... with Dropout in front of `linear` (st_dropout above: p_out only; NULL = the calls above) */
+size_t st_attn_dropout_bytes(const st_attn_params* p, const st_packed_seq* s);
+int st_attn_forward_drop(const st_attn_params* p, const st_packed_seq* s, const float* cnn_feature, const long* caption_T,
+                         void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
+                         float* alphas, int save_for_backward, const st_dropout* drop, void* stream);
+int st_attn_backward_drop(const st_attn_params* p, const st_attn_grads* g, const st_packed_seq* s, const long* caption_T,
+                          const void* dlogits, int ldd, const float* alphas, const float* dalphas, float alpha_c,
+                          const float* grad_scale_dev, void* workspace, size_t workspace_bytes, const st_dropout* drop, void* stream);
 /* rnn_attn.py:120-145 (test branch 77-94): `steps` greedy iterations from <start>; ids_out[B][steps] int64 */
 size_t st_attn_greedy_workspace_bytes(const st_attn_params* p, int B);
 int st_attn_greedy(const st_attn_params* p, const float* cnn_feature, int B, int steps, long start_id,

@@ -173,6 +173,15 @@ _SIGS = {
     "st_rnn_fused_dlogits_ls": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_f, c_p, c_i, c_p], c_i),
     "st_rnn_backward": ([C.POINTER(RnnParams), C.POINTER(RnnGrads), C.POINTER(PackedSeq), c_p, c_p, c_i, c_p, c_p, C.c_size_t,
                          c_p, c_p, c_p], c_i),
+    "st_dropout_rows": ([c_p, c_p, c_i, c_i, c_i, c_i, c_i, C.c_double, c_l, c_i, c_i, c_i, c_p], c_i),
+    "st_rnn_dropout_bytes": ([C.POINTER(RnnParams), C.POINTER(PackedSeq)], C.c_size_t),
+    "st_rnn_forward_drop": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, c_p, c_p, C.c_size_t, c_p, c_i, c_i, c_p, c_i, c_p, c_p], c_i),
+    "st_rnn_fused_loss_drop": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, C.c_size_t, c_p, c_p, C.c_size_t, c_p, c_p, c_p, c_f, c_p,
+                               C.c_size_t, c_p, c_p, c_p], c_i),
+    "st_rnn_fused_dlogits_drop": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_f, c_p, c_i, c_p, c_p],
+                                  c_i),
+    "st_rnn_backward_drop": ([C.POINTER(RnnParams), C.POINTER(RnnGrads), C.POINTER(PackedSeq), c_p, c_p, c_i, c_p, c_p, C.c_size_t,
+                              c_p, c_p, c_p, c_p], c_i),
     "st_rnn_greedy_workspace_bytes": ([C.POINTER(RnnParams), c_i], C.c_size_t),
     "st_rnn_greedy": ([C.POINTER(RnnParams), c_p, c_i, c_i, c_p, C.c_size_t, c_p, c_p, c_p], c_i),
     "st_rnn_greedy_last_route": ([], c_i),
@@ -187,6 +196,9 @@ _SIGS = {
     "st_attn_workspace_bytes": ([c_p, c_p], C.c_size_t),
     "st_attn_forward": ([c_p, c_p, c_p, c_p, c_p, C.c_size_t, c_p, c_i, c_i, c_p, c_i, c_p], c_i),
     "st_attn_backward": ([c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_f, c_p, c_p, C.c_size_t, c_p], c_i),
+    "st_attn_dropout_bytes": ([c_p, c_p], C.c_size_t),
+    "st_attn_forward_drop": ([c_p, c_p, c_p, c_p, c_p, C.c_size_t, c_p, c_i, c_i, c_p, c_i, c_p, c_p], c_i),
+    "st_attn_backward_drop": ([c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_f, c_p, c_p, C.c_size_t, c_p, c_p], c_i),
     "st_attn_reg_loss": ([c_p, c_i, c_i, c_i, c_f, c_p, c_p], c_i),
     "st_attn_greedy_workspace_bytes": ([c_p, c_i], C.c_size_t),
     "st_attn_greedy": ([c_p, c_p, c_i, c_i, c_l, c_p, C.c_size_t, c_p, c_p], c_i),

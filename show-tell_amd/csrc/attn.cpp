@@ -139,10 +139,16 @@ extern "C" size_t st_attn_workspace_bytes(const st_attn_params* p, const st_pack
   return make_plan(p, s).total;
 }
 
-extern "C" int st_attn_forward(const st_attn_params* p, const st_packed_seq* s, const float* cnn_feature, const long* caption_T,
-                               void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
-                               float* alphas, int save_for_backward, void* stream) {
+// Dropout (st_dropout, NULL = none): the Show-Attend-Tell placement, in front of `linear` only.  The recurrence and the next step's
+// attention read the plain top state; the dropped copy of y_top (the caller's buffer) feeds the projection and dW_lin, and dy_top is
+// masked before the step loop of the backward pass.
+namespace {
+int attn_forward(const st_attn_params* p, const st_packed_seq* s, const float* cnn_feature, const long* caption_T,
+                 void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
+                 float* alphas, int save_for_backward, const st_dropout* drop, void* stream) {
   if (check_common(p, s, "st_attn_forward")) return 1;
+  DropPlan dp;
+  if (st_drop_plan(drop, p->rnn.L, s->ntok, p->rnn.H, p->rnn.dtype, true, "st_attn_forward", &dp)) return 1;
   ST_CHECK(cnn_feature && caption_T && workspace && alphas, "st_attn_forward: null pointer");
   const Plan q = make_plan(p, s);
   ST_CHECK(workspace_bytes >= q.total, "st_attn_forward: workspace too small (%zu < %zu)", workspace_bytes, q.total);
@@ -177,11 +183,32 @@ extern "C" int st_attn_forward(const st_attn_params* p, const st_packed_seq* s, 
       if (rnn_gemm_launch(a, dt, rnn_cell_epi(r.cell), 1, st)) return 1;
     }
   }
+  const char* ytop = ws + q.y + (size_t)(L - 1) * n * H * es;
+  if (dp.out) {
+    if (dropout_rows_launch(ytop, dp.rows(L - 1), dt, n, H, H, H, dp.kout, L - 1, 0, st)) return 1;
+    ytop = dp.rows(L - 1);
+  }
   if (logits) {
     ST_CHECK(r.w_lin && r.b_lin, "st_attn_forward: logits requested without the vocabulary projection");
-    if (st_gemm_nt(ws + q.y + (size_t)(L - 1) * n * H * es, H, r.w_lin, H, logits, ldl, n, r.V, H, dt, logits_dtype, r.b_lin, stream)) return 1;
+    if (st_gemm_nt(ytop, H, r.w_lin, H, logits, ldl, n, r.V, H, dt, logits_dtype, r.b_lin, stream)) return 1;
   }
   return 0;
+}
+}  // namespace
+
+extern "C" int st_attn_forward(const st_attn_params* p, const st_packed_seq* s, const float* cnn_feature, const long* caption_T,
+                               void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
+                               float* alphas, int save_for_backward, void* stream) {
+  return attn_forward(p, s, cnn_feature, caption_T, workspace, workspace_bytes, logits, logits_dtype, ldl, alphas, save_for_backward, nullptr, stream);
+}
+extern "C" int st_attn_forward_drop(const st_attn_params* p, const st_packed_seq* s, const float* cnn_feature, const long* caption_T,
+                                    void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
+                                    float* alphas, int save_for_backward, const st_dropout* drop, void* stream) {
+  return attn_forward(p, s, cnn_feature, caption_T, workspace, workspace_bytes, logits, logits_dtype, ldl, alphas, save_for_backward, drop, stream);
+}
+extern "C" size_t st_attn_dropout_bytes(const st_attn_params* p, const st_packed_seq* s) {
+  if (!p || !s) return 0;
+  return st_dropout_buf_bytes(p->rnn.L, s->ntok, p->rnn.H, p->rnn.dtype);
 }
 
 extern "C" int st_attn_reg_loss(const float* alphas, int B, int T, int P, float alpha_c, float* loss_accum, void* stream) {
@@ -189,10 +216,13 @@ extern "C" int st_attn_reg_loss(const float* alphas, int B, int T, int P, float 
   return attn_reg_launch(alphas, B, T, P, alpha_c, loss_accum, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream));
 }
 
-extern "C" int st_attn_backward(const st_attn_params* p, const st_attn_grads* g, const st_packed_seq* s, const long* caption_T,
-                                const void* dlogits, int ldd, const float* alphas, const float* dalphas, float alpha_c,
-                                const float* grad_scale_dev, void* workspace, size_t workspace_bytes, void* stream) {
+namespace {
+int attn_backward(const st_attn_params* p, const st_attn_grads* g, const st_packed_seq* s, const long* caption_T,
+                  const void* dlogits, int ldd, const float* alphas, const float* dalphas, float alpha_c,
+                  const float* grad_scale_dev, void* workspace, size_t workspace_bytes, const st_dropout* drop, void* stream) {
   if (check_common(p, s, "st_attn_backward")) return 1;
+  DropPlan dp;
+  if (st_drop_plan(drop, p->rnn.L, s->ntok, p->rnn.H, p->rnn.dtype, true, "st_attn_backward", &dp)) return 1;
   ST_CHECK(g && caption_T && dlogits && alphas && workspace, "st_attn_backward: null pointer");
   const Plan q = make_plan(p, s);
   ST_CHECK(workspace_bytes >= q.total, "st_attn_backward: workspace too small (%zu < %zu)", workspace_bytes, q.total);
@@ -204,7 +234,7 @@ extern "C" int st_attn_backward(const st_attn_params* p, const st_attn_grads* g,
   ST_CHECK(ldd >= q.Vp && ldd % 8 == 0, "st_attn_backward: dlogits leading dimension must be a multiple of 8 and >= %d", q.Vp);
   ST_CHECK(Np >= n && Np >= BP, "st_attn_backward: plan Np=%d n=%d BP=%d P=%d B=%d T=%d", Np, n, BP, P, B, s->T);
   const std::vector<int> off = st_packed_offsets(s);
-  const char* ytop = ws + q.y + (size_t)(L - 1) * n * H * es;
+  const char* ytop = dp.out ? dp.rows(L - 1) : ws + q.y + (size_t)(L - 1) * n * H * es;   // what `linear` read
   float* dytop = reinterpret_cast<float*>(ws + q.dytop);
   float* dhc = reinterpret_cast<float*>(ws + q.dhc);
   float* dcc = reinterpret_cast<float*>(ws + q.dcc);
@@ -219,6 +249,7 @@ extern "C" int st_attn_backward(const st_attn_params* p, const st_attn_grads* g,
   if (st_gemm_nt(ws + q.tA, Np, ws + q.tB, Np, g->rnn.w_lin, H, r.V, H, Np, dt, ST_F32, nullptr, stream, 1)) return 1;
   if (st_transpose(r.w_lin, ws + q.wTmisc, dt, r.V, H, H, q.Vp, stream)) return 1;
   if (st_gemm_nt(dlogits, ldd, ws + q.wTmisc, q.Vp, dytop, H, n, H, q.Vp, dt, ST_F32, nullptr, stream)) return 1;
+  if (dp.out && dropout_rows_launch(dytop, dytop, ST_F32, n, H, H, H, dp.kout, L - 1, 0, st)) return 1;   // d dropped y_top -> d y_top
 
   // transposed operands used inside the time loop
   for (int l = 0; l < L; ++l) {
@@ -317,6 +348,19 @@ extern "C" int st_attn_backward(const st_attn_params* p, const st_attn_grads* g,
     if (st_gemm_nt(ws + q.tA, Bp, ws + q.tB, Bp, gw, F, H, F, Bp, dt, ST_F32, nullptr, stream, 1)) return 1;
   }
   return 0;
+}
+}  // namespace
+
+extern "C" int st_attn_backward(const st_attn_params* p, const st_attn_grads* g, const st_packed_seq* s, const long* caption_T,
+                                const void* dlogits, int ldd, const float* alphas, const float* dalphas, float alpha_c,
+                                const float* grad_scale_dev, void* workspace, size_t workspace_bytes, void* stream) {
+  return attn_backward(p, g, s, caption_T, dlogits, ldd, alphas, dalphas, alpha_c, grad_scale_dev, workspace, workspace_bytes, nullptr, stream);
+}
+extern "C" int st_attn_backward_drop(const st_attn_params* p, const st_attn_grads* g, const st_packed_seq* s, const long* caption_T,
+                                     const void* dlogits, int ldd, const float* alphas, const float* dalphas, float alpha_c,
+                                     const float* grad_scale_dev, void* workspace, size_t workspace_bytes, const st_dropout* drop,
+                                     void* stream) {
+  return attn_backward(p, g, s, caption_T, dlogits, ldd, alphas, dalphas, alpha_c, grad_scale_dev, workspace, workspace_bytes, drop, stream);
 }
 
 // ---- greedy decoding (rnn_attn.py:77-94,120-145) -----------------------------------------------------------

@@ -57,6 +57,36 @@ inline std::vector<int> st_packed_offsets(const st_packed_seq* s) {
   return off;
 }
 
+// A call's dropout (st_dropout, NULL = none) as the entry points use it: which sites are on, their mask keys, and the caller's buffer of
+// dropped copies carved into L slots of [ntok][H] rows in the compute dtype (slot l = the dropped output of layer l).
+struct DropPlan {
+  bool in = false, layer = false, out = false;
+  DropKey kin, klayer, kout;
+  char* buf = nullptr;
+  size_t slot = 0;
+  char* rows(int l) const { return buf + (size_t)l * slot; }
+  bool any() const { return in || layer || out; }
+};
+inline size_t st_dropout_buf_bytes(int L, size_t ntok, int H, int dtype) { return (size_t)L * st_al256(ntok * H * st_dtype_size(dtype)); }
+// out_only: the attention decoders take p_out alone
+inline int st_drop_plan(const st_dropout* d, int L, size_t ntok, int H, int dtype, bool out_only, const char* who, DropPlan* q) {
+  *q = DropPlan();
+  if (!d) return 0;
+  ST_CHECK(d->p_in >= 0.0 && d->p_in < 1.0 && d->p_layer >= 0.0 && d->p_layer < 1.0 && d->p_out >= 0.0 && d->p_out < 1.0,
+           "%s: dropout probabilities must be in [0, 1) (p_in=%g, p_layer=%g, p_out=%g)", who, d->p_in, d->p_layer, d->p_out);
+  ST_CHECK(d->step >= 0, "%s: dropout step %d is negative", who, d->step);
+  ST_CHECK(!out_only || (d->p_in == 0.0 && d->p_layer == 0.0), "%s: this decoder takes p_out only", who);
+  q->in = d->p_in > 0.0; q->layer = d->p_layer > 0.0 && L > 1; q->out = d->p_out > 0.0;
+  q->kin = drop_key(d->p_in, d->seed, d->step); q->klayer = drop_key(d->p_layer, d->seed, d->step); q->kout = drop_key(d->p_out, d->seed, d->step);
+  if (q->layer || q->out) {
+    ST_CHECK(d->buf && d->buf_bytes >= st_dropout_buf_bytes(L, ntok, H, dtype), "%s: dropout buffer too small (%zu < %zu)", who,
+             d->buf ? d->buf_bytes : (size_t)0, st_dropout_buf_bytes(L, ntok, H, dtype));
+    q->buf = reinterpret_cast<char*>(d->buf);
+    q->slot = st_al256(ntok * H * st_dtype_size(dtype));
+  }
+  return 0;
+}
+
 // Whole-row arg-max (first maximum, like torch.max(1)) of n rows of fp32 logits -> ids[row * ids_stride + t] and, when cur is
 // given, cur[row]: csrc/decode.hip, argmax_embed_kernel without its embedding gather.
 int argmax_rows_launch(const float* logits, int ldl, int n, int V, long* ids, int ids_stride, int t, long* cur, hipStream_t st);

@@ -20,6 +20,12 @@
 //           whose K-major operands come from transposes that also sum the bias gradients.  ST_BPTT_FUSED=0 keeps the
 //           earlier push route (a gate-gradient launch and a skinny-GEMM launch per diagonal)
 //           -> st_rnn_backward
+// dropout:  the _drop forms of the entry points take an st_dropout (NULL: the calls above, launch for launch).  The input rows and the
+//           rows in front of `linear` are masked outside the recurrence (st_dropout_rows: x0 in place, y_top into the caller's buffer,
+//           and on the way back the fp32 dy_top and dx0 in place); the inter-layer site of nn.GRU(dropout=p) rides in the wavefront's
+//           own launches (the DROP forms of the cell kernels): layer l writes h' for its recurrence and the dropped h' for layer l + 1,
+//           and the BPTT cell masks the from-above product in registers.  dW_ih_{l+1} and dW_lin read the dropped copies, dW_hh_l the
+//           plain rows.  With inter-layer dropout the backward pass is the fused route whatever ST_BPTT_FUSED says.
 #include "decoder_host.h"
 #include <stdlib.h>
 
@@ -91,10 +97,14 @@ extern "C" size_t st_rnn_workspace_bytes(const st_rnn_params* p, const st_packed
   return make_plan(p, s).total;
 }
 
-extern "C" int st_rnn_forward(const st_rnn_params* p, const st_packed_seq* s, const void* x0_override, const void* feat,
-                              void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
-                              long* targets, int save_for_backward, void* stream) {
+namespace {
+int rnn_forward(const st_rnn_params* p, const st_packed_seq* s, const void* x0_override, const void* feat,
+                void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
+                long* targets, int save_for_backward, const st_dropout* drop, void* stream) {
   if (check_common(p, s, "st_rnn_forward")) return 1;
+  DropPlan dp;
+  if (st_drop_plan(drop, p->L, s->ntok, p->H, p->dtype, false, "st_rnn_forward", &dp)) return 1;
+  ST_CHECK(!(dp.in && x0_override), "st_rnn_forward: input dropout needs the call's own x0 rows (no x0_override)");
   ST_CHECK(workspace && (x0_override || (feat && p->emb)), "st_rnn_forward: null pointer");
   const Plan q = make_plan(p, s);
   ST_CHECK(workspace_bytes >= q.total, "st_rnn_forward: workspace too small (%zu < %zu)", workspace_bytes, q.total);
@@ -108,17 +118,22 @@ extern "C" int st_rnn_forward(const st_rnn_params* p, const st_packed_seq* s, co
     ST_CHECK(p->in0 == p->E, "st_rnn_forward: in0 != E needs x0_override");
     if (pack_inputs_launch(feat, p->emb, s->caption, s->Tcap, s->rows_b, s->rows_t, ws + q.x0, targets, n, p->E, p->V, 0, dt, st)) return 1;
     x0 = ws + q.x0;
+    if (dp.in && dropout_rows_launch(x0, ws + q.x0, dt, n, p->in0, p->in0, p->in0, dp.kin, kDropSiteInput, 0, st)) return 1;
   }
   const std::vector<int> off = st_packed_offsets(s);
 
   const int L = p->L, T = s->T;
   for (int d = 0; d < T + L - 1; ++d) {
     RnnGemmArgs cells[ST_MAX_LAYERS];
+    RnnDropArgs da;
+    memset(&da, 0, sizeof(da));
+    da.key = dp.klayer;
     int nc = 0;
     for (int l = d < T ? 0 : d - (T - 1); l <= d && l < L; ++l) {
       const int t = d - l;
       const int bt = s->batch_sizes_host[t];
-      const char* xl = l == 0 ? reinterpret_cast<const char*>(x0) : ws + q.y + (size_t)(l - 1) * n * H * es;
+      // with inter-layer dropout layer l reads the dropped copy of y_{l-1}; the recurrence keeps the plain rows
+      const char* xl = l == 0 ? reinterpret_cast<const char*>(x0) : dp.layer ? dp.rows(l - 1) : ws + q.y + (size_t)(l - 1) * n * H * es;
       const int in = l == 0 ? p->in0 : H;
       char* yl = ws + q.y + (size_t)l * n * H * es;
       char* gl = ws + q.gates + (size_t)l * n * 4 * H * es;
@@ -126,15 +141,40 @@ extern "C" int st_rnn_forward(const st_rnn_params* p, const st_packed_seq* s, co
       cells[nc++] = rnn_full_cell(p, l, xl + (size_t)off[t] * in * es, in, t > 0 ? yl + (size_t)off[t - 1] * H * es : nullptr,
                                   t > 0 ? cl + (size_t)off[t - 1] * H * es : nullptr, yl + (size_t)off[t] * H * es, cl + (size_t)off[t] * H * es,
                                   bt, save_for_backward ? gl + (size_t)off[t] * 4 * H * es : nullptr);
+      if (dp.layer) {
+        if (l + 1 < L) { cells[nc - 1].hout2 = dp.rows(l) + (size_t)off[t] * H * es; cells[nc - 1].ldho2 = H; }
+        da.site[nc - 1] = l; da.row0[nc - 1] = off[t];
+      }
     }
-    if (rnn_gemm_launch_batch(cells, nc, dt, rnn_cell_epi(p->cell), 1, st)) return 1;
+    if (dp.layer ? rnn_gemm_launch_batch_drop(cells, nc, dt, rnn_cell_epi(p->cell), da, st)
+                 : rnn_gemm_launch_batch(cells, nc, dt, rnn_cell_epi(p->cell), 1, st)) return 1;
+  }
+  const char* ytop = ws + q.y + (size_t)(p->L - 1) * n * H * es;
+  if (dp.out) {                                    // Dropout in front of `linear`: the projection and dW_lin read the dropped copy
+    if (dropout_rows_launch(ytop, dp.rows(L - 1), dt, n, H, H, H, dp.kout, L - 1, 0, st)) return 1;
+    ytop = dp.rows(L - 1);
   }
   if (logits) {
     ST_CHECK(p->w_lin && p->b_lin, "st_rnn_forward: logits requested without the vocabulary projection");
-    const char* ytop = ws + q.y + (size_t)(p->L - 1) * n * H * es;
     if (st_gemm_nt(ytop, H, p->w_lin, H, logits, ldl, n, p->V, H, dt, logits_dtype, p->b_lin, stream)) return 1;
   }
   return 0;
+}
+}  // namespace
+
+extern "C" int st_rnn_forward(const st_rnn_params* p, const st_packed_seq* s, const void* x0_override, const void* feat,
+                              void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
+                              long* targets, int save_for_backward, void* stream) {
+  return rnn_forward(p, s, x0_override, feat, workspace, workspace_bytes, logits, logits_dtype, ldl, targets, save_for_backward, nullptr, stream);
+}
+extern "C" int st_rnn_forward_drop(const st_rnn_params* p, const st_packed_seq* s, const void* x0_override, const void* feat,
+                                   void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
+                                   long* targets, int save_for_backward, const st_dropout* drop, void* stream) {
+  return rnn_forward(p, s, x0_override, feat, workspace, workspace_bytes, logits, logits_dtype, ldl, targets, save_for_backward, drop, stream);
+}
+extern "C" size_t st_rnn_dropout_bytes(const st_rnn_params* p, const st_packed_seq* s) {
+  if (!p || !s) return 0;
+  return st_dropout_buf_bytes(p->L, s->ntok, p->H, p->dtype);
 }
 
 // ---- vocabulary projection + nn.CrossEntropyLoss() fused (csrc/vocab_ce.hip): the logits are never written ---------------------------------
@@ -223,11 +263,61 @@ extern "C" int st_rnn_fused_dlogits_ls(const st_rnn_params* p, const st_packed_s
                           reinterpret_cast<hipStream_t>(stream), true, label_smoothing);
 }
 
-extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,
-                               const void* x0_override, const void* dlogits, int ldd, const float* dy_top_extra,
-                               void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, void* stream) {
+// ---- the fused loss after st_rnn_forward_drop: ONE form for row weights and label smoothing (they combine).  The rows handed to the
+// vocabulary kernels are the dropped copy of y_top when drop->p_out > 0, else the workspace's; label_smoothing = 0 takes the kernels of
+// the _w calls (tile_sums may then be NULL), > 0 those of the _ls calls
+namespace {
+int fused_rows(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes, const st_dropout* drop,
+               const char* who, const char** ytop) {
+  if (check_common(p, s, who)) return 1;
+  ST_CHECK(st_rnn_fused_loss_supported(p), "%s: needs bf16, H = 512 and the vocabulary projection", who);
+  const Plan q = make_plan(p, s);
+  ST_CHECK(workspace && workspace_bytes >= q.total, "%s: workspace too small", who);
+  DropPlan dp;
+  if (st_drop_plan(drop, p->L, s->ntok, p->H, p->dtype, false, who, &dp)) return 1;
+  *ytop = dp.out ? dp.rows(p->L - 1) : reinterpret_cast<const char*>(workspace) + q.y + (size_t)(p->L - 1) * s->ntok * p->H * q.es;
+  return 0;
+}
+}  // namespace
+extern "C" int st_rnn_fused_loss_drop(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
+                                      const long* targets, float* scratch, size_t scratch_bytes, const float* row_weight, float* nll_out,
+                                      float* smooth_out, float label_smoothing, float* tile_sums, size_t tile_sums_bytes, float* loss_accum,
+                                      const st_dropout* drop, void* stream) {
+  const char* ytop;
+  if (fused_rows(p, s, workspace, workspace_bytes, drop, "st_rnn_fused_loss_drop", &ytop)) return 1;
+  ST_CHECK(targets && scratch && (loss_accum || nll_out || smooth_out), "st_rnn_fused_loss_drop: null pointer");
+  ST_CHECK(label_smoothing >= 0.f && label_smoothing < 1.f, "st_rnn_fused_loss_drop: label_smoothing=%g outside [0, 1)", (double)label_smoothing);
+  ST_CHECK(scratch_bytes >= st_rnn_fused_loss_bytes(p, s), "st_rnn_fused_loss_drop: scratch too small");
+  const int n = s->ntok;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (label_smoothing == 0.f && !smooth_out)
+    return vocab_ce_forward(ytop, p->w_lin, p->b_lin, targets, n, p->V, scratch + 2 * (size_t)n, scratch + n, scratch, loss_accum, row_weight,
+                            nll_out, st);
+  ST_CHECK(tile_sums && tile_sums_bytes >= st_rnn_fused_loss_ls_bytes(p, s), "st_rnn_fused_loss_drop: tile_sums too small");
+  return vocab_ce_forward(ytop, p->w_lin, p->b_lin, targets, n, p->V, scratch + 2 * (size_t)n, scratch + n, scratch, loss_accum, row_weight,
+                          nll_out, st, tile_sums, smooth_out, label_smoothing);
+}
+extern "C" int st_rnn_fused_dlogits_drop(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
+                                         const long* targets, const float* scratch, const float* grad_scale_dev, const float* row_weight,
+                                         float label_smoothing, void* dlogits, int ldd, const st_dropout* drop, void* stream) {
+  const char* ytop;
+  if (fused_rows(p, s, workspace, workspace_bytes, drop, "st_rnn_fused_dlogits_drop", &ytop)) return 1;
+  ST_CHECK(targets && scratch && dlogits, "st_rnn_fused_dlogits_drop: null pointer");
+  ST_CHECK(label_smoothing >= 0.f && label_smoothing < 1.f, "st_rnn_fused_dlogits_drop: label_smoothing=%g outside [0, 1)", (double)label_smoothing);
+  return vocab_ce_dlogits(ytop, p->w_lin, p->b_lin, targets, scratch, s->ntok, p->V, dlogits, ldd, 1.0f, grad_scale_dev, row_weight,
+                          reinterpret_cast<hipStream_t>(stream), label_smoothing != 0.f, label_smoothing);
+}
+
+namespace {
+int rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,
+                 const void* x0_override, const void* dlogits, int ldd, const float* dy_top_extra,
+                 void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, const st_dropout* drop, void* stream) {
   if (check_common(p, s, "st_rnn_backward")) return 1;
   ST_CHECK(g && workspace, "st_rnn_backward: null pointer");
+  DropPlan dp;
+  if (st_drop_plan(drop, p->L, s->ntok, p->H, p->dtype, false, "st_rnn_backward", &dp)) return 1;
+  ST_CHECK(!(dp.in && x0_override), "st_rnn_backward: input dropout needs the call's own x0 rows (no x0_override)");
+  ST_CHECK(!(dp.out && !dlogits), "st_rnn_backward: p_out masks the gradient of the vocabulary projection (needs dlogits, not dy_top)");
   const Plan q = make_plan(p, s);
   ST_CHECK(workspace_bytes >= q.total, "st_rnn_backward: workspace too small (%zu < %zu)", workspace_bytes, q.total);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -238,7 +328,7 @@ extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, co
   const int L = p->L, T = s->T;
   auto dyl = [&](int l) { return reinterpret_cast<float*>(ws + q.dyl) + (size_t)l * n * H; };   // d loss / d y_l
   float* dy = dyl(L - 1);
-  const char* ytop = ws + q.y + (size_t)(p->L - 1) * n * H * es;
+  const char* ytop = dp.out ? dp.rows(L - 1) : ws + q.y + (size_t)(p->L - 1) * n * H * es;   // what `linear` read
 
   if (dlogits) {
     ST_CHECK(p->w_lin && g->w_lin && g->b_lin, "st_rnn_backward: vocabulary projection gradients requested without buffers");
@@ -255,6 +345,7 @@ extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, co
     const int split = (ldd % (8 * bk) == 0 && ldd >= 16 * bk) ? 8 : 0;
     if (st_gemm_nt(dlogits, ldd, ws + q.wT, ldd, dy, H, n, H, ldd, dt, ST_F32, nullptr, stream, 0, split)) return 1;
     if (dy_top_extra) { st_set_error("st_rnn_backward: dlogits and dy_top_extra are exclusive"); return 1; }
+    if (dp.out && dropout_rows_launch(dy, dy, ST_F32, n, H, H, H, dp.kout, L - 1, 0, st)) return 1;   // d dropped y_top -> d y_top
   } else {
     ST_CHECK(dy_top_extra, "st_rnn_backward: need dlogits or dy_top");
     if (hipMemcpyAsync(dy, dy_top_extra, (size_t)n * H * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
@@ -303,17 +394,21 @@ extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, co
   };
   // reversed wavefront: the cells of a diagonal need only cells of the diagonal above
   const char* env = getenv("ST_BPTT_FUSED");       // read per call: ST_BPTT_FUSED=0 keeps the two-launch push route (A/B runs, tests)
-  const bool fused = !(env && env[0] == '0');
+  const bool fused = !(env && env[0] == '0') || dp.layer;   // the inter-layer mask lives in the fused cell only
   // pull form, one launch per diagonal: cell (l, t) takes dgh_{l,t+1} W_hh_l and dgx_{l+1,t} W_ih_{l+1} from what the diagonal
   // above wrote, adds dy (top layer) and its own dh z carry, and does its gate gradients in the epilogue
   for (int d = T + L - 2; fused && d >= 0; --d) {
     RnnBwdFused fc[ST_MAX_LAYERS];
+    RnnDropArgs da;
+    memset(&da, 0, sizeof(da));
+    da.key = dp.klayer;
     int nf = 0;
     for (int l = d < T ? 0 : d - (T - 1); l <= d && l < L; ++l) {
       const int t = d - l;
       RnnBwdFused& f = fc[nf++];
       memset(&f, 0, sizeof(f));
       f.e = bwd_cell(l, t, l == L - 1 ? dy : nullptr);
+      da.site[nf - 1] = l; da.row0[nf - 1] = off[t];
       RnnGemmArgs& a = f.g;
       a.M = f.e.Bt; a.N = H;
       if (t + 1 < T) {                             // rows [B_{t+1}, B_t) end here: no recurrent term
@@ -323,7 +418,7 @@ extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, co
         a.A2 = dgxl(l + 1) + (size_t)off[t] * GH * es; a.W2 = wTih(l + 1); a.K2 = GH; a.lda2 = GH; a.ldw2 = GH;
       }
     }
-    if (rnn_bwd_fused_launch_batch(fc, nf, p->cell, dt, st)) return 1;
+    if (dp.layer ? rnn_bwd_fused_launch_batch_drop(fc, nf, p->cell, dt, da, st) : rnn_bwd_fused_launch_batch(fc, nf, p->cell, dt, st)) return 1;
   }
   // dx0 = dgx_0 W_ih_0 feeds only the embedding / feature gradients: one whole-sequence GEMM off the recurrence
   if (fused && need_dx0 && st_gemm_nt(dgxl(0), GH, wTih(0), GH, dx0, p->in0, n, p->in0, GH, dt, ST_F32, nullptr, stream)) return 1;
@@ -352,6 +447,8 @@ extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, co
     if (rnn_bwd_gates_launch_batch(gc, ng, H, p->cell, dt, st)) return 1;
     if (rnn_gemm_launch_batch(mc, nm, dt, 0, 0, st)) return 1;
   }
+  // d dropped x0 -> d x0, before the embedding / feature gradients read it
+  if (dp.in && need_dx0 && dropout_rows_launch(dx0, dx0, ST_F32, n, p->in0, p->in0, p->in0, dp.kin, kDropSiteInput, 0, st)) return 1;
   // parameter gradients: K-major copies of every layer's operands (the transposes also sum the bias gradients), then the
   // 2L weight-gradient GEMMs -- 48 tiles each -- as grouped launches (st_conv_batch) that fill the chip
   st_conv_desc gd[2 * ST_MAX_LAYERS];
@@ -363,7 +460,8 @@ extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, co
   int nx = 0;                                                                                   // layers whose input width is H
   for (int l = 0; l < L; ++l) {
     const int in = l == 0 ? p->in0 : H;
-    const char* xl = l == 0 ? reinterpret_cast<const char*>(x0) : ws + q.y + (size_t)(l - 1) * n * H * es;
+    // dW_ih_l contracts with what layer l READ: the dropped copy of y_{l-1} (x0 was dropped in place); dW_hh_l with the plain y_l
+    const char* xl = l == 0 ? reinterpret_cast<const char*>(x0) : dp.layer ? dp.rows(l - 1) : ws + q.y + (size_t)(l - 1) * n * H * es;
     char* aIh = ws + q.gA + (size_t)(2 * l) * GH * Np * es;
     char* aHh = ws + q.gA + (size_t)(2 * l + 1) * GH * Np * es;
     char* bIh = ws + q.gB + (size_t)(2 * l) * q.maxw * Np * es;
@@ -399,4 +497,18 @@ extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, co
     if (embedding_bwd_launch(dx0, s->caption, s->Tcap, s->rows_b, s->rows_t, dfeat, g->emb, n, p->E, p->V, 0, st)) return 1;
   }
   return 0;
+}
+}  // namespace
+
+extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,
+                               const void* x0_override, const void* dlogits, int ldd, const float* dy_top_extra,
+                               void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, void* stream) {
+  return rnn_backward(p, g, s, x0_override, dlogits, ldd, dy_top_extra, workspace, workspace_bytes, dfeat, dx0_out, nullptr, stream);
+}
+// after st_rnn_forward_drop with the same descriptor (its buffer holds the dropped copies the weight gradients read)
+extern "C" int st_rnn_backward_drop(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,
+                                    const void* x0_override, const void* dlogits, int ldd, const float* dy_top_extra,
+                                    void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, const st_dropout* drop,
+                                    void* stream) {
+  return rnn_backward(p, g, s, x0_override, dlogits, ldd, dy_top_extra, workspace, workspace_bytes, dfeat, dx0_out, drop, stream);
 }

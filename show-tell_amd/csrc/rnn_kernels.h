@@ -1,6 +1,7 @@
 // Internal (non-ABI) launch interface of the recurrent-decoder kernels.
 #pragma once
 #include "common.h"
+#include "dropout.h"
 
 // alignas(16): a launch carries up to kRnnBatch of these back to back in the kernel-argument segment, and a size that is no
 // multiple of 16 puts every second cell's pointer pairs across a 16-byte boundary -- the kernels' scalar loads of them split, and the
@@ -50,6 +51,15 @@ struct RnnBwdFused { RnnGemmArgs g; RnnBwdCell e; };
 struct RnnBwdFusedBatch { RnnBwdFused c[ST_MAX_LAYERS]; };
 static_assert(sizeof(RnnBwdFusedBatch) <= 4000, "kernel-argument segment is 4 KiB");
 
+// Inter-layer dropout of one wavefront launch (the DROP forms of rnn_gemm_kernel and rnn_bwd_cell_kernel): the mask of csrc/dropout.h
+// at p_layer, and per cell of the launch (blockIdx.z) the site (= the layer whose output is dropped) and the packed row of the cell's
+// row 0.  A second by-value kernel argument: RnnGemmArgs has no spare room; in the plain forms that argument is an empty struct.
+//   forward:  cell (l, t) writes h' to hout and the dropped h' to hout2 (site l; a cell without hout2 -- the top layer -- drops nothing)
+//   backward: cell (l, t) takes mask * scale * (dgx_{l+1,t} W_ih_{l+1}) (site l; a cell without the (A2, W2) pair masks nothing)
+struct RnnDropArgs { DropKey key; int site[ST_MAX_LAYERS]; int row0[ST_MAX_LAYERS]; };
+static_assert(sizeof(RnnGemmBatch) + sizeof(RnnDropArgs) <= 4000 && sizeof(RnnBwdFusedBatch) + sizeof(RnnDropArgs) <= 4000,
+              "kernel-argument segment is 4 KiB");
+
 // One GRU unit (torch.nn.GRU, gate order r, z, n; reference rnn.py:32 / rnn.py:49):  x* = W_i* x + b_i*, h* = W_h* h + b_h*,
 //   r = s(xr + hr), z = s(xz + hz), n = tanh(xn + r hn), h' = (1 - z) n + z h.
 // ONE definition with explicit fused multiply-adds for every kernel that evaluates a cell (rnn_gemm_kernel, decode_pipe_kernel): the
@@ -93,6 +103,12 @@ int rnn_gemm_launch(const RnnGemmArgs& a, int dtype, int epi, int has_x, hipStre
 int rnn_gemm_launch_batch(const RnnGemmArgs* cells, int ncells, int dtype, int epi, int has_x, hipStream_t st);
 int rnn_bwd_gates_launch_batch(const RnnBwdCell* cells, int ncells, int H, int cell_kind, int dtype, hipStream_t st);
 int rnn_bwd_fused_launch_batch(const RnnBwdFused* cells, int ncells, int cell_kind, int dtype, hipStream_t st);
+// the DROP forms: full cells (has_x) of at most one per layer / fused BPTT cells, `drop` indexed like `cells`
+int rnn_gemm_launch_batch_drop(const RnnGemmArgs* cells, int ncells, int dtype, int epi, const RnnDropArgs& drop, hipStream_t st);
+int rnn_bwd_fused_launch_batch_drop(const RnnBwdFused* cells, int ncells, int cell_kind, int dtype, const RnnDropArgs& drop, hipStream_t st);
+// csrc/dropout.hip: st_dropout_rows without the public call's argument checks
+int dropout_rows_launch(const void* x, void* y, int dtype, int rows, int cols, int ldx, int ldy, const DropKey& key, int site, int row0,
+                        hipStream_t st);
 int pack_inputs_launch(const void* feat, const void* emb, const long* cap, int Tcap, const int* rows_b, const int* rows_t,
                        void* x0, long* target, int ntok, int E, int V, int mode, int dtype, hipStream_t st);
 int embedding_bwd_launch(const float* dx0, const long* cap, int Tcap, const int* rows_b, const int* rows_t,

@@ -168,8 +168,25 @@ __device__ __forceinline__ void skinny_mma(const RnnGemmArgs& a, int mbase, int 
 // EPI 0: out_f32[m][n] (+)= acc (+bias)         (BPTT dh += dgh W_hh, generic small products)
 // EPI 1: GRU gates (training fwd with precomputed gx, or decode with fused x-projection)
 // EPI 2: LSTM gates
-template <typename T, int NG, int EPI, bool HAS_X, int MT>
-__global__ __launch_bounds__(256) void rnn_gemm_kernel(RnnGemmBatch batch) {
+// DROP (inter-layer dropout, full GRU / LSTM cells only): h' goes to hout unchanged, for the recurrence, and hout2 -- the row the layer
+// above reads as its input -- receives the dropped h': the stored value times the mask of csrc/dropout.h at (site, packed row, unit) of
+// `drop`, the kernel's second argument.  In the plain forms that argument is an empty struct and the code is what it was.
+template <typename T> __device__ __forceinline__ float storage_round(float v);          // v as a T in memory holds it
+template <> __device__ __forceinline__ float storage_round<float>(float v) { return v; }
+template <> __device__ __forceinline__ float storage_round<bf16_t>(float v) { return bf16_bits_to_f32(f32_to_bf16_bits(v)); }
+template <typename T>
+__device__ __forceinline__ void drop_units4(const RnnDropArgs& d, int cell, int m, int n, const float* h, float* out) {
+  const DropWords w = drop_words(d.key, d.site[cell], d.row0[cell] + m, n >> 2);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) out[e] = w.w[e] >= d.key.thr ? storage_round<T>(h[e]) * d.key.scale : 0.f;
+}
+
+struct RnnNoDrop {};                                     // the second kernel argument of the plain forms: nothing
+template <bool DROP> struct DropParam { typedef RnnNoDrop type; };
+template <> struct DropParam<true> { typedef RnnDropArgs type; };
+
+template <typename T, int NG, int EPI, bool HAS_X, int MT, bool DROP = false>
+__global__ __launch_bounds__(256) void rnn_gemm_kernel(RnnGemmBatch batch, typename DropParam<DROP>::type drop) {
   // block = MT x 16 rows x 16 units (all NG gates); its 4 waves each take a quarter of K and the partial
   // accumulators meet in LDS: one round of L2 latency per launch instead of four.  Wave t < MT then runs the
   // epilogue of row tile t.  blockIdx.z selects one of the launch's independent cells (kernel-argument segment).
@@ -263,7 +280,11 @@ __global__ __launch_bounds__(256) void rnn_gemm_kernel(RnnGemmBatch batch) {
       hnew[e] = st_gru_unit(xg[0][e], xg[1][e], xg[2][e], hr, hz, hn[e], hp[e], r[e], z[e], nn[e]);
     }
     store4<T>(reinterpret_cast<T*>(a.hout) + (long)m * a.ldho + n, hnew);
-    if (a.hout2) store4<T>(reinterpret_cast<T*>(a.hout2) + (long)m * a.ldho2 + n, hnew);
+    if constexpr (DROP) {
+      if (a.hout2) { float hd[4]; drop_units4<T>(drop, blockIdx.z, m, n, hnew, hd); store4<T>(reinterpret_cast<T*>(a.hout2) + (long)m * a.ldho2 + n, hd); }
+    } else {
+      if (a.hout2) store4<T>(reinterpret_cast<T*>(a.hout2) + (long)m * a.ldho2 + n, hnew);
+    }
     if (a.cache) {
       T* c = reinterpret_cast<T*>(a.cache) + (long)m * a.ldcache + n;
       store4<T>(c, r); store4<T>(c + H, z); store4<T>(c + 2 * H, nn); store4<T>(c + 3 * H, hn);
@@ -280,7 +301,11 @@ __global__ __launch_bounds__(256) void rnn_gemm_kernel(RnnGemmBatch batch) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) hnew[e] = st_lstm_unit(pre[0][e], pre[1][e], pre[2][e], pre[3][e], cp[e], ig[e], fg[e], gg[e], og[e], cn[e]);
     store4<T>(reinterpret_cast<T*>(a.hout) + (long)m * a.ldho + n, hnew);
-    if (a.hout2) store4<T>(reinterpret_cast<T*>(a.hout2) + (long)m * a.ldho2 + n, hnew);
+    if constexpr (DROP) {
+      if (a.hout2) { float hd[4]; drop_units4<T>(drop, blockIdx.z, m, n, hnew, hd); store4<T>(reinterpret_cast<T*>(a.hout2) + (long)m * a.ldho2 + n, hd); }
+    } else {
+      if (a.hout2) store4<T>(reinterpret_cast<T*>(a.hout2) + (long)m * a.ldho2 + n, hnew);
+    }
     store4<T>(reinterpret_cast<T*>(a.cout) + (long)m * a.ldho + n, cn);
     if (a.cache) {
       T* c = reinterpret_cast<T*>(a.cache) + (long)m * a.ldcache + n;
@@ -450,8 +475,11 @@ template <> __device__ __forceinline__ void unpack4<bf16_t>(const u32x2& t, floa
   v[2] = __uint_as_float(t[1] << 16); v[3] = __uint_as_float(t[1] & 0xffff0000u);
 }
 
-template <typename T, bool LSTM, int MT, int NT>
-__global__ __launch_bounds__(256) void rnn_bwd_cell_kernel(RnnBwdFusedBatch batch) {
+// DROP (inter-layer dropout): the from-above product dgx_{l+1,t} W_ih_{l+1} is the gradient of the DROPPED y_l, so it takes the mask
+// of csrc/dropout.h times scale before it joins the recurrent product, which is not masked.  Each lane's accX[t][g] is 4 consecutive units
+// of one row: one Philox call per tile and lane, in registers, before the cross-wave reduction (the mask is the same in all 4 K slices).
+template <typename T, bool LSTM, int MT, int NT, bool DROP = false>
+__global__ __launch_bounds__(256) void rnn_bwd_cell_kernel(RnnBwdFusedBatch batch, typename DropParam<DROP>::type drop) {
   typedef typename Raw4<T>::type raw_t;
   const RnnGemmArgs& a = batch.c[blockIdx.z].g;
   const RnnBwdCell& c = batch.c[blockIdx.z].e;
@@ -500,7 +528,18 @@ __global__ __launch_bounds__(256) void rnn_bwd_cell_kernel(RnnBwdFusedBatch batc
 #pragma unroll
   for (int t = 0; t < MT; ++t)
 #pragma unroll
-    for (int g = 0; g < NT; ++g) red[wid][t * NT + g][lane] = accH[t][g] + accX[t][g];
+    for (int g = 0; g < NT; ++g) {
+      if constexpr (DROP) {
+        f32x4 mk = f32x4{1.f, 1.f, 1.f, 1.f};
+        if (a.A2) {
+          const DropWords w = drop_words(drop.key, drop.site[blockIdx.z], drop.row0[blockIdx.z] + mbase + t * 16 + r16, (n0 + g * 16) / 4 + q4);
+          mk = f32x4{drop_mult(drop.key, w.w[0]), drop_mult(drop.key, w.w[1]), drop_mult(drop.key, w.w[2]), drop_mult(drop.key, w.w[3])};
+        }
+        red[wid][t * NT + g][lane] = accH[t][g] + mk * accX[t][g];
+      } else {
+        red[wid][t * NT + g][lane] = accH[t][g] + accX[t][g];
+      }
+    }
   __syncthreads();
 #pragma unroll
   for (int j = 0; j < TPW; ++j) {
@@ -657,15 +696,18 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, fl
 // ---------------------------------------------------------------------------------------
 // internal launchers (declared in rnn_kernels.h)
 // ---------------------------------------------------------------------------------------
-int rnn_gemm_launch_batch(const RnnGemmArgs* cells, int ncells, int dtype, int epi, int has_x, hipStream_t st) {
+// drop (NULL: the plain forms): the DROP forms of a forward diagonal -- full cells (has_x) with a gate epilogue, at most one per layer,
+// none empty, because drop->site / drop->row0 are indexed like `cells`
+static int gemm_launch(const RnnGemmArgs* cells, int ncells, int dtype, int epi, int has_x, const RnnDropArgs* drop, hipStream_t st) {
   ST_CHECK(ncells >= 0 && ncells <= kRnnBatch, "rnn_gemm: %d cells in one launch (max %d)", ncells, kRnnBatch);
+  ST_CHECK(!drop || (ncells <= ST_MAX_LAYERS && has_x && (epi == 1 || epi == 2)), "rnn_gemm(drop): full gate cells only, at most %d", ST_MAX_LAYERS);
   RnnGemmBatch b;
   memset(&b, 0, sizeof(b));
   const int epc = dtype == ST_BF16 ? 8 : 4;
   int nc = 0, maxM = 0, maxN = 0;
   for (int i = 0; i < ncells; ++i) {
     const RnnGemmArgs& a = cells[i];
-    if (a.M <= 0) continue;
+    if (a.M <= 0) { ST_CHECK(!drop, "rnn_gemm(drop): empty cell"); continue; }
     ST_CHECK(a.N % 4 == 0, "rnn_gemm: N=%d must be a multiple of 4", a.N);
     ST_CHECK(a.K % epc == 0 && a.lda % epc == 0 && a.ldw % epc == 0, "rnn_gemm: K/lda/ldw must be multiples of %d", epc);
     if (has_x) ST_CHECK(a.K2 % epc == 0 && a.lda2 % epc == 0 && a.ldw2 % epc == 0, "rnn_gemm: K2/lda2/ldw2 must be multiples of %d", epc);
@@ -679,9 +721,14 @@ int rnn_gemm_launch_batch(const RnnGemmArgs* cells, int ncells, int dtype, int e
   // ... and so do the 16-row tiles of one tall cell (beam search steps 1280 rows at a time: 80 row tiles re-read the weights)
   const bool mt2 = (nc >= 2 || maxM >= 512) && maxM > 16;
   const dim3 grid2((maxN + 15) / 16, (maxM + 31) / 32, nc);
-#define RG(T, NG, EPI, HX) do { if (mt2) hipLaunchKernelGGL((rnn_gemm_kernel<T, NG, EPI, HX, 2>), grid2, block, 0, st, b); \
-                               else hipLaunchKernelGGL((rnn_gemm_kernel<T, NG, EPI, HX, 1>), grid, block, 0, st, b); } while (0)
-  if (dtype == ST_BF16) {
+#define RG(T, NG, EPI, HX) do { if (mt2) hipLaunchKernelGGL((rnn_gemm_kernel<T, NG, EPI, HX, 2>), grid2, block, 0, st, b, RnnNoDrop{}); \
+                               else hipLaunchKernelGGL((rnn_gemm_kernel<T, NG, EPI, HX, 1>), grid, block, 0, st, b, RnnNoDrop{}); } while (0)
+#define RGD(T, NG, EPI) do { if (mt2) hipLaunchKernelGGL((rnn_gemm_kernel<T, NG, EPI, true, 2, true>), grid2, block, 0, st, b, *drop); \
+                            else hipLaunchKernelGGL((rnn_gemm_kernel<T, NG, EPI, true, 1, true>), grid, block, 0, st, b, *drop); } while (0)
+  if (drop) {
+    if (dtype == ST_BF16) { if (epi == 1) RGD(bf16_t, 3, 1); else RGD(bf16_t, 4, 2); }
+    else { if (epi == 1) RGD(float, 3, 1); else RGD(float, 4, 2); }
+  } else if (dtype == ST_BF16) {
     if (epi == 0) RG(bf16_t, 1, 0, false);
     else if (epi == 1) { if (has_x) RG(bf16_t, 3, 1, true); else RG(bf16_t, 3, 1, false); }
     else { if (has_x) RG(bf16_t, 4, 2, true); else RG(bf16_t, 4, 2, false); }
@@ -691,8 +738,16 @@ int rnn_gemm_launch_batch(const RnnGemmArgs* cells, int ncells, int dtype, int e
     else { if (has_x) RG(float, 4, 2, true); else RG(float, 4, 2, false); }
   }
 #undef RG
+#undef RGD
   ST_LAUNCH_CHECK();
   return 0;
+}
+
+int rnn_gemm_launch_batch(const RnnGemmArgs* cells, int ncells, int dtype, int epi, int has_x, hipStream_t st) {
+  return gemm_launch(cells, ncells, dtype, epi, has_x, nullptr, st);
+}
+int rnn_gemm_launch_batch_drop(const RnnGemmArgs* cells, int ncells, int dtype, int epi, const RnnDropArgs& drop, hipStream_t st) {
+  return gemm_launch(cells, ncells, dtype, epi, 1, &drop, st);
 }
 
 int rnn_gemm_launch(const RnnGemmArgs& a, int dtype, int epi, int has_x, hipStream_t st) {
@@ -725,7 +780,7 @@ int rnn_bwd_gates_launch_batch(const RnnBwdCell* cells, int ncells, int H, int c
 // One launch for the cells of a reversed diagonal.  Block shape: 32 rows x 32 units, the fastest of 32 x 16, 32 x 32, 32 x 64,
 // 64 x 32 and 64 x 64 at the bench shape (profiles/r05_bptt_tile_shapes.txt): larger blocks halve the operand bytes but leave
 // CUs without a block and lengthen the K chain of every wave.
-int rnn_bwd_fused_launch_batch(const RnnBwdFused* cells, int ncells, int cell_kind, int dtype, hipStream_t st) {
+static int bwd_fused_launch(const RnnBwdFused* cells, int ncells, int cell_kind, int dtype, const RnnDropArgs* drop, hipStream_t st) {
   ST_CHECK(ncells >= 0 && ncells <= ST_MAX_LAYERS, "rnn_bwd_fused: %d cells in one launch (max %d)", ncells, ST_MAX_LAYERS);
   RnnBwdFusedBatch b;
   memset(&b, 0, sizeof(b));
@@ -733,7 +788,7 @@ int rnn_bwd_fused_launch_batch(const RnnBwdFused* cells, int ncells, int cell_ki
   int nc = 0, maxM = 0, maxN = 0;
   for (int i = 0; i < ncells; ++i) {
     const RnnGemmArgs& a = cells[i].g;
-    if (a.M <= 0) continue;
+    if (a.M <= 0) { ST_CHECK(!drop, "rnn_bwd_fused(drop): empty cell"); continue; }   // drop is indexed like `cells`: no compaction
     ST_CHECK(a.N % 8 == 0, "rnn_bwd_fused: H=%d must be a multiple of 8", a.N);
     ST_CHECK(!a.A || (a.K % epc == 0 && a.lda % epc == 0 && a.ldw % epc == 0 && a.M2 >= 0 && a.M2 <= a.M),
              "rnn_bwd_fused: bad recurrent operand pair");
@@ -749,15 +804,30 @@ int rnn_bwd_fused_launch_batch(const RnnBwdFused* cells, int ncells, int cell_ki
   const bool lstm = cell_kind == ST_CELL_LSTM;
   constexpr int MT = 2, NT = 2;
   const dim3 grid((maxN + 16 * NT - 1) / (16 * NT), (maxM + 16 * MT - 1) / (16 * MT), nc), block(256);
-  if (dtype == ST_BF16) {
-    if (lstm) hipLaunchKernelGGL((rnn_bwd_cell_kernel<bf16_t, true, MT, NT>), grid, block, 0, st, b);
-    else hipLaunchKernelGGL((rnn_bwd_cell_kernel<bf16_t, false, MT, NT>), grid, block, 0, st, b);
+  if (drop) {
+    if (dtype == ST_BF16) {
+      if (lstm) hipLaunchKernelGGL((rnn_bwd_cell_kernel<bf16_t, true, MT, NT, true>), grid, block, 0, st, b, *drop);
+      else hipLaunchKernelGGL((rnn_bwd_cell_kernel<bf16_t, false, MT, NT, true>), grid, block, 0, st, b, *drop);
+    } else {
+      if (lstm) hipLaunchKernelGGL((rnn_bwd_cell_kernel<float, true, MT, NT, true>), grid, block, 0, st, b, *drop);
+      else hipLaunchKernelGGL((rnn_bwd_cell_kernel<float, false, MT, NT, true>), grid, block, 0, st, b, *drop);
+    }
+  } else if (dtype == ST_BF16) {
+    if (lstm) hipLaunchKernelGGL((rnn_bwd_cell_kernel<bf16_t, true, MT, NT>), grid, block, 0, st, b, RnnNoDrop{});
+    else hipLaunchKernelGGL((rnn_bwd_cell_kernel<bf16_t, false, MT, NT>), grid, block, 0, st, b, RnnNoDrop{});
   } else {
-    if (lstm) hipLaunchKernelGGL((rnn_bwd_cell_kernel<float, true, MT, NT>), grid, block, 0, st, b);
-    else hipLaunchKernelGGL((rnn_bwd_cell_kernel<float, false, MT, NT>), grid, block, 0, st, b);
+    if (lstm) hipLaunchKernelGGL((rnn_bwd_cell_kernel<float, true, MT, NT>), grid, block, 0, st, b, RnnNoDrop{});
+    else hipLaunchKernelGGL((rnn_bwd_cell_kernel<float, false, MT, NT>), grid, block, 0, st, b, RnnNoDrop{});
   }
   ST_LAUNCH_CHECK();
   return 0;
+}
+
+int rnn_bwd_fused_launch_batch(const RnnBwdFused* cells, int ncells, int cell_kind, int dtype, hipStream_t st) {
+  return bwd_fused_launch(cells, ncells, cell_kind, dtype, nullptr, st);
+}
+int rnn_bwd_fused_launch_batch_drop(const RnnBwdFused* cells, int ncells, int cell_kind, int dtype, const RnnDropArgs& drop, hipStream_t st) {
+  return bwd_fused_launch(cells, ncells, cell_kind, dtype, &drop, st);
 }
 
 static inline int grid1d(long work, int threads = 256) {

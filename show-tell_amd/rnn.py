@@ -10,6 +10,7 @@ Same constructor, same attribute names (``embeddings``, ``unit``, ``linear``) an
     loss   = rnn.loss(cnn_feature, image_caption, caption_size, sequence_weight=advantage)   # sum w * nll / N_tok (reward-weighted)
     loss   = rnn.loss(cnn_feature, image_caption, caption_size, label_smoothing=0.1)         # CrossEntropyLoss(label_smoothing=0.1)
     logp   = rnn.token_logp(cnn_feature, image_caption, caption_size)                        # (B, T) log p of every given token
+    rnn    = RNN(E, H, V, L, dropout=0.3, dropout_out=0.5); rnn.train() / rnn.eval()         # nn.GRU(dropout=) + Dropout before linear
 
 ``nn.Embedding`` / ``nn.GRU`` / ``nn.Linear`` objects are parameter containers only; all
 arithmetic runs in libshowtell_hip (st_rnn_forward / st_rnn_backward / st_rnn_greedy /
@@ -28,6 +29,7 @@ import torch.nn as nn
 from . import _lib, ops
 from ._lib import ST_CELL_GRU, ST_CELL_LSTM, ST_F32, RnnGrads, RnnParams, check, dtype_code, lib
 from ._lib import ptr as _cp, stream as _stream  # noqa: F401  (tests and tools import these names from here)
+from .dropout import DropoutState
 from ._weights import FollowsMoves, grad_buffer, working_copy  # noqa: F401  (rnn.working_copy stays importable)
 from .seq import plan_for
 
@@ -195,8 +197,18 @@ class _DecoderFn(torch.autograd.Function):
         fused = mode != "logits" and os.environ.get("ST_FUSED_CE", "1") != "0" and bool(lib().st_rnn_fused_loss_supported(C.byref(prm)))
         ldt = dt if mode == "loss" else torch.float32
         logits = None if fused else torch.empty(n, Vp, device=dev, dtype=ldt)
-        check(lib().st_rnn_forward(C.byref(prm), C.byref(seq), None, _cp(featd), _cp(ws), nbytes, _cp(logits), dtype_code(ldt), Vp,
-                                   _cp(targets), int(need_grad), _stream()), "st_rnn_forward")
+        # dropout: forward() and loss() of a module in train() with a site on; token_logp ('nll') scores the deterministic model.
+        # The call's (seed, step) stay in ctx: the backward pass regenerates the same masks
+        took = None if mode == "nll" else m._dropout.take(m.training)
+        drop = dbuf = None
+        if took is not None:
+            drop, dbuf = m._dropout.desc(took, lib().st_rnn_dropout_bytes(C.byref(prm), C.byref(seq)), dev)
+            check(lib().st_rnn_forward_drop(C.byref(prm), C.byref(seq), None, _cp(featd), _cp(ws), nbytes, _cp(logits), dtype_code(ldt), Vp,
+                                            _cp(targets), int(need_grad), C.byref(drop), _stream()), "st_rnn_forward_drop")
+        else:
+            check(lib().st_rnn_forward(C.byref(prm), C.byref(seq), None, _cp(featd), _cp(ws), nbytes, _cp(logits), dtype_code(ldt), Vp,
+                                       _cp(targets), int(need_grad), _stream()), "st_rnn_forward")
+        ctx.drop, ctx.dbuf = drop, dbuf
         ctx.m, ctx.plan, ctx.caption, ctx.ws, ctx.mode, ctx.keep = m, plan, caption, ws, mode, keep
         ctx.feat_dtype = feat.dtype
         ctx.fused, ctx.roww, ctx.eps = fused, roww, eps
@@ -207,7 +219,13 @@ class _DecoderFn(torch.autograd.Function):
         if fused:
             sb = lib().st_rnn_fused_loss_bytes(C.byref(prm), C.byref(seq))
             scratch = torch.empty(sb // 4, device=dev, dtype=torch.float32)
-            if eps:       # label smoothing: the tile sums of the rows' logits live in a buffer of this call only
+            if drop is not None:     # one form for weights and label smoothing, over the dropped copy of y_top
+                tb = lib().st_rnn_fused_loss_ls_bytes(C.byref(prm), C.byref(seq)) if eps else 0
+                tsum = torch.empty(tb // 4, device=dev, dtype=torch.float32) if eps else None
+                check(lib().st_rnn_fused_loss_drop(C.byref(prm), C.byref(seq), _cp(ws), nbytes, _cp(targets), _cp(scratch), sb, _cp(roww),
+                                                   _cp(nll), None, eps, _cp(tsum), tb, _cp(loss), C.byref(drop), _stream()),
+                      "st_rnn_fused_loss_drop")
+            elif eps:       # label smoothing: the tile sums of the rows' logits live in a buffer of this call only
                 tb = lib().st_rnn_fused_loss_ls_bytes(C.byref(prm), C.byref(seq))
                 tsum = torch.empty(tb // 4, device=dev, dtype=torch.float32)
                 check(lib().st_rnn_fused_loss_ls(C.byref(prm), C.byref(seq), _cp(ws), nbytes, _cp(targets), _cp(scratch), sb, _cp(roww),
@@ -242,7 +260,11 @@ class _DecoderFn(torch.autograd.Function):
         elif ctx.fused:
             gsc = gout.detach().float().contiguous()
             dlog = torch.empty(n, Vp, device=dev, dtype=dt)
-            if ctx.eps:
+            if ctx.drop is not None:
+                check(lib().st_rnn_fused_dlogits_drop(C.byref(prm), C.byref(seq), _cp(ctx.ws), ctx.ws.numel(), _cp(ctx.targets),
+                                                      _cp(ctx.scratch), _cp(gsc), _cp(ctx.roww), ctx.eps, _cp(dlog), Vp, C.byref(ctx.drop),
+                                                      _stream()), "st_rnn_fused_dlogits_drop")
+            elif ctx.eps:
                 check(lib().st_rnn_fused_dlogits_ls(C.byref(prm), C.byref(seq), _cp(ctx.ws), ctx.ws.numel(), _cp(ctx.targets),
                                                     _cp(ctx.scratch), _cp(gsc), _cp(ctx.roww), ctx.eps, _cp(dlog), Vp, _stream()),
                       "st_rnn_fused_dlogits_ls")
@@ -257,9 +279,13 @@ class _DecoderFn(torch.autograd.Function):
             dlog, gsc = ce_loss_backward(ctx.logits, dt, ctx.targets, n, V, Vp, gout, ctx.roww, ctx.eps)
         grads, keep2 = m._c_grads()
         dfeat = torch.empty(plan.B, m.embed_dim, device=dev, dtype=torch.float32)
-        check(lib().st_rnn_backward(C.byref(prm), C.byref(grads), C.byref(seq), None, _cp(dlog), Vp, None, _cp(ctx.ws),
-                                    ctx.ws.numel(), _cp(dfeat), None, _stream()), "st_rnn_backward")
-        ctx.ws = None
+        if ctx.drop is not None:
+            check(lib().st_rnn_backward_drop(C.byref(prm), C.byref(grads), C.byref(seq), None, _cp(dlog), Vp, None, _cp(ctx.ws),
+                                             ctx.ws.numel(), _cp(dfeat), None, C.byref(ctx.drop), _stream()), "st_rnn_backward_drop")
+        else:
+            check(lib().st_rnn_backward(C.byref(prm), C.byref(grads), C.byref(seq), None, _cp(dlog), Vp, None, _cp(ctx.ws),
+                                        ctx.ws.numel(), _cp(dfeat), None, _stream()), "st_rnn_backward")
+        ctx.ws = ctx.dbuf = None
         return dfeat.to(ctx.feat_dtype), None, None, None, None, None, None, None, None, None
 
 
@@ -269,6 +295,19 @@ class Decoder(FollowsMoves, nn.Module):
     ``compute_dtype``."""
 
     cell = "gru"
+
+    def seed_dropout(self, seed):
+        """Set the 64-bit seed of this module's dropout masks and zero its step counter (the default seed is
+        torch.initial_seed(), taken at construction).  The mask of a call is a pure function of (seed, step, site, packed row,
+        column), so two modules with equal seeds and step counts drop the same elements; data-parallel replicas want different
+        seeds (the Trainer seeds rank r with seed + r).  The state is two host integers and is NOT part of ``state_dict``: a
+        run resumed from a checkpoint starts its masks over unless the caller seeds it."""
+        self._dropout.reseed(seed)
+
+    @property
+    def dropout_seed(self):
+        """The 64-bit seed of this module's dropout masks (``seed_dropout`` sets it)."""
+        return self._dropout.seed
 
     def _layer_params(self):
         u = self.unit
@@ -324,7 +363,8 @@ class Decoder(FollowsMoves, nn.Module):
 
 class RNN(Decoder):
 
-    def __init__(self, embed_dim, num_hidden_units, vocab_size, num_layers, dtype=torch.float32):
+    def __init__(self, embed_dim, num_hidden_units, vocab_size, num_layers, dtype=torch.float32, dropout=0.0, dropout_in=0.0,
+                 dropout_out=0.0):
         '''
         Args (as the reference, rnn.py:12-19):
             embed_dim (int) : Embedding dimension between CNN and RNN
@@ -332,8 +372,18 @@ class RNN(Decoder):
             vocab_size (int) : Size of the vocabulary
             num_layers (int) : # of layers
             dtype : kernel storage type (float32 = parity mode, bfloat16 = performance mode)
+            dropout : as nn.GRU(dropout=) / nn.LSTM(dropout=): on the output of every recurrent layer but the last (warns with
+                num_layers == 1, as torch does)
+            dropout_in : on the layer-0 input rows [feature ; embeddings]
+            dropout_out : nn.Dropout in front of `linear`
+        Dropout (each p in [0, 1)) is active only while ``self.training`` and only in ``forward()`` and ``loss()`` (with every
+        combination of weights and label smoothing, on the fused route and on the launch chain).  ``token_logp``,
+        ``sentence_index``, ``beam_search`` and ``sample`` always run the deterministic model.  With every p = 0, or in
+        ``eval()``, each call is the launch sequence it was.  Each training-mode call consumes one step of the module's mask
+        counter (``seed_dropout``); its backward regenerates the same masks.  ``state_dict`` keys stay the reference's.
         '''
         super(RNN, self).__init__()
+        self._dropout = DropoutState(dropout_in, dropout, dropout_out, num_layers)
         if num_layers > _lib.ST_MAX_LAYERS:
             raise ValueError(f"num_layers={num_layers} exceeds the kernel limit of {_lib.ST_MAX_LAYERS}")
         self.embeddings = nn.Embedding(vocab_size, embed_dim)
@@ -358,7 +408,8 @@ class RNN(Decoder):
 
     # ---- reference surface -------------------------------------------------------------
     def forward(self, cnn_feature, image_caption, caption_size):
-        """rnn.py:27-35: teacher-forced logits over the packed sequence, (N_tok, V) fp32."""
+        """rnn.py:27-35: teacher-forced logits over the packed sequence, (N_tok, V) fp32.  In train() with a dropout site on, one
+        step of the masks is applied (see __init__)."""
         return _DecoderFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "logits", torch.is_grad_enabled(), None, None)
 
     def loss(self, cnn_feature, image_caption, caption_size, sequence_weight=None, token_weight=None, label_smoothing=0.0):
@@ -371,7 +422,9 @@ class RNN(Decoder):
 
         `label_smoothing` = eps in [0, 1) is CrossEntropyLoss(label_smoothing=eps): every row's term becomes
         (1 - eps) * nll + eps * (logsumexp(x) - mean(x)), times its weight where weights are given (the divisor stays N_tok).  The
-        rows' mean logit is formed inside the loss kernels too; with eps = 0 the call is the one it was."""
+        rows' mean logit is formed inside the loss kernels too; with eps = 0 the call is the one it was.
+
+        In train() with a dropout site on (see __init__) the loss is that of one draw of the masks; eval() is deterministic."""
         eps = check_label_smoothing(label_smoothing)
         if sequence_weight is None and token_weight is None and not eps:
             return _DecoderFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "loss", torch.is_grad_enabled(),
@@ -383,7 +436,7 @@ class RNN(Decoder):
 
     def token_logp(self, cnn_feature, image_caption, caption_size):
         """log p(image_caption[b, t] | image b, image_caption[b, :t]) for every token of the given captions: (B, T) fp32, T the
-        caption tensor's width, 0 past caption_size[b].  No gradient.  -token_logp.sum() / N_tok is loss(); with the output of
+        caption tensor's width, 0 past caption_size[b].  No gradient, and never any dropout (train() or not: it scores the model).  -token_logp.sum() / N_tok is loss(); with the output of
         ``sample`` as captions it scores what that call's `logp` scored (at temperature 1, top_k 0; the two passes round differently).  On the fused route (bf16,
         H = 512) the vocabulary projection runs tile by tile: there is no logits tensor."""
         check_caption_args(image_caption, caption_size)

@@ -27,6 +27,7 @@ from ._lib import AttnGrads, AttnParams, check, dtype_code, lib
 from ._lib import ptr as _cp, stream as _stream
 from .rnn import (CAP_MAX, Decoder, ce_loss, ce_loss_backward, check_caption_args, check_label_smoothing, check_weight_args, logits_grad,
                   pack_row_weights, sample_lengths, unpack_rows, up8)
+from .dropout import DropoutState
 from .seq import plan_for
 
 
@@ -69,8 +70,18 @@ class _AttnFn(torch.autograd.Function):
         alphas = torch.zeros(B, T, P, device=dev, dtype=torch.float32)        # rnn_attn.py:65
         roww = pack_row_weights(plan, sequence_weight, token_weight, dev)
         logits = torch.empty(n, Vp, device=dev, dtype=dt if mode == "loss" else torch.float32)
-        check(lib().st_attn_forward(C.byref(prm), C.byref(seq), _cp(featc), _cp(cap_T), _cp(ws), nbytes, _cp(logits),
-                                    dtype_code(logits.dtype), Vp, _cp(alphas), int(need_grad), _stream()), "st_attn_forward")
+        # dropout in front of `linear`: forward() and loss() in train(); token_logp ('nll') scores the deterministic model
+        took = None if mode == "nll" else m._dropout.take(m.training)
+        drop = dbuf = None
+        if took is not None:
+            drop, dbuf = m._dropout.desc(took, lib().st_attn_dropout_bytes(C.byref(prm), C.byref(seq)), dev)
+            check(lib().st_attn_forward_drop(C.byref(prm), C.byref(seq), _cp(featc), _cp(cap_T), _cp(ws), nbytes, _cp(logits),
+                                             dtype_code(logits.dtype), Vp, _cp(alphas), int(need_grad), C.byref(drop), _stream()),
+                  "st_attn_forward_drop")
+        else:
+            check(lib().st_attn_forward(C.byref(prm), C.byref(seq), _cp(featc), _cp(cap_T), _cp(ws), nbytes, _cp(logits),
+                                        dtype_code(logits.dtype), Vp, _cp(alphas), int(need_grad), _stream()), "st_attn_forward")
+        ctx.drop, ctx.dbuf = drop, dbuf
         # st_attn_forward steps over plan.T columns; alphas has T (padded) columns: strides must agree
         ctx.m, ctx.plan, ctx.caption, ctx.cap_T, ctx.ws, ctx.mode, ctx.P = m, plan, caption, cap_T, ws, mode, P
         ctx.alphas, ctx.alpha_c, ctx.keep, ctx.roww, ctx.eps = alphas, alpha_c, keep, roww, eps
@@ -108,19 +119,30 @@ class _AttnFn(torch.autograd.Function):
         prm.P = ctx.P
         grads, keep2 = m._c_grads()
         seq = plan.c_struct(ctx.caption)
-        check(lib().st_attn_backward(C.byref(prm), C.byref(grads), C.byref(seq), _cp(ctx.cap_T), _cp(dlog), Vp, _cp(ctx.alphas), _cp(dal),
-                                     float(alpha_c), _cp(gs), _cp(ctx.ws), ctx.ws.numel(), _stream()), "st_attn_backward")
-        ctx.ws = None
+        if ctx.drop is not None:
+            check(lib().st_attn_backward_drop(C.byref(prm), C.byref(grads), C.byref(seq), _cp(ctx.cap_T), _cp(dlog), Vp, _cp(ctx.alphas),
+                                              _cp(dal), float(alpha_c), _cp(gs), _cp(ctx.ws), ctx.ws.numel(), C.byref(ctx.drop), _stream()),
+                  "st_attn_backward_drop")
+        else:
+            check(lib().st_attn_backward(C.byref(prm), C.byref(grads), C.byref(seq), _cp(ctx.cap_T), _cp(dlog), Vp, _cp(ctx.alphas), _cp(dal),
+                                         float(alpha_c), _cp(gs), _cp(ctx.ws), ctx.ws.numel(), _stream()), "st_attn_backward")
+        ctx.ws = ctx.dbuf = None
         return None, None, None, None, None, None, None, None, None, None, None
 
 
 class RNN_Attn(Decoder):
 
-    def __init__(self, embed_dim, nos_filters, attention_dim, num_hidden_units, vocab_size, num_layers, dtype=torch.float32):
+    def __init__(self, embed_dim, nos_filters, attention_dim, num_hidden_units, vocab_size, num_layers, dtype=torch.float32,
+                 dropout_out=0.0):
         '''
-        Args (as the reference, rnn_attn.py:35-42) + dtype (kernel storage type).
+        Args (as the reference, rnn_attn.py:35-42) + dtype (kernel storage type) + dropout_out: nn.Dropout(p) in front of `linear`,
+        the Show-Attend-Tell placement.  The recurrence and the next step's attention read the plain top state; only the vocabulary
+        projection (and its weight gradient) sees the dropped copy.  Active only while ``self.training``, in ``forward()`` and
+        ``loss()``; ``token_logp``, ``sentence_index``, ``beam_search`` and ``sample`` always run the deterministic model.  With
+        p = 0, or in ``eval()``, each call is the launch sequence it was.  Seed and step counter: ``seed_dropout``.
         '''
         super(RNN_Attn, self).__init__()
+        self._dropout = DropoutState(0.0, 0.0, dropout_out, num_layers)
         if num_layers > _lib.ST_MAX_LAYERS:
             raise ValueError(f"num_layers={num_layers} exceeds the kernel limit of {_lib.ST_MAX_LAYERS}")
         self.nos_filters = nos_filters

@@ -74,15 +74,27 @@ def sample_caption_batch(ids, lengths):
     return order, ids.reshape(B * S, T)[order].contiguous(), [int(l) for l in flat_len[order].tolist()]
 
 
+def dropout_rank():
+    """This process's rank among the data-parallel replicas (0 without torch.distributed)."""
+    import torch.distributed as dist
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+
 class Trainer:
     def __init__(self, cnn, rnn, optimizer, world_size=1, label_smoothing=0.0):
         """`label_smoothing` in [0, 1): `step` trains on CrossEntropyLoss(label_smoothing=..) (``rnn.loss(.., label_smoothing=)``);
-        0 is the reference's plain cross entropy."""
+        0 is the reference's plain cross entropy.
+        Dropout is the decoder's own (``RNN(.., dropout=, dropout_in=, dropout_out=)``, active in ``rnn.train()``): `step` and the
+        loss half of `step_self_critical` draw one step of its masks each; the sampling half of `step_self_critical` (``sample``,
+        ``sentence_index``) always runs the deterministic model.  The decoder of rank r (0 without torch.distributed) is re-seeded
+        with its seed + r here, which also zeroes its step counter, so that data-parallel replicas draw different masks."""
         self.label_smoothing = check_label_smoothing(label_smoothing)
         self.cnn, self.rnn, self.opt = cnn, rnn, optimizer
         self.reducer = GradAllReducer(world_size)
         if world_size > 1:
             broadcast_state([cnn, rnn], optimizer)         # replicas start from rank 0's weights and BN buffers
+        if hasattr(rnn, "seed_dropout"):                   # data-parallel replicas draw different dropout masks: rank r gets seed + r
+            rnn.seed_dropout(rnn.dropout_seed + dropout_rank())
         self.pending = False
         optimizer._pending_owner = self                    # optimizer.state_dict() / utils.create_checkpoint flush the deferred step
         self._pre = []        # FIFO of (images, pooled features, event, undo): backbone forwards issued ahead on the side streams
