@@ -524,6 +524,17 @@ int st_rnn_fused_dlogits_drop(const st_rnn_params* p, const st_packed_seq* s, co
 int st_rnn_backward_drop(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,
                          const void* x0_override, const void* dlogits, int ldd, const float* dy_top,
                          void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, const st_dropout* drop, void* stream);
+/* The _drop forms with input ids apart from the targets (scheduled sampling): input_ids [B][Tcap] int64 on the device, NULL =
+ * s->caption (then each call is its _drop form, launch for launch).  The layer-0 rows t >= 1 gather emb[input_ids[b][t-1]], the
+ * targets still come from s->caption, and the backward pass scatters the embedding gradient to input_ids.  Exclusive with
+ * x0_override.  The workspaces, st_packed_seq and the fused loss / dlogits calls (they take `targets`) stay what they are. */
+int st_rnn_forward_ids(const st_rnn_params* p, const st_packed_seq* s, const void* x0_override, const void* feat,
+                       void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
+                       long* targets, int save_for_backward, const st_dropout* drop, const long* input_ids, void* stream);
+int st_rnn_backward_ids(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,
+                        const void* x0_override, const void* dlogits, int ldd, const float* dy_top,
+                        void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, const st_dropout* drop,
+                        const long* input_ids, void* stream);
 
 /* nn.CrossEntropyLoss() (mean) forward + backward (main.py:94,149):
  *   *loss_accum += mean_r( logsumexp(x_r) - x_r[target_r] );  dlogits = (softmax - onehot) * grad_scale / rows
@@ -641,6 +652,28 @@ int st_sample_rows(const float* logits, int ldl, int n, int V, const float* u, i
 size_t st_rnn_sample_workspace_bytes(const st_rnn_params* p, int n);
 int st_rnn_sample(const st_rnn_params* p, const void* feat, int n, int steps, const float* u, float inv_temperature, int top_k,
                   long end_id, void* workspace, size_t workspace_bytes, long* ids_out, float* logp_out, void* stream);
+/* Scheduled sampling (Bengio et al., 2015): the inputs of a teacher-forced pass with some slots holding the model's own draw.
+ * st_sample_mix_rows: st_sample_rows' draw (same rule, same routes, same u) and the mix in one launch, without a finished state
+ *   (the caption decides a row's length).  Row r is REPLACED iff step < lens[r] and coin[r * coin_stride] < p (strict: p = 0
+ *   replaces nothing, p = 1 every valid row; a NaN coin never): the drawn token goes to mixed_out[r * out_stride + t], to cur[r]
+ *   and to ids_out[r * out_stride + t], its log-probability to logp_out, and replaced_out[r * out_stride + t] = 1.  Every other
+ *   row skips the draw: the teacher's token teacher[r * teacher_stride + teacher_col] goes to mixed_out and cur, replaced_out = 0,
+ *   ids_out = -1, logp_out = 0.  `step` is the step the slot feeds, lens [n] int32 on the device; ids_out / logp_out may be NULL.
+ * st_rnn_sched_inputs: the loop of st_rnn_sample following the caption [n][Tcap] instead of free-running, all n rows for
+ *   max_len - 1 steps (max_len = max(lens), given by the caller: nothing is read back): step t's logits decide slot t, which
+ *   feeds step t + 1 and is valid iff t + 1 < lens[r].  coin, u [n][Tcap] fp32.  Outputs, all [n][Tcap] and written in full:
+ *   input_ids (int64; the caption wherever replaced is 0), replaced (bytes), and optionally (NULL: not wanted) drawn (int64, the
+ *   drawn token, -1 where not replaced) and logp (fp32, its log-probability, 0 where not replaced).  Workspace: that of
+ *   st_rnn_sample.  Never any dropout: the roll-in runs the deterministic model, as st_rnn_sample does.
+ * Nothing is allocated or synchronised inside these calls. */
+int st_sample_mix_rows(const float* logits, int ldl, int n, int V, const float* u, int u_stride, float inv_temperature, int top_k,
+                       const float* coin, int coin_stride, float p, const long* teacher, int teacher_stride, long teacher_col,
+                       const int* lens, int step, long* ids_out, float* logp_out, long* mixed_out, uint8_t* replaced_out,
+                       int out_stride, int t, long* cur, void* stream);
+size_t st_rnn_sched_inputs_workspace_bytes(const st_rnn_params* p, int n);
+int st_rnn_sched_inputs(const st_rnn_params* p, const void* feat, int n, const long* caption, int Tcap, const int* lens, int max_len,
+                        const float* coin, const float* u, float prob, float inv_temperature, int top_k, void* workspace,
+                        size_t workspace_bytes, long* input_ids, uint8_t* replaced, long* drawn, float* logp, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Soft-attention decoder (Attention/rnn_attn.py, rnn_attn_LSTM.py; train step Attention/main_attn.py:123-134).
@@ -699,6 +732,14 @@ size_t st_attn_sample_workspace_bytes(const st_attn_params* p, int n);
 int st_attn_sample(const st_attn_params* p, const float* cnn_feature, int n, int steps, long start_id, const float* u,
                    float inv_temperature, int top_k, long end_id, void* workspace, size_t workspace_bytes,
                    long* ids_out, float* logp_out, float* alphas_out, void* stream);
+/* st_rnn_sched_inputs for the attention decoders (the loop of st_attn_sample following the caption): step t feeds slot t, so
+ * step t's logits decide slot t + 1, valid iff t + 1 < lens[r]; slot 0 (<start>) is never replaced.  caption [n][Tcap] and its
+ * transpose caption_T [Tcap][n] (what st_attn_forward takes); coin, u and the outputs as st_rnn_sched_inputs. */
+size_t st_attn_sched_inputs_workspace_bytes(const st_attn_params* p, int n);
+int st_attn_sched_inputs(const st_attn_params* p, const float* cnn_feature, int n, const long* caption, const long* caption_T, int Tcap,
+                         const int* lens, int max_len, const float* coin, const float* u, float prob, float inv_temperature, int top_k,
+                         void* workspace, size_t workspace_bytes, long* input_ids, uint8_t* replaced, long* drawn, float* logp,
+                         void* stream);
 /* beam_search.py:45-97 on the attention decoder for B images, W slots each (1 <= W <= 8, so W*min(W,V) <= 64): initial state
  * h0 = init_h(mean_p feat) (and c0) over all layers, generate = one test-branch step (rnn_attn.py:77-94) from the node's token.
  * Rows are fixed (image, slot) pairs b*W + w.  Records use beam.py's layout: rec_tok/rec_cost/rec_par [max_length+1][B][W]

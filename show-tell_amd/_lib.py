@@ -182,6 +182,9 @@ _SIGS = {
                                   c_i),
     "st_rnn_backward_drop": ([C.POINTER(RnnParams), C.POINTER(RnnGrads), C.POINTER(PackedSeq), c_p, c_p, c_i, c_p, c_p, C.c_size_t,
                               c_p, c_p, c_p, c_p], c_i),
+    "st_rnn_forward_ids": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, c_p, c_p, C.c_size_t, c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_p], c_i),
+    "st_rnn_backward_ids": ([C.POINTER(RnnParams), C.POINTER(RnnGrads), C.POINTER(PackedSeq), c_p, c_p, c_i, c_p, c_p, C.c_size_t,
+                             c_p, c_p, c_p, c_p, c_p], c_i),
     "st_rnn_greedy_workspace_bytes": ([C.POINTER(RnnParams), c_i], C.c_size_t),
     "st_rnn_greedy": ([C.POINTER(RnnParams), c_p, c_i, c_i, c_p, C.c_size_t, c_p, c_p, c_p], c_i),
     "st_rnn_greedy_last_route": ([], c_i),
@@ -193,6 +196,11 @@ _SIGS = {
     "st_sample_rows": ([c_p, c_i, c_i, c_i, c_p, c_i, c_f, c_i, c_l, c_p, c_p, c_p, c_i, c_i, c_p, c_p], c_i),
     "st_rnn_sample_workspace_bytes": ([C.POINTER(RnnParams), c_i], C.c_size_t),
     "st_rnn_sample": ([C.POINTER(RnnParams), c_p, c_i, c_i, c_p, c_f, c_i, c_l, c_p, C.c_size_t, c_p, c_p, c_p], c_i),
+    "st_sample_mix_rows": ([c_p, c_i, c_i, c_i, c_p, c_i, c_f, c_i, c_p, c_i, c_f, c_p, c_i, c_l, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p,
+                            c_p], c_i),
+    "st_rnn_sched_inputs_workspace_bytes": ([C.POINTER(RnnParams), c_i], C.c_size_t),
+    "st_rnn_sched_inputs": ([C.POINTER(RnnParams), c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_f, c_f, c_i, c_p, C.c_size_t, c_p, c_p, c_p, c_p,
+                             c_p], c_i),
     "st_attn_workspace_bytes": ([c_p, c_p], C.c_size_t),
     "st_attn_forward": ([c_p, c_p, c_p, c_p, c_p, C.c_size_t, c_p, c_i, c_i, c_p, c_i, c_p], c_i),
     "st_attn_backward": ([c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_f, c_p, c_p, C.c_size_t, c_p], c_i),
@@ -205,6 +213,8 @@ _SIGS = {
     "st_attn_greedy_alphas": ([c_p, c_p, c_i, c_i, c_l, c_p, C.c_size_t, c_p, c_p, c_p], c_i),
     "st_attn_sample_workspace_bytes": ([c_p, c_i], C.c_size_t),
     "st_attn_sample": ([c_p, c_p, c_i, c_i, c_l, c_p, c_f, c_i, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p], c_i),
+    "st_attn_sched_inputs_workspace_bytes": ([c_p, c_i], C.c_size_t),
+    "st_attn_sched_inputs": ([c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_f, c_f, c_i, c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p], c_i),
     "st_attn_beam_workspace_bytes": ([c_p, c_i, c_i], C.c_size_t),
     "st_attn_beam_search": ([c_p, c_p, c_i, c_i, c_i, c_l, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p, c_p], c_i),
     "st_cross_entropy": ([c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_f, c_p, c_p], c_i),

@@ -391,13 +391,18 @@ extern "C" size_t st_attn_greedy_workspace_bytes(const st_attn_params* p, int B)
 namespace {
 // how a step turns its logits into the next token: NULL = arg-max (rnn_attn.py:141), else a draw by st_sample_rows
 struct SampleSpec { const float* u; float inv_temperature; int top_k; long end_id; float* logp_out; };
+// scheduled sampling's roll-in (st_attn_sched_inputs): step 0 reads the captions' first column, step t's logits decide slot t + 1 by
+// st_sample_mix_rows, which also hands the next step its token
+struct MixSpec { const long* caption_T; int Tcap; const int* lens; const float* coin; const float* u; float prob, inv_temperature; int top_k;
+                 long* input_ids; uint8_t* replaced; long* drawn; float* logp; };
 
 // rnn_attn.py:120-145; alphas_out [B][steps][P] keeps every step's attention map (else it goes to a scratch row).
 // The greedy and the sampling searches share this loop; sampling keeps its per-row finished bytes behind the greedy plan.
 int attn_greedy_run(const st_attn_params* p, const float* cnn_feature, int B, int steps, long start_id, void* workspace,
-                    size_t workspace_bytes, long* ids_out, float* alphas_out, void* stream, const char* who, const SampleSpec* sp = nullptr) {
+                    size_t workspace_bytes, long* ids_out, float* alphas_out, void* stream, const char* who, const SampleSpec* sp = nullptr,
+                    const MixSpec* mix = nullptr) {
   if (check_common(p, nullptr, who)) return 1;
-  ST_CHECK(cnn_feature && workspace && ids_out && B > 0 && steps > 0, "%s: bad arguments", who);
+  ST_CHECK(cnn_feature && workspace && (ids_out || mix) && B > 0 && steps > 0, "%s: bad arguments", who);
   const st_rnn_params& r = p->rnn;
   ST_CHECK(r.w_lin && r.b_lin, "%s: null vocabulary projection", who);
   const GPlan q = make_gplan(p, B);
@@ -413,8 +418,10 @@ int attn_greedy_run(const st_attn_params* p, const float* cnn_feature, int B, in
   if (r.cell == ST_CELL_LSTM && replicate_rows_launch(ws + q.c0, ws + q.c[0], (long)B * H, L, dt, st)) return 1;
   long* cur = reinterpret_cast<long*>(ws + q.ids);
   float* alpha_scratch = reinterpret_cast<float*>(ws + q.ids + (size_t)B * sizeof(long));
-  hipLaunchKernelGGL(fill_ids_kernel, dim3((B + 255) / 256), dim3(256), 0, st, cur, B, start_id);
-  ST_LAUNCH_CHECK();
+  if (!mix) {
+    hipLaunchKernelGGL(fill_ids_kernel, dim3((B + 255) / 256), dim3(256), 0, st, cur, B, start_id);
+    ST_LAUNCH_CHECK();
+  }
   float* att2 = reinterpret_cast<float*>(ws + q.att2);
   float* logits = reinterpret_cast<float*>(ws + q.logits);
   int c = 0;
@@ -425,10 +432,14 @@ int attn_greedy_run(const st_attn_params* p, const float* cnn_feature, int B, in
     const long alpha_stride = alphas_out ? (long)steps * P : (long)P;
     if (skinny(htop, H, p->w_dec, H, att2, A, B, A, H, p->b_dec, 0, dt, st)) return 1;
     if (attn_fwd_launch(ws + q.att1, att2, p->w_full, p->b_full, ws + q.feat, alpha_t, alpha_stride, ws + q.z, B, P, A, F, dt, st)) return 1;
-    if (st_embedding_rows(r.emb, cur, ws + q.x, B, E, r.V, 2 * E, dt, stream)) return 1;
+    if (st_embedding_rows(r.emb, mix && t == 0 ? mix->caption_T : cur, ws + q.x, B, E, r.V, 2 * E, dt, stream)) return 1;
     if (skinny(ws + q.z, F, p->w_embed, F, ws + q.x + (size_t)E * es, 2 * E, B, E, F, p->b_embed, 0, dt, st, true)) return 1;
     if (st_rnn_step(&r, ws + q.x, B, ws + q.h[c], ws + q.c[c], ws + q.h[nx], ws + q.c[nx], logits, Vp, stream)) return 1;
-    if (sp) {
+    if (mix) {                                     // slot t + 1 of caption_T [Tcap][B]: row stride 1, column offset (t + 1) * B
+      if (st_sample_mix_rows(logits, Vp, B, r.V, mix->u + t + 1, mix->Tcap, mix->inv_temperature, mix->top_k, mix->coin + t + 1, mix->Tcap, mix->prob,
+                             mix->caption_T, 1, (long)(t + 1) * B, mix->lens, t + 1, mix->drawn, mix->logp, mix->input_ids, mix->replaced, mix->Tcap,
+                             t + 1, cur, stream)) return 1;
+    } else if (sp) {
       if (st_sample_rows(logits, Vp, B, r.V, sp->u + t, steps, sp->inv_temperature, sp->top_k, sp->end_id, fin, ids_out, sp->logp_out, steps, t,
                          cur, stream)) return 1;
     } else if (argmax_rows_launch(logits, Vp, B, r.V, ids_out, steps, t, cur, st)) return 1;   // first maximum, like torch.max (rnn_attn.py:141)
@@ -460,6 +471,26 @@ extern "C" int st_attn_sample(const st_attn_params* p, const float* cnn_feature,
   ST_CHECK(u && logp_out, "st_attn_sample: null pointer");
   const SampleSpec sp = {u, inv_temperature, top_k, end_id, logp_out};
   return attn_greedy_run(p, cnn_feature, n, steps, start_id, workspace, workspace_bytes, ids_out, alphas_out, stream, "st_attn_sample", &sp);
+}
+
+// ---- scheduled sampling: the roll-in of the attention decoders (the loop above following the caption) -----------------------------
+extern "C" size_t st_attn_sched_inputs_workspace_bytes(const st_attn_params* p, int n) {
+  if (!p || n <= 0) return 0;
+  return make_gplan(p, n).total;
+}
+
+extern "C" int st_attn_sched_inputs(const st_attn_params* p, const float* cnn_feature, int n, const long* caption, const long* caption_T, int Tcap,
+                                    const int* lens, int max_len, const float* coin, const float* u, float prob, float inv_temperature, int top_k,
+                                    void* workspace, size_t workspace_bytes, long* input_ids, uint8_t* replaced, long* drawn, float* logp,
+                                    void* stream) {
+  ST_CHECK(caption && caption_T && lens && coin && u && input_ids && replaced, "st_attn_sched_inputs: null pointer");
+  ST_CHECK(n > 0 && max_len >= 1 && max_len <= Tcap, "st_attn_sched_inputs: need n > 0 and 1 <= max_len <= Tcap (got %d, %d)", max_len, Tcap);
+  if (st_sched_init_outputs(caption, n, Tcap, input_ids, replaced, drawn, logp, reinterpret_cast<hipStream_t>(stream), "st_attn_sched_inputs"))
+    return 1;
+  if (max_len == 1) return 0;                      // slot 0 (<start>) is never replaced
+  const MixSpec mix = {caption_T, Tcap, lens, coin, u, prob, inv_temperature, top_k, input_ids, replaced, drawn, logp};
+  return attn_greedy_run(p, cnn_feature, n, max_len - 1, 0, workspace, workspace_bytes, nullptr, nullptr, stream, "st_attn_sched_inputs", nullptr,
+                         &mix);
 }
 
 // ---- beam search (beam_search.py:45-97 driven by the test branch rnn_attn.py:77-94) --------------------------------

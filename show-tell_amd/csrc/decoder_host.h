@@ -87,6 +87,20 @@ inline int st_drop_plan(const st_dropout* d, int L, size_t ntok, int H, int dtyp
   return 0;
 }
 
+// scheduled sampling (st_rnn_sched_inputs / st_attn_sched_inputs): input_ids = caption, replaced = 0, drawn = -1, logp = 0 before the roll-in
+inline int st_sched_init_outputs(const long* caption, int n, int Tcap, long* input_ids, uint8_t* replaced, long* drawn, float* logp, hipStream_t st,
+                                 const char* who) {
+  const size_t cells = (size_t)n * Tcap;
+  if (hipMemcpyAsync(input_ids, caption, cells * sizeof(long), hipMemcpyDeviceToDevice, st) != hipSuccess ||
+      hipMemsetAsync(replaced, 0, cells, st) != hipSuccess ||
+      (drawn && hipMemsetAsync(drawn, 0xff, cells * sizeof(long), st) != hipSuccess) ||      // every byte 0xff: -1
+      (logp && hipMemsetAsync(logp, 0, cells * sizeof(float), st) != hipSuccess)) {
+    st_set_error("%s: initialising the outputs failed", who);
+    return 1;
+  }
+  return 0;
+}
+
 // Whole-row arg-max (first maximum, like torch.max(1)) of n rows of fp32 logits -> ids[row * ids_stride + t] and, when cur is
 // given, cur[row]: csrc/decode.hip, argmax_embed_kernel without its embedding gather.
 int argmax_rows_launch(const float* logits, int ldl, int n, int V, long* ids, int ids_stride, int t, long* cur, hipStream_t st);

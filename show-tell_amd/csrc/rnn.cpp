@@ -100,7 +100,7 @@ extern "C" size_t st_rnn_workspace_bytes(const st_rnn_params* p, const st_packed
 namespace {
 int rnn_forward(const st_rnn_params* p, const st_packed_seq* s, const void* x0_override, const void* feat,
                 void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
-                long* targets, int save_for_backward, const st_dropout* drop, void* stream) {
+                long* targets, int save_for_backward, const st_dropout* drop, const long* input_ids, void* stream) {
   if (check_common(p, s, "st_rnn_forward")) return 1;
   DropPlan dp;
   if (st_drop_plan(drop, p->L, s->ntok, p->H, p->dtype, false, "st_rnn_forward", &dp)) return 1;
@@ -116,7 +116,8 @@ int rnn_forward(const st_rnn_params* p, const st_packed_seq* s, const void* x0_o
   const void* x0 = x0_override;
   if (!x0) {
     ST_CHECK(p->in0 == p->E, "st_rnn_forward: in0 != E needs x0_override");
-    if (pack_inputs_launch(feat, p->emb, s->caption, s->Tcap, s->rows_b, s->rows_t, ws + q.x0, targets, n, p->E, p->V, 0, dt, st)) return 1;
+    // input_ids (scheduled sampling): the rows t >= 1 gather emb[input_ids[b][t-1]]; the targets stay the caption's
+    if (pack_inputs_launch(feat, p->emb, s->caption, s->Tcap, s->rows_b, s->rows_t, ws + q.x0, targets, n, p->E, p->V, 0, dt, st, input_ids)) return 1;
     x0 = ws + q.x0;
     if (dp.in && dropout_rows_launch(x0, ws + q.x0, dt, n, p->in0, p->in0, p->in0, dp.kin, kDropSiteInput, 0, st)) return 1;
   }
@@ -165,12 +166,19 @@ int rnn_forward(const st_rnn_params* p, const st_packed_seq* s, const void* x0_o
 extern "C" int st_rnn_forward(const st_rnn_params* p, const st_packed_seq* s, const void* x0_override, const void* feat,
                               void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
                               long* targets, int save_for_backward, void* stream) {
-  return rnn_forward(p, s, x0_override, feat, workspace, workspace_bytes, logits, logits_dtype, ldl, targets, save_for_backward, nullptr, stream);
+  return rnn_forward(p, s, x0_override, feat, workspace, workspace_bytes, logits, logits_dtype, ldl, targets, save_for_backward, nullptr, nullptr, stream);
 }
 extern "C" int st_rnn_forward_drop(const st_rnn_params* p, const st_packed_seq* s, const void* x0_override, const void* feat,
                                    void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
                                    long* targets, int save_for_backward, const st_dropout* drop, void* stream) {
-  return rnn_forward(p, s, x0_override, feat, workspace, workspace_bytes, logits, logits_dtype, ldl, targets, save_for_backward, drop, stream);
+  return rnn_forward(p, s, x0_override, feat, workspace, workspace_bytes, logits, logits_dtype, ldl, targets, save_for_backward, drop, nullptr, stream);
+}
+// input_ids [B][Tcap] (NULL: s->caption): what the layer-0 rows t >= 1 embed, apart from the targets (scheduled sampling)
+extern "C" int st_rnn_forward_ids(const st_rnn_params* p, const st_packed_seq* s, const void* x0_override, const void* feat,
+                                  void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
+                                  long* targets, int save_for_backward, const st_dropout* drop, const long* input_ids, void* stream) {
+  ST_CHECK(!(input_ids && x0_override), "st_rnn_forward_ids: input_ids and x0_override are exclusive");
+  return rnn_forward(p, s, x0_override, feat, workspace, workspace_bytes, logits, logits_dtype, ldl, targets, save_for_backward, drop, input_ids, stream);
 }
 extern "C" size_t st_rnn_dropout_bytes(const st_rnn_params* p, const st_packed_seq* s) {
   if (!p || !s) return 0;
@@ -311,7 +319,7 @@ extern "C" int st_rnn_fused_dlogits_drop(const st_rnn_params* p, const st_packed
 namespace {
 int rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,
                  const void* x0_override, const void* dlogits, int ldd, const float* dy_top_extra,
-                 void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, const st_dropout* drop, void* stream) {
+                 void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, const st_dropout* drop, const long* input_ids, void* stream) {
   if (check_common(p, s, "st_rnn_backward")) return 1;
   ST_CHECK(g && workspace, "st_rnn_backward: null pointer");
   DropPlan dp;
@@ -494,7 +502,7 @@ int rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_
   }
   if (need_dx0 && !x0_override) {
     ST_CHECK(g->emb, "st_rnn_backward: embedding gradient buffer missing");
-    if (embedding_bwd_launch(dx0, s->caption, s->Tcap, s->rows_b, s->rows_t, dfeat, g->emb, n, p->E, p->V, 0, st)) return 1;
+    if (embedding_bwd_launch(dx0, input_ids ? input_ids : s->caption, s->Tcap, s->rows_b, s->rows_t, dfeat, g->emb, n, p->E, p->V, 0, st)) return 1;
   }
   return 0;
 }
@@ -503,12 +511,20 @@ int rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_
 extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,
                                const void* x0_override, const void* dlogits, int ldd, const float* dy_top_extra,
                                void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, void* stream) {
-  return rnn_backward(p, g, s, x0_override, dlogits, ldd, dy_top_extra, workspace, workspace_bytes, dfeat, dx0_out, nullptr, stream);
+  return rnn_backward(p, g, s, x0_override, dlogits, ldd, dy_top_extra, workspace, workspace_bytes, dfeat, dx0_out, nullptr, nullptr, stream);
 }
 // after st_rnn_forward_drop with the same descriptor (its buffer holds the dropped copies the weight gradients read)
 extern "C" int st_rnn_backward_drop(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,
                                     const void* x0_override, const void* dlogits, int ldd, const float* dy_top_extra,
                                     void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, const st_dropout* drop,
                                     void* stream) {
-  return rnn_backward(p, g, s, x0_override, dlogits, ldd, dy_top_extra, workspace, workspace_bytes, dfeat, dx0_out, drop, stream);
+  return rnn_backward(p, g, s, x0_override, dlogits, ldd, dy_top_extra, workspace, workspace_bytes, dfeat, dx0_out, drop, nullptr, stream);
+}
+// after st_rnn_forward_ids with the same input_ids: the embedding gradient scatters to the tokens that were fed
+extern "C" int st_rnn_backward_ids(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,
+                                   const void* x0_override, const void* dlogits, int ldd, const float* dy_top_extra,
+                                   void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, const st_dropout* drop,
+                                   const long* input_ids, void* stream) {
+  ST_CHECK(!(input_ids && x0_override), "st_rnn_backward_ids: input_ids and x0_override are exclusive");
+  return rnn_backward(p, g, s, x0_override, dlogits, ldd, dy_top_extra, workspace, workspace_bytes, dfeat, dx0_out, drop, input_ids, stream);
 }

@@ -110,7 +110,8 @@ int rnn_bwd_fused_launch_batch_drop(const RnnBwdFused* cells, int ncells, int ce
 int dropout_rows_launch(const void* x, void* y, int dtype, int rows, int cols, int ldx, int ldy, const DropKey& key, int site, int row0,
                         hipStream_t st);
 int pack_inputs_launch(const void* feat, const void* emb, const long* cap, int Tcap, const int* rows_b, const int* rows_t,
-                       void* x0, long* target, int ntok, int E, int V, int mode, int dtype, hipStream_t st);
+                       void* x0, long* target, int ntok, int E, int V, int mode, int dtype, hipStream_t st,
+                       const long* ids = nullptr);   // ids [B][Tcap]: what the rows embed when it is not cap (the targets stay cap's)
 int embedding_bwd_launch(const float* dx0, const long* cap, int Tcap, const int* rows_b, const int* rows_t,
                          float* dfeat, float* demb, int ntok, int E, int V, int mode, hipStream_t st);
 int gather_hprev_launch(const void* y, const int* rows_t, const int* prev_row, void* hp, int ntok, int H, int dtype, hipStream_t st,

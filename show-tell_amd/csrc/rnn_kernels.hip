@@ -318,13 +318,14 @@ __global__ __launch_bounds__(256) void rnn_gemm_kernel(RnnGemmBatch batch, typen
 // packed input rows: x0[row(t,b)] = t == 0 ? feat[b] : emb[caption[b][t-1]]   (rnn.py:29-31)
 //                    target[row(t,b)] = caption[b][t]                          (main.py:145)
 // mode 1 (attention decoder, rnn_attn.py:70): x0[row] = emb[caption[b][t]]
+// `ids` ([B][Tcap]; the launcher passes cap when the caller has none) is what the rows embed, `cap` what the targets are
 // ---------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void pack_inputs_kernel(const T* __restrict__ feat, const T* __restrict__ emb,
                                                           const long* __restrict__ cap, int Tcap,
                                                           const int* __restrict__ rows_b, const int* __restrict__ rows_t,
                                                           T* __restrict__ x0, long* __restrict__ target,
-                                                          int ntok, int E, int V, int mode) {
+                                                          int ntok, int E, int V, int mode, const long* __restrict__ ids) {
   constexpr int N = 16 / (int)sizeof(T);
   const int cpr = E / N;
   const long total = (long)ntok * cpr;
@@ -334,7 +335,7 @@ __global__ __launch_bounds__(256) void pack_inputs_kernel(const T* __restrict__ 
     const T* src;
     if (mode == 0 && t == 0) src = feat + (long)b * E + c;
     else {
-      long tok = cap[(long)b * Tcap + (mode == 0 ? t - 1 : t)];
+      long tok = ids[(long)b * Tcap + (mode == 0 ? t - 1 : t)];
       tok = tok < 0 ? 0 : (tok >= V ? V - 1 : tok);   // keep a corrupt id from faulting the GPU
       src = emb + tok * E + c;
     }
@@ -836,13 +837,14 @@ static inline int grid1d(long work, int threads = 256) {
 }
 
 int pack_inputs_launch(const void* feat, const void* emb, const long* cap, int Tcap, const int* rows_b, const int* rows_t,
-                       void* x0, long* target, int ntok, int E, int V, int mode, int dtype, hipStream_t st) {
+                       void* x0, long* target, int ntok, int E, int V, int mode, int dtype, hipStream_t st, const long* ids) {
   if (ntok <= 0) return 0;
+  if (!ids) ids = cap;
   const int n = dtype == ST_BF16 ? 8 : 4;
   ST_CHECK(E % n == 0, "pack_inputs: E=%d must be a multiple of %d", E, n);
   const int grid = grid1d((long)ntok * (E / n));
-  if (dtype == ST_BF16) hipLaunchKernelGGL(pack_inputs_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)feat, (const bf16_t*)emb, cap, Tcap, rows_b, rows_t, (bf16_t*)x0, target, ntok, E, V, mode);
-  else hipLaunchKernelGGL(pack_inputs_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)feat, (const float*)emb, cap, Tcap, rows_b, rows_t, (float*)x0, target, ntok, E, V, mode);
+  if (dtype == ST_BF16) hipLaunchKernelGGL(pack_inputs_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)feat, (const bf16_t*)emb, cap, Tcap, rows_b, rows_t, (bf16_t*)x0, target, ntok, E, V, mode, ids);
+  else hipLaunchKernelGGL(pack_inputs_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)feat, (const float*)emb, cap, Tcap, rows_b, rows_t, (float*)x0, target, ntok, E, V, mode, ids);
   ST_LAUNCH_CHECK();
   return 0;
 }

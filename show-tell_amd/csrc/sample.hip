@@ -64,18 +64,39 @@ struct RowReg {
   }
 };
 
-template <typename Row>
+// What the MIX form (scheduled sampling, st_sample_mix_rows) takes beyond the draw's arguments: the row's slot takes the draw iff the
+// step it feeds is inside the row's caption and its coin fell below p; every other row skips the three passes and keeps the
+// teacher's token.  No finished state there: the caption decides a row's length.
+struct MixArgs {
+  const float* coin; int coin_stride; float p;
+  const long* teacher; int teacher_stride; long teacher_col;
+  const int* lens; int step;
+  long* mixed_out; uint8_t* replaced_out;
+};
+
+template <typename Row, bool MIX = false>
 __global__ __launch_bounds__(kSampleThreads) void sample_rows_kernel(const float* __restrict__ logits, int ldl, int V, const float* __restrict__ u,
                                                                      int u_stride, float inv_t, int top_k, long end_id, uint8_t* __restrict__ finished,
                                                                      long* __restrict__ ids_out, float* __restrict__ logp_out, int out_stride, int t,
-                                                                     long* __restrict__ cur) {
+                                                                     long* __restrict__ cur, MixArgs mix) {
   __shared__ float s_tm[kSampleThreads];
   __shared__ float c_v[kSampleCap]; __shared__ int c_i[kSampleCap];
   __shared__ float s_max[4], s_sum[4], s_bv[4]; __shared__ int s_bi[4], s_last[4], s_first[4];
   __shared__ int s_cnt, s_Ti, s_tok; __shared__ float s_T;
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const long out = (long)row * out_stride + t;
-  if (finished[row]) {                                       // (block-uniform) <pad> after <end>
+  if constexpr (MIX) {
+    // (block-uniform) strict comparison: p = 0 takes nothing, a NaN coin never
+    if (!(mix.step < mix.lens[row] && mix.coin[(long)row * mix.coin_stride] < mix.p)) {
+      if (tid == 0) {
+        const long tk = mix.teacher[(long)row * mix.teacher_stride + mix.teacher_col];
+        mix.mixed_out[out] = tk; cur[row] = tk; mix.replaced_out[out] = 0;
+        if (ids_out) ids_out[out] = -1;
+        if (logp_out) logp_out[out] = 0.f;
+      }
+      return;
+    }
+  } else if (finished[row]) {                                // (block-uniform) <pad> after <end>
     if (tid == 0) { ids_out[out] = 0; logp_out[out] = 0.f; if (cur) cur[row] = 0; }
     return;
   }
@@ -171,10 +192,16 @@ __global__ __launch_bounds__(kSampleThreads) void sample_rows_kernel(const float
   if (tid == 0) {
     int tok = s_tok;
     if (tok < 0 || tok >= V) tok = 0;                        // a row without a finite entry: keep the index in range (logp is NaN)
-    ids_out[out] = tok;
-    logp_out[out] = (l[tok] - M) * inv_t - logf(S);
-    if (cur) cur[row] = tok;
-    if (tok == end_id) finished[row] = 1;
+    if constexpr (MIX) {
+      mix.mixed_out[out] = tok; cur[row] = tok; mix.replaced_out[out] = 1;
+      if (ids_out) ids_out[out] = tok;
+      if (logp_out) logp_out[out] = (l[tok] - M) * inv_t - logf(S);
+    } else {
+      ids_out[out] = tok;
+      logp_out[out] = (l[tok] - M) * inv_t - logf(S);
+      if (cur) cur[row] = tok;
+      if (tok == end_id) finished[row] = 1;
+    }
   }
 }
 
@@ -193,13 +220,42 @@ extern "C" int st_sample_rows(const float* logits, int ldl, int n, int V, const 
   const bool regs = vec && V <= kSampleThreads * kSampleRegs;       // the kernel's chunk = V / 256 rounded up to 4 fits kSampleRegs
   if (regs)
     hipLaunchKernelGGL(sample_rows_kernel<RowReg>, dim3(n), dim3(kSampleThreads), 0, st, logits, ldl, V, u, u_stride, inv_temperature, top_k, end_id,
-                       finished, ids_out, logp_out, out_stride, t, cur);
+                       finished, ids_out, logp_out, out_stride, t, cur, MixArgs{});
   else if (vec)
     hipLaunchKernelGGL(sample_rows_kernel<RowMem<true>>, dim3(n), dim3(kSampleThreads), 0, st, logits, ldl, V, u, u_stride, inv_temperature, top_k, end_id,
-                       finished, ids_out, logp_out, out_stride, t, cur);
+                       finished, ids_out, logp_out, out_stride, t, cur, MixArgs{});
   else
     hipLaunchKernelGGL(sample_rows_kernel<RowMem<false>>, dim3(n), dim3(kSampleThreads), 0, st, logits, ldl, V, u, u_stride, inv_temperature, top_k, end_id,
-                       finished, ids_out, logp_out, out_stride, t, cur);
+                       finished, ids_out, logp_out, out_stride, t, cur, MixArgs{});
+  ST_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int st_sample_mix_rows(const float* logits, int ldl, int n, int V, const float* u, int u_stride, float inv_temperature, int top_k,
+                                  const float* coin, int coin_stride, float p, const long* teacher, int teacher_stride, long teacher_col,
+                                  const int* lens, int step, long* ids_out, float* logp_out, long* mixed_out, uint8_t* replaced_out,
+                                  int out_stride, int t, long* cur, void* stream) {
+  ST_CHECK(logits && u && coin && teacher && lens && mixed_out && replaced_out && cur, "st_sample_mix_rows: null pointer");
+  ST_CHECK(V >= 1 && ldl >= V, "st_sample_mix_rows: need 1 <= V <= ldl (got V=%d ldl=%d)", V, ldl);
+  ST_CHECK(inv_temperature > 0.f, "st_sample_mix_rows: inv_temperature must be > 0");
+  ST_CHECK(top_k >= 0 && top_k <= 32 && top_k <= V, "st_sample_mix_rows: need 0 <= top_k <= min(32, V) (got %d)", top_k);
+  ST_CHECK(p >= 0.f && p <= 1.f, "st_sample_mix_rows: p=%g outside [0, 1]", (double)p);
+  ST_CHECK(t >= 0 && t < out_stride && u_stride >= 0 && coin_stride >= 0, "st_sample_mix_rows: bad output column %d of %d", t, out_stride);
+  ST_CHECK(teacher_stride >= 0 && teacher_col >= 0 && step >= 0, "st_sample_mix_rows: bad teacher column or step");
+  if (n <= 0) return 0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const bool vec = ldl % 4 == 0 && reinterpret_cast<uintptr_t>(logits) % 16 == 0;
+  const bool regs = vec && V <= kSampleThreads * kSampleRegs;       // the routes of st_sample_rows
+  const MixArgs mix = {coin, coin_stride, p, teacher, teacher_stride, teacher_col, lens, step, mixed_out, replaced_out};
+  if (regs)
+    hipLaunchKernelGGL((sample_rows_kernel<RowReg, true>), dim3(n), dim3(kSampleThreads), 0, st, logits, ldl, V, u, u_stride, inv_temperature, top_k, 0L,
+                       (uint8_t*)nullptr, ids_out, logp_out, out_stride, t, cur, mix);
+  else if (vec)
+    hipLaunchKernelGGL((sample_rows_kernel<RowMem<true>, true>), dim3(n), dim3(kSampleThreads), 0, st, logits, ldl, V, u, u_stride, inv_temperature, top_k,
+                       0L, (uint8_t*)nullptr, ids_out, logp_out, out_stride, t, cur, mix);
+  else
+    hipLaunchKernelGGL((sample_rows_kernel<RowMem<false>, true>), dim3(n), dim3(kSampleThreads), 0, st, logits, ldl, V, u, u_stride, inv_temperature, top_k,
+                       0L, (uint8_t*)nullptr, ids_out, logp_out, out_stride, t, cur, mix);
   ST_LAUNCH_CHECK();
   return 0;
 }
@@ -250,6 +306,38 @@ extern "C" int st_rnn_sample(const st_rnn_params* p, const void* feat, int n, in
                     lstm ? ws + q.c[nx] : nullptr, logits, Vp, stream)) return 1;
     if (st_sample_rows(logits, Vp, n, p->V, u + t, steps, inv_temperature, top_k, end_id, fin, ids_out, logp_out, steps, t, cur, stream)) return 1;
     if (t + 1 < steps && st_embedding_rows(p->emb, cur, ws + q.x, n, p->E, p->V, p->E, p->dtype, stream)) return 1;
+    c = nx;
+  }
+  return 0;
+}
+
+// ---- scheduled sampling: the roll-in of the plain decoders (the loop above, following the caption instead of free-running) ----
+extern "C" size_t st_rnn_sched_inputs_workspace_bytes(const st_rnn_params* p, int n) { return st_rnn_sample_workspace_bytes(p, n); }
+
+extern "C" int st_rnn_sched_inputs(const st_rnn_params* p, const void* feat, int n, const long* caption, int Tcap, const int* lens, int max_len,
+                                   const float* coin, const float* u, float prob, float inv_temperature, int top_k, void* workspace,
+                                   size_t workspace_bytes, long* input_ids, uint8_t* replaced, long* drawn, float* logp, void* stream) {
+  ST_CHECK(p && feat && caption && lens && coin && u && workspace && input_ids && replaced, "st_rnn_sched_inputs: null pointer");
+  ST_CHECK(n > 0 && max_len >= 1 && max_len <= Tcap, "st_rnn_sched_inputs: need n > 0 and 1 <= max_len <= Tcap (got %d, %d)", max_len, Tcap);
+  ST_CHECK(p->L >= 1 && p->L <= ST_MAX_LAYERS && p->in0 == p->E, "st_rnn_sched_inputs: bad decoder configuration");
+  ST_CHECK(p->emb && p->w_lin && p->b_lin, "st_rnn_sched_inputs: null weights");
+  const SPlan q = make_splan(p, n);
+  ST_CHECK(workspace_bytes >= q.total, "st_rnn_sched_inputs: workspace too small");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  char* ws = reinterpret_cast<char*>(workspace);
+  const bool lstm = p->cell == ST_CELL_LSTM;
+  const int Vp = st_up8(p->V);
+  float* logits = reinterpret_cast<float*>(ws + q.logits);
+  long* cur = reinterpret_cast<long*>(ws + q.cur);
+  if (st_sched_init_outputs(caption, n, Tcap, input_ids, replaced, drawn, logp, st, "st_rnn_sched_inputs")) return 1;
+  int c = 0;
+  for (int t = 0; t + 1 < max_len; ++t) {           // step t's logits decide slot t, which feeds step t + 1; the last step's are never fed
+    const int nx = c ^ 1;
+    if (st_rnn_step(p, t == 0 ? feat : ws + q.x, n, t == 0 ? nullptr : ws + q.h[c], (t == 0 || !lstm) ? nullptr : ws + q.c[c], ws + q.h[nx],
+                    lstm ? ws + q.c[nx] : nullptr, logits, Vp, stream)) return 1;
+    if (st_sample_mix_rows(logits, Vp, n, p->V, u + t, Tcap, inv_temperature, top_k, coin + t, Tcap, prob, caption, Tcap, t, lens, t + 1, drawn,
+                           logp, input_ids, replaced, Tcap, t, cur, stream)) return 1;
+    if (t + 2 < max_len && st_embedding_rows(p->emb, cur, ws + q.x, n, p->E, p->V, p->E, p->dtype, stream)) return 1;
     c = nx;
   }
   return 0;

@@ -11,6 +11,8 @@ Same constructor, same attribute names (``embeddings``, ``unit``, ``linear``) an
     loss   = rnn.loss(cnn_feature, image_caption, caption_size, label_smoothing=0.1)         # CrossEntropyLoss(label_smoothing=0.1)
     logp   = rnn.token_logp(cnn_feature, image_caption, caption_size)                        # (B, T) log p of every given token
     rnn    = RNN(E, H, V, L, dropout=0.3, dropout_out=0.5); rnn.train() / rnn.eval()         # nn.GRU(dropout=) + Dropout before linear
+    ids, replaced = rnn.scheduled_inputs(cnn_feature, image_caption, caption_size, p=0.25)    # scheduled sampling's roll-in
+    loss   = rnn.loss(cnn_feature, image_caption, caption_size, input_ids=ids)                # ... or scheduled_sampling=0.25
 
 ``nn.Embedding`` / ``nn.GRU`` / ``nn.Linear`` objects are parameter containers only; all
 arithmetic runs in libshowtell_hip (st_rnn_forward / st_rnn_backward / st_rnn_greedy /
@@ -104,6 +106,67 @@ def check_caption_args(caption, lens):
         raise ValueError(f"caption_size must hold {caption.shape[0]} lengths of at most {caption.shape[1]}")
 
 
+def check_probability(p, name="p"):
+    """Argument error of a scheduled-sampling rate (both decoders and the Trainer): a number in [0, 1] (NaN is refused).  Returns it
+    as a float."""
+    try:
+        q = float(p)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a number in [0, 1] (got {p!r})") from None
+    if not 0.0 <= q <= 1.0:
+        raise ValueError(f"{name} must be in [0, 1] (got {p!r})")
+    return q
+
+
+def check_scheduled_args(vocab_size, feat, caption, lens, p, temperature, top_k, uniforms):
+    """Argument errors of ``scheduled_inputs`` (both decoders), raised before anything touches the device.  Returns p as a float."""
+    check_caption_args(caption, lens)
+    if min(int(l) for l in lens) < 1:
+        raise ValueError("caption_size must hold lengths of at least 1")
+    if feat.shape[0] != caption.shape[0]:
+        raise ValueError(f"cnn_feature holds {feat.shape[0]} images, image_caption {caption.shape[0]} captions")
+    q = check_probability(p)
+    if not temperature > 0:
+        raise ValueError(f"temperature must be > 0 (got {temperature})")
+    if int(top_k) != top_k or not 0 <= top_k <= min(32, vocab_size):
+        raise ValueError(f"top_k must be 0 (the whole vocabulary) or 1..{min(32, vocab_size)} (got {top_k})")
+    if uniforms is not None:
+        want = (2,) + tuple(caption.shape)
+        if not torch.is_tensor(uniforms) or tuple(uniforms.shape) != want or uniforms.dtype != torch.float32:
+            raise ValueError(f"uniforms must be a float32 tensor of shape {want} (coins and draws; images; slots)")
+        if uniforms.device != caption.device:
+            raise ValueError(f"uniforms must be on the captions' device {caption.device} (got {uniforms.device})")
+    return q
+
+
+def check_input_ids(input_ids, caption, vocab_size):
+    """Argument errors of `input_ids` (both decoders), raised before any kernel runs: an int64 tensor of the caption tensor's shape
+    and device with every id in [0, vocab_size).  The range check reads the tensor (one synchronisation when it lives on the
+    device); ``loss(.., scheduled_sampling=p)`` feeds the roll-in's own ids and skips it."""
+    if not torch.is_tensor(caption) or caption.dim() != 2 or caption.dtype != torch.int64:
+        raise ValueError("image_caption must be a (B, T) LongTensor")
+    if not torch.is_tensor(input_ids) or input_ids.dtype != torch.int64 or tuple(input_ids.shape) != tuple(caption.shape):
+        raise ValueError(f"input_ids must be a LongTensor of the captions' shape {tuple(caption.shape)}")
+    if input_ids.device != caption.device:
+        raise ValueError(f"input_ids must be on the captions' device {caption.device} (got {input_ids.device})")
+    if input_ids.numel() and not bool(((input_ids >= 0) & (input_ids < vocab_size)).all()):
+        raise ValueError(f"input_ids must lie in [0, {vocab_size})")
+
+
+def scheduled_loss_inputs(module, feat, caption, lens, input_ids, scheduled_sampling, temperature, top_k, generator, uniforms):
+    """The `input_ids` a ``loss`` call trains on: the caller's (checked), the roll-in's for scheduled_sampling = p > 0, or None
+    (p = 0: no roll-in, the plain call).  Argument errors are raised before anything touches the device."""
+    p = check_probability(scheduled_sampling, "scheduled_sampling")
+    if input_ids is not None:
+        if p:
+            raise ValueError("input_ids and scheduled_sampling are exclusive")
+        check_input_ids(input_ids, caption, module.vocab_size)
+        return input_ids
+    if not p:
+        return None
+    return module.scheduled_inputs(feat, caption, lens, p, temperature, top_k, generator, uniforms)[0]
+
+
 def pack_row_weights(plan, sequence_weight, token_weight, device):
     """The weight of every packed row (t, b) as the kernels read it: sequence_weight[b] * token_weight[b, t], fp32 (ntok,) on
     `device`, gathered there with the plan's row map; None when neither is given.  Constants of the loss: detached."""
@@ -176,7 +239,7 @@ class _DecoderFn(torch.autograd.Function):
     rows' -log p(target) (no gradient)."""
 
     @staticmethod
-    def forward(ctx, feat, _anchor, module, caption, lens, mode, need_grad, sequence_weight, token_weight, eps=0.0):
+    def forward(ctx, feat, _anchor, module, caption, lens, mode, need_grad, sequence_weight, token_weight, eps=0.0, input_ids=None):
         m = module
         dev = feat.device
         if not feat.is_cuda or not m.linear.weight.is_cuda:
@@ -203,12 +266,19 @@ class _DecoderFn(torch.autograd.Function):
         drop = dbuf = None
         if took is not None:
             drop, dbuf = m._dropout.desc(took, lib().st_rnn_dropout_bytes(C.byref(prm), C.byref(seq)), dev)
+        # input_ids (scheduled sampling): the rows embed them, the targets stay the caption's; None is the call it was
+        ids = None if input_ids is None else input_ids.detach().contiguous()
+        if ids is not None:
+            check(lib().st_rnn_forward_ids(C.byref(prm), C.byref(seq), None, _cp(featd), _cp(ws), nbytes, _cp(logits), dtype_code(ldt), Vp,
+                                           _cp(targets), int(need_grad), C.byref(drop) if drop is not None else None, _cp(ids), _stream()),
+                  "st_rnn_forward_ids")
+        elif took is not None:
             check(lib().st_rnn_forward_drop(C.byref(prm), C.byref(seq), None, _cp(featd), _cp(ws), nbytes, _cp(logits), dtype_code(ldt), Vp,
                                             _cp(targets), int(need_grad), C.byref(drop), _stream()), "st_rnn_forward_drop")
         else:
             check(lib().st_rnn_forward(C.byref(prm), C.byref(seq), None, _cp(featd), _cp(ws), nbytes, _cp(logits), dtype_code(ldt), Vp,
                                        _cp(targets), int(need_grad), _stream()), "st_rnn_forward")
-        ctx.drop, ctx.dbuf = drop, dbuf
+        ctx.drop, ctx.dbuf, ctx.ids = drop, dbuf, ids
         ctx.m, ctx.plan, ctx.caption, ctx.ws, ctx.mode, ctx.keep = m, plan, caption, ws, mode, keep
         ctx.feat_dtype = feat.dtype
         ctx.fused, ctx.roww, ctx.eps = fused, roww, eps
@@ -279,14 +349,18 @@ class _DecoderFn(torch.autograd.Function):
             dlog, gsc = ce_loss_backward(ctx.logits, dt, ctx.targets, n, V, Vp, gout, ctx.roww, ctx.eps)
         grads, keep2 = m._c_grads()
         dfeat = torch.empty(plan.B, m.embed_dim, device=dev, dtype=torch.float32)
-        if ctx.drop is not None:
+        if ctx.ids is not None:
+            check(lib().st_rnn_backward_ids(C.byref(prm), C.byref(grads), C.byref(seq), None, _cp(dlog), Vp, None, _cp(ctx.ws),
+                                            ctx.ws.numel(), _cp(dfeat), None, C.byref(ctx.drop) if ctx.drop is not None else None,
+                                            _cp(ctx.ids), _stream()), "st_rnn_backward_ids")
+        elif ctx.drop is not None:
             check(lib().st_rnn_backward_drop(C.byref(prm), C.byref(grads), C.byref(seq), None, _cp(dlog), Vp, None, _cp(ctx.ws),
                                              ctx.ws.numel(), _cp(dfeat), None, C.byref(ctx.drop), _stream()), "st_rnn_backward_drop")
         else:
             check(lib().st_rnn_backward(C.byref(prm), C.byref(grads), C.byref(seq), None, _cp(dlog), Vp, None, _cp(ctx.ws),
                                         ctx.ws.numel(), _cp(dfeat), None, _stream()), "st_rnn_backward")
         ctx.ws = ctx.dbuf = None
-        return dfeat.to(ctx.feat_dtype), None, None, None, None, None, None, None, None, None
+        return dfeat.to(ctx.feat_dtype), None, None, None, None, None, None, None, None, None, None
 
 
 class Decoder(FollowsMoves, nn.Module):
@@ -350,6 +424,36 @@ class Decoder(FollowsMoves, nn.Module):
         check_sample_args(self.vocab_size, B, num_samples, temperature, top_k, max_length, uniforms)
         return B, int(num_samples), int(max_length)
 
+    def scheduled_inputs(self, cnn_feature, image_caption, caption_size, p, temperature=1.0, top_k=0, generator=None, uniforms=None):
+        """Scheduled sampling's roll-in (Bengio et al., 2015): a copy of `image_caption` in which some slots hold the model's own
+        prediction, for ``forward / loss / token_logp(.., input_ids=)``.  Returns (input_ids (B, T) int64, replaced (B, T) bool).
+
+        A slot is replaced iff the packed forward reads it (the step it feeds is < caption_size[b]) and coin[b, j] < p -- strict,
+        so p = 0 replaces nothing and p = 1 every valid slot; every other slot keeps the caption's value.  RNN (GRU, LSTM): slot j
+        feeds step j + 1 and takes a token drawn from step j's logits.  RNN_Attn: slot j feeds step j and, for j >= 1, takes a token
+        drawn from step j - 1's logits; slot 0 (<start>) is never replaced.  The draw is that of ``sample`` (`temperature`,
+        `top_k` <= 32, top_k = 1 the arg-max) on draw_u[b, j], from logits conditioned on the mixed prefix so far: true sequential
+        scheduled sampling in one call (st_rnn_sched_inputs / st_attn_sched_inputs), no host round trip per token.  The randomness
+        is `uniforms` (2, B, T) fp32 in [0, 1) on the device, [0] the coins and [1] the draws, or torch.rand from `generator`.
+
+        No gradient flows through the choice (the call runs under no_grad) and the targets stay the caption.  The roll-in never
+        applies dropout, as ``sample`` does not: it runs the deterministic model, train() or not; the training pass that follows
+        applies dropout as usual."""
+        q = check_scheduled_args(self.vocab_size, cnn_feature, image_caption, caption_size, p, temperature, top_k, uniforms)
+        if not cnn_feature.is_cuda or not image_caption.is_cuda:
+            raise _lib.ShowTellHipError("cnn_feature and image_caption must be on the HIP device (no CPU fallback)")
+        with torch.no_grad():
+            dev = cnn_feature.device
+            cap = image_caption.contiguous()
+            B, T = cap.shape
+            u = sample_uniforms(uniforms, (2, B, T), dev, generator)
+            lens = torch.tensor([int(l) for l in caption_size], dtype=torch.int32).to(dev, non_blocking=True)
+            ids = torch.empty_like(cap)
+            replaced = torch.empty(B, T, device=dev, dtype=torch.uint8)
+            self._sched_inputs(cnn_feature, cap, lens, max(int(l) for l in caption_size), u, q, 1.0 / float(temperature), int(top_k), ids,
+                               replaced)
+            return ids, replaced.bool()
+
     @staticmethod
     def _sample_buffers(feat, B, S, T, uniforms, generator):
         """`feat` repeated for the S draws of every image (row b * S + s), n = B * S, and the per-row buffers of a ``sample``
@@ -407,12 +511,27 @@ class RNN(Decoder):
         return g, keep
 
     # ---- reference surface -------------------------------------------------------------
-    def forward(self, cnn_feature, image_caption, caption_size):
-        """rnn.py:27-35: teacher-forced logits over the packed sequence, (N_tok, V) fp32.  In train() with a dropout site on, one
-        step of the masks is applied (see __init__)."""
-        return _DecoderFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "logits", torch.is_grad_enabled(), None, None)
+    def _sched_inputs(self, cnn_feature, cap, lens, max_len, u, p, inv_t, top_k, ids, replaced):
+        prm, keep = self._c_params()
+        feat = self._feature(cnn_feature)
+        B, T = cap.shape
+        nbytes = lib().st_rnn_sched_inputs_workspace_bytes(C.byref(prm), B)
+        ws = torch.empty(nbytes, device=feat.device, dtype=torch.uint8)
+        check(lib().st_rnn_sched_inputs(C.byref(prm), _cp(feat), B, _cp(cap), T, _cp(lens), max_len, _cp(u[0]), _cp(u[1]), p, inv_t, top_k,
+                                        _cp(ws), nbytes, _cp(ids), _cp(replaced), None, None, _stream()), "st_rnn_sched_inputs")
 
-    def loss(self, cnn_feature, image_caption, caption_size, sequence_weight=None, token_weight=None, label_smoothing=0.0):
+    def forward(self, cnn_feature, image_caption, caption_size, input_ids=None):
+        """rnn.py:27-35: teacher-forced logits over the packed sequence, (N_tok, V) fp32.  In train() with a dropout site on, one
+        step of the masks is applied (see __init__).  `input_ids` (B, T) int64 (``scheduled_inputs``): the tokens the steps
+        t >= 1 embed, input_ids[b, t - 1], in place of the caption's; None is the call it was."""
+        if input_ids is None:
+            return _DecoderFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "logits", torch.is_grad_enabled(), None, None)
+        check_input_ids(input_ids, image_caption, self.vocab_size)
+        return _DecoderFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "logits", torch.is_grad_enabled(), None, None,
+                                0.0, input_ids)
+
+    def loss(self, cnn_feature, image_caption, caption_size, sequence_weight=None, token_weight=None, label_smoothing=0.0, input_ids=None,
+             scheduled_sampling=0.0, ss_temperature=1.0, ss_top_k=0, ss_generator=None, ss_uniforms=None):
         """main.py:145-149 fused: CrossEntropyLoss()(rnn(feat, cap, lens), packed(cap)) as one scalar.
 
         With `sequence_weight` (B,) and / or `token_weight` (B, T) (float tensors, signed, T the caption tensor's width; both:
@@ -424,24 +543,34 @@ class RNN(Decoder):
         (1 - eps) * nll + eps * (logsumexp(x) - mean(x)), times its weight where weights are given (the divisor stays N_tok).  The
         rows' mean logit is formed inside the loss kernels too; with eps = 0 the call is the one it was.
 
-        In train() with a dropout site on (see __init__) the loss is that of one draw of the masks; eval() is deterministic."""
+        In train() with a dropout site on (see __init__) the loss is that of one draw of the masks; eval() is deterministic.
+
+        `input_ids` (B, T) int64: the tokens the steps t >= 1 embed in place of the caption's (``scheduled_inputs``); the targets
+        stay the caption and the embedding gradient goes to the tokens that were fed.  It combines with weights, label smoothing
+        and dropout; None is the call it was.  `scheduled_sampling` = p in [0, 1] is the two-step convenience:
+        ``scheduled_inputs(.., p, ss_temperature, ss_top_k, ss_generator, ss_uniforms)`` and then this loss on its ids; p = 0 runs
+        no roll-in at all.  The roll-in runs the deterministic model (no dropout); this pass applies dropout as usual."""
         eps = check_label_smoothing(label_smoothing)
-        if sequence_weight is None and token_weight is None and not eps:
+        input_ids = scheduled_loss_inputs(self, cnn_feature, image_caption, caption_size, input_ids, scheduled_sampling, ss_temperature,
+                                          ss_top_k, ss_generator, ss_uniforms)
+        if sequence_weight is None and token_weight is None and not eps and input_ids is None:
             return _DecoderFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "loss", torch.is_grad_enabled(),
                                     None, None)
         check_caption_args(image_caption, caption_size)
         check_weight_args(image_caption.shape[0], image_caption.shape[1], sequence_weight, token_weight)
         return _DecoderFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "loss", torch.is_grad_enabled(),
-                                sequence_weight, token_weight, eps)
+                                sequence_weight, token_weight, eps, input_ids)
 
-    def token_logp(self, cnn_feature, image_caption, caption_size):
+    def token_logp(self, cnn_feature, image_caption, caption_size, input_ids=None):
         """log p(image_caption[b, t] | image b, image_caption[b, :t]) for every token of the given captions: (B, T) fp32, T the
         caption tensor's width, 0 past caption_size[b].  No gradient, and never any dropout (train() or not: it scores the model).  -token_logp.sum() / N_tok is loss(); with the output of
         ``sample`` as captions it scores what that call's `logp` scored (at temperature 1, top_k 0; the two passes round differently).  On the fused route (bf16,
-        H = 512) the vocabulary projection runs tile by tile: there is no logits tensor."""
+        H = 512) the vocabulary projection runs tile by tile: there is no logits tensor.  `input_ids`: as in ``forward``."""
         check_caption_args(image_caption, caption_size)
+        if input_ids is not None:
+            check_input_ids(input_ids, image_caption, self.vocab_size)
         with torch.no_grad():
-            nll = _DecoderFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "nll", False, None, None)
+            nll = _DecoderFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "nll", False, None, None, 0.0, input_ids)
             return unpack_rows(plan_for(caption_size, nll.device), -nll, image_caption.shape[1], nll.device)
 
     def beam_search(self, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50, start_id=1, end_id=2):

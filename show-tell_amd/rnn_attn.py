@@ -25,8 +25,8 @@ import torch.nn as nn
 from . import _lib
 from ._lib import AttnGrads, AttnParams, check, dtype_code, lib
 from ._lib import ptr as _cp, stream as _stream
-from .rnn import (CAP_MAX, Decoder, ce_loss, ce_loss_backward, check_caption_args, check_label_smoothing, check_weight_args, logits_grad,
-                  pack_row_weights, sample_lengths, unpack_rows, up8)
+from .rnn import (CAP_MAX, Decoder, ce_loss, ce_loss_backward, check_caption_args, check_input_ids, check_label_smoothing,
+                  check_weight_args, logits_grad, pack_row_weights, sample_lengths, scheduled_loss_inputs, unpack_rows, up8)
 from .dropout import DropoutState
 from .seq import plan_for
 
@@ -48,7 +48,7 @@ class Attention_Net(nn.Module):
 
 class _AttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feat, _anchor, module, caption, lens, mode, alpha_c, need_grad, sequence_weight, token_weight, eps=0.0):
+    def forward(ctx, feat, _anchor, module, caption, lens, mode, alpha_c, need_grad, sequence_weight, token_weight, eps=0.0, input_ids=None):
         m = module
         dev = feat.device
         if not feat.is_cuda or not m.linear.weight.is_cuda:
@@ -56,7 +56,8 @@ class _AttnFn(torch.autograd.Function):
         plan = plan_for(lens, dev)
         caption = caption.contiguous()
         seq = plan.c_struct(caption)
-        cap_T = caption.t().contiguous()
+        # the kernels embed caption_T; with input_ids (scheduled sampling) that is the mixed ids, and the targets below stay the caption's
+        cap_T = (caption if input_ids is None else input_ids.detach()).t().contiguous()
         prm, keep = m._c_params()
         dt = m.compute_dtype
         B, Fd, P = feat.shape
@@ -127,7 +128,7 @@ class _AttnFn(torch.autograd.Function):
             check(lib().st_attn_backward(C.byref(prm), C.byref(grads), C.byref(seq), _cp(ctx.cap_T), _cp(dlog), Vp, _cp(ctx.alphas), _cp(dal),
                                          float(alpha_c), _cp(gs), _cp(ctx.ws), ctx.ws.numel(), _stream()), "st_attn_backward")
         ctx.ws = ctx.dbuf = None
-        return None, None, None, None, None, None, None, None, None, None, None
+        return None, None, None, None, None, None, None, None, None, None, None, None
 
 
 class RNN_Attn(Decoder):
@@ -193,29 +194,55 @@ class RNN_Attn(Decoder):
         g.w_embed, g.b_embed = gb(self.embed.weight), gb(self.embed.bias)
         return g, keep
 
-    def forward(self, cnn_feature, image_caption, caption_size):
-        """rnn_attn.py:98-118: (packed logits (N_tok,V) fp32, alphas (B,T,P))."""
-        return _AttnFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "logits", 0.0, torch.is_grad_enabled(), None, None)
+    def _sched_inputs(self, cnn_feature, cap, lens, max_len, u, p, inv_t, top_k, ids, replaced):
+        prm, keep, featc, B, P = self._decode_inputs(cnn_feature)
+        T = cap.shape[1]
+        cap_T = cap.t().contiguous()
+        nbytes = lib().st_attn_sched_inputs_workspace_bytes(C.byref(prm), B)
+        ws = torch.empty(nbytes, device=featc.device, dtype=torch.uint8)
+        check(lib().st_attn_sched_inputs(C.byref(prm), _cp(featc), B, _cp(cap), _cp(cap_T), T, _cp(lens), max_len, _cp(u[0]), _cp(u[1]), p, inv_t,
+                                         top_k, _cp(ws), nbytes, _cp(ids), _cp(replaced), None, None, _stream()), "st_attn_sched_inputs")
 
-    def loss(self, cnn_feature, image_caption, caption_size, alpha_c=1.0, sequence_weight=None, token_weight=None, label_smoothing=0.0):
+    def forward(self, cnn_feature, image_caption, caption_size, input_ids=None):
+        """rnn_attn.py:98-118: (packed logits (N_tok,V) fp32, alphas (B,T,P)).  `input_ids` (B, T) int64 (``scheduled_inputs``):
+        the token step t embeds, input_ids[b, t], in place of the caption's; None is the call it was."""
+        if input_ids is None:
+            return _AttnFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "logits", 0.0, torch.is_grad_enabled(), None, None)
+        check_input_ids(input_ids, image_caption, self.vocab_size)
+        return _AttnFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "logits", 0.0, torch.is_grad_enabled(), None, None,
+                             0.0, input_ids)
+
+    def loss(self, cnn_feature, image_caption, caption_size, alpha_c=1.0, sequence_weight=None, token_weight=None, label_smoothing=0.0,
+             input_ids=None, scheduled_sampling=0.0, ss_temperature=1.0, ss_top_k=0, ss_generator=None, ss_uniforms=None):
         """main_attn.py:126-131 fused: CE(packed logits, packed caption) + alpha_c * mean((1 - sum_t alpha)^2).
         `sequence_weight` (B,) / `token_weight` (B, T) weight the cross-entropy terms as in RNN.loss (the divisor stays N_tok, no
         gradient into the weights); `label_smoothing` in [0, 1) smooths them as CrossEntropyLoss(label_smoothing=) does (0: the
-        call it was); the doubly-stochastic term stays unweighted and unsmoothed."""
+        call it was); the doubly-stochastic term stays unweighted and unsmoothed.
+        `input_ids` / `scheduled_sampling` (+ ss_*): as in RNN.loss -- the steps embed the mixed ids, the targets stay the caption,
+        the embedding gradient goes to the tokens that were fed; the roll-in runs without dropout, this pass with it as usual."""
         eps = check_label_smoothing(label_smoothing)
+        input_ids = scheduled_loss_inputs(self, cnn_feature, image_caption, caption_size, input_ids, scheduled_sampling, ss_temperature,
+                                          ss_top_k, ss_generator, ss_uniforms)
         if sequence_weight is not None or token_weight is not None:
             check_caption_args(image_caption, caption_size)
             check_weight_args(image_caption.shape[0], image_caption.shape[1], sequence_weight, token_weight)
-        out, _ = _AttnFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "loss", float(alpha_c), torch.is_grad_enabled(),
-                               sequence_weight, token_weight, eps)
+        if input_ids is None:
+            out, _ = _AttnFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "loss", float(alpha_c),
+                                   torch.is_grad_enabled(), sequence_weight, token_weight, eps)
+        else:
+            out, _ = _AttnFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "loss", float(alpha_c),
+                                   torch.is_grad_enabled(), sequence_weight, token_weight, eps, input_ids)
         return out
 
-    def token_logp(self, cnn_feature, image_caption, caption_size):
+    def token_logp(self, cnn_feature, image_caption, caption_size, input_ids=None):
         """log p(image_caption[b, t]) at every step of the teacher-forced pass (rnn_attn.py:98-118): (B, T) fp32, 0 past
-        caption_size[b]; no gradient.  -token_logp.sum() / N_tok is the cross-entropy part of loss()."""
+        caption_size[b]; no gradient.  -token_logp.sum() / N_tok is the cross-entropy part of loss().  `input_ids`: as in ``forward``."""
         check_caption_args(image_caption, caption_size)
+        if input_ids is not None:
+            check_input_ids(input_ids, image_caption, self.vocab_size)
         with torch.no_grad():
-            nll, _ = _AttnFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "nll", 0.0, False, None, None)
+            nll, _ = _AttnFn.apply(cnn_feature, self.linear.bias, self, image_caption, caption_size, "nll", 0.0, False, None, None, 0.0,
+                                   input_ids)
             return unpack_rows(plan_for(caption_size, nll.device), -nll, image_caption.shape[1], nll.device)
 
     def _decode_inputs(self, cnn_feature):

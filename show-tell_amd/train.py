@@ -17,6 +17,7 @@ each other's launch tails and pair the HBM-bound normalise passes with the MFMA-
 forward measured, tools/two_stream_encoder.py).  The arithmetic and its order per sample are unchanged -- the running
 BatchNorm buffers are updated in minibatch order (cnn.py) -- only the schedule is.
 """
+import math
 import os
 
 import numpy as np
@@ -24,7 +25,7 @@ import torch
 
 from .head import linear_bn1d
 from .parallel import GradAllReducer, broadcast_state
-from .rnn import check_label_smoothing, sample_lengths
+from .rnn import check_label_smoothing, check_probability, sample_lengths
 
 
 def synthetic_batch(B, V, seed=1, device="cuda", image_size=224, mean=12.5, std=2.5, lo=6, hi=25):
@@ -80,15 +81,46 @@ def dropout_rank():
     return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
 
 
+def linear_ss_schedule(start, end, steps):
+    """The linear decay of Bengio et al. (2015) as a scheduled-sampling rate: p(i) = start + (end - start) * min(i, steps) / steps for
+    the i-th `Trainer.step` (the paper decays the teacher-forcing probability 1 - p; a rate that rises from 0 is start < end)."""
+    start, end = check_probability(start, "start"), check_probability(end, "end")
+    if int(steps) != steps or steps < 1:
+        raise ValueError(f"steps must be an integer >= 1 (got {steps!r})")
+    return lambda i: start + (end - start) * min(max(int(i), 0), steps) / steps
+
+
+def inverse_sigmoid_ss_schedule(k):
+    """The inverse-sigmoid decay of Bengio et al. (2015): the teacher-forcing probability is k / (k + exp(i / k)), k >= 1, so the
+    scheduled-sampling rate of the i-th `Trainer.step` is p(i) = 1 - k / (k + exp(i / k)): 1 / (k + 1) at i = 0, towards 1."""
+    k = float(k)
+    if not k >= 1.0:
+        raise ValueError(f"k must be >= 1 (got {k!r})")
+
+    def rate(i):
+        x = max(int(i), 0) / k
+        return 1.0 if x > 700.0 else 1.0 - k / (k + math.exp(x))
+    return rate
+
+
 class Trainer:
-    def __init__(self, cnn, rnn, optimizer, world_size=1, label_smoothing=0.0):
+    def __init__(self, cnn, rnn, optimizer, world_size=1, label_smoothing=0.0, scheduled_sampling=0.0, ss_temperature=1.0, ss_top_k=0,
+                 ss_generator=None):
         """`label_smoothing` in [0, 1): `step` trains on CrossEntropyLoss(label_smoothing=..) (``rnn.loss(.., label_smoothing=)``);
         0 is the reference's plain cross entropy.
         Dropout is the decoder's own (``RNN(.., dropout=, dropout_in=, dropout_out=)``, active in ``rnn.train()``): `step` and the
         loss half of `step_self_critical` draw one step of its masks each; the sampling half of `step_self_critical` (``sample``,
         ``sentence_index``) always runs the deterministic model.  The decoder of rank r (0 without torch.distributed) is re-seeded
-        with its seed + r here, which also zeroes its step counter, so that data-parallel replicas draw different masks."""
+        with its seed + r here, which also zeroes its step counter, so that data-parallel replicas draw different masks.
+        `scheduled_sampling`: a rate p in [0, 1], or a callable that gets the count of earlier `step` calls (0, 1, ..) and returns
+        it (`linear_ss_schedule`, `inverse_sigmoid_ss_schedule`).  With p > 0 `step` first rolls the deterministic decoder along
+        the caption (``rnn.scheduled_inputs(.., p, ss_temperature, ss_top_k, ss_generator)``, no dropout) and trains on the mixed
+        inputs; p = 0 is the step it was.  `step_self_critical` is unaffected."""
         self.label_smoothing = check_label_smoothing(label_smoothing)
+        self.scheduled_sampling = scheduled_sampling if callable(scheduled_sampling) else check_probability(scheduled_sampling,
+                                                                                                            "scheduled_sampling")
+        self.ss_temperature, self.ss_top_k, self.ss_generator = ss_temperature, ss_top_k, ss_generator
+        self.steps = 0        # `step` calls so far: what a scheduled-sampling schedule is asked with
         self.cnn, self.rnn, self.opt = cnn, rnn, optimizer
         self.reducer = GradAllReducer(world_size)
         if world_size > 1:
@@ -177,9 +209,16 @@ class Trainer:
         """One training step.  `upcoming`: the images of the next minibatches, in order (at most `depth` are used).
         Gradient clipping, weight decay and the non-finite guard are the optimizer's keywords (``max_grad_norm``,
         ``weight_decay``, ``skip_nonfinite``, optim.py): they act inside the deferred optimizer step, after the all-reduce, on
-        the device, and need nothing here."""
+        the device, and need nothing here.  With scheduled sampling on (see __init__) the roll-in runs after the trainable head, on
+        this step's features; the deferred optimizer step and `upcoming` work as without it."""
+        ss = self.scheduled_sampling
+        p = check_probability(ss(self.steps), "scheduled_sampling") if callable(ss) else ss
+        self.steps += 1
         feat = self._features(image, upcoming)
-        if self.label_smoothing:
+        if p:
+            loss = self.rnn.loss(feat, caption, caption_len, label_smoothing=self.label_smoothing, scheduled_sampling=p,
+                                 ss_temperature=self.ss_temperature, ss_top_k=self.ss_top_k, ss_generator=self.ss_generator)
+        elif self.label_smoothing:
             loss = self.rnn.loss(feat, caption, caption_len, label_smoothing=self.label_smoothing)
         else:
             loss = self.rnn.loss(feat, caption, caption_len)    # main.py:148-149
