@@ -170,7 +170,7 @@ class RNN_Attn(Decoder):
     def _c_params(self):
         p, keep = AttnParams(), []
         wc = self._rnn_params(p.rnn, 2 * self.embed_dim, keep)
-        p.F, p.A, p.P = self.nos_filters, self.attention_dim, 49
+        p.F, p.A, p.P = self.nos_filters, self.attention_dim, 0      # every caller sets P from its feature map; 0 is rejected
         a = self.attn
         p.w_enc, p.b_enc = wc(a.encoder_att.weight), a.encoder_att.bias.data.data_ptr()
         p.w_dec, p.b_dec = wc(a.decoder_att.weight), a.decoder_att.bias.data.data_ptr()

@@ -1,0 +1,248 @@
+"""Input conditions of tests/test_gpu_attention_geometry.py, from the float64 oracle alone (no GPU): the cases take the kernel paths
+they are named for, their attention is peaked but not saturated, the greedy GAP excludes few steps, the beam bounds written in the
+GPU file are 4 x the floors of its inputs, and every seeded fault (applied to a copy of the oracle's arithmetic,
+tests/_attention_geometry_cases.py) moves a checked quantity by at least 10 x its fp32 and 2 x its bf16 bound.
+
+Measured (8 CPU threads; the file takes 16 s):
+  peakedness, median / largest per-row max alpha over the live rows, GRU | LSTM (required: median >= min(3 / P, 0.5), largest <= 0.97)
+    full_wave         P = 64   0.131 / 0.153 | 0.107 / 0.280      odd        P = 33   0.327 / 0.531 | 0.171 / 0.389
+    tokens_gt_pixels  P = 4    0.686 / 0.864 | 0.601 / 0.870      wide_att   P = 17   0.266 / 0.548 | 0.275 / 0.483
+    wide_feat         P = 9    0.517 / 0.650 | 0.482 / 0.589      many_rows  P = 10   0.347 / 0.924 | 0.366 / 0.949
+    (full_att.weight x 8 and seed 3, but tokens_gt_pixels x 10 seed 4, wide_feat x 16, many_rows x 9 seed 5: at x 8, seed 3 their
+    medians were 0.562 | 0.588, 0.299 | 0.310 and 0.313 | 0.349, at or under what is required)
+  GAP = 4 x the largest |d logp|, fp32 against float64 arithmetic of the greedy restatement: fp32 2.1e-6, bf16 7.5e-3 (wide_att GRU;
+    full_wave saw no stored value round the other way: 4.5e-7).  Share of the float64 walk's own steps with a top-two gap within
+    GAP, over the four cases of a cell (required <= 0.10): fp32 0.000 | 0.002, bf16 0.038 | 0.033; the single worst case is wide_att
+    LSTM bf16 with 0.12, whose default-initialised one-layer LSTM hardly separates its tokens
+  power = min(moved / (10 x fp32 bound), moved / (2 x bf16 bound)) of the quantity that moves most, GRU | LSTM (required >= 1):
+    last pixel left out of softmax and context          full_wave 13.3 | 5.5, odd 3.2 | 11.1            (alpha rel_l2)
+    context taken with the neighbouring pixel's alpha   full_wave 3.2 | 2.5, tokens_gt_pixels 8.3 | 9.8   (embed.weight rel_l2)
+    score channels >= 1024 ignored                      wide_att 7.1 | 5.0                              (encoder_att.weight rel_max)
+    feature channels >= 4096 left out of z              wide_feat 3.9 | 3.8                             (embed.weight rel_max)
+    phantom row in the encoder_att contraction          tokens_gt_pixels 2.5 | 2.0                      (encoder_att.weight rel_l2)
+    d att1 of the last pixel group not accumulated      tokens_gt_pixels 13.3 | 10.6, many_rows 2.1 | 1.9, odd 5.3 | 1.8
+        (full_wave's last backward group holds one pixel of 64: GRU 8.8, LSTM 0.44 -- 263 x the fp32 bound, 0.9 x the bf16 one, so
+        there the fp32 run alone catches it; not asserted)
+    beam slot w reads att2 of slot w - 1                W = 2 | 7: full_wave GRU 26 | 51, LSTM 8.4 | 8.4; tokens_gt_pixels GRU 21 | 15,
+                                                        LSTM 7.3 | 14 (the bf16 figures; fp32 355 and more)
+"""
+import pytest
+import torch
+
+from tests import _attention_geometry_cases as G
+from tests.test_gpu_attention_bench_shape import (ALPHA_L2, ALPHA_MAX, DEC_ATT_L2, DEC_ATT_MAX, F32_L2, F32_MAX, GRAD_L2, GRAD_MAX,
+                                                  LOSS_REL, _live)
+from tests.test_gpu_attention_geometry import BEAM_BOUNDS, EXCLUDED, GAP, STORAGE_BOUNDS, _beam_bounds
+from tests.test_gpu_decoder_bench_shape import _rel_l2, _rel_max
+
+CELLS = ("gru", "lstm")
+
+
+# ====================================================================================================================
+# paths
+# ====================================================================================================================
+
+def _steps(case, bf16, threads):
+    return [s for s in G.paths(case, bf16)["steps"] if s["threads"] == threads]
+
+
+def test_every_case_takes_the_paths_it_is_named_for():
+    for name, c in G.CASES.items():
+        assert all(c[k] % 8 == 0 for k in "EFAH") and 1 <= c["P"] <= 64, name
+        assert c["lens"] == sorted(c["lens"], reverse=True), name
+    # 1. n_tok > B*P: Np comes from the tokens, the encoder_att contraction has more than 7 pad columns, the token ones fewer than 8
+    for bf16 in (False, True):
+        p = G.paths("tokens_gt_pixels", bf16)
+        assert p["n_tok"] == 60 > p["BP"] == 28 and p["Np"] == G.up8(p["n_tok"]) and p["pad_pixels"] > 7 and p["pad_tokens"] < 8
+        for other in ("full_wave", "odd", "wide_att", "wide_feat", "many_rows"):           # every other case: Np from B*P
+            q = G.paths(other, bf16)
+            assert q["BP"] > q["n_tok"] and q["Np"] == G.up8(q["BP"]), other
+    # 2. a full softmax wave, and a single pixel
+    assert G.CASES["full_wave"]["P"] == 64 and G.CASES["one_pixel"]["P"] == 1
+    # 3. pixel groups with idle threads and empty trailing groups at 1024 threads, in bf16
+    for s in G.paths("full_wave", True)["steps"]:
+        assert s["threads"] == 1024 and s["nchunk"] == 6
+        assert s["fwd"]["G"] == 170 > 64 and s["fwd"]["idle"] == 1024 % 6 == 4 and s["fwd"]["per"] == 1 and s["fwd"]["empty"] == 170 - 64
+        assert s["bwd"]["G"] == 25 and s["bwd"]["idle"] == 24 and s["bwd"]["per"] == 3 and s["bwd"]["empty"] == 3
+        assert s["bwd"]["last_group"] == [63]
+    for s in G.paths("full_wave", False)["steps"]:
+        assert s["fwd"]["G"] == 85 and s["fwd"]["idle"] == 4 and s["fwd"]["empty"] == 21
+    # 4. G == 1 at 1024 threads.  Backward: A = 1032 > 1024, threads 0..7 take a second trip.  Forward: F / N > 512 gives G == 1;
+    #    the second trip needs F / N > 1024, which fp32 (1026 chunks) has and bf16 (513 chunks, one trip) has not
+    for bf16 in (False, True):
+        for s in G.paths("wide_att", bf16)["steps"]:
+            assert s["threads"] == 1024 and s["bwd"]["G"] == 1 and s["bwd"]["trips"] == 2 and G.CASES["wide_att"]["A"] - 1024 == 8
+        for s in G.paths("wide_feat", bf16)["steps"]:
+            assert s["threads"] == 1024 and s["fwd"]["G"] == 1 and s["nchunk"] == (513 if bf16 else 1026)
+            assert s["fwd"]["trips"] == (1 if bf16 else 2)
+    # 5. 256-thread workgroups with G > 1 and idle threads, and 1024-thread steps, in the same backward
+    rows = G.paths("many_rows", True)["rows"]
+    print(f"MEASURE many_rows rows per step: {rows}")
+    assert any(r >= 512 for r in rows) and any(r < 512 for r in rows)
+    for bf16 in (False, True):
+        wide, narrow = _steps("many_rows", bf16, 256), _steps("many_rows", bf16, 1024)
+        assert wide and narrow
+        for s in wide:
+            assert s["fwd"]["G"] == (42 if bf16 else 21) and s["fwd"]["idle"] == 4 and s["bwd"]["G"] == 6 and s["bwd"]["idle"] == 16
+            assert s["fwd"]["empty"] > 0 and s["bwd"]["per"] == 2 and s["bwd"]["empty"] == 1
+    # 6. the score loop's partial last trip
+    for case, trips in (("full_wave", (1, 1)), ("wide_att", (5, 3))):
+        for bf16 in (False, True):
+            s = G.paths(case, bf16)["steps"][0]
+            assert s["score_partial"] and s["score_trips"] == trips[bf16], (case, bf16)
+    # 7. the beam instantiations no other test launches; kU switches between bf16 W = 6 and W = 7
+    assert set(G.BEAM_WIDTHS) == {2, 4, 6, 7} and G.V >= max(G.BEAM_WIDTHS)
+    for case in G.BEAM_CASES:
+        c = G.CASES[case]
+        for bf16 in (False, True):
+            for W in G.BEAM_WIDTHS:
+                b = G.beam_paths(c["F"], c["A"], c["P"], W, bf16)
+                assert b["G"] > 1 and b["lds"] <= 64 * 1024 and b["kU"] == (2 if bf16 and W == 7 else 4)
+    # 8. the LDS guard of the beam launch: A = 2056 fits at W = 7 and not at W = 8
+    assert G.beam_paths(16, 2056, 4, 8, False)["lds"] > 64 * 1024 >= G.beam_paths(16, 2056, 4, 7, False)["lds"]
+    # every dynamic LDS size of the training kernels stays inside a workgroup's 64 KB
+    for case in G.CASES:
+        for bf16 in (False, True):
+            assert all(s[d]["lds"] <= 64 * 1024 for s in G.paths(case, bf16)["steps"] for d in ("fwd", "bwd"))
+
+
+# ====================================================================================================================
+# peakedness, and the copy is the oracle
+# ====================================================================================================================
+
+@pytest.mark.parametrize("cell", CELLS)
+@pytest.mark.parametrize("case", sorted(G.CASES))
+def test_attention_is_peaked_but_not_saturated_and_the_copy_is_the_oracle(case, cell):
+    from oracle import restatement as R
+    params, feat, cap, lens = G.problem(case, cell, False)
+    po = {k: v.double().clone().requires_grad_(True) for k, v in params.items()}
+    lo, _, al = R.attn_train_loss(po, feat.double(), cap, lens, 1.0, cell)
+    lo.backward()
+    lc, alc, gc = G.train_copy_grads(case, cell)
+    assert abs(lc - lo.item()) <= 1e-12 * abs(lo.item()) and (alc - al.detach()).abs().max() <= 1e-12
+    for k, p in po.items():
+        assert (gc[k] - p.grad).abs().max() <= 1e-12 * max(1.0, p.grad.abs().max().item()), k
+    P = G.CASES[case]["P"]
+    if P == 1:
+        assert (al.detach()[0, :lens[0]] == 1).all()
+        for k, p in po.items():                             # alpha is identically 1: nothing reaches the attention network
+            if k.startswith("attn."):
+                assert (p.grad == 0).all(), k
+        return
+    peak = _live(al.detach(), lens).max(1)[0]
+    print(f"MEASURE {case} {cell}: per-row max alpha median {peak.median():.3f} largest {peak.max():.3f} (uniform {1 / P:.3f})")
+    assert peak.median() >= min(3.0 / P, 0.5) and peak.max() <= 0.97
+
+
+# ====================================================================================================================
+# GAP of the greedy check
+# ====================================================================================================================
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["fp32", "bf16"])
+def test_greedy_gap_is_four_times_the_floor_and_excludes_few_steps(bf16):
+    """GAP of the GPU file against the floor recomputed here (to a factor of 2, as the beam bounds), and the share of the float64
+    walk's own steps whose top-two gap is within it, per cell over the four cases as the GPU test takes it"""
+    now = G.greedy_gap(bf16)
+    print(f"MEASURE greedy {'bf16' if bf16 else 'fp32'}: 4 x floor {now:.3e}, written GAP {GAP[bf16]:.3e}")
+    assert GAP[bf16] / 2 <= now <= GAP[bf16] * 2
+    for cell in CELLS:
+        n = below = 0
+        for case in G.GREEDY_CASES:
+            d, gaps = G.greedy_floor(case, cell, bf16)
+            share = (gaps <= GAP[bf16]).double().mean().item()
+            print(f"MEASURE greedy {case} {cell}: |d logp| fp32 vs float64 {d:.2e}; top-two gap min {gaps.min():.2e}, share <= GAP {share:.3f}")
+            n += gaps.numel(); below += int((gaps <= GAP[bf16]).sum())
+        print(f"MEASURE greedy {cell} {'bf16' if bf16 else 'fp32'}: excluded share of the oracle's own steps {below / n:.3f}")
+        assert below / n <= EXCLUDED
+
+
+def test_storage_bounds_are_four_times_the_storage_distance_and_needed():
+    """every entry of STORAGE_BOUNDS is 4 x the float64 distance that bf16 storage alone causes, and that distance does exceed
+    the standing bound it replaces; no other gradient of any case does"""
+    over = set()
+    for case in G.CASES:
+        for cell in CELLS:
+            for k, (l2, mx) in G.storage_distance(case, cell).items():
+                if k == "attn.full_att.bias":
+                    continue
+                dec = k == "attn.decoder_att.weight"
+                if l2 > (DEC_ATT_L2 if dec else GRAD_L2) or mx > (DEC_ATT_MAX if dec else GRAD_MAX):
+                    over.add((case, cell, k))
+                    print(f"MEASURE storage distance {case} {cell} {k}: rel_l2 {l2:.2e} rel_max {mx:.2e}")
+                    b = STORAGE_BOUNDS[(case, cell, k)]
+                    assert abs(b[0] - 4 * l2) <= 0.02 * b[0] and abs(b[1] - 4 * mx) <= 0.02 * b[1], (case, cell, k, l2, mx)
+    assert over == set(STORAGE_BOUNDS)
+
+
+# ====================================================================================================================
+# the beam bounds are 4 x the floors
+# ====================================================================================================================
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("cell", CELLS)
+@pytest.mark.parametrize("case", G.BEAM_CASES)
+def test_beam_bounds_are_four_times_the_floor(case, cell, bf16):
+    """the constants of the GPU file against the floors recomputed here (max over the four widths).  fp32 sums on another CPU may
+    round a stored value the other way somewhere, so the match is held to a factor of 2, not to the digit."""
+    fl = [G.beam_floor(case, cell, bf16, W) for W in G.BEAM_WIDTHS]
+    now = [4 * max(f[k] for f in fl) for k in ("nll", "a_max", "a_l2")]
+    written = BEAM_BOUNDS[(case, cell, "bf16" if bf16 else "fp32")]
+    print(f"MEASURE beam floor x 4 {case} {cell} {'bf16' if bf16 else 'fp32'}: nll {now[0]:.2e} alpha max {now[1]:.2e} rel_l2 {now[2]:.2e}; "
+          f"written {written[0]:.2e} {written[1]:.2e} {written[2]:.2e}")
+    assert max(f["nll"] for f in fl) == max(f["nll_word"] for f in fl)       # <end> has no floor of its own in these decoders
+    for a, b in zip(now, written):
+        assert b / 2 <= a <= b * 2
+
+
+# ====================================================================================================================
+# power
+# ====================================================================================================================
+
+def _moved(case, cell, fault):
+    """min(moved / (10 x fp32 bound), moved / (2 x bf16 bound)) of the quantity check A of the GPU file sees move most"""
+    lens = G.CASES[case]["lens"]
+    lo, al, g = G.train_copy_grads(case, cell)
+    lf, alf, gf = G.train_copy_grads(case, cell, fault)
+    q = [("loss", abs(lf - lo) / abs(lo), F32_L2, LOSS_REL),
+         ("alpha rel_l2", _rel_l2(_live(alf, lens), _live(al, lens)), F32_L2, ALPHA_L2),
+         ("alpha rel_max", _rel_max(_live(alf, lens), _live(al, lens)), F32_MAX, ALPHA_MAX)]
+    for k in g:
+        if k == "attn.full_att.bias":
+            continue
+        dec = k == "attn.decoder_att.weight"
+        q.append((k + " rel_l2", _rel_l2(gf[k], g[k]), F32_L2, DEC_ATT_L2 if dec else GRAD_L2))
+        q.append((k + " rel_max", _rel_max(gf[k], g[k]), F32_MAX, DEC_ATT_MAX if dec else GRAD_MAX))
+    best = max(q, key=lambda v: min(v[1] / (10 * v[2]), v[1] / (2 * v[3])))
+    ratio = min(best[1] / (10 * best[2]), best[1] / (2 * best[3]))
+    print(f"MEASURE power {fault} {case} {cell}: {best[0]} moved by {best[1]:.2e} = {best[1] / best[2]:.0f} x its fp32 bound, "
+          f"{best[1] / best[3]:.1f} x its bf16 bound; ratio {ratio:.2f}")
+    return ratio
+
+
+@pytest.mark.parametrize("cell", CELLS)
+@pytest.mark.parametrize("fault,case", [("last_pixel_out", "full_wave"), ("last_pixel_out", "odd"),
+                                        ("neighbour_alpha", "full_wave"), ("neighbour_alpha", "tokens_gt_pixels"),
+                                        ("score_cut", "wide_att"), ("feat_cut", "wide_feat"),
+                                        ("phantom_row", "tokens_gt_pixels"),
+                                        ("last_group_datt1", "tokens_gt_pixels"), ("last_group_datt1", "many_rows"), ("last_group_datt1", "odd")])
+def test_training_faults_move_a_checked_quantity(fault, case, cell):
+    assert _moved(case, cell, fault) >= 1.0
+
+
+@pytest.mark.parametrize("W", [2, 7])
+@pytest.mark.parametrize("cell", CELLS)
+@pytest.mark.parametrize("case", G.BEAM_CASES)
+def test_slot_fault_moves_the_beam_checks(case, cell, W):
+    """Slot w reading att2 of slot w - 1, on the GPU's BEAM_IMAGES images along the float64 oracle's own records: the step cost
+    (check B) or an attention map (check D) moves by >= 10 x the fp32 and >= 2 x the bf16 bound of the case.  The ratios are in the file's docstring."""
+    ratios = []
+    for bf16 in (False, True):
+        params, feat = G.params_of(case, cell, bf16), G.beam_features(case, bf16)[:G.BEAM_IMAGES]
+        good = G.BeamOracle(cell, params, feat, W, bf16)
+        d = G.beam_distance(G.BeamOracle(cell, params, feat, W, bf16, slot_fault=True), good, good.free_run(), W)
+        nll, (a_max, a_l2) = _beam_bounds(case, cell, bf16)
+        mult = 2 if bf16 else 10
+        ratios.append(max(d["nll"] / nll[1], d["a_max"] / a_max, d["a_l2"] / a_l2) / mult)
+        print(f"MEASURE power slot fault {case} {cell} W={W} {'bf16' if bf16 else 'fp32'}: d nll {d['nll']:.2e} (bound {nll[1]:.2e}), "
+              f"alpha max {d['a_max']:.2e} ({a_max:.2e}) rel_l2 {d['a_l2']:.2e} ({a_l2:.2e}); ratio {ratios[-1]:.1f}")
+    assert min(ratios) >= 1.0
