@@ -630,6 +630,26 @@ int st_softmax_topk(const float* logits, int ldl, int n, int V, int k, float* to
  * done[b] (no live node left).  Needs k <= W and W * k <= 64. */
 int st_beam_select(const long* tok, const float* cost, uint8_t* done, const float* top_p, const long* top_id, int B, int W, int k,
                    long end_id, long* new_tok, float* new_cost, int* parent, uint8_t* ended, int* gather, void* stream);
+/* Constrained beam search: the two kernels a constrained iteration puts in the place of st_softmax_topk and st_beam_select.
+ * st_beam_ban_topk: st_softmax_topk (probabilities) with a per-row ban set.  Entry v of a row is banned iff it is one of the
+ *   n_suppress ids of `suppress` (device memory; ids outside [0, V) are ignored), or v == end_id and ban_end != 0 (the host's
+ *   "fewer than min_length words so far"), or ngram = g >= 1 and appending v to the row's path s_0 .. s_t (hist [n][hist_ld]
+ *   int32, t = hist_len - 1, s_0 = <start>; NULL allowed with g == 0) would repeat an n-gram of size g already on it:
+ *   s[i .. i+g-2] == s[t-g+2 .. t] and s[i+g-1] == v for some 0 <= i <= t-g+1 (g == 1 bans every token of the path).
+ *   The softmax still runs over all V entries, so a probability is the model's own; the k results are the k most probable
+ *   unbanned entries (lowest index first among equals), and a row with fewer than k of them ends in (p = 0, id = 0) entries.
+ *   With an empty ban set the outputs are st_softmax_topk's, bit for bit.
+ * st_beam_select_hist: st_beam_select, which also hands every new node its path: hist_out[b*W + rank] = hist_in[b*W + parent]
+ *   [0 .. hist_len) followed by the node's token (zeros for an empty slot); hist_in != hist_out, hist_len + 1 <= hist_ld. */
+#define ST_BEAM_MAX_NGRAM 16
+#define ST_BEAM_MAX_SUPPRESS 64
+#define ST_BEAM_MAX_HIST 64          /* tokens of a path, <start> included: max_length + 1 */
+#define ST_BEAM_MAX_VOCAB 524288     /* bits of the ban map (64 KB of LDS) */
+int st_beam_ban_topk(const float* logits, int ldl, int n, int V, int k, const int* hist, int hist_ld, int hist_len, int ngram,
+                     const long* suppress, int n_suppress, long end_id, int ban_end, float* top_p, long* top_id, void* stream);
+int st_beam_select_hist(const long* tok, const float* cost, uint8_t* done, const float* top_p, const long* top_id, int B, int W, int k,
+                        long end_id, long* new_tok, float* new_cost, int* parent, uint8_t* ended, int* gather,
+                        const int* hist_in, int* hist_out, int hist_ld, int hist_len, void* stream);
 
 /* Caption sampling (the multinomial counterpart of the max(1)[1] of rnn.py:52 and rnn_attn.py:141).  The kernels hold no
  * random-number generator: the caller supplies one uniform in [0, 1) per row and step.
@@ -750,6 +770,20 @@ size_t st_attn_beam_workspace_bytes(const st_attn_params* p, int B, int W);
 int st_attn_beam_search(const st_attn_params* p, const float* cnn_feature, int B, int W, int max_length,
                         long start_id, long end_id, void* workspace, size_t workspace_bytes,
                         long* rec_tok, float* rec_cost, int* rec_par, uint8_t* rec_end, float* rec_alpha, void* stream);
+/* The same search under constraints (st_beam_ban_topk's rules): <end> is banned while a node has generated fewer than
+ * min_length words (iteration t < min_length), ngram = no-repeat n-gram size (0: off; needs max_length + 1 <=
+ * ST_BEAM_MAX_HIST), suppress = n_suppress ids in DEVICE memory that never appear.  Every iteration runs st_beam_ban_topk and
+ * st_beam_select_hist in the place of st_softmax_topk and st_beam_select -- no launch more; the workspace is
+ * st_attn_beam_workspace_bytes' plan (its size is the offset of the first) followed by the two path buffers [B*W][max_length + 1]
+ * int32, each padded to a multiple of 256 bytes; iteration t reads buffer t & 1 and writes the other, so buffer max_length & 1
+ * holds the paths of the last fringe on return (a longer search keeps no paths: st_beam_select, and ngram must be 0).
+ * The ids of `suppress` cannot be checked here without a device round trip: ids outside [0, V) are ignored (the Python
+ * callers reject them before the call). */
+size_t st_attn_beam_ex_workspace_bytes(const st_attn_params* p, int B, int W, int max_length);
+int st_attn_beam_search_ex(const st_attn_params* p, const float* cnn_feature, int B, int W, int max_length,
+                           long start_id, long end_id, void* workspace, size_t workspace_bytes,
+                           long* rec_tok, float* rec_cost, int* rec_par, uint8_t* rec_end, float* rec_alpha,
+                           int min_length, int ngram, const long* suppress, int n_suppress, void* stream);
 
 #ifdef __cplusplus
 }

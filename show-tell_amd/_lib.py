@@ -193,6 +193,8 @@ _SIGS = {
     "st_gather_state": ([c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p], c_i),
     "st_softmax_topk": ([c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p], c_i),
     "st_beam_select": ([c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_p, c_p, c_p, c_p, c_p, c_p], c_i),
+    "st_beam_ban_topk": ([c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_i, c_l, c_i, c_p, c_p, c_p], c_i),
+    "st_beam_select_hist": ([c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p], c_i),
     "st_sample_rows": ([c_p, c_i, c_i, c_i, c_p, c_i, c_f, c_i, c_l, c_p, c_p, c_p, c_i, c_i, c_p, c_p], c_i),
     "st_rnn_sample_workspace_bytes": ([C.POINTER(RnnParams), c_i], C.c_size_t),
     "st_rnn_sample": ([C.POINTER(RnnParams), c_p, c_i, c_i, c_p, c_f, c_i, c_l, c_p, C.c_size_t, c_p, c_p, c_p], c_i),
@@ -217,6 +219,8 @@ _SIGS = {
     "st_attn_sched_inputs": ([c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_f, c_f, c_i, c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p], c_i),
     "st_attn_beam_workspace_bytes": ([c_p, c_i, c_i], C.c_size_t),
     "st_attn_beam_search": ([c_p, c_p, c_i, c_i, c_i, c_l, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p, c_p], c_i),
+    "st_attn_beam_ex_workspace_bytes": ([c_p, c_i, c_i, c_i], C.c_size_t),
+    "st_attn_beam_search_ex": ([c_p, c_p, c_i, c_i, c_i, c_l, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_p], c_i),
     "st_cross_entropy": ([c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_f, c_p, c_p], c_i),
     "st_cross_entropy_w": ([c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_p, c_p], c_i),
     "st_cross_entropy_ls": ([c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_i, c_i, c_f, c_p, c_p], c_i),

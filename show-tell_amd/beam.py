@@ -11,6 +11,13 @@ Two different things exist in the reference and both are mirrored:
   The reference's list bookkeeping (``Node`` parents, stable ``sorted``) is reproduced literally, including its
   float32 cost accumulation under NumPy 2 and the fact that nodes ending on the last iteration are never
   harvested; ``beam_search_host`` keeps that bookkeeping on the host per iteration (the cross-check).
+
+Constrained search (``min_length``, ``no_repeat_ngram_size``, ``suppress_tokens``, ``length_penalty``): a successor v of a node
+with the path s_0 .. s_t (s_0 = <start>) is BANNED iff v is suppressed, or v is <end> and t < min_length, or appending v would
+repeat an n-gram of size g already on the path.  Bans act before a row is cut to its k successors (st_beam_ban_topk takes the
+k most probable unbanned entries) and leave the probabilities alone: a cost stays the model's own -log p.  Every node inherits
+its parent's path inside the selection kernel (st_beam_select_hist), so a constrained iteration has the launches of an
+unconstrained one.  ``length_penalty`` a only re-ranks the harvested hypotheses, by cost / n**a.
 """
 import ctypes as C
 
@@ -20,6 +27,47 @@ import torch
 from ._lib import check, dtype_code as _dtc, lib
 from ._lib import ptr as _cp, stream as _stream
 from .rnn import CAP_MAX, up8
+
+# include/showtell_hip.h
+ST_BEAM_MAX_NGRAM, ST_BEAM_MAX_SUPPRESS, ST_BEAM_MAX_HIST, ST_BEAM_MAX_VOCAB = 16, 64, 64, 524288
+
+
+class BeamConstraints:
+    """The validated constraints of one search; ``active`` says whether the constrained kernels run at all (any of the three set:
+    an empty ``suppress_tokens`` list counts, so ``suppress_tokens=[]`` is the constrained path with an empty ban set).
+    ``keep_paths``: the search carries every node's path (needed for n-gram blocking, kept whenever it fits)."""
+
+    def __init__(self, vocab_size, max_length, min_length=0, no_repeat_ngram_size=0, suppress_tokens=None, length_penalty=0.0):
+        m, g = int(min_length), int(no_repeat_ngram_size)
+        if m != min_length or g != no_repeat_ngram_size:
+            raise ValueError(f"min_length and no_repeat_ngram_size must be integers (got {min_length}, {no_repeat_ngram_size})")
+        if m < 0:
+            raise ValueError(f"min_length must be >= 0 (got {m})")
+        if not 0 <= g <= ST_BEAM_MAX_NGRAM:
+            raise ValueError(f"no_repeat_ngram_size must be 0..{ST_BEAM_MAX_NGRAM} (got {g})")
+        sup = None if suppress_tokens is None else [int(v) for v in suppress_tokens]
+        if sup is not None:
+            if len(sup) > ST_BEAM_MAX_SUPPRESS:
+                raise ValueError(f"at most {ST_BEAM_MAX_SUPPRESS} suppress_tokens (got {len(sup)})")
+            bad = [v for v in sup if not 0 <= v < vocab_size]
+            if bad:
+                raise ValueError(f"suppress_tokens outside [0, {vocab_size}): {bad}")
+        if g > 0 and max_length + 1 > ST_BEAM_MAX_HIST:
+            raise ValueError(f"no_repeat_ngram_size needs max_length + 1 <= {ST_BEAM_MAX_HIST} (got max_length={max_length})")
+        a = float(length_penalty)
+        if a != a:
+            raise ValueError("length_penalty is NaN")
+        self.min_length, self.ngram, self.suppress, self.length_penalty = m, g, sup, a
+        self.active = m > 0 or g > 0 or sup is not None
+        if self.active and vocab_size > ST_BEAM_MAX_VOCAB:
+            raise ValueError(f"constrained beam search needs a vocabulary of at most {ST_BEAM_MAX_VOCAB} entries (got {vocab_size})")
+        self.keep_paths = self.active and max_length + 1 <= ST_BEAM_MAX_HIST
+
+    def suppress_on(self, device):
+        """(device tensor or None, count): the suppress list as st_beam_ban_topk takes it, uploaded once per search."""
+        if not self.suppress:
+            return None, 0
+        return torch.tensor(self.suppress, dtype=torch.long, device=device), len(self.suppress)
 
 
 class _Stepper:
@@ -69,6 +117,15 @@ class _Stepper:
         check(lib().st_softmax_topk(_cp(logits), self.Vp, n, self.V, k, _cp(p), _cp(i), int(raw), _stream()), "st_softmax_topk")
         return p.cpu().numpy(), i.cpu().numpy()
 
+    def ban_topk(self, logits, k, hist, hist_len, ngram, suppress, n_suppress, end_id, ban_end):
+        """topk(raw=False) over the entries outside each row's ban set; hist (n, ld) int32 on the device holds the rows' paths."""
+        n = logits.shape[0]
+        p = torch.empty(n, k, device=self.dev, dtype=torch.float32)
+        i = torch.empty(n, k, device=self.dev, dtype=torch.long)
+        check(lib().st_beam_ban_topk(_cp(logits), self.Vp, n, self.V, k, _cp(hist), hist.shape[1] if hist is not None else 0, hist_len,
+                                     ngram, _cp(suppress), n_suppress, end_id, int(ban_end), _cp(p), _cp(i), _stream()), "st_beam_ban_topk")
+        return p.cpu().numpy(), i.cpu().numpy()
+
 
 def _feat(rnn, cnn_feature):
     return rnn._feature(cnn_feature)
@@ -100,25 +157,37 @@ def quirky_beam(rnn, cnn_feature, beam_size, steps=CAP_MAX):
         return torch.tensor(old_sent[0], dtype=torch.long, device=cnn_feature.device)   # rnn.py:106-108
 
 
-def beam_search(rnn, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50, start_id=1, end_id=2, on_device=True):
+def beam_search(rnn, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50, start_id=1, end_id=2, on_device=True,
+                min_length=0, no_repeat_ngram_size=0, suppress_tokens=None, length_penalty=0.0):
     """beam_search.py:45-97 for every image of the batch; see ``beam_search_host`` for the contract.  With ``on_device`` (and
     beam_width**2 <= 64) the fringe selection of every iteration also runs on the GPU (``st_beam_select``) over fixed
     (image, slot) rows, so the whole search needs ONE host round trip instead of three per iteration; the Node bookkeeping
     (harvest order, stable sort of the hypotheses, parent back-tracking) is replayed on the host from the recorded fringes.
     The only arithmetic that differs from the host path is -log p: a correctly rounded float32 logarithm on the device, NumPy's
-    float32 log on the host (<= 1 ulp apart; the golden sequences are reproduced by both)."""
+    float32 log on the host (<= 1 ulp apart; the golden sequences are reproduced by both).
+
+    Constraints (module docstring): ``min_length`` words before <end>, ``no_repeat_ngram_size``, ``suppress_tokens`` (ids that never
+    appear) act inside the device loop; ``length_penalty`` a ranks the harvested hypotheses by cost / n**a (n tokens after <start>,
+    <end> included) and returns the raw cost.  With all four at their defaults the call is the launch sequence it was."""
     k = min(beam_width, rnn.vocab_size)
+    cons = dict(min_length=min_length, no_repeat_ngram_size=no_repeat_ngram_size, suppress_tokens=suppress_tokens)
     if not on_device or beam_width * k > 64:
-        return beam_search_host(rnn, cnn_feature, beam_width, num_hypotheses, max_length, start_id, end_id)
-    r = beam_search_records(rnn, cnn_feature, beam_width, max_length, start_id, end_id)
-    return replay_hypotheses(r["tok"], r["cost"], r["par"], r["end"], num_hypotheses)
+        return beam_search_host(rnn, cnn_feature, beam_width, num_hypotheses, max_length, start_id, end_id, length_penalty=length_penalty,
+                                **cons)
+    BeamConstraints(rnn.vocab_size, max_length, length_penalty=length_penalty, **cons)      # (length_penalty checked before the search)
+    r = beam_search_records(rnn, cnn_feature, beam_width, max_length, start_id, end_id, **cons)
+    return replay_hypotheses(r["tok"], r["cost"], r["par"], r["end"], num_hypotheses, length_penalty=length_penalty)
 
 
-def beam_search_records(rnn, cnn_feature, beam_width=4, max_length=50, start_id=1, end_id=2):
+def beam_search_records(rnn, cnn_feature, beam_width=4, max_length=50, start_id=1, end_id=2, min_length=0, no_repeat_ngram_size=0,
+                        suppress_tokens=None):
     """The device loop of ``beam_search`` on its own: every iteration's fringe over fixed (image, slot) rows, as numpy arrays
     dict(tok, cost, par [max_length+1][B][W], end [max_length][B][W]) -- what ``replay_hypotheses`` reads.  Needs
-    beam_width * min(beam_width, V) <= 64 (st_beam_select)."""
+    beam_width * min(beam_width, V) <= 64 (st_beam_select).  Under constraints the loop runs st_beam_ban_topk and
+    st_beam_select_hist in their place, and the records gain hist [B][W][max_length+1] int32: the path of every slot of the last
+    fringe, as the search itself kept it."""
     k = min(beam_width, rnn.vocab_size)
+    bc = BeamConstraints(rnn.vocab_size, max_length, min_length, no_repeat_ngram_size, suppress_tokens)
     with torch.no_grad():
         st = _Stepper(rnn)
         dev = st.dev
@@ -137,26 +206,58 @@ def beam_search_records(rnn, cnn_feature, beam_width=4, max_length=50, start_id=
         gidx = torch.empty(n, device=dev, dtype=torch.int32)
         tp = torch.empty(n, k, device=dev, dtype=torch.float32)
         ti = torch.empty(n, k, device=dev, dtype=torch.long)
+        hist = None
+        if bc.active:
+            sup, n_sup = bc.suppress_on(dev)
+            if bc.keep_paths:                                                         # two buffers: a fringe reads one, writes the other
+                ld = max_length + 1
+                hist = torch.zeros(2, n, ld, device=dev, dtype=torch.int32); hist[0, :, 0] = start_id
+                hp = (_cp(hist[0]), _cp(hist[1]))
         for t in range(max_length):                                                   # beam_search.py:69
             x = st.embed(tok.view(-1))
             logits, new_state = st.step(x, state)
-            check(lib().st_softmax_topk(_cp(logits), st.Vp, n, st.V, k, _cp(tp), _cp(ti), 0, _stream()), "st_softmax_topk")
             ntok, ncost = rec_tok[t + 1], rec_cost[t + 1]
-            check(lib().st_beam_select(_cp(tok), _cp(cost), _cp(done), _cp(tp), _cp(ti), B, W, k, end_id, _cp(ntok), _cp(ncost),
-                                       _cp(rec_par[t + 1]), _cp(rec_end[t]), _cp(gidx), _stream()), "st_beam_select")
+            if not bc.active:
+                check(lib().st_softmax_topk(_cp(logits), st.Vp, n, st.V, k, _cp(tp), _cp(ti), 0, _stream()), "st_softmax_topk")
+            else:                                                                     # the path of a fringe-t node has t + 1 tokens
+                check(lib().st_beam_ban_topk(_cp(logits), st.Vp, n, st.V, k, hp[t & 1] if hist is not None else None,
+                                             ld if hist is not None else 0, t + 1, bc.ngram, _cp(sup), n_sup, end_id,
+                                             int(t < bc.min_length), _cp(tp), _cp(ti), _stream()), "st_beam_ban_topk")
+            if hist is None:
+                check(lib().st_beam_select(_cp(tok), _cp(cost), _cp(done), _cp(tp), _cp(ti), B, W, k, end_id, _cp(ntok), _cp(ncost),
+                                           _cp(rec_par[t + 1]), _cp(rec_end[t]), _cp(gidx), _stream()), "st_beam_select")
+            else:
+                check(lib().st_beam_select_hist(_cp(tok), _cp(cost), _cp(done), _cp(tp), _cp(ti), B, W, k, end_id, _cp(ntok), _cp(ncost),
+                                                _cp(rec_par[t + 1]), _cp(rec_end[t]), _cp(gidx), hp[t & 1], hp[(t + 1) & 1], ld, t + 1,
+                                                _stream()), "st_beam_select_hist")
             state = st.gather(new_state, gidx)
             tok, cost = ntok, ncost
-        return dict(tok=rec_tok.cpu().numpy(), cost=rec_cost.cpu().numpy(), par=rec_par.cpu().numpy(), end=rec_end.cpu().numpy())
+        rec = dict(tok=rec_tok.cpu().numpy(), cost=rec_cost.cpu().numpy(), par=rec_par.cpu().numpy(), end=rec_end.cpu().numpy())
+        if hist is not None:
+            rec["hist"] = hist[max_length & 1].view(B, W, ld).cpu().numpy()
+        return rec
 
 
-def replay_hypotheses(h_tok, h_cost, h_par, h_end, num_hypotheses, alphas=None):
+def _ranked(hyp, num_hypotheses, length_penalty):
+    """The first `num_hypotheses` of harvested (iteration, slot, cost) triples: a stable sort by cost (beam_search.py:96) or, with
+    length_penalty a != 0, by cost / n**a in float64, n = the harvest iteration = the tokens after <start>, <end> included."""
+    if length_penalty == 0.0:
+        return sorted(hyp, key=lambda e: e[2])[:num_hypotheses]
+    return sorted(hyp, key=lambda e: float(e[2]) / float(max(e[0], 1)) ** length_penalty)[:num_hypotheses]
+
+
+def replay_hypotheses(h_tok, h_cost, h_par, h_end, num_hypotheses, alphas=None, length_penalty=0.0):
     """The Node bookkeeping of beam_search.py:69-97, replayed on the host from the records of a device search over fixed
     (image, slot) rows: h_tok / h_cost / h_par [max_length+1][B][W] (fringe after each iteration, parent slots),
     h_end [max_length][B][W] (harvest flags).  Returns, per image, at most `num_hypotheses` (tokens, cost) pairs.
 
     With `alphas` ([max_length][B*W][P], the attention map of every row at every iteration) each pair becomes
     (tokens, cost, extras), extras a float32 tensor (len(tokens) - 1, P): the extras of a node are the alpha computed while
-    producing it, i.e. that of its PARENT's row one iteration earlier, alphas[t-1][b*W + parent slot] for node (t, w)."""
+    producing it, i.e. that of its PARENT's row one iteration earlier, alphas[t-1][b*W + parent slot] for node (t, w).
+
+    `length_penalty` a ranks the hypotheses by cost / n**a instead (n = tokens after <start>, <end> included; float64 quotient of
+    the recorded float32 cost, stable); the returned cost stays the raw one."""
+    length_penalty = float(length_penalty)
     B, W = h_tok.shape[1], h_tok.shape[2]
     out = []
     for b in range(B):
@@ -164,7 +265,7 @@ def replay_hypotheses(h_tok, h_cost, h_par, h_end, num_hypotheses, alphas=None):
         for t, w in zip(*np.nonzero(h_end[:, b])):                                    # iteration-major, slot order inside (beam_search.py:72-76)
             hyp.append((int(t), int(w), h_cost[t, b, w]))
         res = []
-        for t, w, c in sorted(hyp, key=lambda e: e[2])[:num_hypotheses]:              # beam_search.py:96 (stable)
+        for t, w, c in _ranked(hyp, num_hypotheses, length_penalty):                  # beam_search.py:96 (stable)
             seq, ext = [], []
             while t >= 0 and w >= 0:
                 seq.append(int(h_tok[t, b, w]))
@@ -185,7 +286,8 @@ def replay_hypotheses(h_tok, h_cost, h_par, h_end, num_hypotheses, alphas=None):
     return out
 
 
-def beam_search_host(rnn, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50, start_id=1, end_id=2):
+def beam_search_host(rnn, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50, start_id=1, end_id=2, min_length=0,
+                     no_repeat_ngram_size=0, suppress_tokens=None, length_penalty=0.0):
     """beam_search.py:45-97 for every image of the batch.  Returns, per image, a list of at most
     `num_hypotheses` (token_sequence, cum_cost) pairs; the list is empty when no beam ever emitted
     `end_id` in time (the reference returns [] then).
@@ -194,7 +296,11 @@ def beam_search_host(rnn, cnn_feature, beam_width=4, num_hypotheses=1, max_lengt
     Node objects were 95 % of the time at 256 images) and reproduces the reference's order exactly: candidates are
     laid out node-major in fringe order, each node's k successors in ASCENDING probability (argsort(p)[-k:]), and cut
     with a STABLE sort on the float32 cumulative cost; finished nodes are harvested at the start of an iteration (so
-    nodes that end on the last iteration are never harvested), hypotheses are stably sorted by cost at the end."""
+    nodes that end on the last iteration are never harvested), hypotheses are stably sorted by cost at the end.
+
+    Under constraints every fringe node carries its path (`path`, beside the Node table) and its successors come from
+    st_beam_ban_topk; the hypotheses are ranked as ``replay_hypotheses`` ranks them."""
+    bc = BeamConstraints(rnn.vocab_size, max_length, min_length, no_repeat_ngram_size, suppress_tokens, length_penalty)
     with torch.no_grad():
         st = _Stepper(rnn)
         B = cnn_feature.shape[0]
@@ -211,12 +317,17 @@ def beam_search_host(rnn, cnn_feature, beam_width=4, num_hypotheses=1, max_lengt
         nid = np.full((B, W), -1, dtype=np.int64); nid[:, 0] = np.arange(B)
         valid = np.zeros((B, W), dtype=bool); valid[:, 0] = True
         done = np.zeros(B, dtype=bool)
-        hyp_nodes = [[] for _ in range(B)]                                            # (node id, cost) in harvest order
-        for _ in range(max_length):                                                   # beam_search.py:69
+        hyp_nodes = [[] for _ in range(B)]                                            # (harvest iteration, node id, cost) in harvest order
+        path = None
+        if bc.active:
+            sup, n_sup = bc.suppress_on(st.dev)
+            if bc.keep_paths:
+                path = np.zeros((B, W, max_length + 1), dtype=np.int32); path[:, :, 0] = start_id
+        for t in range(max_length):                                                   # beam_search.py:69
             ended = valid & (tok == end_id) & ~done[:, None]                          # beam_search.py:72-76
             if ended.any():
                 for b, w in zip(*np.nonzero(ended)):
-                    hyp_nodes[b].append((int(nid[b, w]), cost[b, w]))
+                    hyp_nodes[b].append((t, int(nid[b, w]), cost[b, w]))
             live = valid & ~ended & ~done[:, None]
             done |= ~live.any(axis=1)                                                 # beam_search.py:78-79 (break)
             live &= ~done[:, None]
@@ -225,8 +336,13 @@ def beam_search_host(rnn, cnn_feature, beam_width=4, num_hypotheses=1, max_lengt
                 break
             x = st.embed(tok[lb, lw])
             logits, new_state = st.step(x, st.gather(state, row[lb, lw]))
-            tp, ti = st.topk(logits, k, raw=False)                                    # descending; argsort(p)[-k:] is ascending
-            nll = -np.log(tp[:, ::-1].astype(np.float32))                             # beam_search.py:87-92
+            if not bc.active:
+                tp, ti = st.topk(logits, k, raw=False)                                # descending; argsort(p)[-k:] is ascending
+            else:
+                hist = torch.from_numpy(np.ascontiguousarray(path[lb, lw])).to(st.dev) if path is not None else None
+                tp, ti = st.ban_topk(logits, k, hist, t + 1, bc.ngram, sup, n_sup, end_id, t < bc.min_length)
+            with np.errstate(divide="ignore"):                                        # (a missing successor, p = 0, costs +inf)
+                nll = -np.log(tp[:, ::-1].astype(np.float32))                         # beam_search.py:87-92
             cand_cost = np.full((B, W, k), np.inf, dtype=np.float32)
             cand_tok = np.zeros((B, W, k), dtype=np.int64)
             cand_row = np.zeros((B, W, k), dtype=np.int64)
@@ -235,6 +351,7 @@ def beam_search_host(rnn, cnn_feature, beam_width=4, num_hypotheses=1, max_lengt
             cand_tok[lb, lw] = ti[:, ::-1]
             cand_row[lb, lw] = np.arange(lb.size)[:, None]
             cand_par[lb, lw] = nid[lb, lw][:, None]
+            cand_slot = np.broadcast_to(np.arange(W)[None, :, None], (B, W, k))
             flat = cand_cost.reshape(B, W * k)
             order = np.argsort(flat, axis=1, kind="stable")[:, :W]                    # beam_search.py:94 (stable sorted()[:beam_width])
             take = np.take_along_axis
@@ -243,6 +360,9 @@ def beam_search_host(rnn, cnn_feature, beam_width=4, num_hypotheses=1, max_lengt
             tok = take(cand_tok.reshape(B, W * k), order, 1)
             row = take(cand_row.reshape(B, W * k), order, 1)
             par = take(cand_par.reshape(B, W * k), order, 1)
+            if path is not None:                                                      # a child's path = its parent's + its token
+                path = take(path, take(cand_slot.reshape(B, W * k), order, 1)[:, :, None], 1)
+                path[:, :, t + 1] = tok
             cost = np.where(valid, new_cost, np.float32(np.inf)).astype(np.float32)
             # register the new nodes
             vb, vw = np.nonzero(valid)
@@ -254,9 +374,9 @@ def beam_search_host(rnn, cnn_feature, beam_width=4, num_hypotheses=1, max_lengt
         parent = np.concatenate(node_parent); value = np.concatenate(node_value)
         out = []
         for b in range(B):
-            hy = sorted(hyp_nodes[b], key=lambda t: t[1])[:num_hypotheses]            # beam_search.py:96 (stable)
+            hy = _ranked(hyp_nodes[b], num_hypotheses, bc.length_penalty)             # beam_search.py:96 (stable)
             res = []
-            for node, c in hy:
+            for _, node, c in hy:
                 seq = []
                 while node >= 0:
                     seq.append(int(value[node])); node = int(parent[node])

@@ -497,8 +497,9 @@ extern "C" int st_attn_sched_inputs(const st_attn_params* p, const float* cnn_fe
 // Fixed (image, slot) rows b*W + w as in beam.py: every iteration is one set of launches over the B*W rows and the fringe
 // selection runs on the device (st_beam_select), so the caller reads the records back once and replays the Node bookkeeping.
 namespace {
-struct BPlan : AttnPrep { int n, k; size_t h[2], c[2], x, z, att2, logits, tp, ti, gidx, slot, done, alpha, total; };
-BPlan make_bplan(const st_attn_params* p, int B, int W) {
+// hist_ld > 0 (the constrained search): the two path buffers follow the unconstrained plan, whose offsets and total stay as they are
+struct BPlan : AttnPrep { int n, k; size_t h[2], c[2], x, z, att2, logits, tp, ti, gidx, slot, done, alpha, hist[2], total; };
+BPlan make_bplan(const st_attn_params* p, int B, int W, int hist_ld = 0) {
   const st_rnn_params& r = p->rnn;
   const size_t es = st_dtype_size(r.dtype);
   BPlan q; Arena ar;
@@ -514,15 +515,21 @@ BPlan make_bplan(const st_attn_params* p, int B, int W) {
   q.tp = ar.take(n * q.k * sizeof(float)); q.ti = ar.take(n * q.k * sizeof(long));
   q.gidx = ar.take(n * sizeof(int)); q.slot = ar.take(n * sizeof(int)); q.done = ar.take((size_t)B);
   q.alpha = ar.take(n * p->P * sizeof(float));
+  for (int i = 0; i < 2; ++i) q.hist[i] = hist_ld > 0 ? ar.take(n * hist_ld * sizeof(int)) : 0;
   q.total = ar.o;
   return q;
 }
 
+// what st_attn_beam_search_ex adds to the search
+struct BeamLimits { int min_length, ngram; const long* suppress; int n_suppress; };
+
 // slot (b, w) <- image b; fringe 0 = the root alone: slot 0 holds start_id at cost 0, the others are empty (cost +inf)
+// (hist0, nullable: every row's path starts with start_id)
 __global__ void beam_seed_kernel(int B, int W, long start_id, int* __restrict__ slot, long* __restrict__ tok0, float* __restrict__ cost0,
-                                 int* __restrict__ par0, uint8_t* __restrict__ done) {
+                                 int* __restrict__ par0, uint8_t* __restrict__ done, int* __restrict__ hist0, int hist_ld) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < B * W) {
+    if (hist0) hist0[(long)i * hist_ld] = (int)start_id;
     const int w = i % W;
     slot[i] = i / W;
     tok0[i] = w == 0 ? start_id : 0;
@@ -531,24 +538,30 @@ __global__ void beam_seed_kernel(int B, int W, long start_id, int* __restrict__ 
   }
   if (i < B) done[i] = 0;
 }
-}  // namespace
 
-extern "C" size_t st_attn_beam_workspace_bytes(const st_attn_params* p, int B, int W) {
-  if (!p || B <= 0 || W < 1 || W > 8) return 0;
-  return make_bplan(p, B, W).total;
-}
-
-extern "C" int st_attn_beam_search(const st_attn_params* p, const float* cnn_feature, int B, int W, int max_length,
-                                   long start_id, long end_id, void* workspace, size_t workspace_bytes,
-                                   long* rec_tok, float* rec_cost, int* rec_par, uint8_t* rec_end, float* rec_alpha, void* stream) {
-  if (check_common(p, nullptr, "st_attn_beam_search")) return 1;
-  ST_CHECK(cnn_feature && workspace && rec_tok && rec_cost && rec_par && rec_end && B > 0, "st_attn_beam_search: bad arguments");
-  ST_CHECK(W >= 1 && W <= 8, "st_attn_beam_search: beam width must be 1..8 (got %d)", W);
-  ST_CHECK(max_length >= 1, "st_attn_beam_search: max_length must be >= 1 (got %d)", max_length);
+// The search of st_attn_beam_search (lim == nullptr) and st_attn_beam_search_ex: one loop, in which the constrained form swaps
+// st_softmax_topk / st_beam_select for st_beam_ban_topk / st_beam_select_hist.
+int attn_beam_run(const st_attn_params* p, const float* cnn_feature, int B, int W, int max_length, long start_id, long end_id,
+                  void* workspace, size_t workspace_bytes, long* rec_tok, float* rec_cost, int* rec_par, uint8_t* rec_end, float* rec_alpha,
+                  const BeamLimits* lim, void* stream, const char* who) {
+  if (check_common(p, nullptr, who)) return 1;
+  ST_CHECK(cnn_feature && workspace && rec_tok && rec_cost && rec_par && rec_end && B > 0, "%s: bad arguments", who);
+  ST_CHECK(W >= 1 && W <= 8, "%s: beam width must be 1..8 (got %d)", who, W);
+  ST_CHECK(max_length >= 1, "%s: max_length must be >= 1 (got %d)", who, max_length);
   const st_rnn_params& r = p->rnn;
-  ST_CHECK(r.w_lin && r.b_lin, "st_attn_beam_search: null vocabulary projection");
-  const BPlan q = make_bplan(p, B, W);
-  ST_CHECK(workspace_bytes >= q.total, "st_attn_beam_search: workspace too small (%zu < %zu)", workspace_bytes, q.total);
+  ST_CHECK(r.w_lin && r.b_lin, "%s: null vocabulary projection", who);
+  // the paths are kept whenever they fit (n-gram blocking needs them; without them the selection is st_beam_select's)
+  const int hist_ld = lim && max_length + 1 <= ST_BEAM_MAX_HIST ? max_length + 1 : 0;
+  if (lim) {
+    ST_CHECK(lim->min_length >= 0, "%s: min_length must be >= 0 (got %d)", who, lim->min_length);
+    ST_CHECK(lim->ngram >= 0 && lim->ngram <= ST_BEAM_MAX_NGRAM, "%s: no_repeat_ngram_size must be 0..%d (got %d)", who, ST_BEAM_MAX_NGRAM, lim->ngram);
+    ST_CHECK(lim->n_suppress >= 0 && lim->n_suppress <= ST_BEAM_MAX_SUPPRESS && (lim->n_suppress == 0 || lim->suppress),
+             "%s: at most %d suppressed tokens (got %d)", who, ST_BEAM_MAX_SUPPRESS, lim->n_suppress);
+    ST_CHECK(lim->ngram == 0 || hist_ld > 0, "%s: n-gram blocking needs max_length + 1 <= %d (got %d)", who, ST_BEAM_MAX_HIST, max_length + 1);
+    ST_CHECK(r.V <= ST_BEAM_MAX_VOCAB, "%s: V=%d exceeds the ban bitmap's %d entries", who, r.V, ST_BEAM_MAX_VOCAB);
+  }
+  const BPlan q = make_bplan(p, B, W, hist_ld);
+  ST_CHECK(workspace_bytes >= q.total, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, q.total);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   char* ws = reinterpret_cast<char*>(workspace);
   const int dt = r.dtype, H = r.H, E = r.E, L = r.L, P = p->P, A = p->A, F = p->F, Vp = st_up8(r.V), n = q.n, k = q.k;
@@ -563,7 +576,9 @@ extern "C" int st_attn_beam_search(const st_attn_params* p, const float* cnn_fea
   long* ti = reinterpret_cast<long*>(ws + q.ti);
 
   if (prepare(p, cnn_feature, B, ws, q, stream)) return 1;
-  hipLaunchKernelGGL(beam_seed_kernel, dim3((n + 255) / 256), dim3(256), 0, st, B, W, start_id, slot, rec_tok, rec_cost, rec_par, done);
+  int* hist[2] = {reinterpret_cast<int*>(ws + q.hist[0]), reinterpret_cast<int*>(ws + q.hist[1])};
+  hipLaunchKernelGGL(beam_seed_kernel, dim3((n + 255) / 256), dim3(256), 0, st, B, W, start_id, slot, rec_tok, rec_cost, rec_par, done,
+                     hist_ld ? hist[0] : nullptr, hist_ld);
   ST_LAUNCH_CHECK();
   // h0 (c0) repeated over the layers (rnn_attn.py:62), then scattered to the slots of its image
   if (replicate_rows_launch(ws + q.h0, ws + q.h[1], (long)B * H, L, dt, st)) return 1;
@@ -582,11 +597,50 @@ extern "C" int st_attn_beam_search(const st_attn_params* p, const float* cnn_fea
     if (attn_beam_fwd_launch(ws + q.att1, att2, p->w_full, p->b_full, ws + q.feat, alpha_t, ws + q.z, B, W, P, A, F, dt, st)) return 1;
     if (skinny(ws + q.z, F, p->w_embed, F, ws + q.x + (size_t)E * es, 2 * E, n, E, F, p->b_embed, 0, dt, st, true)) return 1;
     if (st_rnn_step(&r, ws + q.x, n, ws + q.h[0], lstm ? ws + q.c[0] : nullptr, ws + q.h[1], lstm ? ws + q.c[1] : nullptr, logits, Vp, stream)) return 1;
-    if (st_softmax_topk(logits, Vp, n, r.V, k, tp, ti, 0, stream)) return 1;
-    if (st_beam_select(tok, cost, done, tp, ti, B, W, k, end_id, rec_tok + (size_t)(t + 1) * n, rec_cost + (size_t)(t + 1) * n,
-                       rec_par + (size_t)(t + 1) * n, rec_end + (size_t)t * n, gidx, stream)) return 1;
+    long* ntok = rec_tok + (size_t)(t + 1) * n;
+    float* ncost = rec_cost + (size_t)(t + 1) * n;
+    int* npar = rec_par + (size_t)(t + 1) * n;
+    uint8_t* end_t = rec_end + (size_t)t * n;
+    if (!lim) {
+      if (st_softmax_topk(logits, Vp, n, r.V, k, tp, ti, 0, stream)) return 1;
+      if (st_beam_select(tok, cost, done, tp, ti, B, W, k, end_id, ntok, ncost, npar, end_t, gidx, stream)) return 1;
+    } else {                                                                               // the path of fringe t has t + 1 tokens
+      if (st_beam_ban_topk(logits, Vp, n, r.V, k, hist_ld ? hist[t & 1] : nullptr, hist_ld, t + 1, lim->ngram, lim->suppress, lim->n_suppress,
+                           end_id, t < lim->min_length, tp, ti, stream)) return 1;
+      if (!hist_ld) {
+        if (st_beam_select(tok, cost, done, tp, ti, B, W, k, end_id, ntok, ncost, npar, end_t, gidx, stream)) return 1;
+      } else if (st_beam_select_hist(tok, cost, done, tp, ti, B, W, k, end_id, ntok, ncost, npar, end_t, gidx, hist[t & 1], hist[(t + 1) & 1], hist_ld,
+                              t + 1, stream)) return 1;
+    }
     if (st_gather_state(ws + q.h[1], gidx, ws + q.h[0], L, n, n, H, dt, stream)) return 1;   // a child inherits its parent's state
     if (lstm && st_gather_state(ws + q.c[1], gidx, ws + q.c[0], L, n, n, H, dt, stream)) return 1;
   }
   return 0;
+}
+}  // namespace
+
+extern "C" size_t st_attn_beam_workspace_bytes(const st_attn_params* p, int B, int W) {
+  if (!p || B <= 0 || W < 1 || W > 8) return 0;
+  return make_bplan(p, B, W).total;
+}
+
+extern "C" int st_attn_beam_search(const st_attn_params* p, const float* cnn_feature, int B, int W, int max_length,
+                                   long start_id, long end_id, void* workspace, size_t workspace_bytes,
+                                   long* rec_tok, float* rec_cost, int* rec_par, uint8_t* rec_end, float* rec_alpha, void* stream) {
+  return attn_beam_run(p, cnn_feature, B, W, max_length, start_id, end_id, workspace, workspace_bytes, rec_tok, rec_cost, rec_par, rec_end,
+                       rec_alpha, nullptr, stream, "st_attn_beam_search");
+}
+
+extern "C" size_t st_attn_beam_ex_workspace_bytes(const st_attn_params* p, int B, int W, int max_length) {
+  if (!p || B <= 0 || W < 1 || W > 8 || max_length < 1) return 0;
+  return make_bplan(p, B, W, max_length + 1 <= ST_BEAM_MAX_HIST ? max_length + 1 : 0).total;
+}
+
+extern "C" int st_attn_beam_search_ex(const st_attn_params* p, const float* cnn_feature, int B, int W, int max_length,
+                                      long start_id, long end_id, void* workspace, size_t workspace_bytes,
+                                      long* rec_tok, float* rec_cost, int* rec_par, uint8_t* rec_end, float* rec_alpha,
+                                      int min_length, int ngram, const long* suppress, int n_suppress, void* stream) {
+  const BeamLimits lim = {min_length, ngram, suppress, n_suppress};
+  return attn_beam_run(p, cnn_feature, B, W, max_length, start_id, end_id, workspace, workspace_bytes, rec_tok, rec_cost, rec_par, rec_end,
+                       rec_alpha, &lim, stream, "st_attn_beam_search_ex");
 }

@@ -66,14 +66,49 @@ __global__ __launch_bounds__(256) void gather_state_kernel(const T* __restrict__
   }
 }
 
+// The per-row ban set of constrained beam search (st_beam_ban_topk): a V-bit map in dynamic LDS, built by the row's block from
+//   the suppress list, <end> while the caption is shorter than min_length (ban_end), and n-gram blocking: with the row's path
+//   s_0 .. s_t in hist (t = hist_len - 1) and g = ngram, every s[i+g-1] whose g-1 predecessors s[i .. i+g-2] equal the path's
+//   last g-1 tokens s[t-g+2 .. t] (0 <= i <= t-g+1; g = 1 bans every token of the path).
+// A banned entry keeps its share of the softmax (the maximum and the sum run over the whole row); it is only never selected.
+struct BanSet {
+  const int* hist; int hist_ld, hist_len, ngram;
+  const long* suppress; int n_suppress;
+  long end_id; int ban_end;
+};
+extern __shared__ unsigned ban_bits[];
+
+__device__ __forceinline__ bool banned(int i) { return (ban_bits[i >> 5] >> (i & 31)) & 1u; }
+__device__ __forceinline__ void ban(long v, int V) { if (v >= 0 && v < V) atomicOr(&ban_bits[v >> 5], 1u << (v & 31)); }
+
+__device__ __forceinline__ void build_ban_set(const BanSet& bs, int row, int V) {
+  for (int i = threadIdx.x; i < (V + 31) / 32; i += blockDim.x) ban_bits[i] = 0u;
+  __syncthreads();
+  for (int i = threadIdx.x; i < bs.n_suppress; i += blockDim.x) ban(bs.suppress[i], V);
+  if (threadIdx.x == 0 && bs.ban_end) ban(bs.end_id, V);
+  if (bs.ngram > 0) {
+    const int* h = bs.hist + (long)row * bs.hist_ld;
+    const int g = bs.ngram, len = bs.hist_len;
+    for (int i = threadIdx.x; i + g <= len; i += blockDim.x) {   // one thread per start i of an earlier n-gram
+      bool match = true;
+      for (int q = 0; q < g - 1; ++q) match &= h[i + q] == h[len - g + 1 + q];
+      if (match) ban(h[i + g - 1], V);
+    }
+  }
+  __syncthreads();
+}
+
 // Per row: softmax probabilities (fp32) of the k largest logits, in DESCENDING order, with their indices.
 // raw != 0: rank and return the raw logits instead (rnn.py:90-91 uses topk on result_state directly).
+// BAN: the k largest entries outside the row's ban set; a row with fewer than k of them ends in (p = 0, id = 0) entries.
+template <bool BAN>
 __global__ __launch_bounds__(256) void softmax_topk_kernel(const float* __restrict__ logits, int ldl, int V, int k,
-                                                           float* __restrict__ top_p, long* __restrict__ top_id, int raw) {
+                                                           float* __restrict__ top_p, long* __restrict__ top_id, int raw, BanSet bs) {
   __shared__ float sv[4]; __shared__ int si[4]; __shared__ float ssum[4];
   __shared__ int chosen[32];
   const int row = blockIdx.x, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const float* l = logits + (long)row * ldl;
+  if constexpr (BAN) build_ban_set(bs, row, V);
   float M = -INFINITY;
   for (int i = threadIdx.x; i < V; i += blockDim.x) M = fmaxf(M, l[i]);
   M = wave_max(M);
@@ -91,6 +126,7 @@ __global__ __launch_bounds__(256) void softmax_topk_kernel(const float* __restri
     for (int i = threadIdx.x; i < V; i += blockDim.x) {
       bool used = false;
       for (int q = 0; q < j; ++q) used |= (chosen[q] == i);
+      if constexpr (BAN) used |= banned(i);
       const float v = l[i];
       if (!used && ranks_before(v, i, best, bi)) { best = v; bi = i; }
     }
@@ -114,24 +150,32 @@ __global__ __launch_bounds__(256) void softmax_topk_kernel(const float* __restri
 //           appended to a candidate list in LDS (typically k .. 2k entries);
 //   then k rounds of a block-wide arg-max over the candidates, value descending, first index wins: the reference's order.
 // More than 256 candidates (rows of equal logits): the block falls back to a serial selection by one wave over the row.
+// BAN: the row maximum M still runs over every entry, the thread maxima behind T over the unbanned ones only (so that T stays a lower
+// bound of the k-th largest UNBANNED element), and only unbanned elements become candidates.
+template <bool BAN>
 __global__ __launch_bounds__(256) void softmax_topk_thr_kernel(const float* __restrict__ logits, int ldl, int V, int k,
-                                                               float* __restrict__ top_p, long* __restrict__ top_id, int raw) {
+                                                               float* __restrict__ top_p, long* __restrict__ top_id, int raw, BanSet bs) {
   constexpr int CAP = 256, UN = 8;
   __shared__ float sv[4]; __shared__ int si[4]; __shared__ float ssum[4];
   __shared__ float cv[CAP]; __shared__ int ci[CAP]; __shared__ int cnt;
   const int row = blockIdx.x, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const float* l = logits + (long)row * ldl;
   if (threadIdx.x == 0) cnt = 0;
+  if constexpr (BAN) build_ban_set(bs, row, V);
   // rows of up to 256 x 40 entries (V = 10000) stay in registers between the passes: the row is read ONCE
   constexpr int NK = 40;
   const bool keep = V <= 256 * NK;
   float rv[NK];
-  float tm = -INFINITY;
+  float tm = -INFINITY, tu = -INFINITY;                      // thread maximum over all / over the unbanned entries (BAN)
   if (keep) {
 #pragma unroll
     for (int j = 0; j < NK; ++j) { const int i = (int)threadIdx.x + 256 * j; rv[j] = i < V ? l[i] : -INFINITY; }
 #pragma unroll
     for (int j = 0; j < NK; ++j) tm = fmaxf(tm, rv[j]);
+    if constexpr (BAN) {
+#pragma unroll
+      for (int j = 0; j < NK; ++j) { const int i = (int)threadIdx.x + 256 * j; if (i < V && !banned(i)) tu = fmaxf(tu, rv[j]); }
+    }
   } else {
     for (int i0 = threadIdx.x; i0 < V; i0 += UN * 256) {
       float vv[UN];
@@ -139,6 +183,10 @@ __global__ __launch_bounds__(256) void softmax_topk_thr_kernel(const float* __re
       for (int u = 0; u < UN; ++u) vv[u] = i0 + u * 256 < V ? l[i0 + u * 256] : -INFINITY;
 #pragma unroll
       for (int u = 0; u < UN; ++u) tm = fmaxf(tm, vv[u]);
+      if constexpr (BAN) {
+#pragma unroll
+        for (int u = 0; u < UN; ++u) { const int i = i0 + u * 256; if (i < V && !banned(i)) tu = fmaxf(tu, vv[u]); }
+      }
     }
   }
   float M = wave_max(tm);
@@ -146,7 +194,7 @@ __global__ __launch_bounds__(256) void softmax_topk_thr_kernel(const float* __re
   __syncthreads();
   M = fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3]));
   // T = the k-th largest thread maximum (k rounds of a block arg-max over (tm, thread); the winner retires)
-  float T = -INFINITY, mine = tm;
+  float T = -INFINITY, mine = BAN ? tu : tm;
   for (int j = 0; j < k; ++j) {
     float best = mine; int bi = (int)threadIdx.x;
     block_first(best, bi, sv, si);
@@ -156,7 +204,9 @@ __global__ __launch_bounds__(256) void softmax_topk_thr_kernel(const float* __re
   float S = 0.f;
   auto visit = [&](float v, int i) {                         // (elements in the order of softmax_topk_kernel: i = thread, thread + 256, ..)
     if (!raw) S += expf(v - M);
-    if (v >= T) { const int p = atomicAdd(&cnt, 1); if (p < CAP) { cv[p] = v; ci[p] = i; } }
+    bool cand = v >= T;
+    if constexpr (BAN) cand = cand && !banned(i);
+    if (cand) { const int p = atomicAdd(&cnt, 1); if (p < CAP) { cv[p] = v; ci[p] = i; } }
   };
   if (keep) {
 #pragma unroll
@@ -185,6 +235,7 @@ __global__ __launch_bounds__(256) void softmax_topk_thr_kernel(const float* __re
         for (int i = lane; i < V; i += 64) {
           bool used = false;
           for (int q = 0; q < j; ++q) used |= (chosen[q] == i);
+          if constexpr (BAN) used |= banned(i);
           const float v = l[i];
           if (!used && ranks_before(v, i, best, bi)) { best = v; bi = i; }
         }
@@ -658,9 +709,41 @@ extern "C" int st_softmax_topk(const float* logits, int ldl, int n, int V, int k
   static int slow = -1;
   if (slow < 0) { const char* e = getenv("ST_TOPK_SLOW"); slow = e ? atoi(e) : 0; }
   if (k <= 8 && !slow && (long)k * 256 <= V)
-    hipLaunchKernelGGL(softmax_topk_thr_kernel, dim3(n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), logits, ldl, V, k, top_p, top_id, raw);
+    hipLaunchKernelGGL(softmax_topk_thr_kernel<false>, dim3(n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), logits, ldl, V, k, top_p,
+                       top_id, raw, BanSet{});
   else
-    hipLaunchKernelGGL(softmax_topk_kernel, dim3(n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), logits, ldl, V, k, top_p, top_id, raw);
+    hipLaunchKernelGGL(softmax_topk_kernel<false>, dim3(n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), logits, ldl, V, k, top_p, top_id,
+                       raw, BanSet{});
+  ST_LAUNCH_CHECK();
+  return 0;
+}
+
+// st_softmax_topk (probabilities) over the entries outside each row's ban set: the same two kernels with the predicate compiled in,
+// chosen by the same rule, so an empty ban set gives st_softmax_topk's bits.
+extern "C" int st_beam_ban_topk(const float* logits, int ldl, int n, int V, int k, const int* hist, int hist_ld, int hist_len, int ngram,
+                                const long* suppress, int n_suppress, long end_id, int ban_end, float* top_p, long* top_id, void* stream) {
+  ST_CHECK(logits && top_p && top_id, "st_beam_ban_topk: null pointer");
+  ST_CHECK(k >= 1 && k <= 32 && k <= V && ldl >= V, "st_beam_ban_topk: need 1 <= k <= min(32, V)");
+  ST_CHECK(V <= ST_BEAM_MAX_VOCAB, "st_beam_ban_topk: V=%d exceeds the ban bitmap's %d entries", V, ST_BEAM_MAX_VOCAB);
+  ST_CHECK(ngram >= 0 && ngram <= ST_BEAM_MAX_NGRAM, "st_beam_ban_topk: no_repeat_ngram_size must be 0..%d (got %d)", ST_BEAM_MAX_NGRAM, ngram);
+  ST_CHECK(ngram == 0 || (hist && hist_len >= 1 && hist_len <= hist_ld && hist_len <= ST_BEAM_MAX_HIST),
+           "st_beam_ban_topk: n-gram blocking needs a history of 1..%d tokens within hist_ld (got %d, ld %d)", ST_BEAM_MAX_HIST, hist_len, hist_ld);
+  ST_CHECK(n_suppress >= 0 && n_suppress <= ST_BEAM_MAX_SUPPRESS && (n_suppress == 0 || suppress),
+           "st_beam_ban_topk: at most %d suppressed tokens (got %d)", ST_BEAM_MAX_SUPPRESS, n_suppress);
+  if (n <= 0) return 0;
+  static int slow = -1;
+  if (slow < 0) { const char* e = getenv("ST_TOPK_SLOW"); slow = e ? atoi(e) : 0; }
+  const BanSet bs = {hist, hist_ld, hist_len, ngram, suppress, n_suppress, end_id, ban_end};
+  const size_t lds = (size_t)((V + 31) / 32) * sizeof(unsigned);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const bool thr = k <= 8 && !slow && (long)k * 256 <= V;
+  if (lds > 32768) {                                         // a large bitmap: allow it beside the kernels' static LDS (per device, so set per call)
+    const void* fn = thr ? reinterpret_cast<const void*>(softmax_topk_thr_kernel<true>) : reinterpret_cast<const void*>(softmax_topk_kernel<true>);
+    ST_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, ST_BEAM_MAX_VOCAB / 8) == hipSuccess,
+             "st_beam_ban_topk: cannot reserve LDS for the ban bitmap");
+  }
+  if (thr) hipLaunchKernelGGL(softmax_topk_thr_kernel<true>, dim3(n), dim3(256), lds, st, logits, ldl, V, k, top_p, top_id, 0, bs);
+  else hipLaunchKernelGGL(softmax_topk_kernel<true>, dim3(n), dim3(256), lds, st, logits, ldl, V, k, top_p, top_id, 0, bs);
   ST_LAUNCH_CHECK();
   return 0;
 }
@@ -672,12 +755,17 @@ extern "C" int st_softmax_topk(const float* logits, int ldl, int n, int V, int k
 // candidates in the reference's order -- node-major, each node's k successors in ASCENDING probability (argsort(p)[-k:]) --
 // cost = float32(cost[w] + (-log p)); the W best by a STABLE ranking (sorted(...)[:beam_width], :94) become the new fringe.
 // Outputs: new tok / cost, the parent slot of every new node, gather[b*W + w] = row of the parent's recurrent state.
+// HIST: every new node also inherits its parent's path: hist_out[b*W + rank] = hist_in[b*W + parent][0 .. hist_len) + its own token
+// (rows of hist_ld int32; an empty slot gets zeros), copied by the image's 64 threads -- what st_beam_ban_topk reads next iteration.
+template <bool HIST>
 __global__ __launch_bounds__(64) void beam_select_kernel(const long* __restrict__ tok, const float* __restrict__ cost, uint8_t* __restrict__ done,
                                                          const float* __restrict__ top_p, const long* __restrict__ top_id, int W, int k, long end_id,
                                                          long* __restrict__ new_tok, float* __restrict__ new_cost, int* __restrict__ parent,
-                                                         uint8_t* __restrict__ ended_rec, int* __restrict__ gather) {
+                                                         uint8_t* __restrict__ ended_rec, int* __restrict__ gather,
+                                                         const int* __restrict__ hist_in, int* __restrict__ hist_out, int hist_ld, int hist_len) {
   __shared__ float cc[64];
   __shared__ int any_live;
+  __shared__ int new_par[64], new_word[64];                  // HIST: parent slot (-1: empty) and token of the new slots
   const int b = blockIdx.x, c = threadIdx.x;
   const bool was_done = done[b] != 0;
   if (c == 0) any_live = 0;
@@ -711,6 +799,15 @@ __global__ __launch_bounds__(64) void beam_select_kernel(const long* __restrict_
       new_tok[b * W + rank] = ok ? top_id[(long)(b * W + w) * k + (k - 1 - j)] : 0;
       parent[b * W + rank] = ok ? w : -1;
       gather[b * W + rank] = b * W + (ok ? w : 0);
+      if constexpr (HIST) { new_par[rank] = ok ? w : -1; new_word[rank] = ok ? (int)top_id[(long)(b * W + w) * k + (k - 1 - j)] : 0; }
+    }
+  }
+  if constexpr (HIST) {
+    __syncthreads();
+    const int len = hist_len + 1;
+    for (int e = c; e < W * len; e += 64) {
+      const int r = e / len, pos = e - r * len, par = new_par[r];
+      hist_out[(long)(b * W + r) * hist_ld + pos] = pos == hist_len ? new_word[r] : (par >= 0 ? hist_in[(long)(b * W + par) * hist_ld + pos] : 0);
     }
   }
 }
@@ -719,8 +816,22 @@ extern "C" int st_beam_select(const long* tok, const float* cost, uint8_t* done,
                               long end_id, long* new_tok, float* new_cost, int* parent, uint8_t* ended, int* gather, void* stream) {
   ST_CHECK(tok && cost && done && top_p && top_id && new_tok && new_cost && parent && ended && gather, "st_beam_select: null pointer");
   ST_CHECK(B > 0 && W >= 1 && k >= 1 && k <= W && W * k <= 64, "st_beam_select: need 1 <= k <= W and W * k <= 64 (got W=%d k=%d)", W, k);
-  hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), tok, cost, done, top_p, top_id, W, k, end_id,
-                     new_tok, new_cost, parent, ended, gather);
+  hipLaunchKernelGGL(beam_select_kernel<false>, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), tok, cost, done, top_p, top_id, W, k,
+                     end_id, new_tok, new_cost, parent, ended, gather, nullptr, nullptr, 0, 0);
+  ST_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int st_beam_select_hist(const long* tok, const float* cost, uint8_t* done, const float* top_p, const long* top_id, int B, int W, int k,
+                                   long end_id, long* new_tok, float* new_cost, int* parent, uint8_t* ended, int* gather,
+                                   const int* hist_in, int* hist_out, int hist_ld, int hist_len, void* stream) {
+  ST_CHECK(tok && cost && done && top_p && top_id && new_tok && new_cost && parent && ended && gather && hist_in && hist_out && hist_in != hist_out,
+           "st_beam_select_hist: null pointer (or hist_in == hist_out)");
+  ST_CHECK(B > 0 && W >= 1 && k >= 1 && k <= W && W * k <= 64, "st_beam_select_hist: need 1 <= k <= W and W * k <= 64 (got W=%d k=%d)", W, k);
+  ST_CHECK(hist_len >= 1 && hist_len + 1 <= hist_ld && hist_len + 1 <= ST_BEAM_MAX_HIST,
+           "st_beam_select_hist: need 1 <= hist_len and hist_len + 1 <= min(hist_ld, %d) (got %d, ld %d)", ST_BEAM_MAX_HIST, hist_len, hist_ld);
+  hipLaunchKernelGGL(beam_select_kernel<true>, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), tok, cost, done, top_p, top_id, W, k,
+                     end_id, new_tok, new_cost, parent, ended, gather, hist_in, hist_out, hist_ld, hist_len);
   ST_LAUNCH_CHECK();
   return 0;
 }

@@ -290,7 +290,7 @@ class RNN_Attn(Decoder):
             return out + (alphas.view(B, S, T, P),) if return_alphas else out
 
     def beam_search(self, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50, start_id=1, end_id=2, return_alphas=False,
-                    return_records=False):
+                    return_records=False, min_length=0, no_repeat_ngram_size=0, suppress_tokens=None, length_penalty=0.0):
         """beam_search.py:45-97 for every image of the batch, driven by the test branch of rnn_attn.py:77-94: the root holds
         start_id with h0 = init_h(mean feature) over all layers (and c0 for the LSTM); a node's successors come from one step
         fed with the node's token, attention keyed on its top-layer state.  The whole search is one st_attn_beam_search call
@@ -300,17 +300,25 @@ class RNN_Attn(Decoder):
         With `return_alphas`: (tokens, cost, alphas), alphas a CPU float32 tensor (len(tokens) - 1, P) holding the extras of
         the nodes after the root: the attention map computed while producing each token.
         With `return_records`: (hypotheses, records), records the search's own numpy arrays dict(tok, cost, par
-        [max_length+1][B][W], end [max_length][B][W]) and, with `return_alphas`, alpha [max_length][B*W][P]."""
-        from .beam import replay_hypotheses
+        [max_length+1][B][W], end [max_length][B][W]) and, with `return_alphas`, alpha [max_length][B*W][P]; a constrained
+        search that keeps paths (max_length + 1 <= 64) adds hist [B][W][max_length+1] int32, the path of every slot of the last
+        fringe as the search itself kept it.
+        `min_length`, `no_repeat_ngram_size`, `suppress_tokens` and `length_penalty` constrain the search as in
+        RNN.beam_search (beam.py); with any of the first three set the call is st_attn_beam_search_ex."""
+        from .beam import BeamConstraints, replay_hypotheses
         if not 1 <= beam_width <= 8:
             raise ValueError(f"beam_width must be 1..8 (got {beam_width})")
         if max_length < 1:
             raise ValueError(f"max_length must be >= 1 (got {max_length})")
+        bc = BeamConstraints(self.vocab_size, max_length, min_length, no_repeat_ngram_size, suppress_tokens, length_penalty)
         with torch.no_grad():
             prm, keep, featc, B, P = self._decode_inputs(cnn_feature)
             W, T = beam_width, max_length
             n = B * W
-            nbytes = lib().st_attn_beam_workspace_bytes(C.byref(prm), B, W)
+            if bc.active:
+                nbytes = lib().st_attn_beam_ex_workspace_bytes(C.byref(prm), B, W, T)
+            else:
+                nbytes = lib().st_attn_beam_workspace_bytes(C.byref(prm), B, W)
             ws = torch.empty(nbytes, device=featc.device, dtype=torch.uint8)
             # the records share one buffer, so that the search ends in ONE device-to-host copy
             layout = [("tok", torch.long, (T + 1, B, W)), ("cost", torch.float32, (T + 1, B, W)), ("par", torch.int32, (T + 1, B, W)),
@@ -324,11 +332,26 @@ class RNN_Attn(Decoder):
                 o += (nb + 255) // 256 * 256
             rec = torch.empty(o, device=featc.device, dtype=torch.uint8)
             view = {name: rec[offs[name][0]:offs[name][0] + offs[name][1]].view(dt).view(shape) for name, dt, shape in layout}
-            check(lib().st_attn_beam_search(C.byref(prm), _cp(featc), B, W, T, int(start_id), int(end_id), _cp(ws), nbytes,
-                                            _cp(view["tok"]), _cp(view["cost"]), _cp(view["par"]), _cp(view["end"]),
-                                            _cp(view.get("alpha")), _stream()), "st_attn_beam_search")
+            if bc.active:
+                sup, n_sup = bc.suppress_on(featc.device)
+                check(lib().st_attn_beam_search_ex(C.byref(prm), _cp(featc), B, W, T, int(start_id), int(end_id), _cp(ws), nbytes,
+                                                   _cp(view["tok"]), _cp(view["cost"]), _cp(view["par"]), _cp(view["end"]),
+                                                   _cp(view.get("alpha")), bc.min_length, bc.ngram, _cp(sup), n_sup, _stream()),
+                      "st_attn_beam_search_ex")
+            else:
+                check(lib().st_attn_beam_search(C.byref(prm), _cp(featc), B, W, T, int(start_id), int(end_id), _cp(ws), nbytes,
+                                                _cp(view["tok"]), _cp(view["cost"]), _cp(view["par"]), _cp(view["end"]),
+                                                _cp(view.get("alpha")), _stream()), "st_attn_beam_search")
             host = rec.cpu().numpy()
+            hist = None
+            if return_records and bc.keep_paths:
+                # the two path buffers follow the unconstrained plan in the workspace (showtell_hip.h); the last fringe's is T & 1
+                base, nb = lib().st_attn_beam_workspace_bytes(C.byref(prm), B, W), n * (T + 1) * 4
+                off = base + (T & 1) * ((nb + 255) // 256 * 256)
+                hist = ws[off:off + nb].view(torch.int32).view(B, W, T + 1).cpu().numpy()
         npdt = {torch.long: np.int64, torch.float32: np.float32, torch.int32: np.int32, torch.uint8: np.uint8}
         h = {name: host[offs[name][0]:offs[name][0] + offs[name][1]].view(npdt[dt]).reshape(shape) for name, dt, shape in layout}
-        hyps = replay_hypotheses(h["tok"], h["cost"], h["par"], h["end"], num_hypotheses, h.get("alpha"))
+        hyps = replay_hypotheses(h["tok"], h["cost"], h["par"], h["end"], num_hypotheses, h.get("alpha"), bc.length_penalty)
+        if hist is not None:
+            h["hist"] = hist
         return (hyps, h) if return_records else hyps

@@ -1,0 +1,89 @@
+"""Time constrained beam search against the unconstrained one: bf16, the benchmark's decoder shape (E = H = 512, V = 10000,
+L = 5, B = 256 images, W = 5, max_length = 25), plain GRU and attention GRU (F = 2048, P = 49, A = 512).  Four calls, in
+alternating rounds in one process (host clock around whole searches, each of which ends in a device-to-host copy):
+
+  plain    beam_search(...) with every constraint at its default: st_softmax_topk + st_beam_select
+  empty    suppress_tokens=[]: st_beam_ban_topk + st_beam_select_hist with an empty ban set
+  g3       no_repeat_ngram_size=3
+  all      min_length=5, no_repeat_ngram_size=3, suppress_tokens=[<pad>, <start>, <unk>]
+
+The yardstick is the unconstrained search of ANOTHER build of the library, measured in the same rounds: ST_YARDSTICK_LIB names a
+libshowtell_hip.so built from the commit to compare with (without it the tool times the four calls alone).  A random decoder
+never emits <end>, so every image stays live for all 25 iterations: the most work a search can do."""
+import ctypes as C
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from oracle import restatement as R
+from showtell_amd import _lib
+from showtell_amd.rnn import RNN
+from showtell_amd.rnn_attn import RNN_Attn
+
+E = H = A = 512
+Fd, P, V, L, B, W, T = 2048, 49, 10000, 5, 256, 5, 25
+ROUNDS = int(os.environ.get("ROUNDS", "9"))
+CALLS = {"plain": {}, "empty": dict(suppress_tokens=[]), "g3": dict(no_repeat_ngram_size=3),
+         "all": dict(min_length=5, no_repeat_ngram_size=3, suppress_tokens=[0, 1, 3])}
+
+
+def _other_build(path):
+    """the entry points of another build of the library, bound like _lib's own (the ones it has)"""
+    cdll = C.CDLL(path)
+    b = _lib._Bound.__new__(_lib._Bound)
+    b.st_last_error = cdll.st_last_error
+    b.st_last_error.argtypes, b.st_last_error.restype = [], C.c_char_p
+    for name, (args, res) in _lib._SIGS.items():
+        if hasattr(cdll, name):
+            fn = getattr(cdll, name)
+            fn.argtypes, fn.restype = args, res
+            setattr(b, name, fn)
+    return b
+
+
+def main():
+    assert torch.cuda.is_available(), "needs a GPU"
+    ours = _lib.lib()
+    yard = _other_build(os.environ["ST_YARDSTICK_LIB"]) if os.environ.get("ST_YARDSTICK_LIB") else None
+    g = torch.Generator().manual_seed(31)
+    plain = RNN(E, H, V, L, dtype=torch.bfloat16)
+    plain.load_state_dict(R.init_decoder_params(E, H, V, L, "gru", seed=31))
+    attn = RNN_Attn(E, Fd, A, H, V, L, dtype=torch.bfloat16)
+    attn.load_state_dict(R.init_decoder_params(E, H, V, L, "gru", seed=31, attn=dict(F=Fd, A=A)))
+    models = {"plain GRU": (plain.cuda().eval(), torch.randn(B, E, generator=g).cuda()),
+              "attention GRU": (attn.cuda().eval(), torch.randn(B, Fd, P, generator=g).abs().cuda())}
+    for tag, (m, feat) in models.items():
+        names = (["yardstick"] if yard else []) + list(CALLS)
+
+        def run(name):
+            _lib._lib = yard if name == "yardstick" else ours
+            try:
+                t0 = time.perf_counter()
+                m.beam_search(feat, beam_width=W, num_hypotheses=1, max_length=T, **CALLS.get(name, {}))
+                torch.cuda.synchronize()
+                return time.perf_counter() - t0
+            finally:
+                _lib._lib = ours
+
+        for name in names * 2:                                                    # warm-up: every call twice
+            run(name)
+        times = {name: [] for name in names}
+        for r in range(ROUNDS):
+            for name in (names if r % 2 == 0 else names[::-1]):                   # alternating order
+                times[name].append(run(name))
+        print(f"{tag}, bf16, B={B} W={W} max_length={T}, {ROUNDS} alternating rounds; ms per search: median / min / max, "
+              f"and us per iteration against the first row")
+        base = None
+        for name in names:
+            ts = sorted(times[name])
+            med = ts[len(ts) // 2]
+            base = med if base is None else base
+            print(f"  {name:10s} {med * 1e3:8.3f} / {ts[0] * 1e3:8.3f} / {ts[-1] * 1e3:8.3f}    {(med - base) / T * 1e6:+7.2f} us/iteration"
+                  f"   (spread of its rounds {(ts[-1] - ts[0]) / T * 1e6:.2f} us/iteration)")
+
+
+if __name__ == "__main__":
+    main()
