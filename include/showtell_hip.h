@@ -425,6 +425,9 @@ typedef struct {
 /* leading dimension (elements) for the logits / dlogits rows of a V-entry vocabulary: up8(V) below 2048 entries, else V
  * rounded up to 512 (the backward product over K = V is then split into 8 even slices); pad columns are zero-filled */
 int st_rnn_vocab_ld(int V);
+/* st_rnn_workspace_bytes, st_rnn_greedy_workspace_bytes, st_rnn_sample_workspace_bytes, st_rnn_sched_inputs_workspace_bytes and
+ * the st_attn_*_workspace_bytes planners return 0 for a descriptor no entry point accepts: a null pointer, a batch below 1, a
+ * layer count outside [1, ST_MAX_LAYERS] (the *_dropout_bytes and *_fused_loss*_bytes counts do not look at the layer count) */
 size_t st_rnn_workspace_bytes(const st_rnn_params* p, const st_packed_seq* s);
 int st_rnn_forward(const st_rnn_params* p, const st_packed_seq* s, const void* x0_override, const void* feat,
                    void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,

@@ -19,6 +19,8 @@
 namespace {
 
 inline size_t mx(size_t a, size_t b) { return a > b ? a : b; }
+// the planners return 0 for a layer count that no entry point accepts
+inline bool layers_ok(const st_attn_params* p) { return p->rnn.L >= 1 && p->rnn.L <= ST_MAX_LAYERS; }
 
 // what prepare() fills, at the head of every attention workspace: feat_pf [B*P][F], its mean over P, h0, c0, att1 [B*P][A]
 struct AttnPrep {
@@ -135,7 +137,7 @@ int prepare(const st_attn_params* p, const float* cnn_feature, int B, char* ws, 
 }  // namespace
 
 extern "C" size_t st_attn_workspace_bytes(const st_attn_params* p, const st_packed_seq* s) {
-  if (!p || !s) return 0;
+  if (!p || !s || !layers_ok(p)) return 0;
   return make_plan(p, s).total;
 }
 
@@ -384,7 +386,7 @@ __global__ void fill_ids_kernel(long* cur, int n, long v) { const int i = blockI
 }  // namespace
 
 extern "C" size_t st_attn_greedy_workspace_bytes(const st_attn_params* p, int B) {
-  if (!p || B <= 0) return 0;
+  if (!p || B <= 0 || !layers_ok(p)) return 0;
   return make_gplan(p, B).total;
 }
 
@@ -461,7 +463,7 @@ extern "C" int st_attn_greedy_alphas(const st_attn_params* p, const float* cnn_f
 }
 
 extern "C" size_t st_attn_sample_workspace_bytes(const st_attn_params* p, int n) {
-  if (!p || n <= 0) return 0;
+  if (!p || n <= 0 || !layers_ok(p)) return 0;
   return make_gplan(p, n).total + st_al256((size_t)n);
 }
 
@@ -475,7 +477,7 @@ extern "C" int st_attn_sample(const st_attn_params* p, const float* cnn_feature,
 
 // ---- scheduled sampling: the roll-in of the attention decoders (the loop above following the caption) -----------------------------
 extern "C" size_t st_attn_sched_inputs_workspace_bytes(const st_attn_params* p, int n) {
-  if (!p || n <= 0) return 0;
+  if (!p || n <= 0 || !layers_ok(p)) return 0;
   return make_gplan(p, n).total;
 }
 
@@ -620,7 +622,7 @@ int attn_beam_run(const st_attn_params* p, const float* cnn_feature, int B, int 
 }  // namespace
 
 extern "C" size_t st_attn_beam_workspace_bytes(const st_attn_params* p, int B, int W) {
-  if (!p || B <= 0 || W < 1 || W > 8) return 0;
+  if (!p || B <= 0 || W < 1 || W > 8 || !layers_ok(p)) return 0;
   return make_bplan(p, B, W).total;
 }
 
@@ -632,7 +634,7 @@ extern "C" int st_attn_beam_search(const st_attn_params* p, const float* cnn_fea
 }
 
 extern "C" size_t st_attn_beam_ex_workspace_bytes(const st_attn_params* p, int B, int W, int max_length) {
-  if (!p || B <= 0 || W < 1 || W > 8 || max_length < 1) return 0;
+  if (!p || B <= 0 || W < 1 || W > 8 || max_length < 1 || !layers_ok(p)) return 0;
   return make_bplan(p, B, W, max_length + 1 <= ST_BEAM_MAX_HIST ? max_length + 1 : 0).total;
 }
 

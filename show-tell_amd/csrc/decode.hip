@@ -545,7 +545,7 @@ int argmax_rows_launch(const float* logits, int ldl, int n, int V, long* ids, in
 }
 
 extern "C" size_t st_rnn_greedy_workspace_bytes(const st_rnn_params* p, int B) {
-  if (!p || B <= 0) return 0;
+  if (!p || B <= 0 || p->L < 1 || p->L > ST_MAX_LAYERS) return 0;
   return make_greedy_plan(p, B).total;
 }
 

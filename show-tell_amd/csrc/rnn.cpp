@@ -93,7 +93,7 @@ int check_common(const st_rnn_params* p, const st_packed_seq* s, const char* who
 extern "C" int st_rnn_vocab_ld(int V) { return V < 2048 ? st_up8(V) : (V + 511) / 512 * 512; }
 
 extern "C" size_t st_rnn_workspace_bytes(const st_rnn_params* p, const st_packed_seq* s) {
-  if (!p || !s) return 0;
+  if (!p || !s || p->L < 1 || p->L > ST_MAX_LAYERS) return 0;   // 0: no entry point accepts this descriptor
   return make_plan(p, s).total;
 }
 

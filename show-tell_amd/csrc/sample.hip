@@ -278,7 +278,7 @@ SPlan make_splan(const st_rnn_params* p, int n) {
 }  // namespace
 
 extern "C" size_t st_rnn_sample_workspace_bytes(const st_rnn_params* p, int n) {
-  if (!p || n <= 0) return 0;
+  if (!p || n <= 0 || p->L < 1 || p->L > ST_MAX_LAYERS) return 0;
   return make_splan(p, n).total;
 }
 

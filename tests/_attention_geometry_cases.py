@@ -176,8 +176,9 @@ def _stored(x):
     return x + (R._round_bf16(x) - x).detach()
 
 
-def train_copy(params, feat, cap, lens, cell, fault=None, storage=False):
-    """R.attn_train_loss(alpha_c = 1) with att1 = encoder_att(feat) computed once.  Returns (loss, alphas, att1 (B, P, A)).
+def train_copy(params, feat, cap, lens, cell, fault=None, storage=False, return_logits=False):
+    """R.attn_train_loss(alpha_c = 1) with att1 = encoder_att(feat) computed once.  Returns (loss, alphas, att1 (B, P, A)), with
+    `return_logits` also the packed logits (N_tok, V).
     With `storage`, every forward value that make_plan (csrc/attn.cpp) keeps in a bf16 buffer is rounded to bf16 where it is
     stored: the mean feature, h0 (c0), att1, z, both halves of x, h after every cell and c of the LSTM (feat and the weights are
     bf16-representable already).  The backward stays float64."""
@@ -213,8 +214,9 @@ def train_copy(params, feat, cap, lens, cell, fault=None, storage=False):
         h, c = torch.stack(hs, 0), (torch.stack(cs, 0) if cs else None)
         preds[:bt, t] = inp @ params["linear.weight"].t() + params["linear.bias"]
         alphas[:bt, t] = alpha
-    loss = R.ce_loss(R.pack_rows(preds, lens), R.pack_rows(cap, lens)) + ((1.0 - alphas.sum(dim=1)) ** 2).mean()
-    return loss, alphas, att1
+    logits = R.pack_rows(preds, lens)
+    loss = R.ce_loss(logits, R.pack_rows(cap, lens)) + ((1.0 - alphas.sum(dim=1)) ** 2).mean()
+    return (loss, alphas, att1, logits) if return_logits else (loss, alphas, att1)
 
 
 @functools.lru_cache(maxsize=None)

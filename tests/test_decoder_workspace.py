@@ -34,6 +34,7 @@ RNN_SHAPES = {
     "narrow": (16, 40, 2, 50, RAGGED),                       # not pipe-eligible, nothing a multiple of a tile
     "v2047": (64, 64, 1, 2047, RAGGED),                      # the two branches of st_rnn_vocab_ld
     "v2049": (64, 64, 1, 2049, RAGGED),
+    "deep8": (32, 32, 8, 50, RAGGED),                        # ST_MAX_LAYERS: the per-layer terms of the planners
 }
 # name -> (E, H, L, V, F, A, P, lens); Np = up8(max(ntok, B * P))
 ATTN_SHAPES = {
@@ -42,6 +43,7 @@ ATTN_SHAPES = {
     "long_p49": (16, 40, 2, 50, 16, 16, 49, LONG),                           # ntok > B * P
     "long_p64": (16, 40, 2, 50, 16, 16, 64, LONG),
     "narrow_p4": (16, 40, 2, 50, 16, 16, 4, RAGGED),
+    "deep8_p10": (32, 32, 8, 50, 48, 40, 10, RAGGED),
 }
 VOCAB_LD = (50, 2040, 2047, 2048, 2049, 10000)
 BEAM_WIDTHS = (1, 8)
