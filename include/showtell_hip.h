@@ -82,6 +82,33 @@ int st_conv(const st_conv_desc* d, void* stream);
 int st_conv_batch(const st_conv_desc* d, int n, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Token-contraction GEMM (csrc/gemm_tn.hip), bf16 operands, fp32 result:
+ *   c[m][n] (+)= sum_k a[k][m] * b[k][n]            a: [K][lda], b: [K][ldb], both ROW-major, K the slow axis
+ * The parameter gradients of the decoder backward (autograd of nn.Linear / nn.GRU / nn.LSTM, main.py:151) contract over
+ * the tokens, which is the slow axis of every operand as stored; both tiles are read as they lie and transposed on the way
+ * out of LDS (ds_read_b64_tr_b16), so no K-major copy is made.  One workgroup owns an output tile over the whole of K:
+ * no atomics, two identical calls give bit-identical results.
+ * Requirements: dtype ST_BF16; lda >= M, ldb >= N, both multiples of 8; a and b 16-byte aligned; ldc >= N.
+ * Columns M .. lda of a and N .. ldb of b may hold anything.
+ * ---------------------------------------------------------------------------------- */
+typedef struct {
+  const void* a;        /* [K][lda] bf16                                                                   */
+  const void* b;        /* [K][ldb] bf16, or the matrix b_row indexes                                      */
+  float* c;             /* [M][ldc] fp32                                                                   */
+  const int* b_row;     /* [K] or NULL: row k of b is b[b_row[k]], a row of zeros where b_row[k] < 0       */
+  const int* b_live;    /* [K] or NULL (needs b_row): row k of b is zero where b_live[k] <= 0, b_row[k] is
+                         * then not read as an index (st_packed_seq.rows_t / prev_row: h_{t-1} of a token)   */
+  float* colsum0;       /* [M] or NULL: colsum0[m] += sum_k a[k][m] (always added, whatever `accumulate`)   */
+  float* colsum1;       /* [M] or NULL: the same sums added to a second vector                             */
+  int dtype;
+  int M, N, K;
+  int lda, ldb, ldc;
+  int accumulate;       /* 0: c = product; 1: c += product                                                 */
+} st_gemm_tn_desc;
+/* n <= 12 problems of any mix of shapes as ONE launch */
+int st_gemm_tn_batch(const st_gemm_tn_desc* d, int n, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Image-resident 3x3 stride-1 pad-1 convolution, bf16 (the conv2 of torchvision's Bottleneck / the convs of BasicBlock
  * behind `self.model(x)`, reference cnn.py:46 / cnn_attn.py:46; csrc/conv_img.hip).  A workgroup keeps a band of one
  * image (+ zero halo) in LDS for all nine taps, the filter bank streams fragment-major from HBM/L2 straight into MFMA

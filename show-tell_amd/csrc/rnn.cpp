@@ -16,8 +16,9 @@
 // backward: dlogits -> dW_lin, db_lin, dy_top; per diagonal (reversed) ONE fused launch in the pull form: cell (l, t) computes
 //           dh = [dy_top] + dgh_{l,t+1} W_hh_l + dgx_{l+1,t} W_ih_{l+1} + its dh z carry from what the diagonal above wrote and
 //           does its gate gradients in the epilogue (22 dependent launches, no fp32 dy round trip below the top layer);
-//           dx0 = dgx_0 W_ih_0 is one whole-sequence GEMM after the wavefront; then per layer two MFMA GEMMs (dW_ih, dW_hh)
-//           whose K-major operands come from transposes that also sum the bias gradients.  ST_BPTT_FUSED=0 keeps the
+//           dx0 = dgx_0 W_ih_0 is one whole-sequence GEMM after the wavefront; then every weight gradient (dW_lin, dW_ih_l, dW_hh_l)
+//           with its bias gradient in grouped token-contraction launches that read the operands as they lie (bf16: st_gemm_tn_batch;
+//           fp32 and ST_WGRAD_TN=0: K-major copies from transposes that also sum the bias gradients, then MFMA GEMMs).  ST_BPTT_FUSED=0 keeps the
 //           earlier push route (a gate-gradient launch and a skinny-GEMM launch per diagonal)
 //           -> st_rnn_backward
 // dropout:  the _drop forms of the entry points take an st_dropout (NULL: the calls above, launch for launch).  The input rows and the
@@ -338,14 +339,35 @@ int rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_
   float* dy = dyl(L - 1);
   const char* ytop = dp.out ? dp.rows(L - 1) : ws + q.y + (size_t)(p->L - 1) * n * H * es;   // what `linear` read
 
+  // bf16: every weight gradient (and the bias gradient that goes with it) is a token contraction of operands read as they lie
+  // (st_gemm_tn_batch, csrc/gemm_tn.hip), collected here and sent as grouped launches after the wavefront.  ST_WGRAD_TN=0 (read per
+  // call: A/B runs, tests) keeps the K-major copies and st_gemm_nt, which is also what fp32 runs (the transposed LDS read is a
+  // 16-bit one).  The regions tA, tB, gA and gB of the workspace stay reserved for that route.
+  const char* env_tn = getenv("ST_WGRAD_TN");
+  const bool tn = dt == ST_BF16 && !(env_tn && env_tn[0] == '0');
+  st_gemm_tn_desc tg[2 * ST_MAX_LAYERS + 1];
+  int ntg = 0;
+  auto tn_desc = [&](const void* a, int lda, const void* b, int ldb, float* c, int rows, int cols, float* cs0, float* cs1, bool hprev) {
+    st_gemm_tn_desc d;                             // c[rows][cols] += a[n][rows]^T b[n][cols]
+    memset(&d, 0, sizeof(d));
+    d.a = a; d.b = b; d.c = c; d.colsum0 = cs0; d.colsum1 = cs1; d.dtype = dt;
+    d.M = rows; d.N = cols; d.K = n; d.lda = lda; d.ldb = ldb; d.ldc = cols; d.accumulate = 1;
+    if (hprev) { d.b_row = s->prev_row; d.b_live = s->rows_t; }   // row r of b is y[prev_row[r]], zero at t = 0
+    return d;
+  };
+
   if (dlogits) {
     ST_CHECK(p->w_lin && g->w_lin && g->b_lin, "st_rnn_backward: vocabulary projection gradients requested without buffers");
     ST_CHECK(ldd >= st_up8(p->V) && ldd % 8 == 0 && ldd <= q.Vp, "st_rnn_backward: dlogits leading dimension %d must be a multiple of 8 in [%d, %d]",
              ldd, st_up8(p->V), q.Vp);
     // db = colsum(dlogits);  dW_lin += dlogits^T y_top;  dy_top = dlogits W_lin
-    if (st_transpose_colsum(dlogits, ws + q.tA, g->b_lin, dt, n, p->V, ldd, Np, stream)) return 1;
-    if (st_transpose(ytop, ws + q.tB, dt, n, H, H, Np, stream)) return 1;
-    if (st_gemm_nt(ws + q.tA, Np, ws + q.tB, Np, g->w_lin, H, p->V, H, Np, dt, ST_F32, nullptr, stream, 1)) return 1;
+    if (tn) {                                      // contracted over the tokens as the operands lie, with the layers' gradients below
+      tg[ntg++] = tn_desc(dlogits, ldd, ytop, H, g->w_lin, p->V, H, g->b_lin, nullptr, false);
+    } else {
+      if (st_transpose_colsum(dlogits, ws + q.tA, g->b_lin, dt, n, p->V, ldd, Np, stream)) return 1;
+      if (st_transpose(ytop, ws + q.tB, dt, n, H, H, Np, stream)) return 1;
+      if (st_gemm_nt(ws + q.tA, Np, ws + q.tB, Np, g->w_lin, H, p->V, H, Np, dt, ST_F32, nullptr, stream, 1)) return 1;
+    }
     // dy = dlogits W_lin is 15 x 4 output tiles over K = V: with the padded leading dimension (st_rnn_vocab_ld: a multiple
     // of 8 K tiles, pad columns zero on both sides) it runs as 8 K slices in one grouped launch
     if (st_transpose(p->w_lin, ws + q.wT, dt, p->V, H, H, ldd, stream)) return 1;
@@ -457,6 +479,24 @@ int rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_
   }
   // d dropped x0 -> d x0, before the embedding / feature gradients read it
   if (dp.in && need_dx0 && dropout_rows_launch(dx0, dx0, ST_F32, n, p->in0, p->in0, p->in0, dp.kin, kDropSiteInput, 0, st)) return 1;
+  if (need_dx0 && !x0_override) {
+    ST_CHECK(g->emb, "st_rnn_backward: embedding gradient buffer missing");
+    if (embedding_bwd_launch(dx0, input_ids ? input_ids : s->caption, s->Tcap, s->rows_b, s->rows_t, dfeat, g->emb, n, p->E, p->V, 0, st)) return 1;
+  }
+  // parameter gradients, bf16: dW_ih_l += dgx_l^T x_l and dW_hh_l += dgh_l^T h_{t-1} (y_l gathered through prev_row) with their bias
+  // gradients as column sums, one group each beside dW_lin's; a layer whose input width is not H is a group like the others
+  for (int l = 0; tn && l < L; ++l) {
+    const int in = l == 0 ? p->in0 : H;
+    // dW_ih_l contracts with what layer l READ: the dropped copy of y_{l-1} (x0 was dropped in place); dW_hh_l with the plain y_l
+    const char* xl = l == 0 ? reinterpret_cast<const char*>(x0) : dp.layer ? dp.rows(l - 1) : ws + q.y + (size_t)(l - 1) * n * H * es;
+    // LSTM: dgh == dgx, so its column sums are both bias gradients and the recurrent group adds none
+    tg[ntg++] = tn_desc(dgxl(l), GH, xl, in, g->w_ih[l], GH, in, g->b_ih[l], gru ? nullptr : g->b_hh[l], false);
+    tg[ntg++] = tn_desc(dghl(l), GH, ws + q.y + (size_t)l * n * H * es, H, g->w_hh[l], GH, H, gru ? g->b_hh[l] : nullptr, nullptr, true);
+  }
+  for (int i = 0; i < ntg; i += 12) {
+    if (st_gemm_tn_batch(tg + i, ntg - i < 12 ? ntg - i : 12, stream)) return 1;
+  }
+  if (tn) return 0;
   // parameter gradients: K-major copies of every layer's operands (the transposes also sum the bias gradients), then the
   // 2L weight-gradient GEMMs -- 48 tiles each -- as grouped launches (st_conv_batch) that fill the chip
   st_conv_desc gd[2 * ST_MAX_LAYERS];
@@ -499,10 +539,6 @@ int rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_
   }
   for (int i = 0; i < ng; i += 12) {
     if (st_conv_batch(gd + i, ng - i < 12 ? ng - i : 12, stream)) return 1;
-  }
-  if (need_dx0 && !x0_override) {
-    ST_CHECK(g->emb, "st_rnn_backward: embedding gradient buffer missing");
-    if (embedding_bwd_launch(dx0, input_ids ? input_ids : s->caption, s->Tcap, s->rows_b, s->rows_t, dfeat, g->emb, n, p->E, p->V, 0, st)) return 1;
   }
   return 0;
 }
