@@ -422,10 +422,15 @@ int st_cast2d(const void* x, void* y, int from_dtype, int to_dtype, int rows, in
  *   batch_sizes_host: HOST array, non-increasing (captions sorted by length, utils.py:66).
  * Weights are [G*H][in] / [G*H][H] in `dtype` (gate order r,z,n / i,f,g,o as torch), biases fp32.
  * The workspace carries the saved activations from st_rnn_forward to st_rnn_backward.
- * st_rnn_forward: logits[ntok][ldl] (optional) and targets[ntok] = caption[b][t] (main.py:145).
+ * st_rnn_forward: logits[ntok][ldl] (optional) and targets[ntok] = caption[b][t] (main.py:145).  in0 must equal E: the layer-0
+ *   rows are [feature ; embeddings], gathered by the call.
  * st_rnn_backward: gradients are ACCUMULATED (+=) into the fp32 buffers of st_rnn_grads;
- *   dlogits is [ntok][ldd] in `dtype` with ldd a multiple of 8 and zero pad columns;
+ *   dlogits (required) is [ntok][ldd] in `dtype` with ldd a multiple of 8 and zero pad columns;
  *   dfeat[B][E] (fp32) receives the gradient w.r.t. the image feature rows.
+ * Both take the step's dropout (st_dropout below; NULL or every p = 0: none) and input_ids [B][Tcap] int64 on the device
+ * (scheduled sampling; NULL = s->caption): the layer-0 rows t >= 1 gather emb[input_ids[b][t-1]], the targets still come from
+ * s->caption, and the backward pass scatters the embedding gradient to input_ids.  NULL for either is the plain call, launch
+ * for launch.
  * ---------------------------------------------------------------------------------- */
 #define ST_MAX_LAYERS 8
 typedef struct {
@@ -456,54 +461,6 @@ int st_rnn_vocab_ld(int V);
  * the st_attn_*_workspace_bytes planners return 0 for a descriptor no entry point accepts: a null pointer, a batch below 1, a
  * layer count outside [1, ST_MAX_LAYERS] (the *_dropout_bytes and *_fused_loss*_bytes counts do not look at the layer count) */
 size_t st_rnn_workspace_bytes(const st_rnn_params* p, const st_packed_seq* s);
-int st_rnn_forward(const st_rnn_params* p, const st_packed_seq* s, const void* x0_override, const void* feat,
-                   void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
-                   long* targets, int save_for_backward, void* stream);
-int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,
-                    const void* x0_override, const void* dlogits, int ldd, const float* dy_top,
-                    void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, void* stream);
-
-/* Vocabulary projection (rnn.py:33) + nn.CrossEntropyLoss() (main.py:94,149) WITHOUT a logits tensor (csrc/vocab_ce.hip; bf16, H = 512):
- * after st_rnn_forward(.., logits = NULL, .., targets, save_for_backward = 1):
- *   st_rnn_fused_loss:    *loss_accum += mean_r( logsumexp(x_r) - x_r[target_r] ), x = y_top W_lin^T + b_lin computed tile by tile;
- *                         `scratch` (st_rnn_fused_loss_bytes) keeps the rows' logsumexp for the backward call;
- *   st_rnn_fused_dlogits: dlogits[ntok][ldd] (bf16) = (softmax - onehot) / ntok * *grad_scale_dev from the same tile products, pad columns
- *                         [V, ldd) zero: the operand st_rnn_backward takes.
- * Replaces st_rnn_forward's logits + two st_cross_entropy passes (the logits are never written, dlogits once). */
-int st_rnn_fused_loss_supported(const st_rnn_params* p);
-size_t st_rnn_fused_loss_bytes(const st_rnn_params* p, const st_packed_seq* s);
-int st_rnn_fused_loss(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
-                      const long* targets, float* scratch, size_t scratch_bytes, float* loss_accum, void* stream);
-int st_rnn_fused_dlogits(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
-                         const long* targets, const float* scratch, const float* grad_scale_dev, void* dlogits, int ldd, void* stream);
-/* The same with a per-row weight and the per-row losses (reward-weighted training, scoring of given captions).  row_weight[ntok] and
- * nll_out[ntok] are fp32 device buffers of the caller in packed-row order; either may be NULL, and with both NULL these are the calls above:
- *   st_rnn_fused_loss_w:    nll_out[r] = logsumexp(x_r) - x_r[target_r] (unweighted);  *loss_accum += sum_r row_weight[r] * nll_r / ntok
- *                           (the divisor stays ntok: row_weight = 1 is the mean); loss_accum may be NULL when nll_out is given;
- *   st_rnn_fused_dlogits_w: row r of dlogits is also multiplied by row_weight[r] (a constant of the loss: it gets no gradient). */
-int st_rnn_fused_loss_w(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
-                        const long* targets, float* scratch, size_t scratch_bytes, const float* row_weight, float* nll_out,
-                        float* loss_accum, void* stream);
-int st_rnn_fused_dlogits_w(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
-                           const long* targets, const float* scratch, const float* grad_scale_dev, const float* row_weight,
-                           void* dlogits, int ldd, void* stream);
-/* The same with label smoothing, torch's nn.CrossEntropyLoss(label_smoothing = eps), 0 <= eps < 1 (checked; NaN is refused):
- *   u_r = logsumexp(x_r) - (1 / V) * sum_{v < V} x_r[v]   (cross entropy against the uniform distribution)
- *   st_rnn_fused_loss_ls:    *loss_accum += sum_r row_weight[r] * ((1 - eps) * nll_r + eps * u_r) / ntok;  smooth_out[r] = u_r;  nll_out[r]
- *                            stays the unsmoothed nll_r.  row_weight / nll_out / smooth_out follow the NULL conventions of _w.  The rows'
- *                            mean logit is formed tile by tile: `tile_sums` (st_rnn_fused_loss_ls_bytes, fp32, the caller's, dead after the
- *                            call) receives each 128-entry tile's sum per token and is added in a fixed order, so u_r is bit-reproducible.
- *                            st_rnn_fused_loss_bytes and the workspace are those of the calls above.
- *   st_rnn_fused_dlogits_ls: dlogits = (softmax - (1 - eps) * onehot - eps / V) / ntok * *grad_scale_dev (* row_weight[r]); pad columns
- *                            [V, ldd) exact zeros.  With eps = 0 both compute what the _w calls compute, bit for bit. */
-size_t st_rnn_fused_loss_ls_bytes(const st_rnn_params* p, const st_packed_seq* s);
-int st_rnn_fused_loss_ls(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
-                         const long* targets, float* scratch, size_t scratch_bytes, const float* row_weight, float* nll_out,
-                         float* smooth_out, float label_smoothing, float* tile_sums, size_t tile_sums_bytes, float* loss_accum,
-                         void* stream);
-int st_rnn_fused_dlogits_ls(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
-                            const long* targets, const float* scratch, const float* grad_scale_dev, const float* row_weight,
-                            float label_smoothing, void* dlogits, int ldd, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Dropout for the teacher-forced decoders: nn.GRU(dropout = p) between layers, nn.Dropout in front of `linear` and on the layer-0
@@ -518,18 +475,17 @@ int st_rnn_fused_dlogits_ls(const st_rnn_params* p, const st_packed_seq* s, cons
  * layer but the last (nothing for L = 1).  `buf` (st_rnn_dropout_bytes / st_attn_dropout_bytes; the caller's, needed when p_layer or
  * p_out is on) receives the dropped copies, L matrices [ntok][H] in the compute dtype, and carries them from the forward call to the
  * loss and backward calls of the same step, which take the same descriptor.  The workspaces stay what they are.
- * The _drop forms with a NULL descriptor (or every p = 0) are the plain calls, launch for launch:
- *   st_rnn_forward_drop:       x0 is masked in place (p_in; not with x0_override); with p_layer the wavefront's cells write h' for
- *                              their recurrence and the dropped h' for the layer above, in the same launches; with p_out the
- *                              projection reads the dropped copy of y_top;
- *   st_rnn_fused_loss_drop /   the fused loss and its dlogits over the dropped y_top: one form for row weights and label smoothing
- *   st_rnn_fused_dlogits_drop: (NULL / 0 conventions of the _w and _ls calls; tile_sums is needed when label_smoothing > 0 or
- *                              smooth_out is given);
- *   st_rnn_backward_drop:      dy_top and dx0 are masked (fp32, in place), the fused BPTT cell masks the product it takes from the
- *                              layer above in registers (with p_layer the call is the fused route whatever ST_BPTT_FUSED says),
- *                              dW_ih_{l+1} and dW_lin contract with the dropped copies, dW_hh_l with the plain rows;
- *   st_attn_forward_drop /     p_out only (p_in, p_layer must be 0): the recurrence and the next step's attention read the plain top
- *   st_attn_backward_drop:     state; the projection and dW_lin the dropped copy; dy_top is masked before the step loop.
+ * A NULL descriptor (or every p = 0) is the plain call, launch for launch:
+ *   st_rnn_forward:        x0 is masked in place (p_in); with p_layer the wavefront's cells write h' for their recurrence and the
+ *                          dropped h' for the layer above, in the same launches; with p_out the projection reads the dropped copy
+ *                          of y_top;
+ *   st_rnn_fused_loss /    the fused loss and its dlogits read the dropped copy of y_top (p_out);
+ *   st_rnn_fused_dlogits:
+ *   st_rnn_backward:       dy_top and dx0 are masked (fp32, in place), the fused BPTT cell masks the product it takes from the
+ *                          layer above in registers (with p_layer the call is the fused route whatever ST_BPTT_FUSED says),
+ *                          dW_ih_{l+1} and dW_lin contract with the dropped copies, dW_hh_l with the plain rows;
+ *   st_attn_forward /      p_out only (p_in, p_layer must be 0): the recurrence and the next step's attention read the plain top
+ *   st_attn_backward:      state; the projection and dW_lin the dropped copy; dy_top is masked before the step loop.
  * ---------------------------------------------------------------------------------- */
 typedef struct {
   double p_in, p_layer, p_out;
@@ -541,48 +497,59 @@ typedef struct {
 int st_dropout_rows(const void* x, void* y, int dtype, int rows, int cols, int ldx, int ldy, double p, long seed, int step,
                     int site, int row0, void* stream);
 size_t st_rnn_dropout_bytes(const st_rnn_params* p, const st_packed_seq* s);
-int st_rnn_forward_drop(const st_rnn_params* p, const st_packed_seq* s, const void* x0_override, const void* feat,
-                        void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
-                        long* targets, int save_for_backward, const st_dropout* drop, void* stream);
-int st_rnn_fused_loss_drop(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
-                           const long* targets, float* scratch, size_t scratch_bytes, const float* row_weight, float* nll_out,
-                           float* smooth_out, float label_smoothing, float* tile_sums, size_t tile_sums_bytes, float* loss_accum,
-                           const st_dropout* drop, void* stream);
-int st_rnn_fused_dlogits_drop(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
-                              const long* targets, const float* scratch, const float* grad_scale_dev, const float* row_weight,
-                              float label_smoothing, void* dlogits, int ldd, const st_dropout* drop, void* stream);
-int st_rnn_backward_drop(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,
-                         const void* x0_override, const void* dlogits, int ldd, const float* dy_top,
-                         void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, const st_dropout* drop, void* stream);
-/* The _drop forms with input ids apart from the targets (scheduled sampling): input_ids [B][Tcap] int64 on the device, NULL =
- * s->caption (then each call is its _drop form, launch for launch).  The layer-0 rows t >= 1 gather emb[input_ids[b][t-1]], the
- * targets still come from s->caption, and the backward pass scatters the embedding gradient to input_ids.  Exclusive with
- * x0_override.  The workspaces, st_packed_seq and the fused loss / dlogits calls (they take `targets`) stay what they are. */
-int st_rnn_forward_ids(const st_rnn_params* p, const st_packed_seq* s, const void* x0_override, const void* feat,
-                       void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
-                       long* targets, int save_for_backward, const st_dropout* drop, const long* input_ids, void* stream);
-int st_rnn_backward_ids(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,
-                        const void* x0_override, const void* dlogits, int ldd, const float* dy_top,
-                        void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, const st_dropout* drop,
-                        const long* input_ids, void* stream);
+int st_rnn_forward(const st_rnn_params* p, const st_packed_seq* s, const void* feat,
+                   void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
+                   long* targets, int save_for_backward, const st_dropout* drop, const long* input_ids, void* stream);
+int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s, const void* dlogits, int ldd,
+                    void* workspace, size_t workspace_bytes, float* dfeat, const st_dropout* drop, const long* input_ids,
+                    void* stream);
 
-/* nn.CrossEntropyLoss() (mean) forward + backward (main.py:94,149):
- *   *loss_accum += mean_r( logsumexp(x_r) - x_r[target_r] );  dlogits = (softmax - onehot) * grad_scale / rows
- * dlogits may alias logits when the dtypes match; pad columns [V, ldd) are zero-filled. */
+/* The terms of a cross-entropy call beyond the plain mean: per-row weights (reward-weighted training), the per-row losses (scoring
+ * of given captions) and label smoothing, torch's nn.CrossEntropyLoss(label_smoothing = eps).  With nll_r = logsumexp(x_r) -
+ * x_r[target_r] and u_r = logsumexp(x_r) - (1 / V) * sum_{v < V} x_r[v] (cross entropy against the uniform distribution):
+ *   *loss_accum += sum_r row_weight[r] * ((1 - eps) * nll_r + eps * u_r) / rows   (the divisor stays `rows`: row_weight = 1 is the mean);
+ *   nll_out[r] = nll_r (unweighted, unsmoothed);  smooth_out[r] = u_r;
+ *   dlogits row r = (softmax - (1 - eps) * onehot - eps / V) * row_weight[r] * grad_scale / rows (the weight is a constant of the loss).
+ * The buffers are the caller's fp32 device buffers.  A NULL st_loss_terms* is the plain mean cross entropy. */
+typedef struct {
+  const float* row_weight;   /* [rows] fp32, packed-row order, or NULL (= 1)                          */
+  float*       nll_out;      /* [rows] or NULL: the rows' unweighted, unsmoothed -log p(target)       */
+  int          smoothing;    /* 0: the kernels without the smoothing term; 1: the label-smoothing
+                                kernels, at any label_smoothing in [0, 1) -- 0 then computes what
+                                smoothing = 0 computes, bit for bit                                   */
+  float        label_smoothing;   /* eps, checked (NaN is refused); must be 0 with smoothing = 0      */
+  float*       smooth_out;   /* [rows] or NULL (smoothing = 1 only): logsumexp - mean logit           */
+  float*       tile_sums; size_t tile_sums_bytes;   /* fused route with smoothing = 1 only
+                                                       (st_rnn_fused_loss_ls_bytes)                   */
+} st_loss_terms;
+
+/* Vocabulary projection (rnn.py:33) + nn.CrossEntropyLoss() (main.py:94,149) WITHOUT a logits tensor (csrc/vocab_ce.hip; bf16, H = 512):
+ * after st_rnn_forward(.., logits = NULL, .., targets, save_for_backward = 1):
+ *   st_rnn_fused_loss:    the loss of st_loss_terms over x = y_top W_lin^T + b_lin computed tile by tile; loss_accum may be NULL when
+ *                         nll_out or smooth_out is given.  `scratch` (st_rnn_fused_loss_bytes) keeps the rows' logsumexp for the
+ *                         backward call.  With smoothing = 1 the rows' mean logit is formed tile by tile too: `tile_sums`
+ *                         (st_rnn_fused_loss_ls_bytes, dead after the call) receives each 128-entry tile's sum per token and is
+ *                         added in a fixed order, so u_r is bit-reproducible;
+ *   st_rnn_fused_dlogits: dlogits[ntok][ldd] (bf16) with grad_scale = *grad_scale_dev from the same tile products, pad columns
+ *                         [V, ldd) exact zeros: the operand st_rnn_backward takes.  Of `terms` it reads row_weight, smoothing and
+ *                         label_smoothing.
+ * Both read the rows `linear` read: with drop->p_out > 0 the dropped copy of y_top in drop->buf, else the workspace's.
+ * Replaces st_rnn_forward's logits + two st_cross_entropy passes (the logits are never written, dlogits once). */
+int st_rnn_fused_loss_supported(const st_rnn_params* p);
+size_t st_rnn_fused_loss_bytes(const st_rnn_params* p, const st_packed_seq* s);
+size_t st_rnn_fused_loss_ls_bytes(const st_rnn_params* p, const st_packed_seq* s);
+int st_rnn_fused_loss(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
+                      const long* targets, float* scratch, size_t scratch_bytes, const st_loss_terms* terms, float* loss_accum,
+                      const st_dropout* drop, void* stream);
+int st_rnn_fused_dlogits(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
+                         const long* targets, const float* scratch, const float* grad_scale_dev, const st_loss_terms* terms,
+                         void* dlogits, int ldd, const st_dropout* drop, void* stream);
+
+/* nn.CrossEntropyLoss() forward + backward (main.py:94,149) on logits rows, with the terms of st_loss_terms (NULL: the plain mean;
+ * tile_sums is not read).  dlogits may alias logits when the dtypes match; pad columns [V, ldd) are zero-filled. */
 int st_cross_entropy(const void* logits, int logits_dtype, const long* target, int rows, int V, int ldl,
-                     float* loss_accum, void* dlogits, int dlogits_dtype, int ldd, float grad_scale,
+                     const st_loss_terms* terms, float* loss_accum, void* dlogits, int dlogits_dtype, int ldd, float grad_scale,
                      const float* grad_scale_dev /* optional device scalar multiplied in */, void* stream);
-/* ... with a per-row weight and the per-row losses (fp32 device buffers of `rows` entries, either may be NULL; both NULL: the call above):
- *   nll_out[r] = logsumexp(x_r) - x_r[target_r];  *loss_accum += sum_r row_weight[r] * nll_r / rows;  dlogits row r times row_weight[r] */
-int st_cross_entropy_w(const void* logits, int logits_dtype, const long* target, int rows, int V, int ldl,
-                       const float* row_weight, float* nll_out, float* loss_accum, void* dlogits, int dlogits_dtype, int ldd,
-                       float grad_scale, const float* grad_scale_dev, void* stream);
-/* ... with label smoothing eps in [0, 1) (checked): smooth_out[r] = logsumexp(x_r) - mean_{v < V} x_r[v] (NULL: not stored);
- *   *loss_accum += sum_r row_weight[r] * ((1 - eps) * nll_r + eps * smooth_r) / rows;  dlogits = (softmax - (1 - eps) * onehot - eps / V)
- *   * row_weight[r] * grad_scale / rows; nll_out stays unsmoothed.  dlogits may alias logits as above. */
-int st_cross_entropy_ls(const void* logits, int logits_dtype, const long* target, int rows, int V, int ldl,
-                        const float* row_weight, float* nll_out, float* smooth_out, float label_smoothing, float* loss_accum,
-                        void* dlogits, int dlogits_dtype, int ldd, float grad_scale, const float* grad_scale_dev, void* stream);
 
 /* Encoder head: y = BatchNorm1d(x W^T + b) (cnn.py:37-38,49; momentum 0.01) and its backward
  * (dx is not needed: the backbone output is detached, cnn.py:47).  Gradients are accumulated. */
@@ -753,22 +720,17 @@ typedef struct {
 } st_attn_grads;
 
 size_t st_attn_workspace_bytes(const st_attn_params* p, const st_packed_seq* s);
+/* `drop`: Dropout in front of `linear` (st_dropout above: p_out only; NULL = none) */
+size_t st_attn_dropout_bytes(const st_attn_params* p, const st_packed_seq* s);
 int st_attn_forward(const st_attn_params* p, const st_packed_seq* s, const float* cnn_feature, const long* caption_T,
                     void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
-                    float* alphas, int save_for_backward, void* stream);
+                    float* alphas, int save_for_backward, const st_dropout* drop, void* stream);
 int st_attn_backward(const st_attn_params* p, const st_attn_grads* g, const st_packed_seq* s, const long* caption_T,
                      const void* dlogits, int ldd, const float* alphas,
                      const float* dalphas /* (B,T,P) gradient w.r.t. alphas from the caller, or NULL: use alpha_c */,
-                     float alpha_c, const float* grad_scale_dev, void* workspace, size_t workspace_bytes, void* stream);
+                     float alpha_c, const float* grad_scale_dev, void* workspace, size_t workspace_bytes, const st_dropout* drop,
+                     void* stream);
 int st_attn_reg_loss(const float* alphas, int B, int T, int P, float alpha_c, float* loss_accum, void* stream);
-/* ... with Dropout in front of `linear` (st_dropout above: p_out only; NULL = the calls above) */
-size_t st_attn_dropout_bytes(const st_attn_params* p, const st_packed_seq* s);
-int st_attn_forward_drop(const st_attn_params* p, const st_packed_seq* s, const float* cnn_feature, const long* caption_T,
-                         void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
-                         float* alphas, int save_for_backward, const st_dropout* drop, void* stream);
-int st_attn_backward_drop(const st_attn_params* p, const st_attn_grads* g, const st_packed_seq* s, const long* caption_T,
-                          const void* dlogits, int ldd, const float* alphas, const float* dalphas, float alpha_c,
-                          const float* grad_scale_dev, void* workspace, size_t workspace_bytes, const st_dropout* drop, void* stream);
 /* rnn_attn.py:120-145 (test branch 77-94): `steps` greedy iterations from <start>; ids_out[B][steps] int64 */
 size_t st_attn_greedy_workspace_bytes(const st_attn_params* p, int B);
 int st_attn_greedy(const st_attn_params* p, const float* cnn_feature, int B, int steps, long start_id,

@@ -107,6 +107,18 @@ class PackedSeq(C.Structure):
                 ("rows_b", c_p), ("rows_t", c_p), ("prev_row", c_p), ("caption", c_p)]
 
 
+class DropoutDesc(C.Structure):
+    """st_dropout: one training step's dropout (dropout.DropoutState.desc fills it)."""
+    _fields_ = [("p_in", C.c_double), ("p_layer", C.c_double), ("p_out", C.c_double), ("seed", c_l), ("step", c_i),
+                ("buf", c_p), ("buf_bytes", C.c_size_t)]
+
+
+class LossTerms(C.Structure):
+    """st_loss_terms: row weights, per-row outputs and label smoothing of a loss call (rnn.loss_terms fills it)."""
+    _fields_ = [("row_weight", c_p), ("nll_out", c_p), ("smoothing", c_i), ("label_smoothing", c_f), ("smooth_out", c_p),
+                ("tile_sums", c_p), ("tile_sums_bytes", C.c_size_t)]
+
+
 class ImageBatchDesc(C.Structure):
     _fields_ = [("src", c_p), ("src_bytes", C.c_int64), ("offset", c_p), ("height", c_p), ("width", c_p), ("flip", c_p), ("batch", c_i),
                 ("max_height", c_i), ("max_width", c_i), ("out_h", c_i), ("out_w", c_i), ("lut", c_p), ("tmp", c_p),
@@ -161,31 +173,19 @@ _SIGS = {
     "st_cast2d": ([c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p], c_i),
     "st_rnn_vocab_ld": ([c_i], c_i),
     "st_rnn_workspace_bytes": ([C.POINTER(RnnParams), C.POINTER(PackedSeq)], C.c_size_t),
-    "st_rnn_forward": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, c_p, c_p, C.c_size_t, c_p, c_i, c_i, c_p, c_i, c_p], c_i),
+    "st_rnn_forward": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, c_p, C.c_size_t, c_p, c_i, c_i, c_p, c_i, C.POINTER(DropoutDesc),
+                        c_p, c_p], c_i),
+    "st_rnn_backward": ([C.POINTER(RnnParams), C.POINTER(RnnGrads), C.POINTER(PackedSeq), c_p, c_i, c_p, C.c_size_t, c_p,
+                         C.POINTER(DropoutDesc), c_p, c_p], c_i),
     "st_rnn_fused_loss_supported": ([C.POINTER(RnnParams)], c_i),
     "st_rnn_fused_loss_bytes": ([C.POINTER(RnnParams), C.POINTER(PackedSeq)], C.c_size_t),
-    "st_rnn_fused_loss": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, C.c_size_t, c_p, c_p, C.c_size_t, c_p, c_p], c_i),
-    "st_rnn_fused_dlogits": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_i, c_p], c_i),
-    "st_rnn_fused_loss_w": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, C.c_size_t, c_p, c_p, C.c_size_t, c_p, c_p, c_p, c_p], c_i),
-    "st_rnn_fused_dlogits_w": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p, c_i, c_p], c_i),
     "st_rnn_fused_loss_ls_bytes": ([C.POINTER(RnnParams), C.POINTER(PackedSeq)], C.c_size_t),
-    "st_rnn_fused_loss_ls": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, C.c_size_t, c_p, c_p, C.c_size_t, c_p, c_p, c_p, c_f, c_p,
-                             C.c_size_t, c_p, c_p], c_i),
-    "st_rnn_fused_dlogits_ls": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_f, c_p, c_i, c_p], c_i),
-    "st_rnn_backward": ([C.POINTER(RnnParams), C.POINTER(RnnGrads), C.POINTER(PackedSeq), c_p, c_p, c_i, c_p, c_p, C.c_size_t,
-                         c_p, c_p, c_p], c_i),
+    "st_rnn_fused_loss": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, C.c_size_t, c_p, c_p, C.c_size_t, C.POINTER(LossTerms), c_p,
+                           C.POINTER(DropoutDesc), c_p], c_i),
+    "st_rnn_fused_dlogits": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, C.c_size_t, c_p, c_p, c_p, C.POINTER(LossTerms), c_p, c_i,
+                              C.POINTER(DropoutDesc), c_p], c_i),
     "st_dropout_rows": ([c_p, c_p, c_i, c_i, c_i, c_i, c_i, C.c_double, c_l, c_i, c_i, c_i, c_p], c_i),
     "st_rnn_dropout_bytes": ([C.POINTER(RnnParams), C.POINTER(PackedSeq)], C.c_size_t),
-    "st_rnn_forward_drop": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, c_p, c_p, C.c_size_t, c_p, c_i, c_i, c_p, c_i, c_p, c_p], c_i),
-    "st_rnn_fused_loss_drop": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, C.c_size_t, c_p, c_p, C.c_size_t, c_p, c_p, c_p, c_f, c_p,
-                               C.c_size_t, c_p, c_p, c_p], c_i),
-    "st_rnn_fused_dlogits_drop": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_f, c_p, c_i, c_p, c_p],
-                                  c_i),
-    "st_rnn_backward_drop": ([C.POINTER(RnnParams), C.POINTER(RnnGrads), C.POINTER(PackedSeq), c_p, c_p, c_i, c_p, c_p, C.c_size_t,
-                              c_p, c_p, c_p, c_p], c_i),
-    "st_rnn_forward_ids": ([C.POINTER(RnnParams), C.POINTER(PackedSeq), c_p, c_p, c_p, C.c_size_t, c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_p], c_i),
-    "st_rnn_backward_ids": ([C.POINTER(RnnParams), C.POINTER(RnnGrads), C.POINTER(PackedSeq), c_p, c_p, c_i, c_p, c_p, C.c_size_t,
-                             c_p, c_p, c_p, c_p, c_p], c_i),
     "st_rnn_greedy_workspace_bytes": ([C.POINTER(RnnParams), c_i], C.c_size_t),
     "st_rnn_greedy": ([C.POINTER(RnnParams), c_p, c_i, c_i, c_p, C.c_size_t, c_p, c_p, c_p], c_i),
     "st_rnn_greedy_last_route": ([], c_i),
@@ -205,11 +205,9 @@ _SIGS = {
     "st_rnn_sched_inputs": ([C.POINTER(RnnParams), c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_f, c_f, c_i, c_p, C.c_size_t, c_p, c_p, c_p, c_p,
                              c_p], c_i),
     "st_attn_workspace_bytes": ([c_p, c_p], C.c_size_t),
-    "st_attn_forward": ([c_p, c_p, c_p, c_p, c_p, C.c_size_t, c_p, c_i, c_i, c_p, c_i, c_p], c_i),
-    "st_attn_backward": ([c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_f, c_p, c_p, C.c_size_t, c_p], c_i),
+    "st_attn_forward": ([c_p, c_p, c_p, c_p, c_p, C.c_size_t, c_p, c_i, c_i, c_p, c_i, C.POINTER(DropoutDesc), c_p], c_i),
+    "st_attn_backward": ([c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_f, c_p, c_p, C.c_size_t, C.POINTER(DropoutDesc), c_p], c_i),
     "st_attn_dropout_bytes": ([c_p, c_p], C.c_size_t),
-    "st_attn_forward_drop": ([c_p, c_p, c_p, c_p, c_p, C.c_size_t, c_p, c_i, c_i, c_p, c_i, c_p, c_p], c_i),
-    "st_attn_backward_drop": ([c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_f, c_p, c_p, C.c_size_t, c_p, c_p], c_i),
     "st_attn_reg_loss": ([c_p, c_i, c_i, c_i, c_f, c_p, c_p], c_i),
     "st_attn_greedy_workspace_bytes": ([c_p, c_i], C.c_size_t),
     "st_attn_greedy": ([c_p, c_p, c_i, c_i, c_l, c_p, C.c_size_t, c_p, c_p], c_i),
@@ -222,9 +220,7 @@ _SIGS = {
     "st_attn_beam_search": ([c_p, c_p, c_i, c_i, c_i, c_l, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p, c_p], c_i),
     "st_attn_beam_ex_workspace_bytes": ([c_p, c_i, c_i, c_i], C.c_size_t),
     "st_attn_beam_search_ex": ([c_p, c_p, c_i, c_i, c_i, c_l, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_p], c_i),
-    "st_cross_entropy": ([c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_f, c_p, c_p], c_i),
-    "st_cross_entropy_w": ([c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_p, c_p], c_i),
-    "st_cross_entropy_ls": ([c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_i, c_i, c_f, c_p, c_p], c_i),
+    "st_cross_entropy": ([c_p, c_i, c_p, c_i, c_i, c_i, C.POINTER(LossTerms), c_p, c_p, c_i, c_i, c_f, c_p, c_p], c_i),
     "st_head_workspace_bytes": ([c_i, c_i, c_i, c_i], C.c_size_t),
     "st_linear_bn1d_forward": ([c_p] * 7 + [c_i, c_i, c_i, c_i, c_i, c_f, c_f] + [c_p] * 6, c_i),
     "st_linear_bn1d_backward": ([c_p] * 6 + [c_i, c_i, c_i, c_i, c_i] + [c_p] * 5 + [C.c_size_t, c_p], c_i),
@@ -261,6 +257,11 @@ class ShowTellHipError(RuntimeError):
 def ptr(t):
     """A tensor's device address as the C ABI takes it; None (NULL) for None."""
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def ref(struct):
+    """A ctypes structure by reference as the C ABI takes a descriptor; None (NULL) for None."""
+    return None if struct is None else C.byref(struct)
 
 
 def stream():

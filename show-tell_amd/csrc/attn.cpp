@@ -144,10 +144,9 @@ extern "C" size_t st_attn_workspace_bytes(const st_attn_params* p, const st_pack
 // Dropout (st_dropout, NULL = none): the Show-Attend-Tell placement, in front of `linear` only.  The recurrence and the next step's
 // attention read the plain top state; the dropped copy of y_top (the caller's buffer) feeds the projection and dW_lin, and dy_top is
 // masked before the step loop of the backward pass.
-namespace {
-int attn_forward(const st_attn_params* p, const st_packed_seq* s, const float* cnn_feature, const long* caption_T,
-                 void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
-                 float* alphas, int save_for_backward, const st_dropout* drop, void* stream) {
+extern "C" int st_attn_forward(const st_attn_params* p, const st_packed_seq* s, const float* cnn_feature, const long* caption_T,
+                               void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
+                               float* alphas, int save_for_backward, const st_dropout* drop, void* stream) {
   if (check_common(p, s, "st_attn_forward")) return 1;
   DropPlan dp;
   if (st_drop_plan(drop, p->rnn.L, s->ntok, p->rnn.H, p->rnn.dtype, true, "st_attn_forward", &dp)) return 1;
@@ -196,18 +195,6 @@ int attn_forward(const st_attn_params* p, const st_packed_seq* s, const float* c
   }
   return 0;
 }
-}  // namespace
-
-extern "C" int st_attn_forward(const st_attn_params* p, const st_packed_seq* s, const float* cnn_feature, const long* caption_T,
-                               void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
-                               float* alphas, int save_for_backward, void* stream) {
-  return attn_forward(p, s, cnn_feature, caption_T, workspace, workspace_bytes, logits, logits_dtype, ldl, alphas, save_for_backward, nullptr, stream);
-}
-extern "C" int st_attn_forward_drop(const st_attn_params* p, const st_packed_seq* s, const float* cnn_feature, const long* caption_T,
-                                    void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
-                                    float* alphas, int save_for_backward, const st_dropout* drop, void* stream) {
-  return attn_forward(p, s, cnn_feature, caption_T, workspace, workspace_bytes, logits, logits_dtype, ldl, alphas, save_for_backward, drop, stream);
-}
 extern "C" size_t st_attn_dropout_bytes(const st_attn_params* p, const st_packed_seq* s) {
   if (!p || !s) return 0;
   return st_dropout_buf_bytes(p->rnn.L, s->ntok, p->rnn.H, p->rnn.dtype);
@@ -218,10 +205,9 @@ extern "C" int st_attn_reg_loss(const float* alphas, int B, int T, int P, float 
   return attn_reg_launch(alphas, B, T, P, alpha_c, loss_accum, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream));
 }
 
-namespace {
-int attn_backward(const st_attn_params* p, const st_attn_grads* g, const st_packed_seq* s, const long* caption_T,
-                  const void* dlogits, int ldd, const float* alphas, const float* dalphas, float alpha_c,
-                  const float* grad_scale_dev, void* workspace, size_t workspace_bytes, const st_dropout* drop, void* stream) {
+extern "C" int st_attn_backward(const st_attn_params* p, const st_attn_grads* g, const st_packed_seq* s, const long* caption_T,
+                                const void* dlogits, int ldd, const float* alphas, const float* dalphas, float alpha_c,
+                                const float* grad_scale_dev, void* workspace, size_t workspace_bytes, const st_dropout* drop, void* stream) {
   if (check_common(p, s, "st_attn_backward")) return 1;
   DropPlan dp;
   if (st_drop_plan(drop, p->rnn.L, s->ntok, p->rnn.H, p->rnn.dtype, true, "st_attn_backward", &dp)) return 1;
@@ -350,19 +336,6 @@ int attn_backward(const st_attn_params* p, const st_attn_grads* g, const st_pack
     if (st_gemm_nt(ws + q.tA, Bp, ws + q.tB, Bp, gw, F, H, F, Bp, dt, ST_F32, nullptr, stream, 1)) return 1;
   }
   return 0;
-}
-}  // namespace
-
-extern "C" int st_attn_backward(const st_attn_params* p, const st_attn_grads* g, const st_packed_seq* s, const long* caption_T,
-                                const void* dlogits, int ldd, const float* alphas, const float* dalphas, float alpha_c,
-                                const float* grad_scale_dev, void* workspace, size_t workspace_bytes, void* stream) {
-  return attn_backward(p, g, s, caption_T, dlogits, ldd, alphas, dalphas, alpha_c, grad_scale_dev, workspace, workspace_bytes, nullptr, stream);
-}
-extern "C" int st_attn_backward_drop(const st_attn_params* p, const st_attn_grads* g, const st_packed_seq* s, const long* caption_T,
-                                     const void* dlogits, int ldd, const float* alphas, const float* dalphas, float alpha_c,
-                                     const float* grad_scale_dev, void* workspace, size_t workspace_bytes, const st_dropout* drop,
-                                     void* stream) {
-  return attn_backward(p, g, s, caption_T, dlogits, ldd, alphas, dalphas, alpha_c, grad_scale_dev, workspace, workspace_bytes, drop, stream);
 }
 
 // ---- greedy decoding (rnn_attn.py:77-94,120-145) -----------------------------------------------------------

@@ -87,6 +87,18 @@ inline int st_drop_plan(const st_dropout* d, int L, size_t ntok, int H, int dtyp
   return 0;
 }
 
+// The terms of a loss call (st_loss_terms; the entry points turn NULL into the all-zero descriptor first): smoothing = 1 needs
+// label_smoothing in [0, 1) (NaN fails), smoothing = 0 takes none of the smoothing arguments
+inline int st_check_loss_terms(const st_loss_terms* t, const char* who) {
+  if (t->smoothing) {
+    ST_CHECK(t->label_smoothing >= 0.f && t->label_smoothing < 1.f, "%s: label_smoothing=%g outside [0, 1)", who, (double)t->label_smoothing);
+  } else {
+    ST_CHECK(t->label_smoothing == 0.f && !t->smooth_out && !t->tile_sums,
+             "%s: smoothing = 0 takes no label_smoothing, smooth_out or tile_sums (set smoothing = 1 for the label-smoothing kernels)", who);
+  }
+  return 0;
+}
+
 // scheduled sampling (st_rnn_sched_inputs / st_attn_sched_inputs): input_ids = caption, replaced = 0, drawn = -1, logp = 0 before the roll-in
 inline int st_sched_init_outputs(const long* caption, int n, int Tcap, long* input_ids, uint8_t* replaced, long* drawn, float* logp, hipStream_t st,
                                  const char* who) {

@@ -21,7 +21,7 @@
 //           fp32 and ST_WGRAD_TN=0: K-major copies from transposes that also sum the bias gradients, then MFMA GEMMs).  ST_BPTT_FUSED=0 keeps the
 //           earlier push route (a gate-gradient launch and a skinny-GEMM launch per diagonal)
 //           -> st_rnn_backward
-// dropout:  the _drop forms of the entry points take an st_dropout (NULL: the calls above, launch for launch).  The input rows and the
+// dropout:  the entry points take an st_dropout (NULL or every p = 0: the plain call, launch for launch).  The input rows and the
 //           rows in front of `linear` are masked outside the recurrence (st_dropout_rows: x0 in place, y_top into the caller's buffer,
 //           and on the way back the fp32 dy_top and dx0 in place); the inter-layer site of nn.GRU(dropout=p) rides in the wavefront's
 //           own launches (the DROP forms of the cell kernels): layer l writes h' for its recurrence and the dropped h' for layer l + 1,
@@ -98,15 +98,15 @@ extern "C" size_t st_rnn_workspace_bytes(const st_rnn_params* p, const st_packed
   return make_plan(p, s).total;
 }
 
-namespace {
-int rnn_forward(const st_rnn_params* p, const st_packed_seq* s, const void* x0_override, const void* feat,
-                void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
-                long* targets, int save_for_backward, const st_dropout* drop, const long* input_ids, void* stream) {
+// input_ids [B][Tcap] (NULL: s->caption): what the layer-0 rows t >= 1 embed, apart from the targets (scheduled sampling)
+extern "C" int st_rnn_forward(const st_rnn_params* p, const st_packed_seq* s, const void* feat,
+                              void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
+                              long* targets, int save_for_backward, const st_dropout* drop, const long* input_ids, void* stream) {
   if (check_common(p, s, "st_rnn_forward")) return 1;
+  ST_CHECK(p->in0 == p->E, "st_rnn_forward: in0=%d != E=%d (the layer-0 rows are [feature ; embeddings])", p->in0, p->E);
   DropPlan dp;
   if (st_drop_plan(drop, p->L, s->ntok, p->H, p->dtype, false, "st_rnn_forward", &dp)) return 1;
-  ST_CHECK(!(dp.in && x0_override), "st_rnn_forward: input dropout needs the call's own x0 rows (no x0_override)");
-  ST_CHECK(workspace && (x0_override || (feat && p->emb)), "st_rnn_forward: null pointer");
+  ST_CHECK(workspace && feat && p->emb, "st_rnn_forward: null pointer");
   const Plan q = make_plan(p, s);
   ST_CHECK(workspace_bytes >= q.total, "st_rnn_forward: workspace too small (%zu < %zu)", workspace_bytes, q.total);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -114,14 +114,10 @@ int rnn_forward(const st_rnn_params* p, const st_packed_seq* s, const void* x0_o
   const int dt = p->dtype, H = p->H, n = s->ntok;
   const size_t es = q.es;
 
-  const void* x0 = x0_override;
-  if (!x0) {
-    ST_CHECK(p->in0 == p->E, "st_rnn_forward: in0 != E needs x0_override");
-    // input_ids (scheduled sampling): the rows t >= 1 gather emb[input_ids[b][t-1]]; the targets stay the caption's
-    if (pack_inputs_launch(feat, p->emb, s->caption, s->Tcap, s->rows_b, s->rows_t, ws + q.x0, targets, n, p->E, p->V, 0, dt, st, input_ids)) return 1;
-    x0 = ws + q.x0;
-    if (dp.in && dropout_rows_launch(x0, ws + q.x0, dt, n, p->in0, p->in0, p->in0, dp.kin, kDropSiteInput, 0, st)) return 1;
-  }
+  // input_ids: the rows t >= 1 gather emb[input_ids[b][t-1]]; the targets stay the caption's
+  const char* x0 = ws + q.x0;
+  if (pack_inputs_launch(feat, p->emb, s->caption, s->Tcap, s->rows_b, s->rows_t, ws + q.x0, targets, n, p->E, p->V, 0, dt, st, input_ids)) return 1;
+  if (dp.in && dropout_rows_launch(x0, ws + q.x0, dt, n, p->in0, p->in0, p->in0, dp.kin, kDropSiteInput, 0, st)) return 1;
   const std::vector<int> off = st_packed_offsets(s);
 
   const int L = p->L, T = s->T;
@@ -135,7 +131,7 @@ int rnn_forward(const st_rnn_params* p, const st_packed_seq* s, const void* x0_o
       const int t = d - l;
       const int bt = s->batch_sizes_host[t];
       // with inter-layer dropout layer l reads the dropped copy of y_{l-1}; the recurrence keeps the plain rows
-      const char* xl = l == 0 ? reinterpret_cast<const char*>(x0) : dp.layer ? dp.rows(l - 1) : ws + q.y + (size_t)(l - 1) * n * H * es;
+      const char* xl = l == 0 ? x0 : dp.layer ? dp.rows(l - 1) : ws + q.y + (size_t)(l - 1) * n * H * es;
       const int in = l == 0 ? p->in0 : H;
       char* yl = ws + q.y + (size_t)l * n * H * es;
       char* gl = ws + q.gates + (size_t)l * n * 4 * H * es;
@@ -162,25 +158,6 @@ int rnn_forward(const st_rnn_params* p, const st_packed_seq* s, const void* x0_o
   }
   return 0;
 }
-}  // namespace
-
-extern "C" int st_rnn_forward(const st_rnn_params* p, const st_packed_seq* s, const void* x0_override, const void* feat,
-                              void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
-                              long* targets, int save_for_backward, void* stream) {
-  return rnn_forward(p, s, x0_override, feat, workspace, workspace_bytes, logits, logits_dtype, ldl, targets, save_for_backward, nullptr, nullptr, stream);
-}
-extern "C" int st_rnn_forward_drop(const st_rnn_params* p, const st_packed_seq* s, const void* x0_override, const void* feat,
-                                   void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
-                                   long* targets, int save_for_backward, const st_dropout* drop, void* stream) {
-  return rnn_forward(p, s, x0_override, feat, workspace, workspace_bytes, logits, logits_dtype, ldl, targets, save_for_backward, drop, nullptr, stream);
-}
-// input_ids [B][Tcap] (NULL: s->caption): what the layer-0 rows t >= 1 embed, apart from the targets (scheduled sampling)
-extern "C" int st_rnn_forward_ids(const st_rnn_params* p, const st_packed_seq* s, const void* x0_override, const void* feat,
-                                  void* workspace, size_t workspace_bytes, void* logits, int logits_dtype, int ldl,
-                                  long* targets, int save_for_backward, const st_dropout* drop, const long* input_ids, void* stream) {
-  ST_CHECK(!(input_ids && x0_override), "st_rnn_forward_ids: input_ids and x0_override are exclusive");
-  return rnn_forward(p, s, x0_override, feat, workspace, workspace_bytes, logits, logits_dtype, ldl, targets, save_for_backward, drop, input_ids, stream);
-}
 extern "C" size_t st_rnn_dropout_bytes(const st_rnn_params* p, const st_packed_seq* s) {
   if (!p || !s) return 0;
   return st_dropout_buf_bytes(p->L, s->ntok, p->H, p->dtype);
@@ -195,138 +172,69 @@ extern "C" size_t st_rnn_fused_loss_bytes(const st_rnn_params* p, const st_packe
   if (!p || !s) return 0;
   return ((size_t)s->ntok * (2 + 2 * (size_t)vocab_ce_tiles(p->V))) * sizeof(float);
 }
-// row_weight / nll_out [ntok] (fp32, packed rows, caller-owned, either may be NULL): *loss_accum += sum_r row_weight[r] * nll_r / ntok,
-// nll_out[r] = nll_r (unweighted).  loss_accum may be NULL when nll_out is given (scoring only)
-extern "C" int st_rnn_fused_loss_w(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
-                                   const long* targets, float* scratch, size_t scratch_bytes, const float* row_weight, float* nll_out,
-                                   float* loss_accum, void* stream) {
-  if (check_common(p, s, "st_rnn_fused_loss")) return 1;
-  ST_CHECK(workspace && targets && scratch && (loss_accum || nll_out), "st_rnn_fused_loss: null pointer");
-  ST_CHECK(st_rnn_fused_loss_supported(p), "st_rnn_fused_loss: needs bf16, H = 512 and the vocabulary projection (use st_rnn_forward's logits + st_cross_entropy)");
-  const Plan q = make_plan(p, s);
-  ST_CHECK(workspace_bytes >= q.total && scratch_bytes >= st_rnn_fused_loss_bytes(p, s), "st_rnn_fused_loss: workspace / scratch too small");
-  const char* ytop = reinterpret_cast<const char*>(workspace) + q.y + (size_t)(p->L - 1) * s->ntok * p->H * q.es;
-  const int n = s->ntok;
-  return vocab_ce_forward(ytop, p->w_lin, p->b_lin, targets, n, p->V, scratch + 2 * (size_t)n, scratch + n, scratch, loss_accum,
-                          row_weight, nll_out, reinterpret_cast<hipStream_t>(stream));
-}
-extern "C" int st_rnn_fused_loss(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
-                                 const long* targets, float* scratch, size_t scratch_bytes, float* loss_accum, void* stream) {
-  ST_CHECK(loss_accum, "st_rnn_fused_loss: null pointer");
-  return st_rnn_fused_loss_w(p, s, workspace, workspace_bytes, targets, scratch, scratch_bytes, nullptr, nullptr, loss_accum, stream);
-}
-// dlogits[ntok][ldd] (bf16) = (softmax - onehot) / ntok * *grad_scale_dev, from the same tile products; pad columns [V, ldd) zero
-// (_w: row r also times row_weight[r]; NULL: 1)
-extern "C" int st_rnn_fused_dlogits_w(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
-                                      const long* targets, const float* scratch, const float* grad_scale_dev, const float* row_weight,
-                                      void* dlogits, int ldd, void* stream) {
-  if (check_common(p, s, "st_rnn_fused_dlogits")) return 1;
-  ST_CHECK(workspace && targets && scratch && dlogits, "st_rnn_fused_dlogits: null pointer");
-  ST_CHECK(st_rnn_fused_loss_supported(p), "st_rnn_fused_dlogits: unsupported configuration");
-  const Plan q = make_plan(p, s);
-  ST_CHECK(workspace_bytes >= q.total, "st_rnn_fused_dlogits: workspace too small");
-  const char* ytop = reinterpret_cast<const char*>(workspace) + q.y + (size_t)(p->L - 1) * s->ntok * p->H * q.es;
-  return vocab_ce_dlogits(ytop, p->w_lin, p->b_lin, targets, scratch, s->ntok, p->V, dlogits, ldd, 1.0f, grad_scale_dev, row_weight,
-                          reinterpret_cast<hipStream_t>(stream));
-}
-extern "C" int st_rnn_fused_dlogits(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
-                                    const long* targets, const float* scratch, const float* grad_scale_dev, void* dlogits, int ldd, void* stream) {
-  return st_rnn_fused_dlogits_w(p, s, workspace, workspace_bytes, targets, scratch, grad_scale_dev, nullptr, dlogits, ldd, stream);
-}
-
-// ---- the same with label smoothing (torch's CrossEntropyLoss(label_smoothing = eps)): the LS kernels of csrc/vocab_ce.hip --------------
-// tile_sums (floats): [tiles][ntok] sums of each tile's valid logits, caller-owned so that st_rnn_fused_loss_bytes stays what it was
+// tile_sums of st_loss_terms (floats): [tiles][ntok] sums of each tile's valid logits, caller-owned so that st_rnn_fused_loss_bytes stays what it was
 extern "C" size_t st_rnn_fused_loss_ls_bytes(const st_rnn_params* p, const st_packed_seq* s) {
   if (!p || !s) return 0;
   return (size_t)s->ntok * (size_t)vocab_ce_tiles(p->V) * sizeof(float);
 }
-extern "C" int st_rnn_fused_loss_ls(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
-                                    const long* targets, float* scratch, size_t scratch_bytes, const float* row_weight, float* nll_out,
-                                    float* smooth_out, float label_smoothing, float* tile_sums, size_t tile_sums_bytes, float* loss_accum,
-                                    void* stream) {
-  if (check_common(p, s, "st_rnn_fused_loss_ls")) return 1;
-  ST_CHECK(workspace && targets && scratch && tile_sums && (loss_accum || nll_out || smooth_out), "st_rnn_fused_loss_ls: null pointer");
-  ST_CHECK(label_smoothing >= 0.f && label_smoothing < 1.f, "st_rnn_fused_loss_ls: label_smoothing=%g outside [0, 1)", (double)label_smoothing);
-  ST_CHECK(st_rnn_fused_loss_supported(p), "st_rnn_fused_loss_ls: needs bf16, H = 512 and the vocabulary projection (use st_rnn_forward's logits + st_cross_entropy_ls)");
-  const Plan q = make_plan(p, s);
-  ST_CHECK(workspace_bytes >= q.total && scratch_bytes >= st_rnn_fused_loss_bytes(p, s), "st_rnn_fused_loss_ls: workspace / scratch too small");
-  ST_CHECK(tile_sums_bytes >= st_rnn_fused_loss_ls_bytes(p, s), "st_rnn_fused_loss_ls: tile_sums too small (%zu < %zu)", tile_sums_bytes,
-           st_rnn_fused_loss_ls_bytes(p, s));
-  const char* ytop = reinterpret_cast<const char*>(workspace) + q.y + (size_t)(p->L - 1) * s->ntok * p->H * q.es;
-  const int n = s->ntok;
-  return vocab_ce_forward(ytop, p->w_lin, p->b_lin, targets, n, p->V, scratch + 2 * (size_t)n, scratch + n, scratch, loss_accum,
-                          row_weight, nll_out, reinterpret_cast<hipStream_t>(stream), tile_sums, smooth_out, label_smoothing);
-}
-// dlogits = (softmax - (1 - eps) * onehot - eps / V) / ntok * *grad_scale_dev (* row_weight[r]); pad columns [V, ldd) zero
-extern "C" int st_rnn_fused_dlogits_ls(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
-                                       const long* targets, const float* scratch, const float* grad_scale_dev, const float* row_weight,
-                                       float label_smoothing, void* dlogits, int ldd, void* stream) {
-  if (check_common(p, s, "st_rnn_fused_dlogits_ls")) return 1;
-  ST_CHECK(workspace && targets && scratch && dlogits, "st_rnn_fused_dlogits_ls: null pointer");
-  ST_CHECK(label_smoothing >= 0.f && label_smoothing < 1.f, "st_rnn_fused_dlogits_ls: label_smoothing=%g outside [0, 1)", (double)label_smoothing);
-  ST_CHECK(st_rnn_fused_loss_supported(p), "st_rnn_fused_dlogits_ls: unsupported configuration");
-  const Plan q = make_plan(p, s);
-  ST_CHECK(workspace_bytes >= q.total, "st_rnn_fused_dlogits_ls: workspace too small");
-  const char* ytop = reinterpret_cast<const char*>(workspace) + q.y + (size_t)(p->L - 1) * s->ntok * p->H * q.es;
-  return vocab_ce_dlogits(ytop, p->w_lin, p->b_lin, targets, scratch, s->ntok, p->V, dlogits, ldd, 1.0f, grad_scale_dev, row_weight,
-                          reinterpret_cast<hipStream_t>(stream), true, label_smoothing);
-}
 
-// ---- the fused loss after st_rnn_forward_drop: ONE form for row weights and label smoothing (they combine).  The rows handed to the
-// vocabulary kernels are the dropped copy of y_top when drop->p_out > 0, else the workspace's; label_smoothing = 0 takes the kernels of
-// the _w calls (tile_sums may then be NULL), > 0 those of the _ls calls
 namespace {
-int fused_rows(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes, const st_dropout* drop,
-               const char* who, const char** ytop) {
+// What the loss and the dlogits call check alike, and the rows they hand to the vocabulary kernels: the dropped copy of y_top when
+// drop->p_out > 0, else the workspace's
+int fused_rows(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes, const st_loss_terms* t,
+               const st_dropout* drop, const char* who, const char** ytop) {
   if (check_common(p, s, who)) return 1;
-  ST_CHECK(st_rnn_fused_loss_supported(p), "%s: needs bf16, H = 512 and the vocabulary projection", who);
+  if (st_check_loss_terms(t, who)) return 1;
+  ST_CHECK(st_rnn_fused_loss_supported(p), "%s: needs bf16, H = 512 and the vocabulary projection (use st_rnn_forward's logits + st_cross_entropy)", who);
   const Plan q = make_plan(p, s);
-  ST_CHECK(workspace && workspace_bytes >= q.total, "%s: workspace too small", who);
+  ST_CHECK(workspace, "%s: null pointer", who);
+  ST_CHECK(workspace_bytes >= q.total, "%s: workspace / scratch too small", who);
   DropPlan dp;
   if (st_drop_plan(drop, p->L, s->ntok, p->H, p->dtype, false, who, &dp)) return 1;
   *ytop = dp.out ? dp.rows(p->L - 1) : reinterpret_cast<const char*>(workspace) + q.y + (size_t)(p->L - 1) * s->ntok * p->H * q.es;
   return 0;
 }
 }  // namespace
-extern "C" int st_rnn_fused_loss_drop(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
-                                      const long* targets, float* scratch, size_t scratch_bytes, const float* row_weight, float* nll_out,
-                                      float* smooth_out, float label_smoothing, float* tile_sums, size_t tile_sums_bytes, float* loss_accum,
-                                      const st_dropout* drop, void* stream) {
+
+// *loss_accum += sum_r row_weight[r] * ((1 - eps) * nll_r + eps * u_r) / ntok over the rows `linear` reads (terms: st_loss_terms, NULL = the
+// plain mean); smoothing = 0 runs the kernels without the tile sums, smoothing = 1 the label-smoothing ones at any eps in [0, 1)
+extern "C" int st_rnn_fused_loss(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
+                                 const long* targets, float* scratch, size_t scratch_bytes, const st_loss_terms* terms, float* loss_accum,
+                                 const st_dropout* drop, void* stream) {
+  const st_loss_terms t = terms ? *terms : st_loss_terms{};
   const char* ytop;
-  if (fused_rows(p, s, workspace, workspace_bytes, drop, "st_rnn_fused_loss_drop", &ytop)) return 1;
-  ST_CHECK(targets && scratch && (loss_accum || nll_out || smooth_out), "st_rnn_fused_loss_drop: null pointer");
-  ST_CHECK(label_smoothing >= 0.f && label_smoothing < 1.f, "st_rnn_fused_loss_drop: label_smoothing=%g outside [0, 1)", (double)label_smoothing);
-  ST_CHECK(scratch_bytes >= st_rnn_fused_loss_bytes(p, s), "st_rnn_fused_loss_drop: scratch too small");
+  if (fused_rows(p, s, workspace, workspace_bytes, &t, drop, "st_rnn_fused_loss", &ytop)) return 1;
+  ST_CHECK(targets && scratch && (loss_accum || t.nll_out || t.smooth_out) && (t.tile_sums || !t.smoothing), "st_rnn_fused_loss: null pointer");
+  ST_CHECK(scratch_bytes >= st_rnn_fused_loss_bytes(p, s), "st_rnn_fused_loss: workspace / scratch too small");
+  ST_CHECK(!t.smoothing || t.tile_sums_bytes >= st_rnn_fused_loss_ls_bytes(p, s), "st_rnn_fused_loss: tile_sums too small (%zu < %zu)",
+           t.tile_sums_bytes, st_rnn_fused_loss_ls_bytes(p, s));
   const int n = s->ntok;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (label_smoothing == 0.f && !smooth_out)
-    return vocab_ce_forward(ytop, p->w_lin, p->b_lin, targets, n, p->V, scratch + 2 * (size_t)n, scratch + n, scratch, loss_accum, row_weight,
-                            nll_out, st);
-  ST_CHECK(tile_sums && tile_sums_bytes >= st_rnn_fused_loss_ls_bytes(p, s), "st_rnn_fused_loss_drop: tile_sums too small");
-  return vocab_ce_forward(ytop, p->w_lin, p->b_lin, targets, n, p->V, scratch + 2 * (size_t)n, scratch + n, scratch, loss_accum, row_weight,
-                          nll_out, st, tile_sums, smooth_out, label_smoothing);
+  // smoothing = 0: tile_sums, smooth_out and label_smoothing are NULL, NULL and 0 (checked), which is vocab_ce_forward without them
+  return vocab_ce_forward(ytop, p->w_lin, p->b_lin, targets, n, p->V, scratch + 2 * (size_t)n, scratch + n, scratch, loss_accum, t.row_weight,
+                          t.nll_out, reinterpret_cast<hipStream_t>(stream), t.tile_sums, t.smooth_out, t.label_smoothing);
 }
-extern "C" int st_rnn_fused_dlogits_drop(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
-                                         const long* targets, const float* scratch, const float* grad_scale_dev, const float* row_weight,
-                                         float label_smoothing, void* dlogits, int ldd, const st_dropout* drop, void* stream) {
+// dlogits[ntok][ldd] (bf16) = (softmax - (1 - eps) * onehot - eps / V) / ntok * *grad_scale_dev (* row_weight[r]) from the same tile
+// products; pad columns [V, ldd) zero.  Reads row_weight, smoothing and label_smoothing of `terms`
+extern "C" int st_rnn_fused_dlogits(const st_rnn_params* p, const st_packed_seq* s, const void* workspace, size_t workspace_bytes,
+                                    const long* targets, const float* scratch, const float* grad_scale_dev, const st_loss_terms* terms,
+                                    void* dlogits, int ldd, const st_dropout* drop, void* stream) {
+  const st_loss_terms t = terms ? *terms : st_loss_terms{};
   const char* ytop;
-  if (fused_rows(p, s, workspace, workspace_bytes, drop, "st_rnn_fused_dlogits_drop", &ytop)) return 1;
-  ST_CHECK(targets && scratch && dlogits, "st_rnn_fused_dlogits_drop: null pointer");
-  ST_CHECK(label_smoothing >= 0.f && label_smoothing < 1.f, "st_rnn_fused_dlogits_drop: label_smoothing=%g outside [0, 1)", (double)label_smoothing);
-  return vocab_ce_dlogits(ytop, p->w_lin, p->b_lin, targets, scratch, s->ntok, p->V, dlogits, ldd, 1.0f, grad_scale_dev, row_weight,
-                          reinterpret_cast<hipStream_t>(stream), label_smoothing != 0.f, label_smoothing);
+  if (fused_rows(p, s, workspace, workspace_bytes, &t, drop, "st_rnn_fused_dlogits", &ytop)) return 1;
+  ST_CHECK(targets && scratch && dlogits, "st_rnn_fused_dlogits: null pointer");
+  return vocab_ce_dlogits(ytop, p->w_lin, p->b_lin, targets, scratch, s->ntok, p->V, dlogits, ldd, 1.0f, grad_scale_dev, t.row_weight,
+                          reinterpret_cast<hipStream_t>(stream), t.smoothing != 0, t.label_smoothing);
 }
 
-namespace {
-int rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,
-                 const void* x0_override, const void* dlogits, int ldd, const float* dy_top_extra,
-                 void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, const st_dropout* drop, const long* input_ids, void* stream) {
+// after st_rnn_forward with the same `drop` (its buffer holds the dropped copies the weight gradients read) and the same input_ids (the
+// embedding gradient scatters to the tokens that were fed)
+extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s, const void* dlogits, int ldd,
+                               void* workspace, size_t workspace_bytes, float* dfeat, const st_dropout* drop, const long* input_ids,
+                               void* stream) {
   if (check_common(p, s, "st_rnn_backward")) return 1;
-  ST_CHECK(g && workspace, "st_rnn_backward: null pointer");
+  ST_CHECK(g && workspace && dlogits, "st_rnn_backward: null pointer");
   DropPlan dp;
   if (st_drop_plan(drop, p->L, s->ntok, p->H, p->dtype, false, "st_rnn_backward", &dp)) return 1;
-  ST_CHECK(!(dp.in && x0_override), "st_rnn_backward: input dropout needs the call's own x0 rows (no x0_override)");
-  ST_CHECK(!(dp.out && !dlogits), "st_rnn_backward: p_out masks the gradient of the vocabulary projection (needs dlogits, not dy_top)");
   const Plan q = make_plan(p, s);
   ST_CHECK(workspace_bytes >= q.total, "st_rnn_backward: workspace too small (%zu < %zu)", workspace_bytes, q.total);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -356,36 +264,28 @@ int rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_
     return d;
   };
 
-  if (dlogits) {
-    ST_CHECK(p->w_lin && g->w_lin && g->b_lin, "st_rnn_backward: vocabulary projection gradients requested without buffers");
-    ST_CHECK(ldd >= st_up8(p->V) && ldd % 8 == 0 && ldd <= q.Vp, "st_rnn_backward: dlogits leading dimension %d must be a multiple of 8 in [%d, %d]",
-             ldd, st_up8(p->V), q.Vp);
-    // db = colsum(dlogits);  dW_lin += dlogits^T y_top;  dy_top = dlogits W_lin
-    if (tn) {                                      // contracted over the tokens as the operands lie, with the layers' gradients below
-      tg[ntg++] = tn_desc(dlogits, ldd, ytop, H, g->w_lin, p->V, H, g->b_lin, nullptr, false);
-    } else {
-      if (st_transpose_colsum(dlogits, ws + q.tA, g->b_lin, dt, n, p->V, ldd, Np, stream)) return 1;
-      if (st_transpose(ytop, ws + q.tB, dt, n, H, H, Np, stream)) return 1;
-      if (st_gemm_nt(ws + q.tA, Np, ws + q.tB, Np, g->w_lin, H, p->V, H, Np, dt, ST_F32, nullptr, stream, 1)) return 1;
-    }
-    // dy = dlogits W_lin is 15 x 4 output tiles over K = V: with the padded leading dimension (st_rnn_vocab_ld: a multiple
-    // of 8 K tiles, pad columns zero on both sides) it runs as 8 K slices in one grouped launch
-    if (st_transpose(p->w_lin, ws + q.wT, dt, p->V, H, H, ldd, stream)) return 1;
-    const int bk = dt == ST_BF16 ? 64 : 32;
-    const int split = (ldd % (8 * bk) == 0 && ldd >= 16 * bk) ? 8 : 0;
-    if (st_gemm_nt(dlogits, ldd, ws + q.wT, ldd, dy, H, n, H, ldd, dt, ST_F32, nullptr, stream, 0, split)) return 1;
-    if (dy_top_extra) { st_set_error("st_rnn_backward: dlogits and dy_top_extra are exclusive"); return 1; }
-    if (dp.out && dropout_rows_launch(dy, dy, ST_F32, n, H, H, H, dp.kout, L - 1, 0, st)) return 1;   // d dropped y_top -> d y_top
+  ST_CHECK(p->w_lin && g->w_lin && g->b_lin, "st_rnn_backward: vocabulary projection gradients requested without buffers");
+  ST_CHECK(ldd >= st_up8(p->V) && ldd % 8 == 0 && ldd <= q.Vp, "st_rnn_backward: dlogits leading dimension %d must be a multiple of 8 in [%d, %d]",
+           ldd, st_up8(p->V), q.Vp);
+  // db = colsum(dlogits);  dW_lin += dlogits^T y_top;  dy_top = dlogits W_lin
+  if (tn) {                                      // contracted over the tokens as the operands lie, with the layers' gradients below
+    tg[ntg++] = tn_desc(dlogits, ldd, ytop, H, g->w_lin, p->V, H, g->b_lin, nullptr, false);
   } else {
-    ST_CHECK(dy_top_extra, "st_rnn_backward: need dlogits or dy_top");
-    if (hipMemcpyAsync(dy, dy_top_extra, (size_t)n * H * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
-      st_set_error("st_rnn_backward: copy failed"); return 1;
-    }
+    if (st_transpose_colsum(dlogits, ws + q.tA, g->b_lin, dt, n, p->V, ldd, Np, stream)) return 1;
+    if (st_transpose(ytop, ws + q.tB, dt, n, H, H, Np, stream)) return 1;
+    if (st_gemm_nt(ws + q.tA, Np, ws + q.tB, Np, g->w_lin, H, p->V, H, Np, dt, ST_F32, nullptr, stream, 1)) return 1;
   }
+  // dy = dlogits W_lin is 15 x 4 output tiles over K = V: with the padded leading dimension (st_rnn_vocab_ld: a multiple
+  // of 8 K tiles, pad columns zero on both sides) it runs as 8 K slices in one grouped launch
+  if (st_transpose(p->w_lin, ws + q.wT, dt, p->V, H, H, ldd, stream)) return 1;
+  const int bk = dt == ST_BF16 ? 64 : 32;
+  const int split = (ldd % (8 * bk) == 0 && ldd >= 16 * bk) ? 8 : 0;
+  if (st_gemm_nt(dlogits, ldd, ws + q.wT, ldd, dy, H, n, H, ldd, dt, ST_F32, nullptr, stream, 0, split)) return 1;
+  if (dp.out && dropout_rows_launch(dy, dy, ST_F32, n, H, H, H, dp.kout, L - 1, 0, st)) return 1;   // d dropped y_top -> d y_top
 
-  const void* x0 = x0_override ? x0_override : ws + q.x0;
-  const bool need_dx0 = dfeat || dx0_out || g->emb;
-  float* dx0 = dx0_out ? dx0_out : reinterpret_cast<float*>(ws + q.dx0);
+  const char* x0 = ws + q.x0;
+  const bool need_dx0 = dfeat || g->emb;
+  float* dx0 = reinterpret_cast<float*>(ws + q.dx0);
   const bool gru = p->cell == ST_CELL_GRU;
   auto dgxl = [&](int l) { return ws + q.dgx + (size_t)l * n * GH * es; };
   auto dghl = [&](int l) { return gru ? ws + q.dgh + (size_t)l * n * GH * es : dgxl(l); };   // LSTM: one gradient feeds both projections
@@ -479,7 +379,7 @@ int rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_
   }
   // d dropped x0 -> d x0, before the embedding / feature gradients read it
   if (dp.in && need_dx0 && dropout_rows_launch(dx0, dx0, ST_F32, n, p->in0, p->in0, p->in0, dp.kin, kDropSiteInput, 0, st)) return 1;
-  if (need_dx0 && !x0_override) {
+  if (need_dx0) {
     ST_CHECK(g->emb, "st_rnn_backward: embedding gradient buffer missing");
     if (embedding_bwd_launch(dx0, input_ids ? input_ids : s->caption, s->Tcap, s->rows_b, s->rows_t, dfeat, g->emb, n, p->E, p->V, 0, st)) return 1;
   }
@@ -488,7 +388,7 @@ int rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_
   for (int l = 0; tn && l < L; ++l) {
     const int in = l == 0 ? p->in0 : H;
     // dW_ih_l contracts with what layer l READ: the dropped copy of y_{l-1} (x0 was dropped in place); dW_hh_l with the plain y_l
-    const char* xl = l == 0 ? reinterpret_cast<const char*>(x0) : dp.layer ? dp.rows(l - 1) : ws + q.y + (size_t)(l - 1) * n * H * es;
+    const char* xl = l == 0 ? x0 : dp.layer ? dp.rows(l - 1) : ws + q.y + (size_t)(l - 1) * n * H * es;
     // LSTM: dgh == dgx, so its column sums are both bias gradients and the recurrent group adds none
     tg[ntg++] = tn_desc(dgxl(l), GH, xl, in, g->w_ih[l], GH, in, g->b_ih[l], gru ? nullptr : g->b_hh[l], false);
     tg[ntg++] = tn_desc(dghl(l), GH, ws + q.y + (size_t)l * n * H * es, H, g->w_hh[l], GH, H, gru ? g->b_hh[l] : nullptr, nullptr, true);
@@ -509,7 +409,7 @@ int rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_
   for (int l = 0; l < L; ++l) {
     const int in = l == 0 ? p->in0 : H;
     // dW_ih_l contracts with what layer l READ: the dropped copy of y_{l-1} (x0 was dropped in place); dW_hh_l with the plain y_l
-    const char* xl = l == 0 ? reinterpret_cast<const char*>(x0) : dp.layer ? dp.rows(l - 1) : ws + q.y + (size_t)(l - 1) * n * H * es;
+    const char* xl = l == 0 ? x0 : dp.layer ? dp.rows(l - 1) : ws + q.y + (size_t)(l - 1) * n * H * es;
     char* aIh = ws + q.gA + (size_t)(2 * l) * GH * Np * es;
     char* aHh = ws + q.gA + (size_t)(2 * l + 1) * GH * Np * es;
     char* bIh = ws + q.gB + (size_t)(2 * l) * q.maxw * Np * es;
@@ -541,26 +441,4 @@ int rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_
     if (st_conv_batch(gd + i, ng - i < 12 ? ng - i : 12, stream)) return 1;
   }
   return 0;
-}
-}  // namespace
-
-extern "C" int st_rnn_backward(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,
-                               const void* x0_override, const void* dlogits, int ldd, const float* dy_top_extra,
-                               void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, void* stream) {
-  return rnn_backward(p, g, s, x0_override, dlogits, ldd, dy_top_extra, workspace, workspace_bytes, dfeat, dx0_out, nullptr, nullptr, stream);
-}
-// after st_rnn_forward_drop with the same descriptor (its buffer holds the dropped copies the weight gradients read)
-extern "C" int st_rnn_backward_drop(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,
-                                    const void* x0_override, const void* dlogits, int ldd, const float* dy_top_extra,
-                                    void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, const st_dropout* drop,
-                                    void* stream) {
-  return rnn_backward(p, g, s, x0_override, dlogits, ldd, dy_top_extra, workspace, workspace_bytes, dfeat, dx0_out, drop, nullptr, stream);
-}
-// after st_rnn_forward_ids with the same input_ids: the embedding gradient scatters to the tokens that were fed
-extern "C" int st_rnn_backward_ids(const st_rnn_params* p, const st_rnn_grads* g, const st_packed_seq* s,
-                                   const void* x0_override, const void* dlogits, int ldd, const float* dy_top_extra,
-                                   void* workspace, size_t workspace_bytes, float* dfeat, float* dx0_out, const st_dropout* drop,
-                                   const long* input_ids, void* stream) {
-  ST_CHECK(!(input_ids && x0_override), "st_rnn_backward_ids: input_ids and x0_override are exclusive");
-  return rnn_backward(p, g, s, x0_override, dlogits, ldd, dy_top_extra, workspace, workspace_bytes, dfeat, dx0_out, drop, input_ids, stream);
 }

@@ -14,6 +14,7 @@
 // and the whole gate nonlinearity runs in the epilogue so a timestep is ONE launch.
 #include "common.h"
 #include "rnn_kernels.h"
+#include "decoder_host.h"
 #include "select.h"
 #include <string.h>
 
@@ -912,39 +913,25 @@ void ce_launch(const void* logits, int logits_dtype, const long* target, int row
 }
 }  // namespace
 
-extern "C" int st_cross_entropy_w(const void* logits, int logits_dtype, const long* target, int rows, int V, int ldl,
-                                  const float* row_weight, float* nll_out, float* loss_accum, void* dlogits, int dlogits_dtype, int ldd,
-                                  float grad_scale, const float* grad_scale_dev, void* stream) {
+// nn.CrossEntropyLoss() on logits rows, forward and / or backward, with the terms of st_loss_terms (NULL: the plain mean).  Instantiations:
+// smoothing = 0 with row_weight or nll_out -> WGT; smoothing = 0 with neither -> the plain kernel; smoothing = 1 -> WGT + LS at any eps
+extern "C" int st_cross_entropy(const void* logits, int logits_dtype, const long* target, int rows, int V, int ldl,
+                                const st_loss_terms* terms, float* loss_accum, void* dlogits, int dlogits_dtype, int ldd,
+                                float grad_scale, const float* grad_scale_dev, void* stream) {
+  const st_loss_terms t = terms ? *terms : st_loss_terms{};
   ST_CHECK(logits && target, "st_cross_entropy: null pointer");
   ST_CHECK(rows >= 0 && V > 0 && ldl >= V, "st_cross_entropy: bad shape");
+  if (st_check_loss_terms(&t, "st_cross_entropy")) return 1;
   if (rows == 0) return 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const float inv = 1.0f / rows, gs = grad_scale / rows;
-  if (row_weight || nll_out)
-    ce_launch<true>(logits, logits_dtype, target, rows, V, ldl, loss_accum, dlogits, dlogits_dtype, ldd, inv, gs, grad_scale_dev, row_weight, nll_out, st);
-  else
+  if (!t.smoothing && (t.row_weight || t.nll_out))
+    ce_launch<true>(logits, logits_dtype, target, rows, V, ldl, loss_accum, dlogits, dlogits_dtype, ldd, inv, gs, grad_scale_dev, t.row_weight, t.nll_out, st);
+  else if (!t.smoothing)
     ce_launch<false>(logits, logits_dtype, target, rows, V, ldl, loss_accum, dlogits, dlogits_dtype, ldd, inv, gs, grad_scale_dev, nullptr, nullptr, st);
+  else
+    ce_launch<true, true>(logits, logits_dtype, target, rows, V, ldl, loss_accum, dlogits, dlogits_dtype, ldd, inv, gs, grad_scale_dev, t.row_weight,
+                          t.nll_out, st, CeSmooth{t.smooth_out, t.label_smoothing, 1.0f / V});
   ST_LAUNCH_CHECK();
   return 0;
-}
-
-// label smoothing: the LS instantiation whatever row_weight / nll_out / smooth_out are (NULL conventions of st_cross_entropy_w)
-extern "C" int st_cross_entropy_ls(const void* logits, int logits_dtype, const long* target, int rows, int V, int ldl,
-                                   const float* row_weight, float* nll_out, float* smooth_out, float label_smoothing, float* loss_accum,
-                                   void* dlogits, int dlogits_dtype, int ldd, float grad_scale, const float* grad_scale_dev, void* stream) {
-  ST_CHECK(logits && target, "st_cross_entropy_ls: null pointer");
-  ST_CHECK(rows >= 0 && V > 0 && ldl >= V, "st_cross_entropy_ls: bad shape");
-  ST_CHECK(label_smoothing >= 0.f && label_smoothing < 1.f, "st_cross_entropy_ls: label_smoothing=%g outside [0, 1)", (double)label_smoothing);
-  if (rows == 0) return 0;
-  ce_launch<true, true>(logits, logits_dtype, target, rows, V, ldl, loss_accum, dlogits, dlogits_dtype, ldd, 1.0f / rows, grad_scale / rows,
-                        grad_scale_dev, row_weight, nll_out, reinterpret_cast<hipStream_t>(stream), CeSmooth{smooth_out, label_smoothing, 1.0f / V});
-  ST_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int st_cross_entropy(const void* logits, int logits_dtype, const long* target, int rows, int V, int ldl,
-                                float* loss_accum, void* dlogits, int dlogits_dtype, int ldd, float grad_scale,
-                                const float* grad_scale_dev, void* stream) {
-  return st_cross_entropy_w(logits, logits_dtype, target, rows, V, ldl, nullptr, nullptr, loss_accum, dlogits, dlogits_dtype, ldd,
-                            grad_scale, grad_scale_dev, stream);
 }

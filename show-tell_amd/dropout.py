@@ -7,21 +7,14 @@ in front of ``linear``), SITE_INPUT = the layer-0 input rows.  A module owns a s
 (``Decoder.seed_dropout``); each training-mode ``forward()`` / ``loss()`` consumes one step and its backward reuses it -- no
 device round trip, and nothing to checkpoint on the device.  tests/_dropout_cases.py holds the numpy replica of the mask.
 """
-import ctypes as C
 import warnings
 
 import torch
 
-from ._lib import check, dtype_code, lib, ptr, stream
+from ._lib import DropoutDesc, check, dtype_code, lib, ptr, stream
 
 SITE_INPUT = 255
 _MASK64 = (1 << 64) - 1
-
-
-class DropoutDesc(C.Structure):
-    """st_dropout of include/showtell_hip.h."""
-    _fields_ = [("p_in", C.c_double), ("p_layer", C.c_double), ("p_out", C.c_double), ("seed", C.c_long), ("step", C.c_int),
-                ("buf", C.c_void_p), ("buf_bytes", C.c_size_t)]
 
 
 def check_p(name, p):

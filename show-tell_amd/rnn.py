@@ -18,6 +18,10 @@ Same constructor, same attribute names (``embeddings``, ``unit``, ``linear``) an
 arithmetic runs in libshowtell_hip (st_rnn_forward / st_rnn_backward / st_rnn_greedy /
 st_cross_entropy).  ``loss()`` is the fused route (vocabulary projection + cross entropy
 without handing fp32 logits to torch) used by the training driver and bench.py.
+A training call is one st_rnn_forward, one loss call (st_rnn_fused_loss, or st_cross_entropy
+on st_rnn_forward's logits), one dlogits call and one st_rnn_backward, whatever the keywords:
+dropout travels as an st_dropout, ``input_ids`` as a pointer, and weights, per-row outputs and
+label smoothing as one st_loss_terms (``loss_terms``); NULL / None for each is the plain call.
 
 Gradients: the backward kernels accumulate straight into ``param.grad`` (fp32), so after
 ``loss.backward()`` the optimizer sees exactly what torch autograd would have produced.
@@ -29,7 +33,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from ._lib import ST_CELL_GRU, ST_CELL_LSTM, ST_F32, RnnGrads, RnnParams, check, dtype_code, lib
+from ._lib import ST_CELL_GRU, ST_CELL_LSTM, ST_F32, LossTerms, RnnGrads, RnnParams, check, dtype_code, lib, ref
 from ._lib import ptr as _cp, stream as _stream  # noqa: F401  (tests and tools import these names from here)
 from .dropout import DropoutState
 from ._weights import FollowsMoves, grad_buffer, working_copy  # noqa: F401  (rnn.working_copy stays importable)
@@ -190,35 +194,31 @@ def unpack_rows(plan, rows, width, device):
     return out
 
 
-def ce_loss(logits, dt, targets, n, V, Vp, loss, roww=None, nll=None, eps=0.0):
-    """loss += mean cross entropy of the (n, Vp) logits rows (V valid columns) against `targets`; with `roww` (n,) every row's
-    term times its weight (the divisor stays n); `nll` (n,) receives the rows' unweighted terms (`loss` may then be None).
-    eps > 0: label smoothing, the row's term is (1 - eps) * nll + eps * (logsumexp - mean logit) (st_cross_entropy_ls)."""
-    if eps:
-        check(lib().st_cross_entropy_ls(_cp(logits), dtype_code(dt), _cp(targets), n, V, Vp, _cp(roww), _cp(nll), None, eps, _cp(loss),
-                                        None, 0, Vp, 1.0, None, _stream()), "st_cross_entropy_ls")
-    elif roww is None and nll is None:
-        check(lib().st_cross_entropy(_cp(logits), dtype_code(dt), _cp(targets), n, V, Vp, _cp(loss), None, 0, Vp, 1.0, None, _stream()),
-              "st_cross_entropy")
-    else:
-        check(lib().st_cross_entropy_w(_cp(logits), dtype_code(dt), _cp(targets), n, V, Vp, _cp(roww), _cp(nll), _cp(loss), None, 0, Vp,
-                                       1.0, None, _stream()), "st_cross_entropy_w")
+def loss_terms(roww=None, nll=None, eps=0.0):
+    """The st_loss_terms of one loss call: `roww` (n,) the rows' weights, `nll` (n,) receives the rows' unweighted, unsmoothed
+    terms, eps > 0 label smoothing (the label-smoothing kernels; eps = 0 the ones without the term).  It holds addresses only:
+    the caller keeps the tensors alive as long as it uses the descriptor."""
+    t = LossTerms()
+    t.row_weight = None if roww is None else roww.data_ptr()
+    t.nll_out = None if nll is None else nll.data_ptr()
+    t.smoothing, t.label_smoothing = (1, eps) if eps else (0, 0.0)
+    return t
 
 
-def ce_loss_backward(logits, dt, targets, n, V, Vp, gout, roww=None, eps=0.0):
-    """The saved logits of ce_loss, overwritten in place by (softmax - onehot) * dLoss / N_tok (row r times roww[r]; eps > 0:
-    softmax - (1 - eps) * onehot - eps / V).  Returns (dlogits, dLoss as the fp32 device scalar the kernel read)."""
+def ce_loss(logits, dt, targets, n, V, Vp, loss, terms):
+    """loss += the cross entropy of the (n, Vp) logits rows (V valid columns) against `targets` with the terms of ``loss_terms``
+    (`loss` may be None when the terms ask for the rows' own)."""
+    check(lib().st_cross_entropy(_cp(logits), dtype_code(dt), _cp(targets), n, V, Vp, ref(terms), _cp(loss), None, 0, Vp, 1.0, None,
+                                 _stream()), "st_cross_entropy")
+
+
+def ce_loss_backward(logits, dt, targets, n, V, Vp, gout, terms):
+    """The saved logits of ce_loss, overwritten in place by (softmax - (1 - eps) * onehot - eps / V) * dLoss / N_tok (row r times
+    its weight), `terms` those of the forward call.  Returns (dlogits, dLoss as the fp32 device scalar the kernel read)."""
     gsc = gout.detach().float().contiguous()
     dtc = dtype_code(dt)
-    if eps:
-        check(lib().st_cross_entropy_ls(_cp(logits), dtc, _cp(targets), n, V, Vp, _cp(roww), None, None, eps, None, _cp(logits), dtc, Vp,
-                                        1.0, _cp(gsc), _stream()), "st_cross_entropy_ls(bwd)")
-    elif roww is None:
-        check(lib().st_cross_entropy(_cp(logits), dtc, _cp(targets), n, V, Vp, None, _cp(logits), dtc, Vp, 1.0, _cp(gsc), _stream()),
-              "st_cross_entropy(bwd)")
-    else:
-        check(lib().st_cross_entropy_w(_cp(logits), dtc, _cp(targets), n, V, Vp, _cp(roww), None, None, _cp(logits), dtc, Vp, 1.0,
-                                       _cp(gsc), _stream()), "st_cross_entropy_w(bwd)")
+    check(lib().st_cross_entropy(_cp(logits), dtc, _cp(targets), n, V, Vp, ref(terms), None, _cp(logits), dtc, Vp, 1.0, _cp(gsc),
+                                 _stream()), "st_cross_entropy(bwd)")
     return logits, gsc
 
 
@@ -268,47 +268,30 @@ class _DecoderFn(torch.autograd.Function):
             drop, dbuf = m._dropout.desc(took, lib().st_rnn_dropout_bytes(C.byref(prm), C.byref(seq)), dev)
         # input_ids (scheduled sampling): the rows embed them, the targets stay the caption's; None is the call it was
         ids = None if input_ids is None else input_ids.detach().contiguous()
-        if ids is not None:
-            check(lib().st_rnn_forward_ids(C.byref(prm), C.byref(seq), None, _cp(featd), _cp(ws), nbytes, _cp(logits), dtype_code(ldt), Vp,
-                                           _cp(targets), int(need_grad), C.byref(drop) if drop is not None else None, _cp(ids), _stream()),
-                  "st_rnn_forward_ids")
-        elif took is not None:
-            check(lib().st_rnn_forward_drop(C.byref(prm), C.byref(seq), None, _cp(featd), _cp(ws), nbytes, _cp(logits), dtype_code(ldt), Vp,
-                                            _cp(targets), int(need_grad), C.byref(drop), _stream()), "st_rnn_forward_drop")
-        else:
-            check(lib().st_rnn_forward(C.byref(prm), C.byref(seq), None, _cp(featd), _cp(ws), nbytes, _cp(logits), dtype_code(ldt), Vp,
-                                       _cp(targets), int(need_grad), _stream()), "st_rnn_forward")
+        check(lib().st_rnn_forward(C.byref(prm), C.byref(seq), _cp(featd), _cp(ws), nbytes, _cp(logits), dtype_code(ldt), Vp, _cp(targets),
+                                   int(need_grad), ref(drop), _cp(ids), _stream()), "st_rnn_forward")
         ctx.drop, ctx.dbuf, ctx.ids = drop, dbuf, ids
         ctx.m, ctx.plan, ctx.caption, ctx.ws, ctx.mode, ctx.keep = m, plan, caption, ws, mode, keep
         ctx.feat_dtype = feat.dtype
-        ctx.fused, ctx.roww, ctx.eps = fused, roww, eps
         if mode == "logits":
             return logits[:, :V]
         loss = torch.zeros((), device=dev, dtype=torch.float32) if mode == "loss" else None
         nll = torch.empty(n, device=dev, dtype=torch.float32) if mode == "nll" else None
+        terms = loss_terms(roww, nll, eps)
+        ctx.fused, ctx.roww, ctx.terms = fused, roww, terms
         if fused:
             sb = lib().st_rnn_fused_loss_bytes(C.byref(prm), C.byref(seq))
             scratch = torch.empty(sb // 4, device=dev, dtype=torch.float32)
-            if drop is not None:     # one form for weights and label smoothing, over the dropped copy of y_top
-                tb = lib().st_rnn_fused_loss_ls_bytes(C.byref(prm), C.byref(seq)) if eps else 0
-                tsum = torch.empty(tb // 4, device=dev, dtype=torch.float32) if eps else None
-                check(lib().st_rnn_fused_loss_drop(C.byref(prm), C.byref(seq), _cp(ws), nbytes, _cp(targets), _cp(scratch), sb, _cp(roww),
-                                                   _cp(nll), None, eps, _cp(tsum), tb, _cp(loss), C.byref(drop), _stream()),
-                      "st_rnn_fused_loss_drop")
-            elif eps:       # label smoothing: the tile sums of the rows' logits live in a buffer of this call only
+            if eps:         # label smoothing: the tile sums of the rows' logits live in a buffer of this call only
                 tb = lib().st_rnn_fused_loss_ls_bytes(C.byref(prm), C.byref(seq))
                 tsum = torch.empty(tb // 4, device=dev, dtype=torch.float32)
-                check(lib().st_rnn_fused_loss_ls(C.byref(prm), C.byref(seq), _cp(ws), nbytes, _cp(targets), _cp(scratch), sb, _cp(roww),
-                                                 _cp(nll), None, eps, _cp(tsum), tb, _cp(loss), _stream()), "st_rnn_fused_loss_ls")
-            elif roww is None and nll is None:
-                check(lib().st_rnn_fused_loss(C.byref(prm), C.byref(seq), _cp(ws), nbytes, _cp(targets), _cp(scratch), sb, _cp(loss),
-                                              _stream()), "st_rnn_fused_loss")
-            else:
-                check(lib().st_rnn_fused_loss_w(C.byref(prm), C.byref(seq), _cp(ws), nbytes, _cp(targets), _cp(scratch), sb, _cp(roww),
-                                                _cp(nll), _cp(loss), _stream()), "st_rnn_fused_loss_w")
+                terms.tile_sums, terms.tile_sums_bytes = tsum.data_ptr(), tb
+            check(lib().st_rnn_fused_loss(C.byref(prm), C.byref(seq), _cp(ws), nbytes, _cp(targets), _cp(scratch), sb, ref(terms), _cp(loss),
+                                          ref(drop), _stream()), "st_rnn_fused_loss")
+            terms.tile_sums, terms.tile_sums_bytes = None, 0      # dead after the call, and st_rnn_fused_dlogits does not read them
             ctx.logits, ctx.targets, ctx.scratch = None, targets, scratch
         else:
-            ce_loss(logits, ldt, targets, n, V, Vp, loss, roww, nll, eps)
+            ce_loss(logits, ldt, targets, n, V, Vp, loss, terms)
             ctx.logits, ctx.targets = logits, targets
         if mode == "nll":
             ctx.mark_non_differentiable(nll)
@@ -330,35 +313,14 @@ class _DecoderFn(torch.autograd.Function):
         elif ctx.fused:
             gsc = gout.detach().float().contiguous()
             dlog = torch.empty(n, Vp, device=dev, dtype=dt)
-            if ctx.drop is not None:
-                check(lib().st_rnn_fused_dlogits_drop(C.byref(prm), C.byref(seq), _cp(ctx.ws), ctx.ws.numel(), _cp(ctx.targets),
-                                                      _cp(ctx.scratch), _cp(gsc), _cp(ctx.roww), ctx.eps, _cp(dlog), Vp, C.byref(ctx.drop),
-                                                      _stream()), "st_rnn_fused_dlogits_drop")
-            elif ctx.eps:
-                check(lib().st_rnn_fused_dlogits_ls(C.byref(prm), C.byref(seq), _cp(ctx.ws), ctx.ws.numel(), _cp(ctx.targets),
-                                                    _cp(ctx.scratch), _cp(gsc), _cp(ctx.roww), ctx.eps, _cp(dlog), Vp, _stream()),
-                      "st_rnn_fused_dlogits_ls")
-            elif ctx.roww is None:
-                check(lib().st_rnn_fused_dlogits(C.byref(prm), C.byref(seq), _cp(ctx.ws), ctx.ws.numel(), _cp(ctx.targets), _cp(ctx.scratch),
-                                                 _cp(gsc), _cp(dlog), Vp, _stream()), "st_rnn_fused_dlogits")
-            else:
-                check(lib().st_rnn_fused_dlogits_w(C.byref(prm), C.byref(seq), _cp(ctx.ws), ctx.ws.numel(), _cp(ctx.targets),
-                                                   _cp(ctx.scratch), _cp(gsc), _cp(ctx.roww), _cp(dlog), Vp, _stream()),
-                      "st_rnn_fused_dlogits_w")
+            check(lib().st_rnn_fused_dlogits(C.byref(prm), C.byref(seq), _cp(ctx.ws), ctx.ws.numel(), _cp(ctx.targets), _cp(ctx.scratch),
+                                             _cp(gsc), ref(ctx.terms), _cp(dlog), Vp, ref(ctx.drop), _stream()), "st_rnn_fused_dlogits")
         else:
-            dlog, gsc = ce_loss_backward(ctx.logits, dt, ctx.targets, n, V, Vp, gout, ctx.roww, ctx.eps)
+            dlog, gsc = ce_loss_backward(ctx.logits, dt, ctx.targets, n, V, Vp, gout, ctx.terms)
         grads, keep2 = m._c_grads()
         dfeat = torch.empty(plan.B, m.embed_dim, device=dev, dtype=torch.float32)
-        if ctx.ids is not None:
-            check(lib().st_rnn_backward_ids(C.byref(prm), C.byref(grads), C.byref(seq), None, _cp(dlog), Vp, None, _cp(ctx.ws),
-                                            ctx.ws.numel(), _cp(dfeat), None, C.byref(ctx.drop) if ctx.drop is not None else None,
-                                            _cp(ctx.ids), _stream()), "st_rnn_backward_ids")
-        elif ctx.drop is not None:
-            check(lib().st_rnn_backward_drop(C.byref(prm), C.byref(grads), C.byref(seq), None, _cp(dlog), Vp, None, _cp(ctx.ws),
-                                             ctx.ws.numel(), _cp(dfeat), None, C.byref(ctx.drop), _stream()), "st_rnn_backward_drop")
-        else:
-            check(lib().st_rnn_backward(C.byref(prm), C.byref(grads), C.byref(seq), None, _cp(dlog), Vp, None, _cp(ctx.ws),
-                                        ctx.ws.numel(), _cp(dfeat), None, _stream()), "st_rnn_backward")
+        check(lib().st_rnn_backward(C.byref(prm), C.byref(grads), C.byref(seq), _cp(dlog), Vp, _cp(ctx.ws), ctx.ws.numel(), _cp(dfeat),
+                                    ref(ctx.drop), _cp(ctx.ids), _stream()), "st_rnn_backward")
         ctx.ws = ctx.dbuf = None
         return dfeat.to(ctx.feat_dtype), None, None, None, None, None, None, None, None, None, None
 

@@ -23,10 +23,10 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import AttnGrads, AttnParams, check, dtype_code, lib
+from ._lib import AttnGrads, AttnParams, check, dtype_code, lib, ref
 from ._lib import ptr as _cp, stream as _stream
 from .rnn import (CAP_MAX, Decoder, ce_loss, ce_loss_backward, check_caption_args, check_input_ids, check_label_smoothing,
-                  check_weight_args, logits_grad, pack_row_weights, sample_lengths, scheduled_loss_inputs, unpack_rows, up8)
+                  check_weight_args, logits_grad, loss_terms, pack_row_weights, sample_lengths, scheduled_loss_inputs, unpack_rows, up8)
 from .dropout import DropoutState
 from .seq import plan_for
 
@@ -76,26 +76,23 @@ class _AttnFn(torch.autograd.Function):
         drop = dbuf = None
         if took is not None:
             drop, dbuf = m._dropout.desc(took, lib().st_attn_dropout_bytes(C.byref(prm), C.byref(seq)), dev)
-            check(lib().st_attn_forward_drop(C.byref(prm), C.byref(seq), _cp(featc), _cp(cap_T), _cp(ws), nbytes, _cp(logits),
-                                             dtype_code(logits.dtype), Vp, _cp(alphas), int(need_grad), C.byref(drop), _stream()),
-                  "st_attn_forward_drop")
-        else:
-            check(lib().st_attn_forward(C.byref(prm), C.byref(seq), _cp(featc), _cp(cap_T), _cp(ws), nbytes, _cp(logits),
-                                        dtype_code(logits.dtype), Vp, _cp(alphas), int(need_grad), _stream()), "st_attn_forward")
+        check(lib().st_attn_forward(C.byref(prm), C.byref(seq), _cp(featc), _cp(cap_T), _cp(ws), nbytes, _cp(logits), dtype_code(logits.dtype),
+                                    Vp, _cp(alphas), int(need_grad), ref(drop), _stream()), "st_attn_forward")
         ctx.drop, ctx.dbuf = drop, dbuf
         # st_attn_forward steps over plan.T columns; alphas has T (padded) columns: strides must agree
         ctx.m, ctx.plan, ctx.caption, ctx.cap_T, ctx.ws, ctx.mode, ctx.P = m, plan, caption, cap_T, ws, mode, P
-        ctx.alphas, ctx.alpha_c, ctx.keep, ctx.roww, ctx.eps = alphas, alpha_c, keep, roww, eps
+        ctx.alphas, ctx.alpha_c, ctx.keep, ctx.roww = alphas, alpha_c, keep, roww
         if mode == "logits":
             return logits[:, :V], alphas
         targets = torch.nn.utils.rnn.pack_padded_sequence(caption, lens, batch_first=True)[0].contiguous()   # main_attn.py:126
         if mode == "nll":
             nll = torch.empty(n, device=dev, dtype=torch.float32)
-            ce_loss(logits, logits.dtype, targets, n, V, Vp, None, None, nll)
+            ce_loss(logits, logits.dtype, targets, n, V, Vp, None, loss_terms(nll=nll))
             ctx.mark_non_differentiable(nll, alphas)
             return nll, alphas
         loss = torch.zeros((), device=dev, dtype=torch.float32)
-        ce_loss(logits, dt, targets, n, V, Vp, loss, roww, None, eps)     # the doubly-stochastic term below stays unweighted and unsmoothed
+        ctx.terms = loss_terms(roww, None, eps)
+        ce_loss(logits, dt, targets, n, V, Vp, loss, ctx.terms)           # the doubly-stochastic term below stays unweighted and unsmoothed
         check(lib().st_attn_reg_loss(_cp(alphas), B, T, P, float(alpha_c), _cp(loss), _stream()), "st_attn_reg_loss")
         ctx.logits, ctx.targets = logits, targets
         return loss, alphas
@@ -114,19 +111,14 @@ class _AttnFn(torch.autograd.Function):
         elif ctx.mode != "loss":
             raise _lib.ShowTellHipError("token_logp has no gradient")
         else:
-            dlog, gs = ce_loss_backward(ctx.logits, dt, ctx.targets, n, V, Vp, g0, ctx.roww, ctx.eps)
+            dlog, gs = ce_loss_backward(ctx.logits, dt, ctx.targets, n, V, Vp, g0, ctx.terms)
             alpha_c = ctx.alpha_c
         prm, keep = m._c_params()
         prm.P = ctx.P
         grads, keep2 = m._c_grads()
         seq = plan.c_struct(ctx.caption)
-        if ctx.drop is not None:
-            check(lib().st_attn_backward_drop(C.byref(prm), C.byref(grads), C.byref(seq), _cp(ctx.cap_T), _cp(dlog), Vp, _cp(ctx.alphas),
-                                              _cp(dal), float(alpha_c), _cp(gs), _cp(ctx.ws), ctx.ws.numel(), C.byref(ctx.drop), _stream()),
-                  "st_attn_backward_drop")
-        else:
-            check(lib().st_attn_backward(C.byref(prm), C.byref(grads), C.byref(seq), _cp(ctx.cap_T), _cp(dlog), Vp, _cp(ctx.alphas), _cp(dal),
-                                         float(alpha_c), _cp(gs), _cp(ctx.ws), ctx.ws.numel(), _stream()), "st_attn_backward")
+        check(lib().st_attn_backward(C.byref(prm), C.byref(grads), C.byref(seq), _cp(ctx.cap_T), _cp(dlog), Vp, _cp(ctx.alphas), _cp(dal),
+                                     float(alpha_c), _cp(gs), _cp(ctx.ws), ctx.ws.numel(), ref(ctx.drop), _stream()), "st_attn_backward")
         ctx.ws = ctx.dbuf = None
         return None, None, None, None, None, None, None, None, None, None, None, None
 

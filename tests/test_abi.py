@@ -33,7 +33,8 @@ def _mirrored_structs():
             (_lib.Conv1x1KfuseDesc, "st_conv1x1_kfuse_desc"), (_lib.StemConvPoolDesc, "st_stem_conv_pool_desc"),
             (_lib.ConvB2bDesc, "st_conv_b2b_desc"), (_lib.ConvC3c1Desc, "st_conv_c3c1_desc"), (_lib.BnActDesc, "st_bn_act_desc"),
             (_lib.RnnParams, "st_rnn_params"), (_lib.RnnGrads, "st_rnn_grads"), (_lib.AttnParams, "st_attn_params"),
-            (_lib.AttnGrads, "st_attn_grads"), (_lib.PackedSeq, "st_packed_seq"), (_lib.ImageBatchDesc, "st_image_batch_desc")]
+            (_lib.AttnGrads, "st_attn_grads"), (_lib.PackedSeq, "st_packed_seq"), (_lib.ImageBatchDesc, "st_image_batch_desc"),
+            (_lib.LossTerms, "st_loss_terms"), (_lib.DropoutDesc, "st_dropout")]
 
 
 def layout_errors(structs):
@@ -193,7 +194,7 @@ def test_struct_sizes_match_the_header():
 
 def test_every_mirrored_struct_has_the_headers_layout():
     structs = _mirrored_structs()
-    assert len(structs) == 14 and sum(len(c._fields_) for c, _ in structs) == 259
+    assert len(structs) == 16 and sum(len(c._fields_) for c, _ in structs) == 273
     from showtell_amd import _lib
     mirrored = {c for c, _ in structs}
     assert {v for v in vars(_lib).values() if isinstance(v, type) and issubclass(v, ctypes.Structure) and v is not ctypes.Structure} == mirrored
@@ -226,7 +227,7 @@ def test_seeded_faults_are_caught():
     args, res = sigs["st_rnn_forward"]
     # an argument dropped from one signature
     errs = prototype_errors(protos, {**sigs, "st_rnn_forward": (args[:-1], res)})
-    assert errs == ["st_rnn_forward: header takes 12 arguments, _SIGS 11"]
+    assert errs == ["st_rnn_forward: header takes 13 arguments, _SIGS 12"]
     # a c_int replaced by a c_float
     i = args.index(ctypes.c_int)
     errs = prototype_errors(protos, {**sigs, "st_rnn_forward": (args[:i] + [ctypes.c_float] + args[i + 1:], res)})

@@ -383,7 +383,7 @@ def test_planners_and_entry_points_refuse_the_layer_count_before_any_launch(L):
                        attn_beam=lib().st_attn_beam_workspace_bytes(C.byref(a), 2, 4))
             assert all(v == 0 for v in got.values()), (cell, dtype, got)
             with pytest.raises(ShowTellHipError, match=f"num_layers={L} out of range"):
-                check(lib().st_rnn_forward(C.byref(p), C.byref(s), None, None, None, 0, None, 0, 0, None, 0, None), "st_rnn_forward")
+                check(lib().st_rnn_forward(C.byref(p), C.byref(s), None, None, 0, None, 0, 0, None, 0, None, None, None), "st_rnn_forward")
     # and 8 layers are planned
     p = _rnn_params("gru", "f32", 16, 16, 16, Z.MAX_LAYERS, Z.V)
     assert lib().st_rnn_workspace_bytes(C.byref(p), C.byref(s)) > 0 and lib().st_rnn_greedy_workspace_bytes(C.byref(p), 2) > 0

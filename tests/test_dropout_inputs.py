@@ -57,7 +57,7 @@ def test_the_c_header_reproduces_the_known_answers_and_the_replicas_words():
 
 
 def test_the_descriptor_mirror_has_the_headers_layout():
-    """showtell_amd.dropout.DropoutDesc against st_dropout, by the check of tests/test_abi.py (the mirror lives outside _lib)."""
+    """showtell_amd.dropout.DropoutDesc against st_dropout, by the check of tests/test_abi.py (dropout.py hands out the mirror of _lib)."""
     from showtell_amd.dropout import DropoutDesc
     from tests.test_abi import layout_errors
     assert layout_errors([(DropoutDesc, "st_dropout")]) == []

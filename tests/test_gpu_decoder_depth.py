@@ -504,7 +504,7 @@ def test_layer_counts_outside_1_to_8_fail_loudly_and_launch_nothing(L):
     assert lib().st_rnn_greedy_workspace_bytes(C.byref(p), 1) == 0
     torch.cuda.synchronize()
     with pytest.raises(ShowTellHipError, match=f"num_layers={L} out of range"):
-        check(lib().st_rnn_forward(C.byref(p), C.byref(s), None, None, None, 0, None, 0, 0, None, 0, None), "st_rnn_forward")
+        check(lib().st_rnn_forward(C.byref(p), C.byref(s), None, None, 0, None, 0, 0, None, 0, None, None, None), "st_rnn_forward")
     # the process is usable: the smallest case still trains
     m = _plain("eight_short", "gru", False).train()
     got = _step(m, "eight_short", "gru", False)

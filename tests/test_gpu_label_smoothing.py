@@ -1,7 +1,7 @@
 """Label smoothing on the GPU: the LS instantiations of csrc/vocab_ce.hip (fused bf16 route) and of ce_kernel (the bf16 and fp32
-launch chains, both attention decoders), the C entry points st_rnn_fused_loss_ls / st_rnn_fused_dlogits_ls /
-st_cross_entropy_ls, rnn.loss(.., label_smoothing=) and Trainer(.., label_smoothing=).  Cases, float64 oracle (torch's
-F.cross_entropy(label_smoothing=) on the logits of oracle/restatement.py) and bounds come from tests/_label_smoothing_cases.py;
+launch chains, both attention decoders), the C entry points st_rnn_fused_loss / st_rnn_fused_dlogits / st_cross_entropy with
+smoothing = 1 in their st_loss_terms, rnn.loss(.., label_smoothing=) and Trainer(.., label_smoothing=).  Cases, float64 oracle
+(torch's F.cross_entropy(label_smoothing=) on the logits of oracle/restatement.py) and bounds come from tests/_label_smoothing_cases.py;
 tests/test_label_smoothing_inputs.py shows on the CPU that these inputs and bounds catch the faults they are meant to catch.
 
 Shapes: E = H = 512 with (gru, V = 777, 66 tokens = two token tiles + 2 rows), (lstm, V = 1500, more than two 64-token blocks of
@@ -89,8 +89,8 @@ class _Rows:
         self.fused = fused == "1" and bool(lib().st_rnn_fused_loss_supported(C.byref(self.prm)))
         assert self.fused == (fused == "1" and dt == torch.bfloat16)
         self.logits = None if self.fused else torch.empty(self.n, self.ldl, device="cuda", dtype=dt)
-        check(lib().st_rnn_forward(C.byref(self.prm), C.byref(self.seq), None, _cp(m._feature(feat.cuda())), _cp(self.ws), self.nbytes,
-                                   _cp(self.logits), dtype_code(dt), self.ldl, _cp(self.targets), 1, _stream()), "st_rnn_forward")
+        check(lib().st_rnn_forward(C.byref(self.prm), C.byref(self.seq), _cp(m._feature(feat.cuda())), _cp(self.ws), self.nbytes,
+                                   _cp(self.logits), dtype_code(dt), self.ldl, _cp(self.targets), 1, None, None, _stream()), "st_rnn_forward")
         if self.fused:
             self.sb = lib().st_rnn_fused_loss_bytes(C.byref(self.prm), C.byref(self.seq))
             self.tb = lib().st_rnn_fused_loss_ls_bytes(C.byref(self.prm), C.byref(self.seq))
@@ -102,8 +102,18 @@ class _Rows:
         exists there), the chain's own rows otherwise."""
         return self.fwd_logits if self.fused else self.logits[:, :self.V].double().cpu()
 
+    @staticmethod
+    def _terms(eps, w, nll=None, u=None):
+        """st_loss_terms of one call: eps None -> smoothing = 0 (the kernels without the term), else
+        smoothing = 1 at label_smoothing = eps (0.0 included: the label-smoothing kernels)."""
+        from showtell_amd._lib import LossTerms
+        t = LossTerms()
+        t.row_weight, t.nll_out, t.smooth_out = (None if x is None else x.data_ptr() for x in (w, nll, u))
+        t.smoothing, t.label_smoothing = (0, 0.0) if eps is None else (1, eps)
+        return t
+
     def loss(self, eps=None, w=None, want_nll=True, want_u=False):
-        """One loss call through the C entry points: eps None -> the _w entry point (the parent's code), else the _ls one.
+        """One loss call through the C entry points: eps None -> smoothing = 0, else smoothing = 1.
         Returns dict(loss, nll, u, lse)."""
         from showtell_amd._lib import check, dtype_code, lib
         from showtell_amd.rnn import _cp, _stream
@@ -112,24 +122,18 @@ class _Rows:
         nll = torch.full((n,), -1.0, device="cuda") if want_nll else None
         u = torch.full((n,), -1.0, device="cuda") if want_u else None
         out = dict(loss=loss, nll=nll, u=u, lse=None)
+        t = self._terms(eps, w, nll, u if eps is not None else None)
         if self.fused:
-            a = (C.byref(self.prm), C.byref(self.seq), _cp(self.ws), self.nbytes, _cp(self.targets))
             self.scratch = torch.empty(self.sb // 4, device="cuda")
-            if eps is None:
-                check(lib().st_rnn_fused_loss_w(*a, _cp(self.scratch), self.sb, _cp(w), _cp(nll), _cp(loss), _stream()), "st_rnn_fused_loss_w")
-            else:
+            if eps is not None:
                 tsum = torch.full((self.tb // 4,), float("nan"), device="cuda")
-                check(lib().st_rnn_fused_loss_ls(*a, _cp(self.scratch), self.sb, _cp(w), _cp(nll), _cp(u), eps, _cp(tsum), self.tb, _cp(loss),
-                                                 _stream()), "st_rnn_fused_loss_ls")
+                t.tile_sums, t.tile_sums_bytes = tsum.data_ptr(), self.tb
+            check(lib().st_rnn_fused_loss(C.byref(self.prm), C.byref(self.seq), _cp(self.ws), self.nbytes, _cp(self.targets),
+                                          _cp(self.scratch), self.sb, C.byref(t), _cp(loss), None, _stream()), "st_rnn_fused_loss")
             out["lse"] = self.scratch[:n]
         else:
-            dtc = dtype_code(self.ldt)
-            if eps is None:
-                check(lib().st_cross_entropy_w(_cp(self.logits), dtc, _cp(self.targets), n, self.V, self.ldl, _cp(w), _cp(nll), _cp(loss), None,
-                                               0, self.ldd, 1.0, None, _stream()), "st_cross_entropy_w")
-            else:
-                check(lib().st_cross_entropy_ls(_cp(self.logits), dtc, _cp(self.targets), n, self.V, self.ldl, _cp(w), _cp(nll), _cp(u), eps,
-                                                _cp(loss), None, 0, self.ldd, 1.0, None, _stream()), "st_cross_entropy_ls")
+            check(lib().st_cross_entropy(_cp(self.logits), dtype_code(self.ldt), _cp(self.targets), n, self.V, self.ldl, C.byref(t), _cp(loss),
+                                         None, 0, self.ldd, 1.0, None, _stream()), "st_cross_entropy")
         torch.cuda.synchronize()
         return out
 
@@ -141,20 +145,14 @@ class _Rows:
         n = self.n
         gsc = torch.full((), GSC, device="cuda")
         d = torch.full((n, self.ldd), 7.0, device="cuda", dtype=self.ldt)
+        t = self._terms(eps, w)
         if self.fused:
-            a = (C.byref(self.prm), C.byref(self.seq), _cp(self.ws), self.nbytes, _cp(self.targets), _cp(self.scratch), _cp(gsc))
-            if eps is None:
-                check(lib().st_rnn_fused_dlogits_w(*a, _cp(w), _cp(d), self.ldd, _stream()), "st_rnn_fused_dlogits_w")
-            else:
-                check(lib().st_rnn_fused_dlogits_ls(*a, _cp(w), eps, _cp(d), self.ldd, _stream()), "st_rnn_fused_dlogits_ls")
+            check(lib().st_rnn_fused_dlogits(C.byref(self.prm), C.byref(self.seq), _cp(self.ws), self.nbytes, _cp(self.targets),
+                                             _cp(self.scratch), _cp(gsc), C.byref(t), _cp(d), self.ldd, None, _stream()), "st_rnn_fused_dlogits")
         else:
             dtc = dtype_code(self.ldt)
-            if eps is None:
-                check(lib().st_cross_entropy_w(_cp(self.logits), dtc, _cp(self.targets), n, self.V, self.ldl, _cp(w), None, None, _cp(d), dtc,
-                                               self.ldd, 1.0, _cp(gsc), _stream()), "st_cross_entropy_w")
-            else:
-                check(lib().st_cross_entropy_ls(_cp(self.logits), dtc, _cp(self.targets), n, self.V, self.ldl, _cp(w), None, None, eps, None,
-                                                _cp(d), dtc, self.ldd, 1.0, _cp(gsc), _stream()), "st_cross_entropy_ls")
+            check(lib().st_cross_entropy(_cp(self.logits), dtc, _cp(self.targets), n, self.V, self.ldl, C.byref(t), None, _cp(d), dtc,
+                                         self.ldd, 1.0, _cp(gsc), _stream()), "st_cross_entropy")
         torch.cuda.synchronize()
         return d
 
@@ -184,7 +182,7 @@ def test_smooth_out_rows_match_logsumexp_minus_mean_in_float64(case, fused):
 
 @pytest.mark.parametrize("case,fused", S.ROUTES)
 def test_eps_zero_through_the_new_entry_points_is_the_weighted_call_bit_for_bit(case, fused):
-    """The LS instantiations with eps = 0, with and without row weights, against the _w entry points (the parent's code):
+    """The LS instantiations (smoothing = 1) with eps = 0, with and without row weights, against smoothing = 0:
     logsumexp, nll_out and dlogits bit for bit -- the extra sum disturbs nothing -- and the loss bit for bit where its fp32
     atomics cannot reorder (the fused reduction adds one term per 64-token block: at most two blocks), to 1e-6 relative
     otherwise (st_cross_entropy adds one term per row)."""
@@ -281,8 +279,9 @@ def test_the_smoothed_scalar_is_the_recombination_of_its_own_rows(case, fused):
 
 
 def test_label_smoothing_zero_is_the_plain_call_on_the_fp32_chain(monkeypatch):
-    """label_smoothing=0.0 through Python takes the path the call always took, without weights and with them: the three _ls entry
-    points are replaced by functions that raise, and loss() + backward() still run.  Loss and gradients then equal the plain
+    """label_smoothing=0.0 through Python takes the path the call always took, without weights and with them: the three loss entry
+    points are wrapped by functions that raise when their st_loss_terms asks for the label-smoothing kernels (smoothing = 1), and
+    loss() + backward() still run.  Loss and gradients then equal the plain
     call's to 1e-6 relative, the bound tests/test_gpu_weighted_loss.py gives "the order of the fp32 atomics only".  Bit for bit
     cannot be asked of them: st_cross_entropy adds one float atomic per row to the loss and the embedding gradient one per token,
     so the plain call does not reproduce its own bits either (measured on an MI355X: 5.315089225769043 and 5.315090179443359 from
@@ -293,15 +292,19 @@ def test_label_smoothing_zero_is_the_plain_call_on_the_fp32_chain(monkeypatch):
     m = _model(case)
     sw, _ = S.weights(case)
 
-    def refuse(*a):
-        raise AssertionError("label_smoothing=0.0 reached a label-smoothing entry point")
+    def guard(real, i):
+        def call(*a):
+            if a[i] is not None and a[i]._obj.smoothing:             # argument i: NULL or the st_loss_terms by reference
+                raise AssertionError("label_smoothing=0.0 reached the label-smoothing kernels")
+            return real(*a)
+        return call
     for kw in ({}, dict(sequence_weight=sw.cuda())):
         loss0, g0 = _run(case, m, **kw)
         with monkeypatch.context() as mp:
-            for name in ("st_rnn_fused_loss_ls", "st_rnn_fused_dlogits_ls", "st_cross_entropy_ls"):
-                mp.setattr(lib(), name, refuse)
+            for name, i in (("st_rnn_fused_loss", 7), ("st_rnn_fused_dlogits", 7), ("st_cross_entropy", 6)):
+                mp.setattr(lib(), name, guard(getattr(lib(), name), i))
             loss1, g1 = _run(case, m, label_smoothing=0.0, **kw)
-            with pytest.raises(AssertionError, match="reached a label-smoothing entry point"):
+            with pytest.raises(AssertionError, match="reached the label-smoothing kernels"):
                 _run(case, m, label_smoothing=0.1, **kw)              # the patch is in the way of the smoothed path
         same = sum(torch.equal(g1[k], g0[k]) for k in g0)
         print(f"MEASURE eps=0 python weights={bool(kw)}: loss {loss1!r} against {loss0!r}; {same} of {len(g0)} gradients bit-equal")

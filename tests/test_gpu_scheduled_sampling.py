@@ -1,5 +1,5 @@
-"""Scheduled sampling on the GPU (st_sample_mix_rows, st_rnn_sched_inputs, st_attn_sched_inputs, st_rnn_forward_ids,
-st_rnn_backward_ids; scheduled_inputs, loss(input_ids=), loss(scheduled_sampling=), Trainer(scheduled_sampling=)).  The kernels hold
+"""Scheduled sampling on the GPU (st_sample_mix_rows, st_rnn_sched_inputs, st_attn_sched_inputs, input_ids of st_rnn_forward /
+st_rnn_backward; scheduled_inputs, loss(input_ids=), loss(scheduled_sampling=), Trainer(scheduled_sampling=)).  The kernels hold
 no generator: the caller's uniforms decide every coin and every draw, so every check is deterministic.
 
 1  st_sample_mix_rows against st_sample_rows on the same logits and draw_u: replaced rows bit for bit, the others the teacher's
@@ -9,7 +9,7 @@ no generator: the caller's uniforms decide every coin and every draw, so every c
    `replaced` the rule exactly, the caption everywhere else
 4  loss(input_ids = X), X random: loss and every gradient against the float64 torch replica, also with dropout and with weights
    plus label smoothing; the embedding rows of tokens only the targets hold get exactly zero
-5  input_ids = None never reaches the new entry points; input_ids = caption is the plain call
+5  input_ids = None never reaches the roll-in entry points and hands the C calls a NULL input_ids; input_ids = caption is the plain call
 6  same seed or same uniforms, same tensors; the roll-in allocates and synchronises nothing
 7  the Trainer's step is scheduled_inputs + loss(input_ids=) + backward + step; a callable schedule is asked with 0, 1, ..
 
@@ -280,7 +280,8 @@ def test_forward_and_token_logp_take_input_ids(case):
 # 5: None and the caption itself
 # ====================================================================================================================
 
-NEW_ENTRY_POINTS = ("st_rnn_forward_ids", "st_rnn_backward_ids", "st_rnn_sched_inputs", "st_attn_sched_inputs", "st_sample_mix_rows")
+ROLL_IN_ENTRY_POINTS = ("st_rnn_sched_inputs", "st_attn_sched_inputs", "st_sample_mix_rows")
+TAKES_INPUT_IDS = (("st_rnn_forward", 11), ("st_rnn_backward", 9))      # entry point, index of its input_ids argument
 
 
 @pytest.mark.parametrize("case,fused", [("gru777", "1"), ("gru777", "0"), ("gru_fp32", "1"), ("attn_fp32", "1")])
@@ -292,10 +293,15 @@ def test_none_is_the_call_it_was_and_the_caption_is_the_plain_loss(case, fused, 
     try:
         def refuse(*a):
             raise AssertionError("input_ids=None reached a scheduled-sampling entry point")
+
+        def refuse_ids(real, i):                              # the call itself goes through; a non-NULL input_ids does not
+            return lambda *a: refuse() if a[i] is not None else real(*a)
         loss0, g0 = _loss_run(case, m, "plain", None)
         with monkeypatch.context() as mp:
-            for name in NEW_ENTRY_POINTS:
+            for name in ROLL_IN_ENTRY_POINTS:
                 mp.setattr(lib(), name, refuse)
+            for name, i in TAKES_INPUT_IDS:
+                mp.setattr(lib(), name, refuse_ids(getattr(lib(), name), i))
             loss1, g1 = _loss_run(case, m, "plain", None)
             loss2, _ = _loss_run(case, m, "plain", None, scheduled_sampling=0.0)      # p = 0 runs no roll-in at all
             with torch.no_grad():

@@ -4,7 +4,7 @@ tests/_weighted_loss_cases.py; tests/test_weighted_loss_inputs.py shows from the
 
 Shapes: E = H = 512, L = 2 with (gru, V = 777, B = 9) and (lstm, V = 1500, B = 33) -- V no multiple of the 128-entry tile, the
 token count no multiple of the 32-token tile, B = 33 more than one 64-token block of the reduction -- on the fused route and on
-ST_FUSED_CE=0; an fp32 decoder at E = H = 64, V = 200 and the fp32 attention fixture for the st_cross_entropy_w route."""
+ST_FUSED_CE=0; an fp32 decoder at E = H = 64, V = 200 and the fp32 attention fixture for st_cross_entropy with row weights."""
 import ctypes as C
 
 import pytest
@@ -77,11 +77,11 @@ def _check_linear(d1, dw, w, V, nll, loss1, lossw):
 
 @pytest.mark.parametrize("case,fused", ROUTES)
 def test_dlogits_are_linear_in_the_row_weight_bit_for_bit(case, fused):
-    """The C entry points directly: dlogits_w[r] == w_r * dlogits_1[r] elementwise, dlogits_1 from the unchanged unweighted entry
-    point (weights from {0, +-0.5, +-1, 2, 4}); zero-weight rows and pad columns all zero; nll_out and the weighted sum agree
+    """The C entry points directly: dlogits_w[r] == w_r * dlogits_1[r] elementwise, dlogits_1 from the call with NULL
+    terms (weights from {0, +-0.5, +-1, 2, 4}); zero-weight rows and pad columns all zero; nll_out and the weighted sum agree
     with the unweighted loss.  Catches a wrong packed-row index, a weight applied to pad columns, a missed tile."""
     from showtell_amd._lib import check, dtype_code, lib
-    from showtell_amd.rnn import _cp, _stream, up8
+    from showtell_amd.rnn import _cp, _stream, loss_terms, up8
     from showtell_amd.seq import plan_for
     family = W.CASES[case][0]
     _, feat, cap, lens, _ = W.inputs(case)
@@ -93,6 +93,7 @@ def test_dlogits_are_linear_in_the_row_weight_bit_for_bit(case, fused):
     gsc = torch.full((), 0.75, device="cuda")
     loss1, lossw = torch.zeros((), device="cuda"), torch.zeros((), device="cuda")
     nll = torch.full((n,), -1.0, device="cuda")
+    terms = loss_terms(w, nll)                                    # plain calls: NULL terms; weighted ones: row_weight and nll_out
     if family == "attn":
         with torch.no_grad():
             logits = m(feat.cuda(), capd, lens)[0].contiguous()
@@ -110,27 +111,27 @@ def test_dlogits_are_linear_in_the_row_weight_bit_for_bit(case, fused):
         use_fused = fused == "1" and bool(lib().st_rnn_fused_loss_supported(C.byref(prm)))
         assert use_fused == (fused == "1" and dt == torch.bfloat16)
         logits = None if use_fused else torch.empty(n, ldl, device="cuda", dtype=ldt)
-        check(lib().st_rnn_forward(C.byref(prm), C.byref(seq), None, _cp(m._feature(feat.cuda())), _cp(ws), nbytes, _cp(logits),
-                                   dtype_code(ldt), ldl, _cp(targets), 1, _stream()), "st_rnn_forward")
+        check(lib().st_rnn_forward(C.byref(prm), C.byref(seq), _cp(m._feature(feat.cuda())), _cp(ws), nbytes, _cp(logits),
+                                   dtype_code(ldt), ldl, _cp(targets), 1, None, None, _stream()), "st_rnn_forward")
         if use_fused:
             sb = lib().st_rnn_fused_loss_bytes(C.byref(prm), C.byref(seq))
             s1, sw_ = (torch.empty(sb // 4, device="cuda") for _ in range(2))
             d1, dw = (torch.full((n, ldd), 7.0, device="cuda", dtype=dt) for _ in range(2))
             a = (C.byref(prm), C.byref(seq), _cp(ws), nbytes, _cp(targets))
-            check(lib().st_rnn_fused_loss(*a, _cp(s1), sb, _cp(loss1), _stream()), "st_rnn_fused_loss")
-            check(lib().st_rnn_fused_dlogits(*a, _cp(s1), _cp(gsc), _cp(d1), ldd, _stream()), "st_rnn_fused_dlogits")
-            check(lib().st_rnn_fused_loss_w(*a, _cp(sw_), sb, _cp(w), _cp(nll), _cp(lossw), _stream()), "st_rnn_fused_loss_w")
-            check(lib().st_rnn_fused_dlogits_w(*a, _cp(sw_), _cp(gsc), _cp(w), _cp(dw), ldd, _stream()), "st_rnn_fused_dlogits_w")
+            check(lib().st_rnn_fused_loss(*a, _cp(s1), sb, None, _cp(loss1), None, _stream()), "st_rnn_fused_loss")
+            check(lib().st_rnn_fused_dlogits(*a, _cp(s1), _cp(gsc), None, _cp(d1), ldd, None, _stream()), "st_rnn_fused_dlogits")
+            check(lib().st_rnn_fused_loss(*a, _cp(sw_), sb, C.byref(terms), _cp(lossw), None, _stream()), "st_rnn_fused_loss")
+            check(lib().st_rnn_fused_dlogits(*a, _cp(sw_), _cp(gsc), C.byref(terms), _cp(dw), ldd, None, _stream()), "st_rnn_fused_dlogits")
             torch.cuda.synchronize()
             assert torch.equal(s1[:n], sw_[:n])                   # the rows' logsumexp does not depend on the weights
             _check_linear(d1, dw, w, V, nll, loss1, lossw)
             return
     d1, dw = (torch.full((n, ldd), 7.0, device="cuda", dtype=ldt) for _ in range(2))
     dtc = dtype_code(ldt)
-    check(lib().st_cross_entropy(_cp(logits), dtc, _cp(targets), n, V, ldl, _cp(loss1), _cp(d1), dtc, ldd, 1.0, _cp(gsc), _stream()),
+    check(lib().st_cross_entropy(_cp(logits), dtc, _cp(targets), n, V, ldl, None, _cp(loss1), _cp(d1), dtc, ldd, 1.0, _cp(gsc), _stream()),
           "st_cross_entropy")
-    check(lib().st_cross_entropy_w(_cp(logits), dtc, _cp(targets), n, V, ldl, _cp(w), _cp(nll), _cp(lossw), _cp(dw), dtc, ldd, 1.0,
-                                   _cp(gsc), _stream()), "st_cross_entropy_w")
+    check(lib().st_cross_entropy(_cp(logits), dtc, _cp(targets), n, V, ldl, C.byref(terms), _cp(lossw), _cp(dw), dtc, ldd, 1.0, _cp(gsc),
+                                 _stream()), "st_cross_entropy")
     torch.cuda.synchronize()
     _check_linear(d1, dw, w, V, nll, loss1, lossw)
 

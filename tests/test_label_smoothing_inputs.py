@@ -74,7 +74,7 @@ def _host_descriptors(V=777, lens=(4, 3, 2)):
 
 
 def test_the_c_entry_points_refuse_a_short_tile_sums_buffer_and_a_bad_label_smoothing():
-    """Checked errors of the new entry points; each is raised on the host before anything is launched."""
+    """Checked errors of the loss entry points' st_loss_terms; each is raised on the host before anything is launched."""
     from showtell_amd import ShowTellHipError, _lib
     lib, check = _lib.lib(), _lib.check
     p, s, a, keep = _host_descriptors()
@@ -84,17 +84,40 @@ def test_the_c_entry_points_refuse_a_short_tile_sums_buffer_and_a_bad_label_smoo
     # the existing queries return what they returned: the tile sums live in a buffer of their own
     assert lib.st_rnn_fused_loss_bytes(C.byref(p), C.byref(s)) == ntok * (2 + 2 * tiles) * 4
     wb, sb = lib.st_rnn_workspace_bytes(C.byref(p), C.byref(s)), lib.st_rnn_fused_loss_bytes(C.byref(p), C.byref(s))
+
+    def terms(smoothing, eps, smooth_out=None, tile_sums=None, tile_sums_bytes=0):
+        return C.byref(_lib.LossTerms(None, None, smoothing, eps, smooth_out, tile_sums, tile_sums_bytes))
+
+    def fused_loss(t):
+        return lib.st_rnn_fused_loss(C.byref(p), C.byref(s), a, wb, a, a, sb, t, a, None, None)
+
+    def fused_dlogits(t):
+        return lib.st_rnn_fused_dlogits(C.byref(p), C.byref(s), a, wb, a, a, a, t, a, 784, None, None)
+
+    def cross_entropy(t):
+        return lib.st_cross_entropy(a, _lib.ST_F32, a, 4, 10, 16, t, a, None, 0, 16, 1.0, None, None)
     with pytest.raises(ShowTellHipError, match="tile_sums too small"):
-        check(lib.st_rnn_fused_loss_ls(C.byref(p), C.byref(s), a, wb, a, a, sb, None, None, a, 0.1, a, need - 4, a, None), "short")
+        check(fused_loss(terms(1, 0.1, a, a, need - 4)), "short")
     with pytest.raises(ShowTellHipError, match="null pointer"):
-        check(lib.st_rnn_fused_loss_ls(C.byref(p), C.byref(s), a, wb, a, a, sb, None, None, a, 0.1, None, need, a, None), "null")
+        check(fused_loss(terms(1, 0.1, a, None, need)), "null")
     for bad in (-0.1, 1.0, float("nan")):
-        with pytest.raises(ShowTellHipError, match="outside"):
-            check(lib.st_rnn_fused_loss_ls(C.byref(p), C.byref(s), a, wb, a, a, sb, None, None, a, bad, a, need, a, None), "eps")
-        with pytest.raises(ShowTellHipError, match="outside"):
-            check(lib.st_rnn_fused_dlogits_ls(C.byref(p), C.byref(s), a, wb, a, a, a, None, bad, a, 784, None), "eps")
-        with pytest.raises(ShowTellHipError, match="outside"):
-            check(lib.st_cross_entropy_ls(a, _lib.ST_F32, a, 4, 10, 16, None, None, None, bad, a, None, 0, 16, 1.0, None, None), "eps")
+        for call in (fused_loss, fused_dlogits, cross_entropy):
+            with pytest.raises(ShowTellHipError, match="outside"):
+                check(call(terms(1, bad, a, a, need)), "eps")
+    # smoothing = 0 takes none of the smoothing arguments: each is an error, not an argument that is silently ignored
+    for t in (dict(eps=0.1), dict(eps=float("nan")), dict(eps=0.0, smooth_out=a), dict(eps=0.0, tile_sums=a, tile_sums_bytes=need)):
+        for call in (fused_loss, fused_dlogits, cross_entropy):
+            with pytest.raises(ShowTellHipError, match="smoothing = 0 takes no label_smoothing, smooth_out or tile_sums"):
+                check(call(terms(0, **t)), "smoothing = 0")
+
+
+def test_st_rnn_forward_refuses_a_layer_0_width_that_is_not_the_embedding_width():
+    """in0 != E: the layer-0 rows are [feature ; embeddings] gathered by the call itself, there is no other source for them."""
+    from showtell_amd import ShowTellHipError, _lib
+    p, s, a, keep = _host_descriptors()
+    p.in0 = 256
+    with pytest.raises(ShowTellHipError, match=r"in0=256 != E=512"):
+        _lib.check(_lib.lib().st_rnn_forward(C.byref(p), C.byref(s), a, a, 1 << 40, None, 0, 0, a, 0, None, None, None), "in0")
 
 
 # ---- the inputs and bounds have power -----------------------------------------------------------------------------------------

@@ -27,7 +27,7 @@ nbytes = lib().st_rnn_workspace_bytes(C.byref(prm), C.byref(seq))
 ws = torch.empty(nbytes, device="cuda", dtype=torch.uint8)
 feat = torch.randn(B, E, device="cuda").bfloat16()
 targets = torch.empty(n, device="cuda", dtype=torch.long)
-check(lib().st_rnn_forward(C.byref(prm), C.byref(seq), None, _cp(feat), _cp(ws), nbytes, None, ST_BF16, Vp, _cp(targets), 1, _stream()),
+check(lib().st_rnn_forward(C.byref(prm), C.byref(seq), _cp(feat), _cp(ws), nbytes, None, ST_BF16, Vp, _cp(targets), 1, None, None, _stream()),
       "st_rnn_forward")
 dlog = (torch.randn(n, Vp, device="cuda") / n).bfloat16()
 dlog[:, V:] = 0
@@ -35,8 +35,8 @@ dfeat = torch.empty(B, E, device="cuda", dtype=torch.float32)
 
 
 def backward():
-    check(lib().st_rnn_backward(C.byref(prm), C.byref(grads), C.byref(seq), None, _cp(dlog), Vp, None, _cp(ws), nbytes, _cp(dfeat),
-                                None, _stream()), "st_rnn_backward")
+    check(lib().st_rnn_backward(C.byref(prm), C.byref(grads), C.byref(seq), _cp(dlog), Vp, _cp(ws), nbytes, _cp(dfeat), None, None,
+                                _stream()), "st_rnn_backward")
 
 
 def timed(warm=5, calls=20):
