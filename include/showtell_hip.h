@@ -669,6 +669,20 @@ int st_sample_rows(const float* logits, int ldl, int n, int V, const float* u, i
 size_t st_rnn_sample_workspace_bytes(const st_rnn_params* p, int n);
 int st_rnn_sample(const st_rnn_params* p, const void* feat, int n, int steps, const float* u, float inv_temperature, int top_k,
                   long end_id, void* workspace, size_t workspace_bytes, long* ids_out, float* logp_out, void* stream);
+/* Nucleus (top-p) sampling (Holtzman et al., 2020): the siblings above with one more filter, 0 < top_p <= 1 (anything else,
+ * NaN included, is refused before a launch).  Order of the filters: temperature, top_k, top_p.  Order the entries of K (above)
+ * by value descending, the lowest index first among equal values (+0.0 and -0.0 are equal); entry j is kept iff the
+ * probability mass, renormalised over K, of the entries strictly before it is below top_p.  The first entry is always kept,
+ * entries of weight 0 (-inf) come last, and the nucleus may be any size from 1 to V.  The token is drawn among the kept
+ * entries in index order from u as above, and logp is its log-probability under the kept, renormalised distribution.
+ * top_p = 1 is the filter OFF, not a nucleus of mass 1: the call is then its sibling's, the same launch bit for bit (the
+ * siblings forward here with top_p = 1).  The draw is a pure function of (logits, u, inv_temperature, top_k, top_p): no
+ * floating-point atomics, every sum in a fixed order.  Same workspaces, same single launch per step. */
+int st_sample_rows_topp(const float* logits, int ldl, int n, int V, const float* u, int u_stride, float inv_temperature, int top_k,
+                        float top_p, long end_id, uint8_t* finished, long* ids_out, float* logp_out, int out_stride, int t, long* cur,
+                        void* stream);
+int st_rnn_sample_topp(const st_rnn_params* p, const void* feat, int n, int steps, const float* u, float inv_temperature, int top_k,
+                       float top_p, long end_id, void* workspace, size_t workspace_bytes, long* ids_out, float* logp_out, void* stream);
 /* Scheduled sampling (Bengio et al., 2015): the inputs of a teacher-forced pass with some slots holding the model's own draw.
  * st_sample_mix_rows: st_sample_rows' draw (same rule, same routes, same u) and the mix in one launch, without a finished state
  *   (the caption decides a row's length).  Row r is REPLACED iff step < lens[r] and coin[r * coin_stride] < p (strict: p = 0
@@ -744,6 +758,10 @@ size_t st_attn_sample_workspace_bytes(const st_attn_params* p, int n);
 int st_attn_sample(const st_attn_params* p, const float* cnn_feature, int n, int steps, long start_id, const float* u,
                    float inv_temperature, int top_k, long end_id, void* workspace, size_t workspace_bytes,
                    long* ids_out, float* logp_out, float* alphas_out, void* stream);
+/* st_attn_sample with the nucleus filter of st_sample_rows_topp (0 < top_p <= 1; top_p = 1 is st_attn_sample itself) */
+int st_attn_sample_topp(const st_attn_params* p, const float* cnn_feature, int n, int steps, long start_id, const float* u,
+                        float inv_temperature, int top_k, float top_p, long end_id, void* workspace, size_t workspace_bytes,
+                        long* ids_out, float* logp_out, float* alphas_out, void* stream);
 /* st_rnn_sched_inputs for the attention decoders (the loop of st_attn_sample following the caption): step t feeds slot t, so
  * step t's logits decide slot t + 1, valid iff t + 1 < lens[r]; slot 0 (<start>) is never replaced.  caption [n][Tcap] and its
  * transpose caption_T [Tcap][n] (what st_attn_forward takes); coin, u and the outputs as st_rnn_sched_inputs. */

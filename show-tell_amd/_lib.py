@@ -197,8 +197,10 @@ _SIGS = {
     "st_beam_ban_topk": ([c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_i, c_l, c_i, c_p, c_p, c_p], c_i),
     "st_beam_select_hist": ([c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p], c_i),
     "st_sample_rows": ([c_p, c_i, c_i, c_i, c_p, c_i, c_f, c_i, c_l, c_p, c_p, c_p, c_i, c_i, c_p, c_p], c_i),
+    "st_sample_rows_topp": ([c_p, c_i, c_i, c_i, c_p, c_i, c_f, c_i, c_f, c_l, c_p, c_p, c_p, c_i, c_i, c_p, c_p], c_i),
     "st_rnn_sample_workspace_bytes": ([C.POINTER(RnnParams), c_i], C.c_size_t),
     "st_rnn_sample": ([C.POINTER(RnnParams), c_p, c_i, c_i, c_p, c_f, c_i, c_l, c_p, C.c_size_t, c_p, c_p, c_p], c_i),
+    "st_rnn_sample_topp": ([C.POINTER(RnnParams), c_p, c_i, c_i, c_p, c_f, c_i, c_f, c_l, c_p, C.c_size_t, c_p, c_p, c_p], c_i),
     "st_sample_mix_rows": ([c_p, c_i, c_i, c_i, c_p, c_i, c_f, c_i, c_p, c_i, c_f, c_p, c_i, c_l, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p,
                             c_p], c_i),
     "st_rnn_sched_inputs_workspace_bytes": ([C.POINTER(RnnParams), c_i], C.c_size_t),
@@ -214,6 +216,7 @@ _SIGS = {
     "st_attn_greedy_alphas": ([c_p, c_p, c_i, c_i, c_l, c_p, C.c_size_t, c_p, c_p, c_p], c_i),
     "st_attn_sample_workspace_bytes": ([c_p, c_i], C.c_size_t),
     "st_attn_sample": ([c_p, c_p, c_i, c_i, c_l, c_p, c_f, c_i, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p], c_i),
+    "st_attn_sample_topp": ([c_p, c_p, c_i, c_i, c_l, c_p, c_f, c_i, c_f, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p], c_i),
     "st_attn_sched_inputs_workspace_bytes": ([c_p, c_i], C.c_size_t),
     "st_attn_sched_inputs": ([c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_f, c_f, c_i, c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p], c_i),
     "st_attn_beam_workspace_bytes": ([c_p, c_i, c_i], C.c_size_t),

@@ -365,7 +365,7 @@ extern "C" size_t st_attn_greedy_workspace_bytes(const st_attn_params* p, int B)
 
 namespace {
 // how a step turns its logits into the next token: NULL = arg-max (rnn_attn.py:141), else a draw by st_sample_rows
-struct SampleSpec { const float* u; float inv_temperature; int top_k; long end_id; float* logp_out; };
+struct SampleSpec { const float* u; float inv_temperature; int top_k; float top_p; long end_id; float* logp_out; };
 // scheduled sampling's roll-in (st_attn_sched_inputs): step 0 reads the captions' first column, step t's logits decide slot t + 1 by
 // st_sample_mix_rows, which also hands the next step its token
 struct MixSpec { const long* caption_T; int Tcap; const int* lens; const float* coin; const float* u; float prob, inv_temperature; int top_k;
@@ -415,8 +415,8 @@ int attn_greedy_run(const st_attn_params* p, const float* cnn_feature, int B, in
                              mix->caption_T, 1, (long)(t + 1) * B, mix->lens, t + 1, mix->drawn, mix->logp, mix->input_ids, mix->replaced, mix->Tcap,
                              t + 1, cur, stream)) return 1;
     } else if (sp) {
-      if (st_sample_rows(logits, Vp, B, r.V, sp->u + t, steps, sp->inv_temperature, sp->top_k, sp->end_id, fin, ids_out, sp->logp_out, steps, t,
-                         cur, stream)) return 1;
+      if (st_sample_rows_topp(logits, Vp, B, r.V, sp->u + t, steps, sp->inv_temperature, sp->top_k, sp->top_p, sp->end_id, fin, ids_out, sp->logp_out,
+                              steps, t, cur, stream)) return 1;
     } else if (argmax_rows_launch(logits, Vp, B, r.V, ids_out, steps, t, cur, st)) return 1;   // first maximum, like torch.max (rnn_attn.py:141)
     c = nx;
   }
@@ -443,8 +443,16 @@ extern "C" size_t st_attn_sample_workspace_bytes(const st_attn_params* p, int n)
 extern "C" int st_attn_sample(const st_attn_params* p, const float* cnn_feature, int n, int steps, long start_id, const float* u,
                               float inv_temperature, int top_k, long end_id, void* workspace, size_t workspace_bytes,
                               long* ids_out, float* logp_out, float* alphas_out, void* stream) {
+  return st_attn_sample_topp(p, cnn_feature, n, steps, start_id, u, inv_temperature, top_k, 1.f, end_id, workspace, workspace_bytes, ids_out, logp_out,
+                             alphas_out, stream);
+}
+
+extern "C" int st_attn_sample_topp(const st_attn_params* p, const float* cnn_feature, int n, int steps, long start_id, const float* u,
+                                   float inv_temperature, int top_k, float top_p, long end_id, void* workspace, size_t workspace_bytes,
+                                   long* ids_out, float* logp_out, float* alphas_out, void* stream) {
+  ST_CHECK(top_p > 0.f && top_p <= 1.f, "st_attn_sample: need 0 < top_p <= 1 (got %g)", (double)top_p);
   ST_CHECK(u && logp_out, "st_attn_sample: null pointer");
-  const SampleSpec sp = {u, inv_temperature, top_k, end_id, logp_out};
+  const SampleSpec sp = {u, inv_temperature, top_k, top_p, end_id, logp_out};
   return attn_greedy_run(p, cnn_feature, n, steps, start_id, workspace, workspace_bytes, ids_out, alphas_out, stream, "st_attn_sample", &sp);
 }
 

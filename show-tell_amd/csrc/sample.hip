@@ -11,11 +11,14 @@
 //           last kept element (T, Ti): v is kept iff v > T or (v == T and index <= Ti);
 //   pass 2  per-thread sum of exp over the kept elements of its range, block scan of the 256 partial sums;
 //   pass 3  the first thread whose inclusive sum exceeds u * sum walks its own range (at most `chunk` elements).
+// With top_p < 1 (the NUC form) a nucleus search between passes 1 and 2 moves (T, Ti) to the last element of the shortest
+// prefix of that order whose mass reaches top_p (of the top_k set when top_k > 0); passes 2 and 3 then run as they are.
 // No lane ever sums a whole row.  Rows of up to 256 x 40 entries (V = 10000) are read ONCE, with all of a thread's loads in
 // flight together, and stay in registers between the passes; longer or unaligned rows take the passes over memory.
 // A row needs at least one finite entry: with none (all -inf or NaN) the token is 0 and logp is NaN.
 #include "decoder_host.h"
 #include "select.h"
+#include <type_traits>
 
 namespace {
 
@@ -64,6 +67,55 @@ struct RowReg {
   }
 };
 
+// The nucleus search's view of a thread's range: above(piv) is the sum, in index order, of the weights wf(value, index) of the
+// entries with value > piv.  Over memory the weights are recomputed in every round; the register-resident row computes them
+// once and keeps them next to the row.
+template <typename Row>
+struct RowWeights {
+  template <typename WF> __device__ __forceinline__ RowWeights(const Row&, WF&&) {}
+  template <typename WF> __device__ __forceinline__ float above(const Row& r, float piv, WF&& wf) const {
+    float s = 0.f;
+    r.each([&](float v, int i) { if (v > piv) s += wf(v, i); });
+    return s;
+  }
+};
+template <>
+struct RowWeights<RowReg> {
+  float w[kSampleRegs];
+  template <typename WF> __device__ __forceinline__ RowWeights(const RowReg& r, WF&& wf) {
+#pragma unroll
+    for (int j = 0; j < kSampleRegs; ++j) w[j] = r.lo + j < r.hi ? wf(r.rv[j], r.lo + j) : 0.f;
+  }
+  template <typename WF> __device__ __forceinline__ float above(const RowReg& r, float piv, WF&&) const {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < kSampleRegs; ++j) s += r.rv[j] > piv ? w[j] : 0.f;      // + 0 leaves a sum of weights >= 0 as it is
+    return s;
+  }
+};
+
+// float <-> unsigned, order preserving (the value half of select.h::argmax_key); -0.0 sits one below +0.0, and the search
+// compares floats, to which the two are one value
+__device__ __forceinline__ unsigned ord_of(float v) { const unsigned b = __float_as_uint(v); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
+__device__ __forceinline__ float ord_value(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
+
+// Sum of a float over the wave, in every lane, always in the same order: pairs, quads, eights and sixteens inside each row
+// of 16 lanes by DPP (no LDS round trip, which six dependent shuffles would make of every round of the search), then the
+// four rows in order.
+__device__ __forceinline__ float wave_sum_dpp(float x) {
+  auto dpp = [](float v, auto ctrl) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), decltype(ctrl)::value, 0xf, 0xf, false));
+  };
+  x += dpp(x, std::integral_constant<int, 0xB1>{});          // quad_perm [1, 0, 3, 2]
+  x += dpp(x, std::integral_constant<int, 0x4E>{});          // quad_perm [2, 3, 0, 1]
+  x += dpp(x, std::integral_constant<int, 0x141>{});         // row_half_mirror
+  x += dpp(x, std::integral_constant<int, 0x140>{});         // row_mirror: every lane of a row holds the row's sum
+  const int xi = __float_as_int(x);
+  const float r0 = __int_as_float(__builtin_amdgcn_readlane(xi, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(xi, 16));
+  const float r2 = __int_as_float(__builtin_amdgcn_readlane(xi, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(xi, 48));
+  return ((r0 + r1) + r2) + r3;
+}
+
 // What the MIX form (scheduled sampling, st_sample_mix_rows) takes beyond the draw's arguments: the row's slot takes the draw iff the
 // step it feeds is inside the row's caption and its coin fell below p; every other row skips the three passes and keeps the
 // teacher's token.  No finished state there: the caption decides a row's length.
@@ -74,11 +126,13 @@ struct MixArgs {
   long* mixed_out; uint8_t* replaced_out;
 };
 
-template <typename Row, bool MIX = false>
+// NUC: top_p < 1, the nucleus search after pass 1 (never with MIX); without it top_p is not read
+template <typename Row, bool MIX = false, bool NUC = false>
 __global__ __launch_bounds__(kSampleThreads) void sample_rows_kernel(const float* __restrict__ logits, int ldl, int V, const float* __restrict__ u,
                                                                      int u_stride, float inv_t, int top_k, long end_id, uint8_t* __restrict__ finished,
                                                                      long* __restrict__ ids_out, float* __restrict__ logp_out, int out_stride, int t,
-                                                                     long* __restrict__ cur, MixArgs mix) {
+                                                                     long* __restrict__ cur, MixArgs mix, float top_p) {
+  static_assert(!(MIX && NUC), "the scheduled-sampling draw has no nucleus");
   __shared__ float s_tm[kSampleThreads];
   __shared__ float c_v[kSampleCap]; __shared__ int c_i[kSampleCap];
   __shared__ float s_max[4], s_sum[4], s_bv[4]; __shared__ int s_bi[4], s_last[4], s_first[4];
@@ -148,6 +202,59 @@ __global__ __launch_bounds__(kSampleThreads) void sample_rows_kernel(const float
     __syncthreads();
     T = s_T; Ti = s_Ti;
   }
+  if constexpr (NUC) {
+    // ---- the nucleus: (T, Ti) moves to the last element whose preceding mass is below top_p * (mass of the set so far) ----
+    // G(x) = sum of the weights of the eligible elements of value > x, always in the same order (a thread's range in index
+    // order, wave_sum_dpp, the four waves): floating-point addition is monotone, so G falls as x rises and the smallest
+    // x with G(x) < P is well defined.  It is the value of the last kept element; bisection over the order-preserving integer
+    // image of the floats between the lowest eligible value and the maximum finds it in at most 32 rounds of one barrier each.
+    __shared__ float s_g[2][4]; __shared__ int s_n[4];
+    const float Tk = T; const int Tki = Ti;
+    auto elig_w = [&](float v, int i) { return (v > Tk || (v == Tk && i <= Tki)) ? expf((v - M) * inv_t) : 0.f; };
+    const RowWeights<Row> rw(row_part, elig_w);
+    int par = 0;
+    auto G = [&](float piv) {
+      float g = wave_sum_dpp(rw.above(row_part, piv, elig_w));
+      if (lane == 0) s_g[par][wid] = g;
+      __syncthreads();                                       // one barrier a round: the next round writes the other half
+      g = ((s_g[par][0] + s_g[par][1]) + s_g[par][2]) + s_g[par][3];
+      par ^= 1;
+      return g;
+    };
+    const float P = top_p * G(-INFINITY);                    // -inf entries weigh 0
+    unsigned xlo = ord_of(Tk), xhi = ord_of(M);              // G(M) = 0 < P
+    float Ghi = 0.f;
+    while (xlo < xhi) {                                      // (block-uniform: every thread holds the same sums)
+      const unsigned mid = xlo + (xhi - xlo) / 2;
+      const float g = G(ord_value(mid));
+      if (g < P) { xhi = mid; Ghi = g; } else xlo = mid + 1;
+    }
+    const float Tn = ord_value(xhi);
+    // among the elements equal to Tn, which weigh wT each, the first m are kept: the j-th of them (from 0) has Ghi + j * wT
+    // before it, a sequence that rises with j.  An integer scan of the per-thread counts finds the m-th one's index.
+    int cnt = 0;
+    row_part.each([&](float v, int i) { if (v == Tn && (v > Tk || i <= Tki)) ++cnt; });
+    int cinc = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(cinc, o, 64); if (lane >= o) cinc += y; }
+    if (lane == 63) s_n[wid] = cinc;
+    __syncthreads();
+    int cex = cinc - cnt;
+    for (int w = 0; w < wid; ++w) cex += s_n[w];
+    const int neq = s_n[0] + s_n[1] + s_n[2] + s_n[3];
+    const float wT = expf((Tn - M) * inv_t);
+    int mlo = 1, mhi = neq;                                  // the largest m in [1, neq] with Ghi + (m - 1) * wT < P; m = 1 holds: Ghi < P
+    while (mlo < mhi) {
+      const int mm = mlo + (mhi - mlo + 1) / 2;
+      if (Ghi + (float)(mm - 1) * wT < P) mlo = mm; else mhi = mm - 1;
+    }
+    if (cex < mlo && mlo <= cex + cnt) {                     // one thread: the m-th equal element is in its range
+      int seen = cex;
+      row_part.each([&](float v, int i) { if (v == Tn && (v > Tk || i <= Tki) && ++seen == mlo) { s_T = Tn; s_Ti = i; } });
+    }
+    __syncthreads();
+    if (neq > 0) { T = s_T; Ti = s_Ti; }                     // neq == 0: a row of NaNs, the set stays what it was
+  }
   auto kept = [&](float v, int i) { return v > T || (v == T && i <= Ti); };
   // (v - M) * inv_t, not v * inv_t - M * inv_t: exactly 0 at the maximum, and no product feeds an addition that the
   // compiler could contract into a fused multiply-add in one pass and not in the other
@@ -207,8 +314,28 @@ __global__ __launch_bounds__(kSampleThreads) void sample_rows_kernel(const float
 
 }  // namespace
 
+namespace {
+template <typename Row>
+void launch_sample_rows(bool nucleus, int n, hipStream_t st, const float* logits, int ldl, int V, const float* u, int u_stride, float inv_t, int top_k,
+                        long end_id, uint8_t* finished, long* ids_out, float* logp_out, int out_stride, int t, long* cur, float top_p) {
+  if (nucleus)
+    hipLaunchKernelGGL((sample_rows_kernel<Row, false, true>), dim3(n), dim3(kSampleThreads), 0, st, logits, ldl, V, u, u_stride, inv_t, top_k, end_id,
+                       finished, ids_out, logp_out, out_stride, t, cur, MixArgs{}, top_p);
+  else
+    hipLaunchKernelGGL(sample_rows_kernel<Row>, dim3(n), dim3(kSampleThreads), 0, st, logits, ldl, V, u, u_stride, inv_t, top_k, end_id, finished,
+                       ids_out, logp_out, out_stride, t, cur, MixArgs{}, 1.f);
+}
+}  // namespace
+
 extern "C" int st_sample_rows(const float* logits, int ldl, int n, int V, const float* u, int u_stride, float inv_temperature, int top_k,
                               long end_id, uint8_t* finished, long* ids_out, float* logp_out, int out_stride, int t, long* cur, void* stream) {
+  return st_sample_rows_topp(logits, ldl, n, V, u, u_stride, inv_temperature, top_k, 1.f, end_id, finished, ids_out, logp_out, out_stride, t, cur, stream);
+}
+
+extern "C" int st_sample_rows_topp(const float* logits, int ldl, int n, int V, const float* u, int u_stride, float inv_temperature, int top_k,
+                                   float top_p, long end_id, uint8_t* finished, long* ids_out, float* logp_out, int out_stride, int t, long* cur,
+                                   void* stream) {
+  ST_CHECK(top_p > 0.f && top_p <= 1.f, "st_sample_rows: need 0 < top_p <= 1 (got %g)", (double)top_p);      // NaN fails both
   ST_CHECK(logits && u && finished && ids_out && logp_out, "st_sample_rows: null pointer");
   ST_CHECK(V >= 1 && ldl >= V, "st_sample_rows: need 1 <= V <= ldl (got V=%d ldl=%d)", V, ldl);
   ST_CHECK(inv_temperature > 0.f, "st_sample_rows: inv_temperature must be > 0");
@@ -218,15 +345,13 @@ extern "C" int st_sample_rows(const float* logits, int ldl, int n, int V, const 
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const bool vec = ldl % 4 == 0 && reinterpret_cast<uintptr_t>(logits) % 16 == 0;
   const bool regs = vec && V <= kSampleThreads * kSampleRegs;       // the kernel's chunk = V / 256 rounded up to 4 fits kSampleRegs
+  const bool nucleus = top_p < 1.f;                                  // top_p = 1 is the feature off: the launch st_sample_rows always made
   if (regs)
-    hipLaunchKernelGGL(sample_rows_kernel<RowReg>, dim3(n), dim3(kSampleThreads), 0, st, logits, ldl, V, u, u_stride, inv_temperature, top_k, end_id,
-                       finished, ids_out, logp_out, out_stride, t, cur, MixArgs{});
+    launch_sample_rows<RowReg>(nucleus, n, st, logits, ldl, V, u, u_stride, inv_temperature, top_k, end_id, finished, ids_out, logp_out, out_stride, t, cur, top_p);
   else if (vec)
-    hipLaunchKernelGGL(sample_rows_kernel<RowMem<true>>, dim3(n), dim3(kSampleThreads), 0, st, logits, ldl, V, u, u_stride, inv_temperature, top_k, end_id,
-                       finished, ids_out, logp_out, out_stride, t, cur, MixArgs{});
+    launch_sample_rows<RowMem<true>>(nucleus, n, st, logits, ldl, V, u, u_stride, inv_temperature, top_k, end_id, finished, ids_out, logp_out, out_stride, t, cur, top_p);
   else
-    hipLaunchKernelGGL(sample_rows_kernel<RowMem<false>>, dim3(n), dim3(kSampleThreads), 0, st, logits, ldl, V, u, u_stride, inv_temperature, top_k, end_id,
-                       finished, ids_out, logp_out, out_stride, t, cur, MixArgs{});
+    launch_sample_rows<RowMem<false>>(nucleus, n, st, logits, ldl, V, u, u_stride, inv_temperature, top_k, end_id, finished, ids_out, logp_out, out_stride, t, cur, top_p);
   ST_LAUNCH_CHECK();
   return 0;
 }
@@ -249,13 +374,13 @@ extern "C" int st_sample_mix_rows(const float* logits, int ldl, int n, int V, co
   const MixArgs mix = {coin, coin_stride, p, teacher, teacher_stride, teacher_col, lens, step, mixed_out, replaced_out};
   if (regs)
     hipLaunchKernelGGL((sample_rows_kernel<RowReg, true>), dim3(n), dim3(kSampleThreads), 0, st, logits, ldl, V, u, u_stride, inv_temperature, top_k, 0L,
-                       (uint8_t*)nullptr, ids_out, logp_out, out_stride, t, cur, mix);
+                       (uint8_t*)nullptr, ids_out, logp_out, out_stride, t, cur, mix, 1.f);
   else if (vec)
     hipLaunchKernelGGL((sample_rows_kernel<RowMem<true>, true>), dim3(n), dim3(kSampleThreads), 0, st, logits, ldl, V, u, u_stride, inv_temperature, top_k,
-                       0L, (uint8_t*)nullptr, ids_out, logp_out, out_stride, t, cur, mix);
+                       0L, (uint8_t*)nullptr, ids_out, logp_out, out_stride, t, cur, mix, 1.f);
   else
     hipLaunchKernelGGL((sample_rows_kernel<RowMem<false>, true>), dim3(n), dim3(kSampleThreads), 0, st, logits, ldl, V, u, u_stride, inv_temperature, top_k,
-                       0L, (uint8_t*)nullptr, ids_out, logp_out, out_stride, t, cur, mix);
+                       0L, (uint8_t*)nullptr, ids_out, logp_out, out_stride, t, cur, mix, 1.f);
   ST_LAUNCH_CHECK();
   return 0;
 }
@@ -284,6 +409,12 @@ extern "C" size_t st_rnn_sample_workspace_bytes(const st_rnn_params* p, int n) {
 
 extern "C" int st_rnn_sample(const st_rnn_params* p, const void* feat, int n, int steps, const float* u, float inv_temperature, int top_k,
                              long end_id, void* workspace, size_t workspace_bytes, long* ids_out, float* logp_out, void* stream) {
+  return st_rnn_sample_topp(p, feat, n, steps, u, inv_temperature, top_k, 1.f, end_id, workspace, workspace_bytes, ids_out, logp_out, stream);
+}
+
+extern "C" int st_rnn_sample_topp(const st_rnn_params* p, const void* feat, int n, int steps, const float* u, float inv_temperature, int top_k,
+                                  float top_p, long end_id, void* workspace, size_t workspace_bytes, long* ids_out, float* logp_out, void* stream) {
+  ST_CHECK(top_p > 0.f && top_p <= 1.f, "st_rnn_sample: need 0 < top_p <= 1 (got %g)", (double)top_p);
   ST_CHECK(p && feat && u && workspace && ids_out && logp_out, "st_rnn_sample: null pointer");
   ST_CHECK(n > 0 && steps > 0, "st_rnn_sample: need n > 0 and steps > 0");
   ST_CHECK(p->L >= 1 && p->L <= ST_MAX_LAYERS && p->in0 == p->E, "st_rnn_sample: bad decoder configuration");
@@ -304,7 +435,7 @@ extern "C" int st_rnn_sample(const st_rnn_params* p, const void* feat, int n, in
     // step 0: the image feature from a zero state (rnn.py:44-47); later steps: the embedding of the row's last token (rnn.py:53)
     if (st_rnn_step(p, t == 0 ? feat : ws + q.x, n, t == 0 ? nullptr : ws + q.h[c], (t == 0 || !lstm) ? nullptr : ws + q.c[c], ws + q.h[nx],
                     lstm ? ws + q.c[nx] : nullptr, logits, Vp, stream)) return 1;
-    if (st_sample_rows(logits, Vp, n, p->V, u + t, steps, inv_temperature, top_k, end_id, fin, ids_out, logp_out, steps, t, cur, stream)) return 1;
+    if (st_sample_rows_topp(logits, Vp, n, p->V, u + t, steps, inv_temperature, top_k, top_p, end_id, fin, ids_out, logp_out, steps, t, cur, stream)) return 1;
     if (t + 1 < steps && st_embedding_rows(p->emb, cur, ws + q.x, n, p->E, p->V, p->E, p->dtype, stream)) return 1;
     c = nx;
   }

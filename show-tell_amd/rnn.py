@@ -48,8 +48,10 @@ def up8(v):
     return (v + 7) // 8 * 8
 
 
-def check_sample_args(vocab_size, batch, num_samples, temperature, top_k, max_length, uniforms):
+def check_sample_args(vocab_size, batch, num_samples, temperature, top_k, max_length, uniforms, top_p=1.0):
     """Argument errors of ``sample`` (both decoders), raised before anything touches the device."""
+    if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not 0 < top_p <= 1:        # NaN fails both comparisons
+        raise ValueError(f"top_p must be in (0, 1], 1 switching the nucleus off (got {top_p!r})")
     if not temperature > 0:
         raise ValueError(f"temperature must be > 0 (got {temperature})")
     if int(top_k) != top_k or not 0 <= top_k <= min(32, vocab_size):
@@ -380,10 +382,10 @@ class Decoder(FollowsMoves, nn.Module):
         f = cnn_feature.detach().contiguous()
         return f if f.dtype == self.compute_dtype else ops.cast(f.float(), self.compute_dtype)
 
-    def _sample_shape(self, cnn_feature, num_samples, temperature, top_k, max_length, uniforms):
+    def _sample_shape(self, cnn_feature, num_samples, temperature, top_k, max_length, uniforms, top_p=1.0):
         """(B, S, T) of a ``sample`` call, its arguments checked before anything touches the device."""
         B = cnn_feature.shape[0]
-        check_sample_args(self.vocab_size, B, num_samples, temperature, top_k, max_length, uniforms)
+        check_sample_args(self.vocab_size, B, num_samples, temperature, top_k, max_length, uniforms, top_p)
         return B, int(num_samples), int(max_length)
 
     def scheduled_inputs(self, cnn_feature, image_caption, caption_size, p, temperature=1.0, top_k=0, generator=None, uniforms=None):
@@ -545,15 +547,24 @@ class RNN(Decoder):
                            no_repeat_ngram_size=no_repeat_ngram_size, suppress_tokens=suppress_tokens, length_penalty=length_penalty)
 
     def sample(self, cnn_feature, num_samples=1, temperature=1.0, top_k=0, max_length=CAP_MAX, end_id=2, generator=None,
-               uniforms=None):
+               uniforms=None, top_p=1.0):
         """The loop of rnn.py:37-58 with a draw in place of max(1)[1]: `num_samples` captions per image from
         softmax(logits / temperature), restricted to the `top_k` most likely words when top_k > 0 (at most 32).  One
         st_rnn_sample call for all B * num_samples rows (row b * S + s), no host round trip per token.  The randomness is
         `uniforms` (B, S, T) fp32 in [0, 1) on the device, one per row and step, or torch.rand from `generator`.
 
+        `top_p` < 1 adds nucleus sampling (Holtzman et al., 2020).  The three filters apply in the order temperature, top_k,
+        top_p: with z = logits / temperature, and restricted to the top_k set first when top_k > 0 (the probabilities below
+        are renormalised over it), order the words by z descending, the lowest index first among equal values; a word is kept
+        iff the probability mass strictly before it in that order is below top_p.  The first word is always kept, words of
+        probability 0 come last, and the nucleus may be any size from 1 to the vocabulary.  The token is drawn among the kept
+        words and `logp` is its log-probability under the kept, renormalised distribution.  top_p = 1 (the default) switches
+        the filter off -- it is not a nucleus of mass 1 -- and is the call without the keyword, launch for launch; valid
+        values are 0 < top_p <= 1 (st_rnn_sample_topp).
+
         Returns (ids (B, S, T) int64, 0 after <end>; logp (B, S, T) fp32, the log-probability of each token under the
         distribution it was drawn from, 0 after <end>; lengths (B, S) int64 counting <end>, T if <end> was never drawn)."""
-        B, S, T = self._sample_shape(cnn_feature, num_samples, temperature, top_k, max_length, uniforms)
+        B, S, T = self._sample_shape(cnn_feature, num_samples, temperature, top_k, max_length, uniforms, top_p)
         with torch.no_grad():
             prm, keep = self._c_params()
             if not cnn_feature.is_cuda:
@@ -561,8 +572,12 @@ class RNN(Decoder):
             feat, n, u, ids, logp = self._sample_buffers(self._feature(cnn_feature), B, S, T, uniforms, generator)
             nbytes = lib().st_rnn_sample_workspace_bytes(C.byref(prm), n)
             ws = torch.empty(nbytes, device=feat.device, dtype=torch.uint8)
-            check(lib().st_rnn_sample(C.byref(prm), _cp(feat), n, T, _cp(u), 1.0 / float(temperature), int(top_k), int(end_id), _cp(ws),
-                                      nbytes, _cp(ids), _cp(logp), _stream()), "st_rnn_sample")
+            if top_p == 1.0:
+                check(lib().st_rnn_sample(C.byref(prm), _cp(feat), n, T, _cp(u), 1.0 / float(temperature), int(top_k), int(end_id), _cp(ws),
+                                          nbytes, _cp(ids), _cp(logp), _stream()), "st_rnn_sample")
+            else:
+                check(lib().st_rnn_sample_topp(C.byref(prm), _cp(feat), n, T, _cp(u), 1.0 / float(temperature), int(top_k), float(top_p),
+                                               int(end_id), _cp(ws), nbytes, _cp(ids), _cp(logp), _stream()), "st_rnn_sample_topp")
             return ids.view(B, S, T), logp.view(B, S, T), sample_lengths(ids, end_id).view(B, S)
 
     def sentence_index(self, cnn_feature, beam_size=0, return_logits=False):

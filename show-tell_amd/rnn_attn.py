@@ -264,11 +264,14 @@ class RNN_Attn(Decoder):
         return ids.squeeze()                                                 # rnn_attn.py:143
 
     def sample(self, cnn_feature, num_samples=1, temperature=1.0, top_k=0, max_length=CAP_MAX, start_id=1, end_id=2,
-               generator=None, uniforms=None, return_alphas=False):
+               generator=None, uniforms=None, return_alphas=False, top_p=1.0):
         """The loop of rnn_attn.py:120-145 (test branch 77-94) from `start_id` with a draw in place of the arg-max of
         rnn_attn.py:141; arguments and results as RNN.sample (one st_attn_sample call for all B * num_samples rows).
-        With `return_alphas` also alphas (B, S, T, P) fp32 on the device: the attention map of every step."""
-        B, S, T = self._sample_shape(cnn_feature, num_samples, temperature, top_k, max_length, uniforms)
+        With `return_alphas` also alphas (B, S, T, P) fp32 on the device: the attention map of every step.
+        `top_p` < 1 is the nucleus filter of RNN.sample, same rule and same order (temperature, top_k, top_p): a word is kept
+        iff the mass strictly before it, value descending and the lowest index first among equals, is below top_p; `logp` is
+        renormalised over the kept words; top_p = 1 is the filter off and the call without the keyword (st_attn_sample_topp)."""
+        B, S, T = self._sample_shape(cnn_feature, num_samples, temperature, top_k, max_length, uniforms, top_p)
         with torch.no_grad():
             prm, keep, featc, B, P = self._decode_inputs(cnn_feature)
             featc, n, u, ids, logp = self._sample_buffers(featc, B, S, T, uniforms, generator)
@@ -276,8 +279,13 @@ class RNN_Attn(Decoder):
             nbytes = lib().st_attn_sample_workspace_bytes(C.byref(prm), n)
             ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
             alphas = torch.empty(n, T, P, device=dev, dtype=torch.float32) if return_alphas else None
-            check(lib().st_attn_sample(C.byref(prm), _cp(featc), n, T, int(start_id), _cp(u), 1.0 / float(temperature), int(top_k),
-                                       int(end_id), _cp(ws), nbytes, _cp(ids), _cp(logp), _cp(alphas), _stream()), "st_attn_sample")
+            if top_p == 1.0:
+                check(lib().st_attn_sample(C.byref(prm), _cp(featc), n, T, int(start_id), _cp(u), 1.0 / float(temperature), int(top_k),
+                                           int(end_id), _cp(ws), nbytes, _cp(ids), _cp(logp), _cp(alphas), _stream()), "st_attn_sample")
+            else:
+                check(lib().st_attn_sample_topp(C.byref(prm), _cp(featc), n, T, int(start_id), _cp(u), 1.0 / float(temperature), int(top_k),
+                                                float(top_p), int(end_id), _cp(ws), nbytes, _cp(ids), _cp(logp), _cp(alphas), _stream()),
+                      "st_attn_sample_topp")
             out = (ids.view(B, S, T), logp.view(B, S, T), sample_lengths(ids, end_id).view(B, S))
             return out + (alphas.view(B, S, T, P),) if return_alphas else out
 
