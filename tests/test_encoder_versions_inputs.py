@@ -15,6 +15,9 @@ faults  each seeded into the emulation of one block (from the clean tap before i
           b-minus-1     one layer's batch statistics cover B - 1 images                                                  C
           replica       one of four statistics replicas (128-row tiles, round robin) is left out of the sums             C
           biased-var    the biased variance is absorbed: off by 1 / 245 = 4.1e-3 in layer4, in every channel alike     C (offset)
+        and two kinds that tests/test_encoder_sizes_inputs.py seeds at other image sizes:
+          pad-column    a 3 x 3 convolution reads the column beyond W as the first column of the next row               A
+          pool-49       the pooled mean divides by 49, not by h * w                                                     D
 
 `python -m tests.test_encoder_versions_inputs` prints the figures of every case."""
 import functools
@@ -48,6 +51,13 @@ class Emulation:
         return self.fault == (kind, where)
 
     def conv(self, x, key, stride, pad):
+        if self._is("pad-column", key):
+            # the column beyond W is read as the first column of the NEXT row, not as zero: what a flat (row * W + column)
+            # index does without a pad column.  The last row's neighbour stays zero.
+            assert pad == 1
+            x = F.pad(x, (1, 1, 1, 1))
+            x[:, :, 1:-2, -1] = x[:, :, 2:-1, 1]
+            pad = 0
         o = _store(F.conv2d(x, self.p[key + ".weight"], None, stride, pad))
         if self._is("zero-row", key):
             o[1, :, -1, :] = 0.0
@@ -96,6 +106,11 @@ class Emulation:
         o = F.relu(self.bn(self.conv(image, "model.0", 2, 3), "model.1"))
         return F.max_pool2d(o, 3, 2, 1)
 
+    def pool(self, x):
+        """the pooled features of the last tap: an fp32 sum over the pixels, divided by their count"""
+        n = 49 if self.fault[0] == "pool-49" else x.shape[2] * x.shape[3]
+        return (x.float().sum((2, 3)) / n).double()
+
     def buffers(self, before):
         """`before` after the momentum updates of what was absorbed: fp32, the kernel's constants"""
         out = {k: v.clone() for k, v in before.items()}
@@ -111,43 +126,57 @@ def _run_dict(cfg, name, blocks, emu, before, oracle_p):
     return dict(name=name, cfg=cfg, blocks=blocks, bns=bns, before=before, after=emu.buffers(before), oracle=_running(oracle_p))
 
 
+def _pool_error(pooled, last):
+    """D of the GPU file: the pooled features against the float64 mean of the last tap"""
+    pref = last.mean((2, 3))
+    return ((pooled - pref).abs().max() / pref.abs().max()).item()
+
+
 @functools.lru_cache(maxsize=None)
-def clean(version, train):
+def clean(version, train, H=224, W=224, B=None, seed=None, name=None, keep=None):
     """The clean emulation of a configuration of the GPU file, walked against the oracle: the run the GPU file's checks read,
-    the emulation's taps (taps[k]: the input of block k) and the parameters."""
-    cfg = _cfg(version, 5 if train else 3, train, seed=70 + version + train)
+    the emulation's taps (taps[k]: the input of block k; stored in bf16, which holds them exactly, but for the stem's) and the
+    parameters.  By default 224 x 224, B = 5 (train) / 3 (eval); tests/test_encoder_sizes_inputs.py passes its cases' sizes, seeds
+    and names, and `keep`: the blocks whose input tap is kept (all by default)."""
+    B = B or (5 if train else 3)
+    cfg = _cfg(version, B, train, seed=70 + version + train if seed is None else seed, H=H, W=W)
     params = _params(cfg["seed"], version)
-    image = _bf16(torch.randn(cfg["B"], 3, 224, 224, generator=torch.Generator().manual_seed(cfg["seed"]))).double()
+    image = _bf16(torch.randn(B, 3, H, W, generator=torch.Generator().manual_seed(cfg["seed"]))).double()
     p, before = _double(params), {k: v.clone() for k, v in _running(params).items()}
     emu = Emulation(_double(params), train)
-    mets, taps = [], []
+    mets, taps, shapes = [], [], []
     with torch.no_grad():
         xin = _stem_pool(p, image, train)
         got = emu.stem(image)
         for k, li, bi, bname in _blocks(version):
             ref = R.block_forward(p, xin, version, li, bi, train)
-            taps.append(got)
+            taps.append(None if keep is not None and k not in keep else got if k == 0 else got.bfloat16())
             got = emu.block(got, version, li, bi)
             met = _block_metrics(got, ref, moments=False)
             met.update(k=k, name=bname)
             mets.append(met)
+            shapes.append((B, got.shape[2], got.shape[3], got.shape[1]))
             xin = got
-    return dict(run=_run_dict(cfg, f"r{version}-{'train' if train else 'eval'}", mets, emu, before, p), taps=taps,
-                params=params, before=before)
+        run =_run_dict(cfg, name or f"r{version}-{'train' if train else 'eval'}", mets, emu, before, p)
+        run["pool"] = _pool_error(emu.pool(got), got)
+        run["tap_shapes"] = shapes
+    return dict(run=run, taps=taps, last=got.bfloat16(), params=params, before=before)
 
 
-def faulted(version, train, k, fault):
-    """Block k alone, from the clean tap before it: the oracle against the emulation with `fault`"""
-    c = clean(version, train)
+def faulted(version, train, k, fault, **case):
+    """Block k alone, from the clean tap before it: the oracle against the emulation with `fault`.  case: clean()'s other
+    arguments"""
+    c = clean(version, train, **case)
     _, li, bi, bname = _blocks(version)[k]
     p = _double(c["params"])
     emu = Emulation(_double(c["params"]), train, fault)
     with torch.no_grad():
-        ref = R.block_forward(p, c["taps"][k], version, li, bi, train)
-        got = emu.block(c["taps"][k], version, li, bi)
+        tap = c["taps"][k].double()
+        ref = R.block_forward(p, tap, version, li, bi, train)
+        got = emu.block(tap, version, li, bi)
     met = _block_metrics(got, ref, moments=False)
     met.update(k=k, name=bname)
-    return _run_dict(c["run"]["cfg"], f"r{version} {bname} {fault[0]}", [met], emu, c["before"], p)
+    return _run_dict(c["run"]["cfg"], f"{case.get('name') or 'r%d' % version} {bname} {fault[0] if fault else 'clean'}", [met], emu, c["before"], p)
 
 
 def _figures(run):

@@ -21,6 +21,13 @@ CASES = [
     (3, 4, 4, 256, 128),       # tiny map (a 64x64 input image)
     (1, 9, 5, 64, 128),        # non-square
     (2, 16, 16, 512, 128),     # several bands at 512 channels
+    # the widths of images other than 224 x 224 (tests/_encoder_size_cases.py)
+    (1, 5, 112, 64, 64),       # layer1 of a 448-wide image: bands of 2 rows (2 + 2 + 1)
+    (1, 2, 254, 64, 64),       # the widest 64-channel map: bands of one row
+    (2, 5, 72, 128, 128),      # bands of 3 rows (3 + 2)
+    (2, 16, 16, 256, 256),     # layer3 of a 256-wide image: one workgroup per band of 14 rows (Wp = 18, not the half-band form), 12 + 4
+    (1, 9, 33, 256, 256),      # the widest 256-channel map: bands of 6 rows
+    (1, 3, 40, 512, 512),      # the widest 512-channel map: bands of one row
 ]
 
 
@@ -64,7 +71,7 @@ def test_conv3x3_img_matches_conv2d_and_igemm(case):
     np.testing.assert_allclose(st.cpu().numpy(), s0.cpu().numpy(), rtol=1e-4, atol=1e-3 * scale * np.sqrt(r2.shape[0]))
 
 
-@pytest.mark.parametrize("case", [CASES[0], CASES[1], CASES[2], CASES[4], CASES[7]])
+@pytest.mark.parametrize("case", [CASES[0], CASES[1], CASES[2], CASES[4], CASES[7], CASES[10], CASES[13], CASES[14]])
 def test_conv3x3_img_fused_input_bn_relu_equals_separate_pass(case):
     """in_stats: the fill applies relu(batchnorm(x)) once per element; must equal bn_act followed by the plain kernel BIT
     FOR BIT (same coefficients, same rounding point), halo included (padding stays zero, it is not relu(shift))."""
@@ -576,7 +583,8 @@ def test_conv_c3c1_eval_equals_astat_residual_then_kstream(shape, geo):
 
 
 # ---- st_conv3x3_s2: the stride-2 3x3 convs (B, H, W, C = N) -------------------------------------------------------------------------
-S2_CASES = [(2, 56, 56, 128), (3, 28, 28, 256), (5, 14, 14, 512), (1, 9, 7, 128), (2, 5, 5, 256), (1, 1, 1, 512), (3, 13, 15, 256)]
+S2_CASES = [(2, 56, 56, 128), (3, 28, 28, 256), (5, 14, 14, 512), (1, 9, 7, 128), (2, 5, 5, 256), (1, 1, 1, 512), (3, 13, 15, 256),
+            (1, 6, 112, 128), (1, 5, 113, 256)]     # layer2 / layer3 of a 448- / 449-wide image
 
 
 @pytest.mark.parametrize("case", S2_CASES)

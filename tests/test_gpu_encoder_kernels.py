@@ -40,6 +40,7 @@ CONV_CASES = [
     (2, 56, 56, 64, 64, 3, 1, 1),    # layer1 3x3, 64-channel tile
     (5, 7, 7, 512, 512, 3, 1, 1),    # layer4 3x3, ragged batch
     (200, 7, 7, 64, 256, 3, 1, 1),   # many small images
+    (2, 33, 65, 8, 64, 7, 2, 3),     # the generic stem of an odd-sized image (the two stem tests below need even H, W)
 ]
 
 
@@ -185,7 +186,7 @@ def test_conv_stats_replicas_feed_bn_act(dtype, Cc, R):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("B,H,W", [(2, 64, 64), (3, 32, 48), (1, 224, 224)])
+@pytest.mark.parametrize("B,H,W", [(2, 64, 64), (3, 32, 48), (1, 224, 224), (1, 32, 448), (1, 450, 34)])
 def test_stem_space_to_depth_matches_conv7x7(dtype, B, H, W):
     """The blocked-image stem (st_nchw_to_s2d16 + st_stem_weight_s2d + sliding-window st_conv) is the same sum as
     torchvision's conv1 (7x7, stride 2, pad 3; cnn.py:46)."""
@@ -415,7 +416,7 @@ def test_bad_arguments_fail_loudly():
         ops.cast(torch.zeros(4), torch.bfloat16)                        # CPU tensor: no fallback
 
 
-@pytest.mark.parametrize("B,H,W", [(2, 64, 64), (3, 32, 48), (1, 224, 224), (2, 34, 70), (1, 8, 8)])
+@pytest.mark.parametrize("B,H,W", [(2, 64, 64), (3, 32, 48), (1, 224, 224), (2, 34, 70), (1, 8, 8), (1, 32, 448), (1, 450, 34)])
 def test_stem_conv_pool_one_kernel_matches_conv_bn_relu_maxpool(B, H, W):
     """st_stem_conv_pool (conv1 7x7/2 + statistics + 3x3/2 pool in one kernel) against torch's conv2d -> BatchNorm (batch statistics)
     -> ReLU -> MaxPool2d(3, 2, 1) (torchvision resnet's first four modules, cnn.py:46), and BIT FOR BIT against the two-kernel form

@@ -31,6 +31,8 @@ log  a fresh process logs its launches (ST_LAYER_LOG); the host-only plan must g
 
 tests/test_encoder_versions_inputs.py shows, without a GPU, that the reference alone stays within these bounds and that six
 seeded faults do not.  The worst values measured on the MI355X are written next to each bound.
+tests/test_gpu_encoder_sizes.py runs the same walk and checks at other image sizes (_run with a configuration of its own, the
+check_* functions with the bounds it passes).
 """
 import gc
 import os
@@ -55,8 +57,9 @@ BF16, F32 = torch.bfloat16, torch.float32
 SMALL_B = {True: 4, False: 2}      # the batch sizes test_resnet101_bf16_block_by_block_undamped's bounds were set at
 
 
-def _cfg(version, B, train, dtype=BF16, seed=0, head=False):
-    return dict(version=version, B=B, train=train, dtype=dtype, attn=version in (34, 152) and dtype == BF16, head=head, seed=seed)
+def _cfg(version, B, train, dtype=BF16, seed=0, head=False, H=224, W=224, attn=None):
+    attn = (version in (34, 152) and dtype == BF16) if attn is None else attn
+    return dict(version=version, B=B, train=train, dtype=dtype, attn=attn, head=head, seed=seed, H=H, W=W)
 
 
 CONFIGS = {
@@ -117,7 +120,7 @@ def buffer_limits(cfg):
 
 def _plan(cfg, B=None):
     from tests.test_resnet_plan import plan
-    return plan(cfg["version"], "bf16" if cfg["dtype"] == BF16 else "f32", 224, 224, B or cfg["B"], cfg["train"])
+    return plan(cfg["version"], "bf16" if cfg["dtype"] == BF16 else "f32", cfg["H"], cfg["W"], B or cfg["B"], cfg["train"])
 
 
 def _replica_pairs(lines):
@@ -172,12 +175,15 @@ def _head(cfg, params, image):
                 rv=bn.running_var.cpu().clone(), nbt=int(bn.num_batches_tracked))
 
 
-def _run(name):
-    cfg = CONFIGS[name]
+def _run(name, cfg=None):
+    """One forward with taps of CONFIGS[name], or of `cfg` (tests/test_gpu_encoder_sizes.py: other image sizes), walked block by
+    block against the oracle"""
+    if cfg is None:
+        cfg = CONFIGS[name]
+        check_plan(name)
     v, B, train, attn = cfg["version"], cfg["B"], cfg["train"], cfg["attn"]
-    check_plan(name)
     params = _params(cfg["seed"], v)
-    image = _bf16(torch.randn(B, 3, 224, 224, generator=torch.Generator().manual_seed(cfg["seed"])))
+    image = _bf16(torch.randn(B, 3, cfg["H"], cfg["W"], generator=torch.Generator().manual_seed(cfg["seed"])))
     m = _model(cfg, params, attn)
     before = _buffers(m)
     res = m._bb.block_outputs(image.cuda(), train, want_ncp=attn)
@@ -188,9 +194,12 @@ def _run(name):
     assert len(outs) == len(blocks) == sum(R.RESNET_SPECS[v][1])
     feat = outs[-1].shape[3]
     assert feat == (512 if R.RESNET_SPECS[v][0] == "basic" else 2048) and pooled.shape == (B, feat)
+    out["tap_shapes"] = [tuple(o.shape) for o in outs]
+    pixels = outs[-1].shape[1] * outs[-1].shape[2]       # 49 at 224 x 224
     if attn:
-        out["ncp_exact"] = res[2].shape == (B, feat, 49) and res[2].dtype == F32 and \
-            torch.equal(res[2], outs[-1].float().permute(0, 3, 1, 2).reshape(B, feat, 49))
+        out["ncp_shape"] = tuple(res[2].shape)
+        out["ncp_exact"] = res[2].shape == (B, feat, pixels) and res[2].dtype == F32 and \
+            torch.equal(res[2], outs[-1].float().permute(0, 3, 1, 2).reshape(B, feat, pixels))
     p = _double(params)
     mets = []
     with torch.no_grad():
@@ -219,33 +228,39 @@ def _run(name):
 _stopped = []       # the configuration whose forward raised, or whose child process died: no later GPU work is started
 
 
-@pytest.fixture(scope="module")
-def oracle_run():
+def holder(run, stopped):
+    """A module-scoped fixture's body: get(name) computes run(name) once and holds one configuration at a time; after a
+    RuntimeError from the engine nothing more is started (`stopped`, the module's own list)."""
     held = {}
 
     def get(name):
-        assert not _stopped, f"not run: {_stopped[0]} raised in the engine or died"
+        assert not stopped, f"not run: {stopped[0]} raised in the engine or died"
         if name not in held:
             held.clear()
             gc.collect()
             torch.cuda.empty_cache()
             try:
-                held[name] = _run(name)
+                held[name] = run(name)
             except RuntimeError:        # an engine or HIP error: nothing more is started on the GPU from this module
-                _stopped.append(name)
+                stopped.append(name)
                 raise
         return held[name]
     yield get
     held.clear()
 
 
+@pytest.fixture(scope="module")
+def oracle_run():
+    yield from holder(_run, _stopped)
+
+
 # ====================================================================================================================
 # the checks (tests/test_encoder_versions_inputs.py applies A and C to a CPU emulation of bf16 storage)
 # ====================================================================================================================
 
-def failures_elementwise(run):
-    """A: the blocks beyond their bounds, as text"""
-    lim = limits(run["cfg"])
+def failures_elementwise(run, lim=None):
+    """A: the blocks beyond their bounds, as text.  lim: {'block': ..., 'block0': ...}; by default limits() of the configuration"""
+    lim = lim or limits(run["cfg"])
     bad = []
     for b in run["blocks"]:
         lim_mx, lim_l2, lim_img = lim["block0" if b["k"] == 0 else "block"]
@@ -256,21 +271,21 @@ def failures_elementwise(run):
     return bad
 
 
-def check_elementwise(run):
+def check_elementwise(run, lim=None):
     bl = run["blocks"]
     for sel, what in ((bl[:1], "block 0"), (bl[1:], f"blocks 1-{len(bl) - 1}")):
         for key in ("max", "l2", "img"):
             w = max(sel, key=lambda b: b[key])
             print(f"MEASURE A {run['name']} {what} worst {key}: {w[key]:.2e} ({w['name']})")
-    bad = failures_elementwise(run)
+    bad = failures_elementwise(run, lim)
     assert not bad, f"{run['name']}:\n  " + "\n  ".join(bad)
 
 
-def failures_running_buffers(run):
+def failures_running_buffers(run, bounds=None):
     """C (train): (layers beyond their bounds as text, then (worst error, layer) of the batch mean, the variance and the
-    variance offset)"""
+    variance offset).  bounds: (mean, variance, offset); by default buffer_limits() of the configuration"""
     before, after, orc = run["before"], run["after"], run["oracle"]
-    mean_bound, var_bound, off_bound = buffer_limits(run["cfg"])
+    mean_bound, var_bound, off_bound = bounds or buffer_limits(run["cfg"])
     wm, wv, wo, bad = (0.0, ""), (0.0, ""), (0.0, ""), []
     for bn in run["bns"]:
         if int(after[bn + ".num_batches_tracked"]) != int(before[bn + ".num_batches_tracked"]) + 1:
@@ -282,7 +297,7 @@ def failures_running_buffers(run):
     return bad, wm, wv, wo
 
 
-def check_running_buffers(run):
+def check_running_buffers(run, bounds=None):
     before, after = run["before"], run["after"]
     assert len(run["bns"]) * 3 == len(before) == len(after)
     if not run["cfg"]["train"]:     # eval: nothing moves
@@ -291,15 +306,16 @@ def check_running_buffers(run):
         print(f"MEASURE C {run['name']}: {len(before)} buffers bit-unchanged")
         return
     assert all(int(before[bn + ".num_batches_tracked"]) == 0 for bn in run["bns"])
-    bad, wm, wv, wo = failures_running_buffers(run)
+    bad, wm, wv, wo = failures_running_buffers(run, bounds)
     print(f"MEASURE C {run['name']}: batch mean {wm[0]:.2e} ({wm[1]}), variance {wv[0]:.2e} ({wv[1]}), "
           f"variance offset {wo[0]:.2e} ({wo[1]})")
     assert not bad, f"{run['name']}:\n  " + "\n  ".join(bad)
 
 
-def check_pooled(run):
+def check_pooled(run, bound=None):
+    """bound: by default POOL_MAX (bf16 taps) or the a-priori bound of an fp32 sum over 49 pixels"""
     print(f"MEASURE D {run['name']}: pooled {run['pool']:.2e}")
-    assert run["pool"] < (POOL_MAX_F32 if run["cfg"]["dtype"] == F32 else POOL_MAX)
+    assert run["pool"] < (bound or (POOL_MAX_F32 if run["cfg"]["dtype"] == F32 else POOL_MAX))
 
 
 def check_attention_map(run):
@@ -362,25 +378,28 @@ def test_encoder_version_matches_fp64_oracle(oracle_run, name, check):
 # log: the executor launches what the planner says
 # ====================================================================================================================
 
-@pytest.mark.parametrize("name", list(CONFIGS))
-def test_executor_logs_what_the_planner_says(name, tmp_path):
+def check_launch_log(name, cfg, tmp_path, stopped):
     """One backbone_features in a fresh process with ST_LAYER_LOG set (the engine opens the log once per process), compared
     with st_resnet_plan's text line for line.  Each child runs under its own time limit; after a child that died or ran out of
-    time no further child is started."""
-    assert not _stopped, f"not started: {_stopped[0]} raised in the engine or died"
-    cfg = CONFIGS[name]
+    time no further child is started (`stopped`, the calling module's own list)."""
+    assert not stopped, f"not started: {stopped[0]} raised in the engine or died"
     log = tmp_path / "launches.txt"
     cmd = [sys.executable, os.path.join(ROOT, "tests", "_layer_log_child.py"), str(cfg["version"]),
-           "bf16" if cfg["dtype"] == BF16 else "f32", str(cfg["B"]), str(int(cfg["train"])), str(log)]
+           "bf16" if cfg["dtype"] == BF16 else "f32", str(cfg["B"]), str(int(cfg["train"])), str(log), str(cfg["H"]), str(cfg["W"])]
     try:
         r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=120)
     except subprocess.TimeoutExpired:
-        _stopped.append(name)
+        stopped.append(name)
         raise
     if r.returncode != 0:
-        _stopped.append(name)
+        stopped.append(name)
     assert r.returncode == 0, r.stderr[-2000:]
     got, want = log.read_text().splitlines(), _plan(cfg)
     assert len(got) == len(want), (len(got), len(want))
     for i, (g, w) in enumerate(zip(got, want)):
         assert g == w, "launch %d" % i
+
+
+@pytest.mark.parametrize("name", list(CONFIGS))
+def test_executor_logs_what_the_planner_says(name, tmp_path):
+    check_launch_log(name, CONFIGS[name], tmp_path, _stopped)

@@ -32,7 +32,7 @@ def _sections():
 _handles = {}
 
 
-def plan(version, dtype, H, W, B, train):
+def _handle(version, dtype):
     from showtell_amd import _lib
     L = _lib.lib()
     key = (version, dtype)
@@ -40,7 +40,18 @@ def plan(version, dtype, H, W, B, train):
         h = C.c_void_p()
         _lib.check(L.st_resnet_create(version, _lib.ST_BF16 if dtype == "bf16" else _lib.ST_F32, C.byref(h)), "st_resnet_create")
         _handles[key] = h
-    h = _handles[key]
+    return L, _handles[key]
+
+
+def plan_refusal(version, dtype, H, W, B, train):
+    """(st_resnet_plan's return value, st_last_error's text) for arguments the planner is expected to refuse"""
+    L, h = _handle(version, dtype)
+    n = L.st_resnet_plan(h, B, H, W, int(train), None, 0)
+    return n, L.st_last_error().decode()
+
+
+def plan(version, dtype, H, W, B, train):
+    L, h = _handle(version, dtype)
     n = L.st_resnet_plan(h, B, H, W, int(train), None, 0)
     assert n > 0, L.st_last_error()
     buf = C.create_string_buffer(n + 1)
