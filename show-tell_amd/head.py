@@ -18,7 +18,8 @@ class _HeadFn(torch.autograd.Function):
         B, F = x.shape
         E = linear.out_features
         dtc = dtype_code(dtype)
-        xd = x if x.dtype == dtype else ops.cast(x.contiguous(), dtype)
+        # the kernels read x as dense [B][F] rows: a view (a column slice, say) is copied first, whichever dtype it has
+        xd = x.contiguous() if x.dtype == dtype else ops.cast(x.contiguous(), dtype)
         w = working_copy(linear.weight, dtype)
         z = torch.empty(B, E, device=dev, dtype=torch.float32)
         y = torch.empty(B, E, device=dev, dtype=torch.float32)

@@ -73,6 +73,32 @@ def test_six_steps_match_the_float64_replica(kind, shadow):
         assert torch.equal(_bits(opt.shadow), _bits(opt.flat.to(shadow)))
 
 
+@pytest.mark.parametrize("kind", ["Adam", "AdamW"])
+def test_three_steps_past_the_grid_cap_match_the_float64_replica(kind):
+    """2048 * 1024 + 5 and 3 elements: every block of the capped grid makes a second grid-stride trip, the first tensor's
+    one-element vector tail lies in it, and the step kernel's head adds up 2048 partial sums, eight per thread.
+    Largest measured error / bound on an MI355X: DESIGN.md section 7 (row 'flat Adam past the grid cap')."""
+    from showtell_amd._lib import lib
+    opt = _make(kind, start=G.long_params(), shadow_dtype=torch.bfloat16, **CLIP)
+    assert opt.n == 2097164 and opt.offsets == [0, 2097160]
+    norms = [math.sqrt(sum((t.double() ** 2).sum().item() for t in step)) for step in G.long_grads()]
+    for k, step in enumerate(G.long_grads()):
+        _set_grads(opt, step)
+        opt.step()
+        assert opt._nparts.value == lib().st_grad_sumsq_max_parts() == 2048
+        assert abs(opt.last_grad_norm.item() / norms[k] - 1) <= 1e-5
+        assert abs(opt.last_clip_coef.item() / min(1.0, G.MAX_NORM / (norms[k] + 1e-6)) - 1) <= 1e-5
+    err = G.rel_err(G.unpadded(opt.flat, opt.offsets, G.long_params()), G.replica(kind, long=True))
+    print(f"MEASURE {kind} past the grid cap: max|p - p_ref| / max|p_ref| = {err:.3e} (bound {G.BOUND:.0e})")
+    assert err <= G.BOUND
+    assert opt.steps == 3 and opt.skipped_steps == 0
+    assert torch.equal(_bits(opt.shadow), _bits(opt.flat.to(torch.bfloat16)))
+    pad = torch.ones(opt.n, dtype=torch.bool)
+    for p, o in zip(opt.params, opt.offsets):
+        pad[o:o + p.numel()] = False
+    assert pad.sum() == 4 and (opt.flat.cpu()[pad] == 0).all()                     # the padding elements stay what they were
+
+
 @pytest.mark.parametrize("kind", ["SGD", "Adam"])
 def test_the_clip_coefficient_is_all_that_differs_from_the_plain_step(kind):
     """Without weight decay the new path must be the old kernel with grad_scale = the coefficient it reports: bit for bit, on

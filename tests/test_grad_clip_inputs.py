@@ -55,3 +55,24 @@ def test_world_2_replica_equals_world_1_and_the_norm_of_the_summed_gradient_is_c
     print(f"MEASURE {kind} fault summed_norm, world 2: {err:.3e}  = {err / G.BOUND:.0f} x bound")
     assert err > G.BOUND
 
+
+@pytest.mark.parametrize("kind", ["Adam", "AdamW"])
+def test_past_the_grid_cap_the_float32_replica_is_inside_the_bound_and_the_faults_outside(kind):
+    """The inputs of test_three_steps_past_the_grid_cap_match_the_float64_replica: 2048 * 1024 + 5 and 3 elements."""
+    ps, gs = G.long_params(), G.long_grads()
+    assert [p.numel() for p in ps] == [2048 * 1024 + 5, 3] and len(gs) == 3
+    n = sum((p.numel() + 3) // 4 * 4 for p in ps)
+    trip = 2048 * 256 * 4                                       # what one pass of the capped grid covers
+    assert n == 2097164 and (n // 4 + 255) // 256 > 2048 and trip < ps[0].numel() < trip + 8 and ps[0].numel() % 4 == 1
+    norms = [torch.sqrt(sum((t.double() ** 2).sum() for t in step)).item() for step in gs]
+    print("MEASURE long norms", ["%.4g" % v for v in norms])
+    assert [v > G.MAX_NORM for v in norms] == [True, True, False]
+    ref = G.replica(kind, long=True)
+    assert torch.isfinite(ref).all() and ref.numel() == 2048 * 1024 + 8
+    own = G.rel_err(G.replica(kind, torch.float32, long=True), ref)
+    print(f"MEASURE {kind} long float32 replica vs float64: {own:.3e} (bound {G.BOUND:.0e})")
+    assert own <= G.BOUND
+    for fault in ("no_clip", "per_tensor_norm", "no_decay", "decay_swapped"):
+        err = G.rel_err(G.replica(kind, fault=fault, long=True), ref)
+        print(f"MEASURE {kind} long fault {fault}: {err:.3e}  = {err / G.BOUND:.0f} x bound")
+        assert err > G.BOUND, (kind, fault, err)
