@@ -706,6 +706,37 @@ int st_rnn_sched_inputs(const st_rnn_params* p, const void* feat, int n, const l
                         const float* coin, const float* u, float prob, float inv_temperature, int top_k, void* workspace,
                         size_t workspace_bytes, long* input_ids, uint8_t* replaced, long* drawn, float* logp, void* stream);
 
+/* CIDEr rewards of sampled captions (self-critical training), the score of evaluation.cider_score in one launch, one workgroup per
+ * image.  A caption's words are its ids before the first end_id, within its length.  An n-gram (n = 1 .. 4) is ONE 64-bit key, packed
+ * exactly: token j contributes (id + 1) << (16 * j), ids in [0, 65534]; the highest non-zero field gives the order.
+ *   table      keys [K] int64 sorted ascending AS SIGNED, strictly; df [K] int32 with 1 <= df <= num_docs; log_num_docs =
+ *              log(num_docs) >= 0.  An n-gram the table lacks has df 0, so its idf is log_num_docs.
+ *   references refs [B][R][Tr] int32 words only (the caller has cut them at end_id), ref_len [B][R] int32 words per row,
+ *              ref_count [B] int32 rows of image b in use (the score divides by it; 0 gives a score of 0).
+ *   candidates ids [B][S][T] int64 and lengths [B][S] int64 exactly as st_rnn_sample / sample_lengths leave them; greedy_ids
+ *              [B][Tg] int64 or NULL (its length is Tg).
+ *   weight of an n-gram g: w = tf * (log_num_docs - log(max(1, df(g)))); norm_n = sqrt(sum over distinct g of w^2); per candidate,
+ *   reference and order val_n = sum over the candidate's distinct g of min(w_c, w_r) * w_r, divided by norm_c * norm_r when both are
+ *   non-zero, times exp(-(len_c - len_r)^2 / (2 sigma^2)), len = max(words - 1, 0); score = 10 * mean_n(sum_refs val_n) / ref_count.
+ *   outputs    score64 [B][S + 1] float64 (column S is the greedy caption's and is written only when greedy_ids is given),
+ *              reward [B][S] fp32 = score64 rounded, advantage [B][S] fp32 (baseline 1: reward - greedy reward; 2: reward - the
+ *              mean of the image's OTHER rewards; formed from the fp32 rewards in double and rounded once, as
+ *              train.self_critical_advantage; baseline 0: not written, may be NULL).
+ * Refused before the launch, outputs untouched: R outside [1, ST_CIDER_MAX_REFS], Tr, T or Tg outside [1, ST_CIDER_MAX_TOKENS],
+ * S < 1, baseline outside 0 .. 2, baseline 2 with S < 2, baseline 1 without greedy_ids, sigma <= 0, log_num_docs < 0, end_id outside
+ * [0, 65534].  What lives in device memory cannot be refused here without a round trip: lengths, ref_len and ref_count are CLAMPED
+ * to their rows (the Python callers refuse lengths > T), and a sampled id outside [0, 65534] is taken as impossible and not
+ * checked -- st_rnn_sample draws ids below V, and a vocabulary that large is refused when the references are packed; such an id
+ * would alias another word (16 bits are kept), never touch memory out of bounds.
+ * float64 on the vector ALU throughout; every sum in a fixed order, no floating-point atomics, no workspace: two identical captions
+ * score bit-identically.  Nothing is allocated or synchronised inside the call. */
+#define ST_CIDER_MAX_REFS 8
+#define ST_CIDER_MAX_TOKENS 64
+int st_cider_reward(const long* keys, const int* df, long K, double log_num_docs, const int* refs, const int* ref_len,
+                    const int* ref_count, int B, int R, int Tr, const long* ids, const long* lengths, int S, int T,
+                    const long* greedy_ids, int Tg, long end_id, double sigma, int baseline, double* score64, float* reward,
+                    float* advantage, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Soft-attention decoder (Attention/rnn_attn.py, rnn_attn_LSTM.py; train step Attention/main_attn.py:123-134).
  *   features: cnn_feature (B,F,P) fp32 as cnn_attn.py:49 returns it; caption_T: int64 [Tcap][B] (transposed captions).

@@ -206,6 +206,8 @@ _SIGS = {
     "st_rnn_sched_inputs_workspace_bytes": ([C.POINTER(RnnParams), c_i], C.c_size_t),
     "st_rnn_sched_inputs": ([C.POINTER(RnnParams), c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_f, c_f, c_i, c_p, C.c_size_t, c_p, c_p, c_p, c_p,
                              c_p], c_i),
+    "st_cider_reward": ([c_p, c_p, c_l, C.c_double, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_i, c_l, C.c_double, c_i,
+                         c_p, c_p, c_p, c_p], c_i),
     "st_attn_workspace_bytes": ([c_p, c_p], C.c_size_t),
     "st_attn_forward": ([c_p, c_p, c_p, c_p, c_p, C.c_size_t, c_p, c_i, c_i, c_p, c_i, C.POINTER(DropoutDesc), c_p], c_i),
     "st_attn_backward": ([c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_f, c_p, c_p, C.c_size_t, C.POINTER(DropoutDesc), c_p], c_i),

@@ -238,6 +238,9 @@ class Trainer:
         Backward and the deferred all-reduce / optimizer schedule are those of `step`.  Returns (loss, mean reward of the samples).
         Signed, reward-scaled losses are where an optimizer built with ``max_grad_norm`` (and ``skip_nonfinite``) earns its keep.
         `generator` / `uniforms` fix the draws as in ``RNN.sample``.
+        A `reward_fn` with an ``advantage`` method (``evaluation.cider_reward_device``) scores on the device instead: the ids stay
+        there, rewards and advantages come from one launch, only the lengths are read back (`_self_critical_on_device`), and the
+        mean reward returned is a device tensor.  A plain callable takes the host path above, unchanged.
         The Trainer's `label_smoothing` does not apply here: a reward-weighted log-likelihood of the model's own samples is not a
         target distribution to be smoothed, so this step stays unsmoothed."""
         if baseline not in ("greedy", "mean"):
@@ -247,6 +250,8 @@ class Trainer:
         rnn = self.rnn
         feat = self._features(image, upcoming)
         B, S = feat.shape[0], int(num_samples)
+        if hasattr(reward_fn, "advantage"):
+            return self._self_critical_on_device(feat, reward_fn, S, baseline, generator, uniforms, end_id)
         with torch.no_grad():
             ids, _, lengths = rnn.sample(feat, S, temperature=1.0, top_k=0, end_id=end_id, generator=generator, uniforms=uniforms)
             greedy = None
@@ -262,6 +267,28 @@ class Trainer:
         dev = feat.device
         feat_rep = feat[(order // S).to(dev)]          # the image behind every sorted row
         loss = rnn.loss(feat_rep, cap.to(dev), lens, sequence_weight=advantage.reshape(-1)[order])
+        loss.backward()
+        self.reducer.start(self.opt.flat_grad)
+        self.pending = True
+        return loss, reward.mean()
+
+    def _self_critical_on_device(self, feat, reward_fn, S, baseline, generator, uniforms, end_id):
+        """`step_self_critical` from the features on, for a `reward_fn` that scores on the device
+        (``evaluation.cider_reward_device``): the sampled ids never leave it.  Rewards and advantages come from one
+        ``reward_fn.advantage`` launch; only `lengths` goes to the host, because the packed loss needs Python lengths and the stable
+        length sort of `sample_caption_batch`; the samples, the features and the advantages are gathered by that order on the
+        device.  The mean reward is returned as a 0-d device tensor."""
+        rnn, B = self.rnn, feat.shape[0]
+        with torch.no_grad():
+            ids, _, lengths = rnn.sample(feat, S, temperature=1.0, top_k=0, end_id=end_id, generator=generator, uniforms=uniforms)
+            gids = rnn.sentence_index(feat).reshape(B, -1) if baseline == "greedy" else None
+            reward, advantage, _ = reward_fn.advantage(ids, lengths, baseline, gids, check_lengths=False)   # lengths are sample's own
+            flat_len = lengths.reshape(B * S).cpu()
+        order = torch.sort(flat_len, descending=True, stable=True)[1]             # as sample_caption_batch
+        lens = [int(l) for l in flat_len[order].tolist()]
+        order = order.to(feat.device)
+        cap = ids.reshape(B * S, ids.shape[2])[order].contiguous()
+        loss = rnn.loss(feat[order // S], cap, lens, sequence_weight=advantage.reshape(-1)[order])
         loss.backward()
         self.reducer.start(self.opt.flat_grad)
         self.pending = True
