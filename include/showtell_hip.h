@@ -80,6 +80,15 @@ int st_conv(const st_conv_desc* d, void* stream);
 /* n <= 12 independent problems of identical shape, dtype and options (only the pointers differ) as ONE launch: the
  * per-layer weight-gradient GEMMs of the decoder backward (autograd of nn.GRU, main.py:151) are 48 tiles each. */
 int st_conv_batch(const st_conv_desc* d, int n, void* stream);
+/* Which kernel the calling thread's last st_conv / st_conv_batch launch was: a thread-local record written just before the
+ * launch, for tests that assert the route a shape is meant to take.  It changes no launch.  out[8] =
+ *   [0] main loop: 0 register-staged two-buffer, 1 single-buffer DMA, 2 three-buffer DMA
+ *   [1] BM  [2] BN: tile rows (pixels) and columns (channels)   [3] waves per workgroup   [4] KC: 16-byte chunks per tile row, 8 | 4
+ *   [5] MODE: 0 generic tap walk, 1 whole K tiles inside one tap, 2 the same with the input transform
+ *   [6] group members of the launch (st_conv_batch's n, split_k's slices, else 1)   [7] 1: fp32 atomics into y (split-K), else 0
+ * all -1 before the thread's first launch.  Returns the number of such launches the thread has made; a refused call (non-zero
+ * return of st_conv / st_conv_batch) launches nothing, so it leaves both the record and the count as they were.  out may be NULL. */
+int st_conv_last_route(int* out);
 
 /* ------------------------------------------------------------------------------------
  * Token-contraction GEMM (csrc/gemm_tn.hip), bf16 operands, fp32 result:

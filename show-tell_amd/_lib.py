@@ -130,6 +130,7 @@ _SIGS = {
     "st_image_transform": ([C.POINTER(ImageBatchDesc), c_p], c_i),
     "st_conv": ([C.POINTER(ConvDesc), c_p], c_i),
     "st_conv_batch": ([C.POINTER(ConvDesc), c_i, c_p], c_i),
+    "st_conv_last_route": ([C.POINTER(c_i)], c_i),
     "st_gemm_tn_batch": ([c_p, c_i, c_p], c_i),     # st_gemm_tn_desc[n]: mirrored in gemm_tn.py
     "st_conv3x3_img_supported": ([c_i, c_i, c_i, c_i], c_i),
     "st_conv3x3_img": ([C.POINTER(Conv3x3ImgDesc), c_p], c_i),

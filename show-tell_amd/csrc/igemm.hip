@@ -743,6 +743,15 @@ __global__ __launch_bounds__(256) void igemm_s3b_kernel(IgemmGroup grp) {
   igemm_epilogue<T, BM, BN, WM, WN>(a, acc, smem, bm, bn, tid);
 }
 
+// st_conv_last_route (include/showtell_hip.h): what the calling thread's last igemm launch was, written just before the launch
+struct RouteRec { int v[8]; int launches; };
+thread_local RouteRec g_route = {{-1, -1, -1, -1, -1, -1, -1, -1}, 0};
+inline void route_note(int loop, int bm, int bn, int waves, int kc, int mode, int members, int atomic) {
+  int* v = g_route.v;
+  v[0] = loop; v[1] = bm; v[2] = bn; v[3] = waves; v[4] = kc; v[5] = mode; v[6] = members; v[7] = atomic;
+  ++g_route.launches;
+}
+
 int launch_s3(IgemmArgs* arr, int n, hipStream_t st, bool pipelined = false) {
   IgemmArgs& a = arr[0];
   IgemmGroup grp;
@@ -761,9 +770,9 @@ int launch_s3(IgemmArgs* arr, int n, hipStream_t st, bool pipelined = false) {
       (void)hipEventRecord(rec.e0, st);
     }
   }
-  if (pipelined) hipLaunchKernelGGL(igemm_s3b_kernel, dim3(a.nbm * a.nbn, n), dim3(256), lds, st, grp);
+  if (pipelined) { route_note(2, 128, 128, 4, 4, 1, n, a.atomic); hipLaunchKernelGGL(igemm_s3b_kernel, dim3(a.nbm * a.nbn, n), dim3(256), lds, st, grp); }
 #ifdef ST_EXPERIMENTAL
-  else hipLaunchKernelGGL(igemm_s3_kernel, dim3(a.nbm * a.nbn, n), dim3(256), lds, st, grp);
+  else { route_note(1, 128, 128, 4, 8, 1, n, a.atomic); hipLaunchKernelGGL(igemm_s3_kernel, dim3(a.nbm * a.nbn, n), dim3(256), lds, st, grp); }
 #else
   else { st_set_error("the single-buffer small-block kernel (ST_IGEMM_S3=1|3) needs a `make EXPERIMENTAL=1` build"); return 1; }
 #endif
@@ -805,6 +814,7 @@ int launch_(IgemmArgs* arr, int n, hipStream_t st) {
                         hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     attr_set[dev_] = lds;
   }
+  route_note(0, BM, BN, WM * WN, KC, MODE, n, a.atomic);
   hipLaunchKernelGGL((igemm_kernel<T, BM, BN, WM, WN, KC, MODE>), dim3(a.nbm * a.nbn, n), dim3(64 * WM * WN), lds, st, grp);
   if (prof) {
     (void)hipEventRecord(rec.e1, st);
@@ -942,7 +952,12 @@ extern "C" int st_conv(const st_conv_desc* d, void* stream) {
     ST_CHECK(S <= kGroup && d->KH == 1 && d->KW == 1 && d->Hin == 1 && d->Win == 1 && d->out_dtype == ST_F32 && !d->relu && !d->scale &&
              !d->residual && !d->stats && !d->in_stats && d->Cin % (S * bk) == 0,
              "st_conv: split_k=%d needs a plain fp32-output GEMM with K a multiple of %d", S, S * bk);
-    if (!d->accumulate && hipMemsetAsync(d->y, 0, (size_t)a.M * d->ldy * sizeof(float), st) != hipSuccess) { st_set_error("memset failed"); return 1; }
+    // only the M x N region: columns N .. ldy of y are the caller's, as on every other route (one flat memset where there are none)
+    if (!d->accumulate) {
+      const hipError_t e = d->ldy == d->N ? hipMemsetAsync(d->y, 0, (size_t)a.M * d->ldy * sizeof(float), st)
+                                          : hipMemset2DAsync(d->y, (size_t)d->ldy * sizeof(float), 0, (size_t)d->N * sizeof(float), (size_t)a.M, st);
+      if (e != hipSuccess) { st_set_error("memset failed"); return 1; }
+    }
     IgemmArgs arr[kGroup];
     const int ks = d->Cin / S;
     const size_t es = d->dtype == ST_BF16 ? 2 : 4;
@@ -976,6 +991,14 @@ extern "C" int st_conv_batch(const st_conv_desc* d, int n, void* stream) {
 }
 
 
+
+// Which kernel the calling thread's last st_conv / st_conv_batch launch was (tests assert the route a shape is meant to take):
+// out = {main loop, BM, BN, waves, KC, MODE, group members, atomic}, all -1 before the first launch.  Returns the number of
+// igemm launches this thread has made so far; a refused call adds none and leaves the record as it was.
+extern "C" int st_conv_last_route(int* out) {
+  if (out) memcpy(out, g_route.v, sizeof(g_route.v));
+  return g_route.launches;
+}
 
 // Benchmarking knob (tools/bench_conv.py): main-loop variant selection; -1 keeps the current value.
 extern "C" int st_tune(int ring, int kc, int w8) {
