@@ -656,6 +656,18 @@ int st_beam_ban_topk(const float* logits, int ldl, int n, int V, int k, const in
 int st_beam_select_hist(const long* tok, const float* cost, uint8_t* done, const float* top_p, const long* top_id, int B, int W, int k,
                         long end_id, long* new_tok, float* new_cost, int* parent, uint8_t* ended, int* gather,
                         const int* hist_in, int* hist_out, int hist_ld, int hist_len, void* stream);
+/* Diverse (group) beam search (Vijayakumar et al., AAAI 2018): st_beam_select / st_beam_select_hist over G groups of W' = W / G
+ * slots, group g = slots g*W' .. (g+1)*W' - 1.  Each group is a search of its own: done [B][G], harvest flags per group, and a
+ * parent (an image-wide slot index, as above) always lies in its child's group.  The groups of an image are handled in the order
+ * 0 .. G-1 inside the one launch.  A candidate of group g (its W' nodes x their k list entries, node-major, ascending probability)
+ * has raw = fl32(cost[w] + fl32(-log(double p))) and key = fl32(raw + fl32(diversity_penalty * n_v)), n_v = the number of occupied
+ * slots of the new fringes of groups 0 .. g-1 that hold the candidate's word (a count; <end> counts like any word); raw = +inf
+ * stays +inf.  The group's new fringe is its W' best by a stable ranking of key, in rank order; new_cost records raw, never the
+ * penalty.  hist_in and hist_out are both NULL (no paths kept) or st_beam_select_hist's.  Needs G >= 1, W % G == 0, a finite
+ * diversity_penalty >= 0, k <= W and W * k <= 64.  G = 1 gives st_beam_select's / st_beam_select_hist's outputs bit for bit. */
+int st_beam_select_groups(const long* tok, const float* cost, uint8_t* done, const float* top_p, const long* top_id, int B, int W, int G,
+                          int k, long end_id, float diversity_penalty, long* new_tok, float* new_cost, int* parent, uint8_t* ended,
+                          int* gather, const int* hist_in, int* hist_out, int hist_ld, int hist_len, void* stream);
 
 /* Caption sampling (the multinomial counterpart of the max(1)[1] of rnn.py:52 and rnn_attn.py:141).  The kernels hold no
  * random-number generator: the caller supplies one uniform in [0, 1) per row and step.
@@ -834,6 +846,18 @@ int st_attn_beam_search_ex(const st_attn_params* p, const float* cnn_feature, in
                            long start_id, long end_id, void* workspace, size_t workspace_bytes,
                            long* rec_tok, float* rec_cost, int* rec_par, uint8_t* rec_end, float* rec_alpha,
                            int min_length, int ngram, const long* suppress, int n_suppress, void* stream);
+/* Diverse (group) beam search: st_attn_beam_search_ex's loop over num_groups groups of W / num_groups slots (W % num_groups == 0),
+ * with st_beam_select_groups' rule for the selection (diversity_penalty finite and >= 0).  Fringe 0 holds start_id at cost 0 in the
+ * first slot of every group.  Every iteration runs st_beam_ban_topk (st_softmax_topk when min_length, ngram and n_suppress are
+ * all 0: the same bits) and st_beam_select_groups -- the launches of st_attn_beam_search_ex.  The records keep their layout; rec_par holds image-wide slot
+ * indices, which lie in the child's group.  The workspace is st_attn_beam_ex_workspace_bytes' plan followed, for num_groups > 1,
+ * by the B * num_groups done flags. */
+size_t st_attn_beam_div_workspace_bytes(const st_attn_params* p, int B, int W, int max_length, int num_groups);
+int st_attn_beam_search_div(const st_attn_params* p, const float* cnn_feature, int B, int W, int max_length,
+                            long start_id, long end_id, void* workspace, size_t workspace_bytes,
+                            long* rec_tok, float* rec_cost, int* rec_par, uint8_t* rec_end, float* rec_alpha,
+                            int min_length, int ngram, const long* suppress, int n_suppress, int num_groups, float diversity_penalty,
+                            void* stream);
 
 #ifdef __cplusplus
 }

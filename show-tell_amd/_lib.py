@@ -197,6 +197,7 @@ _SIGS = {
     "st_beam_select": ([c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_p, c_p, c_p, c_p, c_p, c_p], c_i),
     "st_beam_ban_topk": ([c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_i, c_l, c_i, c_p, c_p, c_p], c_i),
     "st_beam_select_hist": ([c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p], c_i),
+    "st_beam_select_groups": ([c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_l, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p], c_i),
     "st_sample_rows": ([c_p, c_i, c_i, c_i, c_p, c_i, c_f, c_i, c_l, c_p, c_p, c_p, c_i, c_i, c_p, c_p], c_i),
     "st_sample_rows_topp": ([c_p, c_i, c_i, c_i, c_p, c_i, c_f, c_i, c_f, c_l, c_p, c_p, c_p, c_i, c_i, c_p, c_p], c_i),
     "st_rnn_sample_workspace_bytes": ([C.POINTER(RnnParams), c_i], C.c_size_t),
@@ -226,6 +227,9 @@ _SIGS = {
     "st_attn_beam_search": ([c_p, c_p, c_i, c_i, c_i, c_l, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p, c_p], c_i),
     "st_attn_beam_ex_workspace_bytes": ([c_p, c_i, c_i, c_i], C.c_size_t),
     "st_attn_beam_search_ex": ([c_p, c_p, c_i, c_i, c_i, c_l, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_p], c_i),
+    "st_attn_beam_div_workspace_bytes": ([c_p, c_i, c_i, c_i, c_i], C.c_size_t),
+    "st_attn_beam_search_div": ([c_p, c_p, c_i, c_i, c_i, c_l, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_f, c_p],
+                                c_i),
     "st_cross_entropy": ([c_p, c_i, c_p, c_i, c_i, c_i, C.POINTER(LossTerms), c_p, c_p, c_i, c_i, c_f, c_p, c_p], c_i),
     "st_head_workspace_bytes": ([c_i, c_i, c_i, c_i], C.c_size_t),
     "st_linear_bn1d_forward": ([c_p] * 7 + [c_i, c_i, c_i, c_i, c_i, c_f, c_f] + [c_p] * 6, c_i),

@@ -18,8 +18,21 @@ repeat an n-gram of size g already on the path.  Bans act before a row is cut to
 k most probable unbanned entries) and leave the probabilities alone: a cost stays the model's own -log p.  Every node inherits
 its parent's path inside the selection kernel (st_beam_select_hist), so a constrained iteration has the launches of an
 unconstrained one.  ``length_penalty`` a only re-ranks the harvested hypotheses, by cost / n**a.
+
+Diverse (group) beam search (Vijayakumar et al., AAAI 2018; ``num_beam_groups`` = G, ``diversity_penalty`` = lambda): the W slots
+are G groups of W' = W / G, group g = slots g*W' .. (g+1)*W' - 1, each a search of its own (its own root in slot g*W', harvest
+flags, done flag and hypotheses; a parent lies in its child's group).  Every iteration runs the model step and the top-k launch on
+all B*W rows as before; the selection (st_beam_select_groups, one launch) handles the groups of an image in the order 0 .. G-1 and
+ranks a candidate (node w, word v) of group g by key = fl32(raw + fl32(lambda * n_v)), raw = fl32(cost[w] + fl32(-log p)), n_v = the
+number of occupied slots of the new fringes of groups 0 .. g-1, chosen in this same iteration, that hold v (a count, <end>
+included).  The recorded cost is raw: the penalty decides the selection of the current step only and is never carried, which is
+the paper's objective (cumulative log-probability plus a current-step diversity term), so a cost stays the model's own -log p.
+HuggingFace lets the penalty accumulate in the beam score; that is deliberately NOT followed here.  k = min(W, V) list entries per
+node suffice: a node of group g is penalised on at most g*W' <= W - W' distinct words, so at least W' of its k most probable
+(unbanned) words carry no penalty, and every word outside the list has a raw cost, hence a key, no smaller than theirs.
 """
 import ctypes as C
+import operator
 
 import numpy as np
 import torch
@@ -68,6 +81,61 @@ class BeamConstraints:
         if not self.suppress:
             return None, 0
         return torch.tensor(self.suppress, dtype=torch.long, device=device), len(self.suppress)
+
+
+DIVERSE_ON_DEVICE_ONLY = "diverse beam search (num_beam_groups > 1) runs on the device only: on_device and beam_width * min(beam_width, V) <= 64"
+
+
+def check_groups(beam_width, vocab_size, num_beam_groups=1, diversity_penalty=0.0, on_device=True):
+    """(G, lambda) of a diverse search, validated before the device is touched: G an integer in 1..W that divides W, lambda >= 0
+    (and 0 with one group: there is nothing to differ from); G > 1 runs on the device only, so it needs W * min(W, V) <= 64."""
+    W = int(beam_width)
+    try:
+        G = None if isinstance(num_beam_groups, bool) else operator.index(num_beam_groups)      # an integer type: 2.0 is none
+    except TypeError:
+        G = None
+    if G is None or not 1 <= G <= W:
+        raise ValueError(f"num_beam_groups must be an integer in 1..beam_width={W} (got {num_beam_groups!r})")
+    if W % G:
+        raise ValueError(f"beam_width={W} is not a multiple of num_beam_groups={G}")
+    lam = float(diversity_penalty)
+    if not 0.0 <= lam < float("inf"):
+        raise ValueError(f"diversity_penalty must be finite and >= 0 (got {diversity_penalty})")
+    if G == 1 and lam != 0.0:
+        raise ValueError(f"diversity_penalty={lam} needs num_beam_groups > 1")
+    if G > 1 and (not on_device or W * min(W, int(vocab_size)) > 64):
+        raise ValueError(DIVERSE_ON_DEVICE_ONLY)
+    return G, lam
+
+
+def group_records(rec, g, num_beam_groups):
+    """Group g of the records of a diverse search as records of a search W' = W / G wide: tok / cost / par / end (and hist, alpha)
+    cut to the group's slots, `par` rebased to the group, so that ``replay_hypotheses`` serves a group unchanged."""
+    G = int(num_beam_groups)
+    W = rec["tok"].shape[2]
+    if G < 1 or W % G or not 0 <= g < G:
+        raise ValueError(f"group {g} of {G} over {W} slots")
+    Wg = W // G
+    sl = slice(g * Wg, (g + 1) * Wg)
+    par = rec["par"][:, :, sl]
+    out = dict(tok=rec["tok"][:, :, sl], cost=rec["cost"][:, :, sl], par=np.where(par >= 0, par - g * Wg, -1).astype(rec["par"].dtype),
+               end=rec["end"][:, :, sl])
+    if "hist" in rec:
+        out["hist"] = rec["hist"][:, sl]
+    if "alpha" in rec:
+        a = rec["alpha"]
+        B = rec["tok"].shape[1]
+        out["alpha"] = np.ascontiguousarray(a.reshape(a.shape[0], B, W, a.shape[2])[:, :, sl]).reshape(a.shape[0], B * Wg, a.shape[2])
+    return out
+
+
+def replay_groups(rec, num_beam_groups, num_hypotheses, length_penalty=0.0):
+    """Per image a list of G lists: ``replay_hypotheses`` of every sliced group (harvested and ranked on its own)."""
+    per = []
+    for g in range(num_beam_groups):
+        r = group_records(rec, g, num_beam_groups)
+        per.append(replay_hypotheses(r["tok"], r["cost"], r["par"], r["end"], num_hypotheses, r.get("alpha"), length_penalty))
+    return [[per[g][b] for g in range(num_beam_groups)] for b in range(rec["tok"].shape[1])]
 
 
 class _Stepper:
@@ -158,7 +226,7 @@ def quirky_beam(rnn, cnn_feature, beam_size, steps=CAP_MAX):
 
 
 def beam_search(rnn, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50, start_id=1, end_id=2, on_device=True,
-                min_length=0, no_repeat_ngram_size=0, suppress_tokens=None, length_penalty=0.0):
+                min_length=0, no_repeat_ngram_size=0, suppress_tokens=None, length_penalty=0.0, num_beam_groups=1, diversity_penalty=0.0):
     """beam_search.py:45-97 for every image of the batch; see ``beam_search_host`` for the contract.  With ``on_device`` (and
     beam_width**2 <= 64) the fringe selection of every iteration also runs on the GPU (``st_beam_select``) over fixed
     (image, slot) rows, so the whole search needs ONE host round trip instead of three per iteration; the Node bookkeeping
@@ -168,9 +236,20 @@ def beam_search(rnn, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50,
 
     Constraints (module docstring): ``min_length`` words before <end>, ``no_repeat_ngram_size``, ``suppress_tokens`` (ids that never
     appear) act inside the device loop; ``length_penalty`` a ranks the harvested hypotheses by cost / n**a (n tokens after <start>,
-    <end> included) and returns the raw cost.  With all four at their defaults the call is the launch sequence it was."""
+    <end> included) and returns the raw cost.  With all four at their defaults the call is the launch sequence it was.
+
+    Diverse beam search (module docstring): ``num_beam_groups`` = G > 1 splits the beam into G groups of beam_width / G slots and
+    ``diversity_penalty`` = lambda >= 0 charges a group's candidates lambda per earlier group's slot that took the same word at
+    this step; the penalty is never recorded in a cost (the paper's objective, not HuggingFace's accumulating score).  The
+    return value is then, per image, a list of G lists of at most `num_hypotheses` (tokens, cost) pairs, each group harvested and
+    ranked on its own.  Device only.  With G = 1 the return value and the launch sequence are what they were."""
+    G, lam = check_groups(beam_width, rnn.vocab_size, num_beam_groups, diversity_penalty, on_device)
     k = min(beam_width, rnn.vocab_size)
     cons = dict(min_length=min_length, no_repeat_ngram_size=no_repeat_ngram_size, suppress_tokens=suppress_tokens)
+    if G > 1:
+        BeamConstraints(rnn.vocab_size, max_length, length_penalty=length_penalty, **cons)
+        r = beam_search_records(rnn, cnn_feature, beam_width, max_length, start_id, end_id, num_beam_groups=G, diversity_penalty=lam, **cons)
+        return replay_groups(r, G, num_hypotheses, float(length_penalty))
     if not on_device or beam_width * k > 64:
         return beam_search_host(rnn, cnn_feature, beam_width, num_hypotheses, max_length, start_id, end_id, length_penalty=length_penalty,
                                 **cons)
@@ -180,12 +259,14 @@ def beam_search(rnn, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50,
 
 
 def beam_search_records(rnn, cnn_feature, beam_width=4, max_length=50, start_id=1, end_id=2, min_length=0, no_repeat_ngram_size=0,
-                        suppress_tokens=None):
+                        suppress_tokens=None, num_beam_groups=1, diversity_penalty=0.0):
     """The device loop of ``beam_search`` on its own: every iteration's fringe over fixed (image, slot) rows, as numpy arrays
     dict(tok, cost, par [max_length+1][B][W], end [max_length][B][W]) -- what ``replay_hypotheses`` reads.  Needs
     beam_width * min(beam_width, V) <= 64 (st_beam_select).  Under constraints the loop runs st_beam_ban_topk and
     st_beam_select_hist in their place, and the records gain hist [B][W][max_length+1] int32: the path of every slot of the last
-    fringe, as the search itself kept it."""
+    fringe, as the search itself kept it.  With ``num_beam_groups`` = G > 1 the selection is st_beam_select_groups: the layout
+    stays, slots g*W/G .. (g+1)*W/G - 1 are group g (``group_records`` cuts one out), `par` holds image-wide slot indices."""
+    G, lam = check_groups(beam_width, rnn.vocab_size, num_beam_groups, diversity_penalty)
     k = min(beam_width, rnn.vocab_size)
     bc = BeamConstraints(rnn.vocab_size, max_length, min_length, no_repeat_ngram_size, suppress_tokens)
     with torch.no_grad():
@@ -195,9 +276,9 @@ def beam_search_records(rnn, cnn_feature, beam_width=4, max_length=50, start_id=
         n = B * W
         _, state = st.step(_feat(rnn, cnn_feature), None, want_logits=False)      # state after the image-feature step (rnn.py:41,49)
         state = st.gather(state, torch.arange(B, device=dev, dtype=torch.int32).repeat_interleave(W))   # slot (b, w) <- image b
-        tok = torch.zeros(B, W, device=dev, dtype=torch.long); tok[:, 0] = start_id    # beam_search.py:66
-        cost = torch.full((B, W), float("inf"), device=dev, dtype=torch.float32); cost[:, 0] = 0.0
-        done = torch.zeros(B, device=dev, dtype=torch.uint8)
+        tok = torch.zeros(B, W, device=dev, dtype=torch.long); tok[:, ::W // G] = start_id    # beam_search.py:66, once per group
+        cost = torch.full((B, W), float("inf"), device=dev, dtype=torch.float32); cost[:, ::W // G] = 0.0
+        done = torch.zeros(B * G, device=dev, dtype=torch.uint8)
         rec_tok = torch.zeros(max_length + 1, B, W, device=dev, dtype=torch.long)
         rec_cost = torch.full((max_length + 1, B, W), float("inf"), device=dev, dtype=torch.float32)
         rec_par = torch.full((max_length + 1, B, W), -1, device=dev, dtype=torch.int32)
@@ -223,7 +304,12 @@ def beam_search_records(rnn, cnn_feature, beam_width=4, max_length=50, start_id=
                 check(lib().st_beam_ban_topk(_cp(logits), st.Vp, n, st.V, k, hp[t & 1] if hist is not None else None,
                                              ld if hist is not None else 0, t + 1, bc.ngram, _cp(sup), n_sup, end_id,
                                              int(t < bc.min_length), _cp(tp), _cp(ti), _stream()), "st_beam_ban_topk")
-            if hist is None:
+            if G > 1:
+                check(lib().st_beam_select_groups(_cp(tok), _cp(cost), _cp(done), _cp(tp), _cp(ti), B, W, G, k, end_id, lam, _cp(ntok),
+                                                  _cp(ncost), _cp(rec_par[t + 1]), _cp(rec_end[t]), _cp(gidx),
+                                                  hp[t & 1] if hist is not None else None, hp[(t + 1) & 1] if hist is not None else None,
+                                                  ld if hist is not None else 0, t + 1, _stream()), "st_beam_select_groups")
+            elif hist is None:
                 check(lib().st_beam_select(_cp(tok), _cp(cost), _cp(done), _cp(tp), _cp(ti), B, W, k, end_id, _cp(ntok), _cp(ncost),
                                            _cp(rec_par[t + 1]), _cp(rec_end[t]), _cp(gidx), _stream()), "st_beam_select")
             else:
@@ -260,9 +346,14 @@ def replay_hypotheses(h_tok, h_cost, h_par, h_end, num_hypotheses, alphas=None, 
     length_penalty = float(length_penalty)
     B, W = h_tok.shape[1], h_tok.shape[2]
     out = []
+    eb, et, ew = np.nonzero(np.transpose(h_end, (1, 0, 2)))                           # one pass over the flags: image-major
+    first = np.searchsorted(eb, np.arange(B + 1))
     for b in range(B):
+        if first[b] == first[b + 1]:                                                  # nothing ended in time
+            out.append([])
+            continue
         hyp = []                                                                      # (iteration of the node, slot, cost) in harvest order
-        for t, w in zip(*np.nonzero(h_end[:, b])):                                    # iteration-major, slot order inside (beam_search.py:72-76)
+        for t, w in zip(et[first[b]:first[b + 1]], ew[first[b]:first[b + 1]]):        # iteration-major, slot order inside (beam_search.py:72-76)
             hyp.append((int(t), int(w), h_cost[t, b, w]))
         res = []
         for t, w, c in _ranked(hyp, num_hypotheses, length_penalty):                  # beam_search.py:96 (stable)
@@ -287,7 +378,7 @@ def replay_hypotheses(h_tok, h_cost, h_par, h_end, num_hypotheses, alphas=None, 
 
 
 def beam_search_host(rnn, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50, start_id=1, end_id=2, min_length=0,
-                     no_repeat_ngram_size=0, suppress_tokens=None, length_penalty=0.0):
+                     no_repeat_ngram_size=0, suppress_tokens=None, length_penalty=0.0, num_beam_groups=1, diversity_penalty=0.0):
     """beam_search.py:45-97 for every image of the batch.  Returns, per image, a list of at most
     `num_hypotheses` (token_sequence, cum_cost) pairs; the list is empty when no beam ever emitted
     `end_id` in time (the reference returns [] then).
@@ -299,7 +390,9 @@ def beam_search_host(rnn, cnn_feature, beam_width=4, num_hypotheses=1, max_lengt
     nodes that end on the last iteration are never harvested), hypotheses are stably sorted by cost at the end.
 
     Under constraints every fringe node carries its path (`path`, beside the Node table) and its successors come from
-    st_beam_ban_topk; the hypotheses are ranked as ``replay_hypotheses`` ranks them."""
+    st_beam_ban_topk; the hypotheses are ranked as ``replay_hypotheses`` ranks them.  Diverse search (num_beam_groups > 1) runs
+    on the device only and is refused here."""
+    check_groups(beam_width, rnn.vocab_size, num_beam_groups, diversity_penalty, on_device=False)
     bc = BeamConstraints(rnn.vocab_size, max_length, min_length, no_repeat_ngram_size, suppress_tokens, length_penalty)
     with torch.no_grad():
         st = _Stepper(rnn)

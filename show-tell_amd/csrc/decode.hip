@@ -836,6 +836,101 @@ extern "C" int st_beam_select_hist(const long* tok, const float* cost, uint8_t* 
   return 0;
 }
 
+// Diverse (group) beam search, Vijayakumar et al. 2018: the W slots of an image are G groups of W' = W / G, group g = slots
+// g*W' .. (g+1)*W' - 1, each a search of its own (its own harvest flags, its own done[b*G + g], parents inside the group).
+// All W*k raw costs are formed at once, as beam_select_kernel forms them.  Then the groups run in the order 0 .. G-1: a candidate
+// (node w, word v) of group g gets key = fl32(raw + fl32(lambda * n_v)), n_v = the number of occupied new slots of groups 0 .. g-1
+// that hold v (a count; chosen[] in LDS, -1 = empty), and the group's W' best by a stable ranking of key fill its slots in rank
+// order.  The recorded cost is raw: the penalty decides this step's selection only.  The keys of a group are ranked across lanes
+// (one wave), so one barrier closes each group: it publishes the group's words to the next.  G = 1: beam_select_kernel's outputs.
+template <bool HIST>
+__global__ __launch_bounds__(64) void beam_select_groups_kernel(const long* __restrict__ tok, const float* __restrict__ cost, uint8_t* __restrict__ done,
+                                                                const float* __restrict__ top_p, const long* __restrict__ top_id, int W, int G, int k,
+                                                                long end_id, float lambda, long* __restrict__ new_tok, float* __restrict__ new_cost,
+                                                                int* __restrict__ parent, uint8_t* __restrict__ ended_rec, int* __restrict__ gather,
+                                                                const int* __restrict__ hist_in, int* __restrict__ hist_out, int hist_ld, int hist_len) {
+  __shared__ int live_g[64];                                 // per group: a live slot exists
+  __shared__ int chosen[64];                                 // word of every new slot chosen so far (-1: empty)
+  __shared__ int new_par[64];                                // HIST: parent slot of the new slots (-1: empty)
+  const int b = blockIdx.x, c = threadIdx.x;
+  const int Wg = W / G, n = W * k, ng = Wg * k;              // slots and candidates of a group
+  live_g[c] = 0;
+  __syncthreads();
+  if (c < W) {
+    const bool was_done = done[b * G + c / Wg] != 0;
+    const bool occupied = cost[b * W + c] < INFINITY;
+    const bool ended = occupied && tok[b * W + c] == end_id && !was_done;
+    ended_rec[b * W + c] = ended ? 1 : 0;
+    if (occupied && !ended && !was_done) live_g[c / Wg] = 1;
+  }
+  __syncthreads();
+  float raw = INFINITY;
+  int word = 0;
+  const int w = c < n ? c / k : 0, j = c - w * k;            // successor j in ascending probability = top-k entry k-1-j
+  const int mine = c < n ? w / Wg : -1;                      // the group of this thread's candidate
+  if (c < n) {
+    const bool finished = done[b * G + mine] != 0 || !live_g[mine];
+    const float cw = cost[b * W + w];
+    word = (int)top_id[(long)(b * W + w) * k + (k - 1 - j)];
+    if (!finished && cw < INFINITY && tok[b * W + w] != end_id)
+      raw = cw + (float)(-log((double)top_p[(long)(b * W + w) * k + (k - 1 - j)]));
+  }
+  __syncthreads();                                           // every read of done[] lies before its update
+  if (c < G) done[b * G + c] = (done[b * G + c] != 0 || !live_g[c]) ? 1 : 0;
+  for (int g = 0; g < G; ++g) {
+    int n_v = 0;
+    for (int s = 0; s < g * Wg; ++s) n_v += chosen[s] == word ? 1 : 0;
+    const float key = raw < INFINITY ? __fadd_rn(raw, __fmul_rn(lambda, (float)n_v)) : INFINITY;
+    int rank = 0;                                            // stable: ties keep candidate order
+    for (int o = g * ng; o < (g + 1) * ng; ++o) {
+      const float ko = __shfl(key, o, 64);
+      rank += (ko < key || (ko == key && o < c)) ? 1 : 0;
+    }
+    if (mine == g && rank < Wg) {
+      const int slot = g * Wg + rank;
+      const bool ok = raw < INFINITY;
+      new_cost[b * W + slot] = ok ? raw : INFINITY;
+      new_tok[b * W + slot] = ok ? (long)word : 0;
+      parent[b * W + slot] = ok ? w : -1;
+      gather[b * W + slot] = b * W + (ok ? w : 0);
+      chosen[slot] = ok ? word : -1;
+      if constexpr (HIST) new_par[slot] = ok ? w : -1;
+    }
+    __syncthreads();
+  }
+  if constexpr (HIST) {
+    const int len = hist_len + 1;
+    for (int e = c; e < W * len; e += 64) {
+      const int r = e / len, pos = e - r * len, par = new_par[r];
+      hist_out[(long)(b * W + r) * hist_ld + pos] = pos == hist_len ? (par >= 0 ? chosen[r] : 0) : (par >= 0 ? hist_in[(long)(b * W + par) * hist_ld + pos] : 0);
+    }
+  }
+}
+
+extern "C" int st_beam_select_groups(const long* tok, const float* cost, uint8_t* done, const float* top_p, const long* top_id, int B, int W, int G,
+                                     int k, long end_id, float diversity_penalty, long* new_tok, float* new_cost, int* parent, uint8_t* ended,
+                                     int* gather, const int* hist_in, int* hist_out, int hist_ld, int hist_len, void* stream) {
+  ST_CHECK(tok && cost && done && top_p && top_id && new_tok && new_cost && parent && ended && gather, "st_beam_select_groups: null pointer");
+  ST_CHECK(B > 0 && W >= 1 && k >= 1 && k <= W && W * k <= 64, "st_beam_select_groups: need 1 <= k <= W and W * k <= 64 (got W=%d k=%d)", W, k);
+  ST_CHECK(G >= 1 && W % G == 0, "st_beam_select_groups: the %d slots do not split into %d groups", W, G);
+  ST_CHECK(diversity_penalty >= 0.f && diversity_penalty < INFINITY, "st_beam_select_groups: diversity_penalty must be finite and >= 0 (got %g)",
+           (double)diversity_penalty);
+  ST_CHECK((hist_in == nullptr) == (hist_out == nullptr) && (!hist_in || hist_in != hist_out),
+           "st_beam_select_groups: hist_in and hist_out are both null or two different buffers");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (hist_in) {
+    ST_CHECK(hist_len >= 1 && hist_len + 1 <= hist_ld && hist_len + 1 <= ST_BEAM_MAX_HIST,
+             "st_beam_select_groups: need 1 <= hist_len and hist_len + 1 <= min(hist_ld, %d) (got %d, ld %d)", ST_BEAM_MAX_HIST, hist_len, hist_ld);
+    hipLaunchKernelGGL(beam_select_groups_kernel<true>, dim3(B), dim3(64), 0, st, tok, cost, done, top_p, top_id, W, G, k, end_id, diversity_penalty,
+                       new_tok, new_cost, parent, ended, gather, hist_in, hist_out, hist_ld, hist_len);
+  } else {
+    hipLaunchKernelGGL(beam_select_groups_kernel<false>, dim3(B), dim3(64), 0, st, tok, cost, done, top_p, top_id, W, G, k, end_id, diversity_penalty,
+                       new_tok, new_cost, parent, ended, gather, nullptr, nullptr, 0, 0);
+  }
+  ST_LAUNCH_CHECK();
+  return 0;
+}
+
 // One timestep of the multi-layer cell for n independent rows (+ optional vocabulary projection).
 extern "C" int st_rnn_step(const st_rnn_params* p, const void* x, int n, const void* h_in, const void* c_in,
                            void* h_out, void* c_out, float* logits, int ldl, void* stream) {

@@ -538,13 +538,16 @@ class RNN(Decoder):
             return unpack_rows(plan_for(caption_size, nll.device), -nll, image_caption.shape[1], nll.device)
 
     def beam_search(self, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50, start_id=1, end_id=2, min_length=0,
-                    no_repeat_ngram_size=0, suppress_tokens=None, length_penalty=0.0):
+                    no_repeat_ngram_size=0, suppress_tokens=None, length_penalty=0.0, num_beam_groups=1, diversity_penalty=0.0):
         """beam_search.py:45-97 over the whole batch (BASELINE config 5: beam_width=5, max_length=25).  The last four arguments
         constrain the search (beam.beam_search): at least `min_length` words before <end>, no n-gram of that size twice in a
-        caption, ids that never appear, and hypotheses ranked by cost / n**length_penalty."""
+        caption, ids that never appear, and hypotheses ranked by cost / n**length_penalty.  `num_beam_groups` = G > 1 is diverse
+        beam search (beam.beam_search): G groups of beam_width / G slots, `diversity_penalty` per earlier group's slot that took the
+        same word at this step; the result is then, per image, a list of G lists of hypotheses."""
         from .beam import beam_search
         return beam_search(self, cnn_feature, beam_width, num_hypotheses, max_length, start_id, end_id, min_length=min_length,
-                           no_repeat_ngram_size=no_repeat_ngram_size, suppress_tokens=suppress_tokens, length_penalty=length_penalty)
+                           no_repeat_ngram_size=no_repeat_ngram_size, suppress_tokens=suppress_tokens, length_penalty=length_penalty,
+                           num_beam_groups=num_beam_groups, diversity_penalty=diversity_penalty)
 
     def sample(self, cnn_feature, num_samples=1, temperature=1.0, top_k=0, max_length=CAP_MAX, end_id=2, generator=None,
                uniforms=None, top_p=1.0):

@@ -290,7 +290,8 @@ class RNN_Attn(Decoder):
             return out + (alphas.view(B, S, T, P),) if return_alphas else out
 
     def beam_search(self, cnn_feature, beam_width=4, num_hypotheses=1, max_length=50, start_id=1, end_id=2, return_alphas=False,
-                    return_records=False, min_length=0, no_repeat_ngram_size=0, suppress_tokens=None, length_penalty=0.0):
+                    return_records=False, min_length=0, no_repeat_ngram_size=0, suppress_tokens=None, length_penalty=0.0,
+                    num_beam_groups=1, diversity_penalty=0.0):
         """beam_search.py:45-97 for every image of the batch, driven by the test branch of rnn_attn.py:77-94: the root holds
         start_id with h0 = init_h(mean feature) over all layers (and c0 for the LSTM); a node's successors come from one step
         fed with the node's token, attention keyed on its top-layer state.  The whole search is one st_attn_beam_search call
@@ -304,18 +305,25 @@ class RNN_Attn(Decoder):
         search that keeps paths (max_length + 1 <= 64) adds hist [B][W][max_length+1] int32, the path of every slot of the last
         fringe as the search itself kept it.
         `min_length`, `no_repeat_ngram_size`, `suppress_tokens` and `length_penalty` constrain the search as in
-        RNN.beam_search (beam.py); with any of the first three set the call is st_attn_beam_search_ex."""
-        from .beam import BeamConstraints, replay_hypotheses
+        RNN.beam_search (beam.py); with any of the first three set the call is st_attn_beam_search_ex.
+        `num_beam_groups` = G > 1 is diverse beam search as in RNN.beam_search (beam.py's docstring has the rule): one
+        st_attn_beam_search_div call; the hypotheses are then, per image, a list of G lists (each entry with its alphas under
+        `return_alphas`), the records keep their layout (beam.group_records cuts a group out) and hist is handed out whenever
+        the paths fit (max_length + 1 <= 64).  With G = 1 the call and its result are what they were."""
+        from .beam import ST_BEAM_MAX_HIST, BeamConstraints, check_groups, replay_groups, replay_hypotheses
         if not 1 <= beam_width <= 8:
             raise ValueError(f"beam_width must be 1..8 (got {beam_width})")
         if max_length < 1:
             raise ValueError(f"max_length must be >= 1 (got {max_length})")
+        G, lam = check_groups(beam_width, self.vocab_size, num_beam_groups, diversity_penalty)
         bc = BeamConstraints(self.vocab_size, max_length, min_length, no_repeat_ngram_size, suppress_tokens, length_penalty)
         with torch.no_grad():
             prm, keep, featc, B, P = self._decode_inputs(cnn_feature)
             W, T = beam_width, max_length
             n = B * W
-            if bc.active:
+            if G > 1:
+                nbytes = lib().st_attn_beam_div_workspace_bytes(C.byref(prm), B, W, T, G)
+            elif bc.active:
                 nbytes = lib().st_attn_beam_ex_workspace_bytes(C.byref(prm), B, W, T)
             else:
                 nbytes = lib().st_attn_beam_workspace_bytes(C.byref(prm), B, W)
@@ -332,7 +340,13 @@ class RNN_Attn(Decoder):
                 o += (nb + 255) // 256 * 256
             rec = torch.empty(o, device=featc.device, dtype=torch.uint8)
             view = {name: rec[offs[name][0]:offs[name][0] + offs[name][1]].view(dt).view(shape) for name, dt, shape in layout}
-            if bc.active:
+            if G > 1:
+                sup, n_sup = bc.suppress_on(featc.device)
+                check(lib().st_attn_beam_search_div(C.byref(prm), _cp(featc), B, W, T, int(start_id), int(end_id), _cp(ws), nbytes,
+                                                    _cp(view["tok"]), _cp(view["cost"]), _cp(view["par"]), _cp(view["end"]),
+                                                    _cp(view.get("alpha")), bc.min_length, bc.ngram, _cp(sup), n_sup, G, lam, _stream()),
+                      "st_attn_beam_search_div")
+            elif bc.active:
                 sup, n_sup = bc.suppress_on(featc.device)
                 check(lib().st_attn_beam_search_ex(C.byref(prm), _cp(featc), B, W, T, int(start_id), int(end_id), _cp(ws), nbytes,
                                                    _cp(view["tok"]), _cp(view["cost"]), _cp(view["par"]), _cp(view["end"]),
@@ -344,14 +358,17 @@ class RNN_Attn(Decoder):
                                                 _cp(view.get("alpha")), _stream()), "st_attn_beam_search")
             host = rec.cpu().numpy()
             hist = None
-            if return_records and bc.keep_paths:
+            if return_records and (bc.keep_paths or (G > 1 and T + 1 <= ST_BEAM_MAX_HIST)):
                 # the two path buffers follow the unconstrained plan in the workspace (showtell_hip.h); the last fringe's is T & 1
                 base, nb = lib().st_attn_beam_workspace_bytes(C.byref(prm), B, W), n * (T + 1) * 4
                 off = base + (T & 1) * ((nb + 255) // 256 * 256)
                 hist = ws[off:off + nb].view(torch.int32).view(B, W, T + 1).cpu().numpy()
         npdt = {torch.long: np.int64, torch.float32: np.float32, torch.int32: np.int32, torch.uint8: np.uint8}
         h = {name: host[offs[name][0]:offs[name][0] + offs[name][1]].view(npdt[dt]).reshape(shape) for name, dt, shape in layout}
-        hyps = replay_hypotheses(h["tok"], h["cost"], h["par"], h["end"], num_hypotheses, h.get("alpha"), bc.length_penalty)
+        if G > 1:
+            hyps = replay_groups(h, G, num_hypotheses, bc.length_penalty)
+        else:
+            hyps = replay_hypotheses(h["tok"], h["cost"], h["par"], h["end"], num_hypotheses, h.get("alpha"), bc.length_penalty)
         if hist is not None:
             h["hist"] = hist
         return (hyps, h) if return_records else hyps

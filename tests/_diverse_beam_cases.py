@@ -1,0 +1,403 @@
+"""Shared by test_diverse_beam_inputs.py (CPU) and test_gpu_diverse_beam.py: the rule of diverse (group) beam search in plain
+Python (written from the text below, not from the kernel), the float64 oracle's own diverse search over the k-lists and over all V
+words of every node, a numpy float32 replica of one selection, and the walk of a search's records, group by group, against the
+oracle.
+
+The rule.  beam_width = W, num_beam_groups = G, W' = W / G, diversity_penalty = lam >= 0.
+  * Slots g*W' .. (g+1)*W' - 1 are group g.  Fringe 0 holds <start> at cost 0 in slot g*W' of every group, the rest is empty (+inf).
+  * A group is a search of its own: its own harvest flags and its own done (no live slot left); a parent lies in its child's group.
+  * Every iteration gives every node its k = min(W, V) most probable unbanned words (bans first, probabilities untouched).
+  * The groups of an image are handled in the order 0 .. G-1.  The candidates of group g are its W' nodes x their k words,
+    node-major, each node's words in ascending probability.  raw = cost[w] + (-log p).  n_v = the number of occupied slots of the
+    new fringes of groups 0 .. g-1 (chosen in this same iteration) that hold word v -- a count, <end> like any word.
+    key = raw + lam * n_v; raw = +inf stays +inf.
+  * The group's new fringe is its W' best candidates by a stable ranking of key (ties keep candidate order), in rank order.
+  * The recorded cost is raw: the penalty decides the selection of the current step only.
+"""
+from collections import Counter
+
+import numpy as np
+import torch
+
+from oracle import restatement as R
+from tests import _beam_constraints_cases as K
+from tests._beam_constraints_cases import END, START, T
+
+INF = float("inf")
+LAMBDAS = (0.5, 2.0)                  # dyadic: lam * n is exact in every precision
+NONE = (0, 0, None)                   # no constraints
+# the decoders of the cases (fp32 and bf16 share them): (kind, cell, W, G, B, V); parameters and images are made as
+# _beam_constraints_cases makes those of its constraint set "all"
+DECODERS = {
+    "plain-gru": ("plain", "gru", 4, 2, 24, 600),
+    "plain-lstm": ("plain", "lstm", 4, 2, 24, 600),
+    "plain-gru-w8": ("plain", "gru", 8, 4, 9, 2056),
+    "attn-gru": ("attn", "gru", 6, 3, 13, 600),
+    "attn-lstm": ("attn", "lstm", 6, 2, 13, 600),
+    "plain-gru-g8": ("plain", "gru", 8, 8, 9, 600),          # W' = 1: every group a greedy chain
+}
+# (boost of <end>'s bias, boost of the hot words' bias, seed of the parameters, factor on <end>'s row of the vocabulary projection)
+# per decoder, searched on the CPU so that the float64 oracle alone meets every input condition of test_diverse_beam_inputs.py.  At
+# the boosts of K.INPUTS' set "all" (seed 9, factor 1) the share decided by the penalty and the count-versus-membership steps are
+# there (251 / 211 of 1344, 653 / 669 of 1344, 267 of 1092 / 352 of 1034, 291 / 295 of 1092 for the four main cases; 55 / 114 / 107
+# / 28 group-steps), but hardly a caption ends within T iterations and no group finishes before another: a group of W' slots
+# finishes only when all of them end in the same iteration.  A sharper <end> row makes <end> swing from negligible to dominant with
+# the state, for the nodes of a group together; the search ran over the two boosts (steps of 0.5, then 0.125), seeds 1 .. 13 and
+# factors 1, 1.5, 2, 3.
+INPUTS = {
+    "plain-gru": (4.375, 3.75, 9, 1.5),
+    "plain-lstm": (2.0, 3.0, 10, 2.0),
+    "plain-gru-w8": (4.5, 3.0, 1, 3.0),
+    "attn-gru": (5.0, 4.0, 9, 3.0),
+    "attn-lstm": (4.5, 4.0, 4, 1.0),
+    "plain-gru-g8": (3.5, 4.0, 9, 1.0),
+}
+_CACHE = {}
+
+
+def decoder_params(name):
+    """K.decoder_params with the settings of INPUTS: bf16-representable, a x10 vocabulary projection (<end>'s row sharpened further),
+    <end> and the hot words raised"""
+    if ("params", name) not in _CACHE:
+        kind, cell, _, _, _, vocab = DECODERS[name]
+        attn = dict(F=72, A=40) if kind == "attn" else None
+        p = {k: v.clone() for k, v in R.init_decoder_params(K.E, K.H, vocab, K.L, cell, seed=INPUTS[name][2], attn=attn).items()}
+        p["linear.weight"] *= 10.0
+        p["linear.weight"][END] *= INPUTS[name][3]
+        p["linear.bias"][END] += INPUTS[name][0]
+        p["linear.bias"][K.HOT] += INPUTS[name][1]
+        _CACHE[("params", name)] = {k: (v.bfloat16().float() if v.is_floating_point() else v) for k, v in p.items()}
+    return _CACHE[("params", name)]
+
+
+def oracle(name, storage=False, dt=torch.float64):
+    key = (name, storage, dt)
+    if key not in _CACHE:
+        kind, cell, W, G, B, vocab = DECODERS[name]
+        _CACHE[key] = K.Oracle(kind, cell, decoder_params(name), K.features(kind, B), W, storage, dt)
+    return _CACHE[key]
+
+
+def group_paths(tok, par, t, G):
+    """K.slot_paths for fringes whose roots sit in the first slot of every group"""
+    out = K.slot_paths(tok, par, t)
+    if t == 0:
+        Wg = tok.shape[2] // G
+        out[:, ::Wg, 0] = tok[0][:, ::Wg]
+    return out
+
+
+# ====================================================================================================================
+# the rule, one image, one iteration
+# ====================================================================================================================
+
+def rule_image(raw, words, W, G, lam, member=False, sign=1.0, scope="earlier", old_words=None):
+    """raw[w] / words[w]: the candidates of node w in ascending probability (raw = +inf: none).  Returns the new fringe, W entries
+    (parent slot, word, raw, key, index of the candidate inside its group) or None for an empty slot.
+    The seeded faults: `member` (was v chosen at all, not how often), `sign` = -1 (the penalty subtracted), `scope` = "prev" (n_v
+    counted over the OLD fringe of the earlier groups, old_words[s] or None) or "all" (over the other groups' slots: the earlier
+    groups' new fringe and the later groups' old one)."""
+    Wg = W // G
+    new = []
+    for g in range(G):
+        if scope == "earlier":
+            prior = [e[1] for e in new if e is not None]
+        elif scope == "prev":
+            prior = [v for v in old_words[:g * Wg] if v is not None]
+        else:
+            prior = [e[1] for e in new if e is not None] + [v for v in old_words[(g + 1) * Wg:] if v is not None]
+        count = Counter(prior)
+        cands = []
+        for w in range(g * Wg, (g + 1) * Wg):
+            for r, v in zip(raw[w], words[w]):
+                n_v = count.get(v, 0)
+                if member:
+                    n_v = min(n_v, 1)
+                cands.append((r + sign * lam * n_v if r < INF else INF, w, v, r))
+        order = sorted(range(len(cands)), key=lambda i: cands[i][0])              # stable: ties keep candidate order
+        fringe = []
+        for i in order[:Wg]:
+            key, w, v, r = cands[i]
+            fringe.append((w, v, r, key, i) if key < INF else None)
+        new += fringe
+    return new
+
+
+# ====================================================================================================================
+# the float64 oracle's own diverse search
+# ====================================================================================================================
+
+def free_run(orc, G, lam, cons=NONE, Tn=T, all_v=False, penalty_in_cost=False, sign=1.0, scope="earlier", member=False,
+             unseeded=False, done_per_image=False, cross_parent=False, after_cut=False):
+    """The rule on K.Oracle, free running.  `all_v`: the candidates of a node are ALL its unbanned words, not its k most probable.
+    The other keywords are the seeded faults of test_diverse_beam_inputs.py.  Returns the records and, per (iteration, image,
+    group): `decided` [T][B][W] (the slot's candidate is not among its group's W' best by raw: the penalty chose it), `member_diff`
+    [T][B][G] (a membership test in place of the count gives another chosen set), `gap` [T][B][G] (key distance between the last
+    candidate taken and the first left out), `live_g` [T][B][G]."""
+    B, W, Vn = orc.B, orc.W, orc.V
+    Wg, k = W // G, min(W, orc.V)
+    grp = np.arange(W) // Wg
+    tok = np.zeros((Tn + 1, B, W), np.int64)
+    cost = np.full((Tn + 1, B, W), np.inf)
+    roots = np.arange(W) % Wg == 0 if not unseeded else np.arange(W) == 0
+    tok[0][:, roots], cost[0][:, roots] = START, 0.0
+    par = np.full((Tn + 1, B, W), -1, np.int32)
+    end = np.zeros((Tn, B, W), np.uint8)
+    decided = np.zeros((Tn, B, W), bool)
+    member_diff, live_rec = np.zeros((Tn, B, G), bool), np.zeros((Tn, B, G), bool)
+    gap = np.full((Tn, B, G), np.inf)
+    done = np.zeros((B, G), bool)
+    state = orc.state0
+    constrained = cons != NONE
+    for t in range(Tn):
+        logp, new_state = orc.step(tok[t], state)
+        logp = logp.double()
+        ban = torch.from_numpy(K.ban_mask(group_paths(tok, par, t, G), Vn, cons)) if constrained else torch.zeros(B * W, Vn, dtype=torch.bool)
+        ranked = torch.sort(-(logp if after_cut else logp.masked_fill(ban, -np.inf)), dim=1, stable=True).indices.numpy()
+        n_ok = (~ban).sum(1).numpy()
+        lp, ban_np = logp.numpy(), ban.numpy()
+        occupied = np.isfinite(cost[t])
+        ended = occupied & (tok[t] == END) & ~done[:, grp]
+        live = occupied & ~ended & ~done[:, grp]
+        live_g = live.reshape(B, G, Wg).any(2)
+        done |= ~live_g
+        if done_per_image:
+            done |= done.any(1, keepdims=True)
+        live &= ~done[:, grp]
+        end[t], live_rec[t] = ended, live.reshape(B, G, Wg).any(2)
+        for b in range(B):
+            raw, words, src = [], [], []
+            for w in range(W):
+                s = (w + Wg) % W if cross_parent else w                              # fault: the nodes of the next group
+                src.append(s)
+                r = b * W + s
+                if not live[b, s]:
+                    raw.append([INF] * k); words.append([0] * k)
+                    continue
+                n = k if after_cut else (int(n_ok[r]) if all_v else min(k, int(n_ok[r])))
+                ids = ranked[r, :n][::-1].tolist()                                 # ascending probability
+                pad = 0 if all_v else k - n                                        # a short list ends in (p = 0, id = 0) entries: first here
+                words.append([0] * pad + ids)
+                raw.append([INF] * pad + [float(cost[t, b, s] - lp[r, v]) for v in ids])
+            old = [int(tok[t, b, s]) if occupied[b, s] else None for s in range(W)]
+            new = rule_image(raw, words, W, G, lam, member, sign, scope, old)
+            if lam and not (member or scope != "earlier" or sign != 1.0):
+                alt = rule_image(raw, words, W, G, lam, True)
+                for g in range(G):
+                    a = {(e[0], e[1]) for e in new[g * Wg:(g + 1) * Wg] if e}
+                    member_diff[t, b, g] = a != {(e[0], e[1]) for e in alt[g * Wg:(g + 1) * Wg] if e}
+            for g in range(G):
+                mine = [e for e in new[g * Wg:(g + 1) * Wg] if e]
+                flat = [r for w in range(g * Wg, (g + 1) * Wg) for r in raw[w]]
+                best = set(sorted(range(len(flat)), key=lambda i: flat[i])[:Wg])
+                keys = sorted(_keys_of_group(raw, words, new, g, Wg, lam))
+                if len(keys) > Wg and keys[Wg] < INF:
+                    gap[t, b, g] = keys[Wg] - keys[Wg - 1]
+                for i, e in enumerate(mine):
+                    decided[t, b, g * Wg + i] = e[4] not in best
+            for s, e in enumerate(new):
+                if e is None or (after_cut and ban_np[b * W + src[e[0]], e[1]]):     # fault: a banned winner leaves its slot empty
+                    continue
+                tok[t + 1, b, s], par[t + 1, b, s] = e[1], src[e[0]]
+                cost[t + 1, b, s] = e[3] if penalty_in_cost else e[2]
+        state = R.beam_gather_state(new_state, par[t + 1], W)
+    return dict(tok=tok, cost=cost, par=par, end=end, decided=decided, member_diff=member_diff, gap=gap, live_g=live_rec)
+
+
+def _keys_of_group(raw, words, new, g, Wg, lam):
+    count = Counter(e[1] for e in new[:g * Wg] if e)
+    return [r + lam * count.get(v, 0) if r < INF else INF for w in range(g * Wg, (g + 1) * Wg) for r, v in zip(raw[w], words[w])]
+
+
+def best_per_group(rec, G, length_penalty=0.0):
+    """per image the first hypothesis of every group that has one (token lists)"""
+    from showtell_amd.beam import group_records, replay_hypotheses
+    per = []
+    for g in range(G):
+        r = group_records(dict(tok=rec["tok"], cost=rec["cost"].astype(np.float32), par=rec["par"], end=rec["end"]), g, G)
+        per.append(replay_hypotheses(r["tok"], r["cost"], r["par"], r["end"], 1, length_penalty=length_penalty))
+    return [[per[g][b][0][0] for g in range(G) if per[g][b]] for b in range(rec["tok"].shape[1])]
+
+
+# ====================================================================================================================
+# one selection in numpy float32, as the kernel's entry point takes it
+# ====================================================================================================================
+
+def hand_fringes(W, G, k, B=40, seed=11):
+    """(tok, cost (B, W), done (B, G), top_p, top_id (B*W, k), descending probability): empty and ended slots, finished groups,
+    p = 0 entries at the end of a list, k + 2 words in all (a word is shared by two and three earlier slots all the time); in
+    the second half of the images costs on a grid of 0.25 and probabilities that are powers of 1/2, so that identical p make
+    exact key ties"""
+    rng = np.random.default_rng(seed + 100 * W + 10 * G + k)
+    tok = rng.integers(3, 9, (B, W)); tok[rng.random((B, W)) < 0.15] = END
+    cost = (rng.random((B, W)) * 4).astype(np.float32)
+    cost[B // 2:] = np.round(cost[B // 2:] * 2) / 4
+    cost[rng.random((B, W)) < 0.15] = np.inf
+    done = (rng.random((B, G)) < 0.15).astype(np.uint8)
+    p = rng.random((B * W, k)).astype(np.float32) / k
+    p[B // 2 * W:] = rng.choice(np.float32([0.25, 0.125, 0.0625]), (B * W - B // 2 * W, k))
+    p = np.sort(p, axis=1)[:, ::-1].copy()
+    p[rng.random(B * W) < 0.1, -1] = 0.0
+    ids = np.stack([rng.permutation(k + 2)[:k] + 3 for _ in range(B * W)]).astype(np.int64)
+    return tok.astype(np.int64), cost, done, p, ids
+
+
+def select_groups_f32(tok, cost, done, top_p, top_id, G, end_id, lam, hist_in=None, hist_len=0):
+    """tok, cost (B, W); done (B, G); top_p, top_id (B*W, k) in DESCENDING probability (the top-k launch's order).  float32 as
+    the rule states it: raw = fl32(cost + fl32(-log(double p))), key = fl32(raw + fl32(lam * n_v)).  Returns dict(tok, cost,
+    par, end, gather, done[, hist])."""
+    B, W = tok.shape
+    k, Wg = top_p.shape[1], W // G
+    grp = np.arange(W) // Wg
+    f32 = np.float32
+    was_done = done.reshape(B, G).astype(bool)
+    occupied = cost < np.inf
+    ended = occupied & (tok == end_id) & ~was_done[:, grp]
+    live = occupied & ~ended & ~was_done[:, grp]
+    finished = was_done | ~live.reshape(B, G, Wg).any(2)
+    live &= ~finished[:, grp]
+    with np.errstate(divide="ignore"):
+        nll = (-np.log(top_p[:, ::-1].astype(np.float64))).astype(f32).reshape(B, W, k)
+    raw = np.where(live[:, :, None], (cost.astype(f32)[:, :, None] + nll).astype(f32), f32(np.inf))
+    words = top_id[:, ::-1].reshape(B, W, k)
+    n_tok, n_cost = np.zeros((B, W), np.int64), np.full((B, W), np.inf, f32)
+    n_par, chosen = np.full((B, W), -1, np.int32), np.full((B, W), -1, np.int64)
+    bb = np.arange(B)[:, None]
+    for g in range(G):
+        sl = slice(g * Wg, (g + 1) * Wg)
+        r, v = raw[:, sl].reshape(B, Wg * k), words[:, sl].reshape(B, Wg * k)
+        n_v = (v[:, :, None] == chosen[:, None, :g * Wg]).sum(2).astype(f32)
+        with np.errstate(invalid="ignore"):
+            key = np.where(r < np.inf, (r + (f32(lam) * n_v).astype(f32)).astype(f32), f32(np.inf))
+        order = np.argsort(key, axis=1, kind="stable")[:, :Wg]
+        ok = key[bb, order] < np.inf
+        n_cost[:, sl] = np.where(ok, r[bb, order], f32(np.inf))
+        n_tok[:, sl] = np.where(ok, v[bb, order], 0)
+        n_par[:, sl] = np.where(ok, g * Wg + order // k, -1)
+        chosen[:, sl] = np.where(ok, v[bb, order], -1)
+    out = dict(tok=n_tok, cost=n_cost, par=n_par, end=ended.astype(np.uint8), done=finished.astype(np.uint8),
+               gather=(np.arange(B)[:, None] * W + np.maximum(n_par, 0)).astype(np.int32))
+    if hist_in is not None:
+        h = np.zeros_like(hist_in).reshape(B, W, -1)
+        src = hist_in.reshape(B, W, -1)[bb, np.maximum(n_par, 0)]
+        h[:, :, :hist_len] = np.where((n_par >= 0)[:, :, None], src[:, :, :hist_len], 0)
+        h[:, :, hist_len] = n_tok
+        out["hist"] = h.reshape(B * W, -1)
+    return out
+
+
+# ====================================================================================================================
+# the walk: a diverse search's records, group by group, against the oracle, teacher-forced on them
+# ====================================================================================================================
+
+def check_group_records(rec, orc, G, lam, cons, nll_abs, tag, hist=None):
+    """K.check_records' method per group.  Exact: fringe 0 holds <start> at cost 0 in slot g*W' of every group and nothing else;
+    harvest flags and done per group; par = -1 exactly where cost = +inf; a parent is a live slot of its child's group; a live
+    group fills every slot for which an unbanned candidate exists; inside a group the keys fl32(cost + fl32(lam * n_v)) ascend, n_v
+    counted from the recorded tokens of the earlier groups at that step; no recorded token is banned for its parent; nothing is
+    harvested before min_length; `hist` [B][W][T+1] equals the paths along par.
+    Within nll_abs (B): the step cost against the oracle's unmasked -log p -- the recorded cost must not contain the penalty.
+    Within sel = 2 nll_abs (C), per group: over the oracle's unbanned candidates of the group's live nodes, keyed with lam * n_v,
+    every chosen candidate is at most sel above the W'-th key and every candidate more than sel below it is chosen.
+    No live slot is left out (asserted).  Returns the measured worst values."""
+    tok, cost, par, end = rec["tok"], rec["cost"], rec["par"], rec["end"].astype(bool)
+    Tn, B, W = end.shape
+    Wg = W // G
+    grp = np.arange(W) // Wg
+    roots = np.arange(W) % Wg == 0
+    m_len, sel = cons[0], 2 * nll_abs
+    f32 = np.float32
+    assert W % G == 0 and tok.shape == cost.shape == par.shape == (Tn + 1, B, W)
+    assert (tok[0][:, roots] == START).all() and (cost[0][:, roots] == 0).all(), (tag, "every group is seeded in its first slot")
+    assert np.isinf(cost[0][:, ~roots]).all() and (tok[0][:, ~roots] == 0).all() and (par[0] == -1).all(), (tag, "fringe 0")
+    done = np.zeros((B, G), bool)
+    m = dict(nll=0.0, chosen=-np.inf, missed=-np.inf, live=0, checked=0, harvested=0)
+    bad = []
+    for t, logp in orc.follow(rec):
+        logp = logp.double()
+        Vn = logp.shape[1]
+        k = min(W, Vn)
+        c_t = cost[t].astype(np.float64)
+        occupied = np.isfinite(c_t)
+        ended = occupied & (tok[t] == END) & ~done[:, grp]
+        assert np.array_equal(end[t], ended), (tag, t, "harvest flags per group")
+        assert not (ended.any() and t <= m_len), (tag, t, "harvested before min_length words")
+        m["harvested"] += int(ended.sum())
+        live = occupied & ~ended & ~done[:, grp]
+        done = done | ~live.reshape(B, G, Wg).any(2)
+        live &= ~done[:, grp]
+        n_c, n_p, n_t = cost[t + 1], par[t + 1], tok[t + 1]
+        filled = n_p >= 0
+        assert np.array_equal(filled, np.isfinite(n_c)), (tag, t, "par = -1 exactly where cost = +inf")
+        assert not filled[done[:, grp]].any(), (tag, t, "a finished group has a non-empty slot")
+        assert (n_p < W).all() and (n_t[~filled] == 0).all(), (tag, t)
+        bb, ww = np.nonzero(filled)
+        pw = n_p[bb, ww].astype(np.int64)
+        assert (pw // Wg == ww // Wg).all(), (tag, t, "a parent lies in its child's group")
+        assert live[bb, pw].all(), (tag, t, "the parent of a non-empty slot is a live slot")
+        assert (n_c[bb, ww] >= cost[t][bb, pw]).all(), (tag, t, "a child costs at least its parent")
+        # n_v of every recorded slot, and the keys of a group in slot order
+        earlier = filled[:, None, :] & (grp[None, None, :] < grp[None, :, None])          # (B, slot, earlier slot)
+        n_rec = ((n_t[:, :, None] == n_t[:, None, :]) & earlier).sum(2)
+        key_rec = np.where(filled, (n_c.astype(f32) + (f32(lam) * n_rec.astype(f32)).astype(f32)).astype(f32), f32(np.inf)).reshape(B, G, Wg)
+        assert (key_rec[:, :, :-1] <= key_rec[:, :, 1:]).all(), (tag, t, "the keys of a group ascend")
+        m["live"] += int(live.sum())
+        ban = K.ban_mask(group_paths(tok, par, t, G), Vn, cons)                            # (B * W, V)
+        n_cand = np.where(live, np.minimum(k, Vn - ban.reshape(B, W, Vn).sum(2)), 0).reshape(B, G, Wg).sum(2)
+        assert np.array_equal(filled.reshape(B, G, Wg).sum(2), np.minimum(Wg, n_cand)), (tag, t, "slots filled")
+        if bb.size == 0:
+            continue
+        assert not ban[bb * W + pw, n_t[bb, ww]].any(), (tag, t, "a recorded token is banned for its parent")
+        # B
+        rows = torch.from_numpy(bb * W + pw)
+        nll_o = -logp[rows, torch.from_numpy(n_t[bb, ww])].numpy()
+        nll_g = n_c[bb, ww].astype(np.float64) - c_t[bb, pw]
+        err = np.abs(nll_g - nll_o) - np.spacing(n_c[bb, ww].astype(f32)).astype(np.float64)
+        m["checked"] += int(bb.size)
+        m["nll"] = max(m["nll"], float(err.max()))
+        if err.max() > nll_abs:
+            i = int(err.argmax())
+            bad.append(("B", t, int(bb[i]), int(ww[i]), float(err[i])))
+        # C: per group, the oracle's unbanned candidates of the group's live nodes with their penalties
+        tv, ti = torch.topk(logp.masked_fill(torch.from_numpy(ban), -np.inf), k, dim=1)
+        tv, ti = tv.view(B, W, k).numpy(), ti.view(B, W, k).numpy()
+        n_o = ((ti[:, :, :, None] == n_t[:, None, None, :]) & earlier[:, :, None, :]).sum(3)      # (B, W, k)
+        cand = np.where(live[:, :, None], c_t[:, :, None] - tv + lam * n_o, np.inf)
+        kth = np.partition(cand.reshape(B, G, Wg * k), Wg - 1, axis=2)[:, :, Wg - 1]              # (B, G)
+        over = (c_t[bb, pw] + nll_o + lam * n_rec[bb, ww]) - kth[bb, ww // Wg]
+        over = np.where(np.isfinite(kth[bb, ww // Wg]), over, -np.inf)                            # fewer than W' candidates: all are chosen
+        m["chosen"] = max(m["chosen"], float(over.max()))
+        ident = np.arange(W)[None, :, None] * Vn + ti
+        chosen = np.where(filled, n_p.astype(np.int64) * Vn + n_t, -1)
+        present = (ident[:, :, :, None] == chosen[:, None, None, :]).any(3)
+        kth_w = np.where(np.isfinite(kth), kth, np.inf)[:, grp]
+        with np.errstate(invalid="ignore"):
+            below = np.where(present | ~np.isfinite(cand), -np.inf, kth_w[:, :, None] - cand)
+        m["missed"] = max(m["missed"], float(below.max()))
+        if over.max() > sel or below.max() > sel:
+            bad.append(("C", t, int(bb[int(over.argmax())]), float(over.max()), float(below.max())))
+    if hist is not None:
+        assert np.array_equal(hist.astype(np.int64), group_paths(tok, par, Tn, G)), (tag, "the kept paths are not the paths along par")
+    excluded = 1.0 - m["checked"] / max(1, int((par[1:] >= 0).sum()))
+    print(f"MEASURE {tag}: |d nll| {m['nll']:.2e} nats; selection: chosen above the W'-th key {m['chosen']:.2e}, missed below it "
+          f"{m['missed']:.2e}; live slots {m['live']}, harvested {m['harvested']}, checked {m['checked']}, excluded share {excluded}")
+    assert excluded == 0.0
+    assert not bad, (tag, nll_abs, bad[:8])
+    return m
+
+
+def floor(name, storage, lam, cons=NONE, Tn=T):
+    """K.floor's method on the diverse free run: |d nll| of the restatement in fp32 against float64 arithmetic, both teacher-forced
+    on the float64 oracle's own diverse search"""
+    G = DECODERS[name][3]
+    o64, o32 = oracle(name, storage), oracle(name, storage, torch.float32)
+    rec = free_run(o64, G, lam, cons, Tn)
+    W = o64.W
+    worst = 0.0
+    for (t, l64), (_, l32) in zip(o64.follow(rec), o32.follow(rec)):
+        bb, ww = np.nonzero(rec["par"][t + 1] >= 0)
+        if bb.size:
+            rows = torch.from_numpy(bb * W + rec["par"][t + 1][bb, ww].astype(np.int64))
+            col = torch.from_numpy(rec["tok"][t + 1][bb, ww])
+            worst = max(worst, float((l64[rows, col].double() - l32[rows, col].double()).abs().max()))
+    return worst
