@@ -629,45 +629,41 @@ int st_rnn_step(const st_rnn_params* p, const void* x, int n, const void* h_in, 
 int st_embedding_rows(const void* emb, const long* ids, void* out, int n, int E, int V, int ldo, int dtype, void* stream);
 int st_gather_state(const void* src, const int* idx, void* dst, int L, int n_src, int n_dst, int H, int dtype, void* stream);
 int st_softmax_topk(const float* logits, int ldl, int n, int V, int k, float* top_p, long* top_id, int raw, void* stream);
-/* One iteration of beam_search.py:69-94 for B images on the device: fringe slots (b, w), w < W, hold (tok, cost) with cost = +inf
- * for an empty slot; top_p/top_id are st_softmax_topk's rows of the B*W slots (k entries, descending).  Writes the new fringe
- * (stable W-best of the node-major, ascending-probability candidate list by float32 cumulative -log p), every new node's parent
- * slot (-1: empty), ended[b][w] = old slot held <end> (to be harvested), gather[b*W+w] = state row of the parent, and updates
- * done[b] (no live node left).  Needs k <= W and W * k <= 64. */
-int st_beam_select(const long* tok, const float* cost, uint8_t* done, const float* top_p, const long* top_id, int B, int W, int k,
-                   long end_id, long* new_tok, float* new_cost, int* parent, uint8_t* ended, int* gather, void* stream);
-/* Constrained beam search: the two kernels a constrained iteration puts in the place of st_softmax_topk and st_beam_select.
- * st_beam_ban_topk: st_softmax_topk (probabilities) with a per-row ban set.  Entry v of a row is banned iff it is one of the
- *   n_suppress ids of `suppress` (device memory; ids outside [0, V) are ignored), or v == end_id and ban_end != 0 (the host's
- *   "fewer than min_length words so far"), or ngram = g >= 1 and appending v to the row's path s_0 .. s_t (hist [n][hist_ld]
- *   int32, t = hist_len - 1, s_0 = <start>; NULL allowed with g == 0) would repeat an n-gram of size g already on it:
+/* st_beam_ban_topk: st_softmax_topk (probabilities) with a per-row ban set, the top-k launch of a beam iteration that has
+ *   something to ban.  Entry v of a row is banned iff it is one of the n_suppress ids of `suppress` (device memory; ids
+ *   outside [0, V) are ignored), or v == end_id and ban_end != 0 (the host's "fewer than min_length words so far"), or
+ *   ngram = g >= 1 and appending v to the row's path s_0 .. s_t (hist [n][hist_ld] int32, t = hist_len - 1, s_0 = <start>;
+ *   NULL allowed with g == 0) would repeat an n-gram of size g already on it:
  *   s[i .. i+g-2] == s[t-g+2 .. t] and s[i+g-1] == v for some 0 <= i <= t-g+1 (g == 1 bans every token of the path).
  *   The softmax still runs over all V entries, so a probability is the model's own; the k results are the k most probable
  *   unbanned entries (lowest index first among equals), and a row with fewer than k of them ends in (p = 0, id = 0) entries.
- *   With an empty ban set the outputs are st_softmax_topk's, bit for bit.
- * st_beam_select_hist: st_beam_select, which also hands every new node its path: hist_out[b*W + rank] = hist_in[b*W + parent]
- *   [0 .. hist_len) followed by the node's token (zeros for an empty slot); hist_in != hist_out, hist_len + 1 <= hist_ld. */
+ *   With an empty ban set the outputs are st_softmax_topk's, bit for bit. */
 #define ST_BEAM_MAX_NGRAM 16
 #define ST_BEAM_MAX_SUPPRESS 64
 #define ST_BEAM_MAX_HIST 64          /* tokens of a path, <start> included: max_length + 1 */
 #define ST_BEAM_MAX_VOCAB 524288     /* bits of the ban map (64 KB of LDS) */
 int st_beam_ban_topk(const float* logits, int ldl, int n, int V, int k, const int* hist, int hist_ld, int hist_len, int ngram,
                      const long* suppress, int n_suppress, long end_id, int ban_end, float* top_p, long* top_id, void* stream);
-int st_beam_select_hist(const long* tok, const float* cost, uint8_t* done, const float* top_p, const long* top_id, int B, int W, int k,
-                        long end_id, long* new_tok, float* new_cost, int* parent, uint8_t* ended, int* gather,
-                        const int* hist_in, int* hist_out, int hist_ld, int hist_len, void* stream);
-/* Diverse (group) beam search (Vijayakumar et al., AAAI 2018): st_beam_select / st_beam_select_hist over G groups of W' = W / G
- * slots, group g = slots g*W' .. (g+1)*W' - 1.  Each group is a search of its own: done [B][G], harvest flags per group, and a
- * parent (an image-wide slot index, as above) always lies in its child's group.  The groups of an image are handled in the order
- * 0 .. G-1 inside the one launch.  A candidate of group g (its W' nodes x their k list entries, node-major, ascending probability)
- * has raw = fl32(cost[w] + fl32(-log(double p))) and key = fl32(raw + fl32(diversity_penalty * n_v)), n_v = the number of occupied
- * slots of the new fringes of groups 0 .. g-1 that hold the candidate's word (a count; <end> counts like any word); raw = +inf
- * stays +inf.  The group's new fringe is its W' best by a stable ranking of key, in rank order; new_cost records raw, never the
- * penalty.  hist_in and hist_out are both NULL (no paths kept) or st_beam_select_hist's.  Needs G >= 1, W % G == 0, a finite
- * diversity_penalty >= 0, k <= W and W * k <= 64.  G = 1 gives st_beam_select's / st_beam_select_hist's outputs bit for bit. */
-int st_beam_select_groups(const long* tok, const float* cost, uint8_t* done, const float* top_p, const long* top_id, int B, int W, int G,
-                          int k, long end_id, float diversity_penalty, long* new_tok, float* new_cost, int* parent, uint8_t* ended,
-                          int* gather, const int* hist_in, int* hist_out, int hist_ld, int hist_len, void* stream);
+/* One iteration of beam_search.py:69-94 for B images on the device, the one fringe selection of every beam search: fringe slots
+ * (b, w), w < W, hold (tok, cost) with cost = +inf for an empty slot; top_p/top_id are the top-k launch's rows of the B*W slots
+ * (k entries, descending).  Writes the new fringe (stable W-best of the node-major, ascending-probability candidate list by
+ * float32 cumulative -log p), every new node's parent slot (-1: empty), ended[b][w] = old slot held <end> (to be harvested),
+ * gather[b*W+w] = state row of the parent, and updates done (no live node left).
+ * Paths: hist_in and hist_out are both NULL (no paths kept) or two different buffers [B*W][hist_ld] int32, and every new node is
+ * handed its path: hist_out[b*W + rank] = hist_in[b*W + parent][0 .. hist_len) followed by the node's token (zeros for an empty
+ * slot); 1 <= hist_len and hist_len + 1 <= min(hist_ld, ST_BEAM_MAX_HIST).
+ * Groups (diverse beam search, Vijayakumar et al., AAAI 2018): the W slots are G groups of W' = W / G slots, group g = slots
+ * g*W' .. (g+1)*W' - 1; G = 1 with diversity_penalty = 0 is the single beam.  Each group is a search of its own: done [B][G],
+ * harvest flags per group, and a parent (an image-wide slot index) always lies in its child's group.  The groups of an image are
+ * handled in the order 0 .. G-1 inside the one launch.  A candidate of group g (its W' nodes x their k list entries, node-major,
+ * ascending probability) has raw = fl32(cost[w] + fl32(-log(double p))) and key = fl32(raw + fl32(diversity_penalty * n_v)),
+ * n_v = the number of occupied slots of the new fringes of groups 0 .. g-1 that hold the candidate's word (a count; <end> counts
+ * like any word); raw = +inf stays +inf.  The group's new fringe is its W' best by a stable ranking of key, in rank order;
+ * new_cost records raw, never the penalty.
+ * Needs G >= 1, W % G == 0, a finite diversity_penalty >= 0, k <= W and W * k <= 64. */
+int st_beam_select(const long* tok, const float* cost, uint8_t* done, const float* top_p, const long* top_id, int B, int W, int G,
+                   int k, long end_id, float diversity_penalty, long* new_tok, float* new_cost, int* parent, uint8_t* ended,
+                   int* gather, const int* hist_in, int* hist_out, int hist_ld, int hist_len, void* stream);
 
 /* Caption sampling (the multinomial counterpart of the max(1)[1] of rnn.py:52 and rnn_attn.py:141).  The kernels hold no
  * random-number generator: the caller supplies one uniform in [0, 1) per row and step.
@@ -827,37 +823,33 @@ int st_attn_sched_inputs(const st_attn_params* p, const float* cnn_feature, int 
  * Rows are fixed (image, slot) pairs b*W + w.  Records use beam.py's layout: rec_tok/rec_cost/rec_par [max_length+1][B][W]
  * (fringe after each iteration; slot 0 of fringe 0 is start_id at cost 0), rec_end [max_length][B][W] (harvest flags),
  * rec_alpha [max_length][B*W][P] fp32 (nullable): the attention map of every row at every iteration, so the extras of node
- * (t >= 1, w) are rec_alpha[t-1][b*W + rec_par[t][b][w]].  The whole search in one call; nothing synchronised inside. */
-size_t st_attn_beam_workspace_bytes(const st_attn_params* p, int B, int W);
+ * (t >= 1, w) are rec_alpha[t-1][b*W + rec_par[t][b][w]].  The whole search in one call; nothing synchronised inside.
+ *
+ * opts (NULL: the plain search -- one group, nothing banned, no paths kept):
+ *   min_length, ngram, suppress, n_suppress: st_beam_ban_topk's rules.  <end> is banned while a node has generated fewer than
+ *     min_length words (iteration t < min_length), ngram = no-repeat n-gram size (0: off, at most ST_BEAM_MAX_NGRAM; needs
+ *     keep_paths), suppress = n_suppress <= ST_BEAM_MAX_SUPPRESS ids in DEVICE memory that never appear.  The ids cannot be
+ *     checked here without a device round trip: ids outside [0, V) are ignored (the Python callers reject them before the call).
+ *     The top-k launch of an iteration is st_beam_ban_topk iff there is something to ban (min_length > 0 || ngram > 0 ||
+ *     n_suppress > 0; then V <= ST_BEAM_MAX_VOCAB), st_softmax_topk otherwise -- the same bits, and no launch more either way.
+ *   keep_paths != 0: every node carries its path through st_beam_select (needs max_length + 1 <= ST_BEAM_MAX_HIST).
+ *   num_groups, diversity_penalty: diverse beam search by st_beam_select's rule over num_groups groups of W / num_groups slots
+ *     (W % num_groups == 0, diversity_penalty finite and >= 0).  Fringe 0 holds start_id at cost 0 in the first slot of every
+ *     group.  The records keep their layout; rec_par holds image-wide slot indices, which lie in the child's group.
+ * Workspace: the plain plan; with keep_paths followed by the two path buffers [B*W][max_length + 1] int32, each padded to a
+ * multiple of 256 bytes (iteration t reads buffer t & 1 and writes the other, so buffer max_length & 1 holds the paths of the
+ * last fringe on return); for num_groups > 1 followed by the B * num_groups done flags.  st_attn_beam_workspace_bytes returns
+ * the size (0 where the layout is undefined: bad B, W, max_length or layer count, num_groups that does not divide W, keep_paths with
+ * max_length + 1 > ST_BEAM_MAX_HIST; the search checks the other options itself) and, through the nullable last_paths_offset, the byte offset of path buffer
+ * max_length & 1 (0 when no paths are kept). */
+typedef struct { int min_length, ngram; const long* suppress; int n_suppress;
+                 int keep_paths; int num_groups; float diversity_penalty; } st_beam_opts;
+size_t st_attn_beam_workspace_bytes(const st_attn_params* p, int B, int W, int max_length, const st_beam_opts* opts,
+                                    size_t* last_paths_offset);
 int st_attn_beam_search(const st_attn_params* p, const float* cnn_feature, int B, int W, int max_length,
                         long start_id, long end_id, void* workspace, size_t workspace_bytes,
-                        long* rec_tok, float* rec_cost, int* rec_par, uint8_t* rec_end, float* rec_alpha, void* stream);
-/* The same search under constraints (st_beam_ban_topk's rules): <end> is banned while a node has generated fewer than
- * min_length words (iteration t < min_length), ngram = no-repeat n-gram size (0: off; needs max_length + 1 <=
- * ST_BEAM_MAX_HIST), suppress = n_suppress ids in DEVICE memory that never appear.  Every iteration runs st_beam_ban_topk and
- * st_beam_select_hist in the place of st_softmax_topk and st_beam_select -- no launch more; the workspace is
- * st_attn_beam_workspace_bytes' plan (its size is the offset of the first) followed by the two path buffers [B*W][max_length + 1]
- * int32, each padded to a multiple of 256 bytes; iteration t reads buffer t & 1 and writes the other, so buffer max_length & 1
- * holds the paths of the last fringe on return (a longer search keeps no paths: st_beam_select, and ngram must be 0).
- * The ids of `suppress` cannot be checked here without a device round trip: ids outside [0, V) are ignored (the Python
- * callers reject them before the call). */
-size_t st_attn_beam_ex_workspace_bytes(const st_attn_params* p, int B, int W, int max_length);
-int st_attn_beam_search_ex(const st_attn_params* p, const float* cnn_feature, int B, int W, int max_length,
-                           long start_id, long end_id, void* workspace, size_t workspace_bytes,
-                           long* rec_tok, float* rec_cost, int* rec_par, uint8_t* rec_end, float* rec_alpha,
-                           int min_length, int ngram, const long* suppress, int n_suppress, void* stream);
-/* Diverse (group) beam search: st_attn_beam_search_ex's loop over num_groups groups of W / num_groups slots (W % num_groups == 0),
- * with st_beam_select_groups' rule for the selection (diversity_penalty finite and >= 0).  Fringe 0 holds start_id at cost 0 in the
- * first slot of every group.  Every iteration runs st_beam_ban_topk (st_softmax_topk when min_length, ngram and n_suppress are
- * all 0: the same bits) and st_beam_select_groups -- the launches of st_attn_beam_search_ex.  The records keep their layout; rec_par holds image-wide slot
- * indices, which lie in the child's group.  The workspace is st_attn_beam_ex_workspace_bytes' plan followed, for num_groups > 1,
- * by the B * num_groups done flags. */
-size_t st_attn_beam_div_workspace_bytes(const st_attn_params* p, int B, int W, int max_length, int num_groups);
-int st_attn_beam_search_div(const st_attn_params* p, const float* cnn_feature, int B, int W, int max_length,
-                            long start_id, long end_id, void* workspace, size_t workspace_bytes,
-                            long* rec_tok, float* rec_cost, int* rec_par, uint8_t* rec_end, float* rec_alpha,
-                            int min_length, int ngram, const long* suppress, int n_suppress, int num_groups, float diversity_penalty,
-                            void* stream);
+                        long* rec_tok, float* rec_cost, int* rec_par, uint8_t* rec_end, float* rec_alpha,
+                        const st_beam_opts* opts, void* stream);
 
 #ifdef __cplusplus
 }

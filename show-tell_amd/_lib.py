@@ -119,6 +119,12 @@ class LossTerms(C.Structure):
                 ("tile_sums", c_p), ("tile_sums_bytes", C.c_size_t)]
 
 
+class BeamOpts(C.Structure):
+    """st_beam_opts: constraints, kept paths and groups of one attention beam search (NULL: the plain search)."""
+    _fields_ = [("min_length", c_i), ("ngram", c_i), ("suppress", c_p), ("n_suppress", c_i), ("keep_paths", c_i), ("num_groups", c_i),
+                ("diversity_penalty", c_f)]
+
+
 class ImageBatchDesc(C.Structure):
     _fields_ = [("src", c_p), ("src_bytes", C.c_int64), ("offset", c_p), ("height", c_p), ("width", c_p), ("flip", c_p), ("batch", c_i),
                 ("max_height", c_i), ("max_width", c_i), ("out_h", c_i), ("out_w", c_i), ("lut", c_p), ("tmp", c_p),
@@ -194,10 +200,8 @@ _SIGS = {
     "st_embedding_rows": ([c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p], c_i),
     "st_gather_state": ([c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p], c_i),
     "st_softmax_topk": ([c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p], c_i),
-    "st_beam_select": ([c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_p, c_p, c_p, c_p, c_p, c_p], c_i),
+    "st_beam_select": ([c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_l, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p], c_i),
     "st_beam_ban_topk": ([c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_i, c_l, c_i, c_p, c_p, c_p], c_i),
-    "st_beam_select_hist": ([c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p], c_i),
-    "st_beam_select_groups": ([c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_l, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p], c_i),
     "st_sample_rows": ([c_p, c_i, c_i, c_i, c_p, c_i, c_f, c_i, c_l, c_p, c_p, c_p, c_i, c_i, c_p, c_p], c_i),
     "st_sample_rows_topp": ([c_p, c_i, c_i, c_i, c_p, c_i, c_f, c_i, c_f, c_l, c_p, c_p, c_p, c_i, c_i, c_p, c_p], c_i),
     "st_rnn_sample_workspace_bytes": ([C.POINTER(RnnParams), c_i], C.c_size_t),
@@ -223,13 +227,8 @@ _SIGS = {
     "st_attn_sample_topp": ([c_p, c_p, c_i, c_i, c_l, c_p, c_f, c_i, c_f, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p], c_i),
     "st_attn_sched_inputs_workspace_bytes": ([c_p, c_i], C.c_size_t),
     "st_attn_sched_inputs": ([c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_f, c_f, c_i, c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p], c_i),
-    "st_attn_beam_workspace_bytes": ([c_p, c_i, c_i], C.c_size_t),
-    "st_attn_beam_search": ([c_p, c_p, c_i, c_i, c_i, c_l, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p, c_p], c_i),
-    "st_attn_beam_ex_workspace_bytes": ([c_p, c_i, c_i, c_i], C.c_size_t),
-    "st_attn_beam_search_ex": ([c_p, c_p, c_i, c_i, c_i, c_l, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_p], c_i),
-    "st_attn_beam_div_workspace_bytes": ([c_p, c_i, c_i, c_i, c_i], C.c_size_t),
-    "st_attn_beam_search_div": ([c_p, c_p, c_i, c_i, c_i, c_l, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_f, c_p],
-                                c_i),
+    "st_attn_beam_workspace_bytes": ([c_p, c_i, c_i, c_i, C.POINTER(BeamOpts), C.POINTER(C.c_size_t)], C.c_size_t),
+    "st_attn_beam_search": ([c_p, c_p, c_i, c_i, c_i, c_l, c_l, c_p, C.c_size_t, c_p, c_p, c_p, c_p, c_p, C.POINTER(BeamOpts), c_p], c_i),
     "st_cross_entropy": ([c_p, c_i, c_p, c_i, c_i, c_i, C.POINTER(LossTerms), c_p, c_p, c_i, c_i, c_f, c_p, c_p], c_i),
     "st_head_workspace_bytes": ([c_i, c_i, c_i, c_i], C.c_size_t),
     "st_linear_bn1d_forward": ([c_p] * 7 + [c_i, c_i, c_i, c_i, c_i, c_f, c_f] + [c_p] * 6, c_i),

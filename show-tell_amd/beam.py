@@ -16,13 +16,13 @@ Constrained search (``min_length``, ``no_repeat_ngram_size``, ``suppress_tokens`
 with the path s_0 .. s_t (s_0 = <start>) is BANNED iff v is suppressed, or v is <end> and t < min_length, or appending v would
 repeat an n-gram of size g already on the path.  Bans act before a row is cut to its k successors (st_beam_ban_topk takes the
 k most probable unbanned entries) and leave the probabilities alone: a cost stays the model's own -log p.  Every node inherits
-its parent's path inside the selection kernel (st_beam_select_hist), so a constrained iteration has the launches of an
-unconstrained one.  ``length_penalty`` a only re-ranks the harvested hypotheses, by cost / n**a.
+its parent's path inside the selection kernel (st_beam_select with its path buffers), so a constrained iteration has the
+launches of an unconstrained one.  ``length_penalty`` a only re-ranks the harvested hypotheses, by cost / n**a.
 
 Diverse (group) beam search (Vijayakumar et al., AAAI 2018; ``num_beam_groups`` = G, ``diversity_penalty`` = lambda): the W slots
 are G groups of W' = W / G, group g = slots g*W' .. (g+1)*W' - 1, each a search of its own (its own root in slot g*W', harvest
 flags, done flag and hypotheses; a parent lies in its child's group).  Every iteration runs the model step and the top-k launch on
-all B*W rows as before; the selection (st_beam_select_groups, one launch) handles the groups of an image in the order 0 .. G-1 and
+all B*W rows as before; the selection (st_beam_select, one launch) handles the groups of an image in the order 0 .. G-1 and
 ranks a candidate (node w, word v) of group g by key = fl32(raw + fl32(lambda * n_v)), raw = fl32(cost[w] + fl32(-log p)), n_v = the
 number of occupied slots of the new fringes of groups 0 .. g-1, chosen in this same iteration, that hold v (a count, <end>
 included).  The recorded cost is raw: the penalty decides the selection of the current step only and is never carried, which is
@@ -46,9 +46,11 @@ ST_BEAM_MAX_NGRAM, ST_BEAM_MAX_SUPPRESS, ST_BEAM_MAX_HIST, ST_BEAM_MAX_VOCAB = 1
 
 
 class BeamConstraints:
-    """The validated constraints of one search; ``active`` says whether the constrained kernels run at all (any of the three set:
-    an empty ``suppress_tokens`` list counts, so ``suppress_tokens=[]`` is the constrained path with an empty ban set).
-    ``keep_paths``: the search carries every node's path (needed for n-gram blocking, kept whenever it fits)."""
+    """The validated constraints of one search; ``active`` says whether the search is a constrained one at all (any of the three
+    set: an empty ``suppress_tokens`` list counts).  ``keep_paths``: the search carries every node's path (needed for n-gram
+    blocking, kept whenever an active search fits it).  ``bans``: there is something to ban, so the top-k launch is
+    st_beam_ban_topk; ``suppress_tokens=[]`` is active and keeps its paths, but bans nothing and runs st_softmax_topk (the same
+    bits)."""
 
     def __init__(self, vocab_size, max_length, min_length=0, no_repeat_ngram_size=0, suppress_tokens=None, length_penalty=0.0):
         m, g = int(min_length), int(no_repeat_ngram_size)
@@ -75,6 +77,7 @@ class BeamConstraints:
         if self.active and vocab_size > ST_BEAM_MAX_VOCAB:
             raise ValueError(f"constrained beam search needs a vocabulary of at most {ST_BEAM_MAX_VOCAB} entries (got {vocab_size})")
         self.keep_paths = self.active and max_length + 1 <= ST_BEAM_MAX_HIST
+        self.bans = m > 0 or g > 0 or bool(sup)
 
     def suppress_on(self, device):
         """(device tensor or None, count): the suppress list as st_beam_ban_topk takes it, uploaded once per search."""
@@ -262,10 +265,10 @@ def beam_search_records(rnn, cnn_feature, beam_width=4, max_length=50, start_id=
                         suppress_tokens=None, num_beam_groups=1, diversity_penalty=0.0):
     """The device loop of ``beam_search`` on its own: every iteration's fringe over fixed (image, slot) rows, as numpy arrays
     dict(tok, cost, par [max_length+1][B][W], end [max_length][B][W]) -- what ``replay_hypotheses`` reads.  Needs
-    beam_width * min(beam_width, V) <= 64 (st_beam_select).  Under constraints the loop runs st_beam_ban_topk and
-    st_beam_select_hist in their place, and the records gain hist [B][W][max_length+1] int32: the path of every slot of the last
-    fringe, as the search itself kept it.  With ``num_beam_groups`` = G > 1 the selection is st_beam_select_groups: the layout
-    stays, slots g*W/G .. (g+1)*W/G - 1 are group g (``group_records`` cuts one out), `par` holds image-wide slot indices."""
+    beam_width * min(beam_width, V) <= 64 (st_beam_select).  With something to ban the top-k launch is st_beam_ban_topk; a
+    constrained search hands st_beam_select its path buffers, and the records gain hist [B][W][max_length+1] int32: the path of
+    every slot of the last fringe, as the search itself kept it.  With ``num_beam_groups`` = G > 1 the layout stays, slots
+    g*W/G .. (g+1)*W/G - 1 are group g (``group_records`` cuts one out), `par` holds image-wide slot indices."""
     G, lam = check_groups(beam_width, rnn.vocab_size, num_beam_groups, diversity_penalty)
     k = min(beam_width, rnn.vocab_size)
     bc = BeamConstraints(rnn.vocab_size, max_length, min_length, no_repeat_ngram_size, suppress_tokens)
@@ -287,35 +290,24 @@ def beam_search_records(rnn, cnn_feature, beam_width=4, max_length=50, start_id=
         gidx = torch.empty(n, device=dev, dtype=torch.int32)
         tp = torch.empty(n, k, device=dev, dtype=torch.float32)
         ti = torch.empty(n, k, device=dev, dtype=torch.long)
-        hist = None
-        if bc.active:
-            sup, n_sup = bc.suppress_on(dev)
-            if bc.keep_paths:                                                         # two buffers: a fringe reads one, writes the other
-                ld = max_length + 1
-                hist = torch.zeros(2, n, ld, device=dev, dtype=torch.int32); hist[0, :, 0] = start_id
-                hp = (_cp(hist[0]), _cp(hist[1]))
+        hist, hp, ld = None, (None, None), 0
+        sup, n_sup = bc.suppress_on(dev)
+        if bc.keep_paths:                                                             # two buffers: a fringe reads one, writes the other
+            ld = max_length + 1
+            hist = torch.zeros(2, n, ld, device=dev, dtype=torch.int32); hist[0, :, 0] = start_id
+            hp = (_cp(hist[0]), _cp(hist[1]))
         for t in range(max_length):                                                   # beam_search.py:69
             x = st.embed(tok.view(-1))
             logits, new_state = st.step(x, state)
             ntok, ncost = rec_tok[t + 1], rec_cost[t + 1]
-            if not bc.active:
+            if not bc.bans:
                 check(lib().st_softmax_topk(_cp(logits), st.Vp, n, st.V, k, _cp(tp), _cp(ti), 0, _stream()), "st_softmax_topk")
             else:                                                                     # the path of a fringe-t node has t + 1 tokens
-                check(lib().st_beam_ban_topk(_cp(logits), st.Vp, n, st.V, k, hp[t & 1] if hist is not None else None,
-                                             ld if hist is not None else 0, t + 1, bc.ngram, _cp(sup), n_sup, end_id,
+                check(lib().st_beam_ban_topk(_cp(logits), st.Vp, n, st.V, k, hp[t & 1], ld, t + 1, bc.ngram, _cp(sup), n_sup, end_id,
                                              int(t < bc.min_length), _cp(tp), _cp(ti), _stream()), "st_beam_ban_topk")
-            if G > 1:
-                check(lib().st_beam_select_groups(_cp(tok), _cp(cost), _cp(done), _cp(tp), _cp(ti), B, W, G, k, end_id, lam, _cp(ntok),
-                                                  _cp(ncost), _cp(rec_par[t + 1]), _cp(rec_end[t]), _cp(gidx),
-                                                  hp[t & 1] if hist is not None else None, hp[(t + 1) & 1] if hist is not None else None,
-                                                  ld if hist is not None else 0, t + 1, _stream()), "st_beam_select_groups")
-            elif hist is None:
-                check(lib().st_beam_select(_cp(tok), _cp(cost), _cp(done), _cp(tp), _cp(ti), B, W, k, end_id, _cp(ntok), _cp(ncost),
-                                           _cp(rec_par[t + 1]), _cp(rec_end[t]), _cp(gidx), _stream()), "st_beam_select")
-            else:
-                check(lib().st_beam_select_hist(_cp(tok), _cp(cost), _cp(done), _cp(tp), _cp(ti), B, W, k, end_id, _cp(ntok), _cp(ncost),
-                                                _cp(rec_par[t + 1]), _cp(rec_end[t]), _cp(gidx), hp[t & 1], hp[(t + 1) & 1], ld, t + 1,
-                                                _stream()), "st_beam_select_hist")
+            check(lib().st_beam_select(_cp(tok), _cp(cost), _cp(done), _cp(tp), _cp(ti), B, W, G, k, end_id, lam, _cp(ntok), _cp(ncost),
+                                       _cp(rec_par[t + 1]), _cp(rec_end[t]), _cp(gidx), hp[t & 1], hp[(t + 1) & 1], ld, t + 1, _stream()),
+                  "st_beam_select")
             state = st.gather(new_state, gidx)
             tok, cost = ntok, ncost
         rec = dict(tok=rec_tok.cpu().numpy(), cost=rec_cost.cpu().numpy(), par=rec_par.cpu().numpy(), end=rec_end.cpu().numpy())

@@ -480,10 +480,10 @@ extern "C" int st_attn_sched_inputs(const st_attn_params* p, const float* cnn_fe
 // Fixed (image, slot) rows b*W + w as in beam.py: every iteration is one set of launches over the B*W rows and the fringe
 // selection runs on the device (st_beam_select), so the caller reads the records back once and replays the Node bookkeeping.
 namespace {
-// hist_ld > 0 (the constrained search): the two path buffers follow the unconstrained plan, whose offsets and total stay as they are
-// G > 1 (the diverse search): its B * G done flags follow the constrained plan, whose offsets stay as they are
+// hist_ld > 0 (keep_paths): the two path buffers follow the plain plan, whose offsets and total stay as they are
+// G > 1 (the diverse search): its B * G done flags follow the path buffers, whose offsets stay as they are
 struct BPlan : AttnPrep { int n, k; size_t h[2], c[2], x, z, att2, logits, tp, ti, gidx, slot, done, alpha, hist[2], done_g, total; };
-BPlan make_bplan(const st_attn_params* p, int B, int W, int hist_ld = 0, int G = 1) {
+BPlan make_bplan(const st_attn_params* p, int B, int W, int hist_ld, int G) {
   const st_rnn_params& r = p->rnn;
   const size_t es = st_dtype_size(r.dtype);
   BPlan q; Arena ar;
@@ -505,31 +505,15 @@ BPlan make_bplan(const st_attn_params* p, int B, int W, int hist_ld = 0, int G =
   return q;
 }
 
-// what st_attn_beam_search_ex adds to the search
-struct BeamLimits { int min_length, ngram; const long* suppress; int n_suppress; };
-// what st_attn_beam_search_div adds to that
-struct BeamGroups { int G; float penalty; };
+// st_beam_opts with the defaults of a NULL pointer: the plain search
+st_beam_opts beam_opts(const st_beam_opts* o) { return o ? *o : st_beam_opts{0, 0, nullptr, 0, 0, 1, 0.f}; }
 
-// slot (b, w) <- image b; fringe 0 = the root alone: slot 0 holds start_id at cost 0, the others are empty (cost +inf)
+// slot (b, w) <- image b; fringe 0 = the roots alone: the first slot of every group of Wg slots (Wg = W with one group) holds
+// start_id at cost 0, the others are empty (cost +inf); one done flag per (image, group)
 // (hist0, nullable: every row's path starts with start_id)
-__global__ void beam_seed_kernel(int B, int W, long start_id, int* __restrict__ slot, long* __restrict__ tok0, float* __restrict__ cost0,
-                                 int* __restrict__ par0, uint8_t* __restrict__ done, int* __restrict__ hist0, int hist_ld) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < B * W) {
-    if (hist0) hist0[(long)i * hist_ld] = (int)start_id;
-    const int w = i % W;
-    slot[i] = i / W;
-    tok0[i] = w == 0 ? start_id : 0;
-    cost0[i] = w == 0 ? 0.f : INFINITY;
-    par0[i] = -1;
-  }
-  if (i < B) done[i] = 0;
-}
-
-// the seed of the diverse search: the root in the first slot of every group of Wg slots, one done flag per (image, group)
-__global__ void beam_seed_groups_kernel(int B, int W, int Wg, long start_id, int* __restrict__ slot, long* __restrict__ tok0,
-                                        float* __restrict__ cost0, int* __restrict__ par0, uint8_t* __restrict__ done, int* __restrict__ hist0,
-                                        int hist_ld) {
+__global__ void beam_seed_kernel(int B, int W, int Wg, long start_id, int* __restrict__ slot, long* __restrict__ tok0,
+                                 float* __restrict__ cost0, int* __restrict__ par0, uint8_t* __restrict__ done, int* __restrict__ hist0,
+                                 int hist_ld) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < B * W) {
     if (hist0) hist0[(long)i * hist_ld] = (int)start_id;
@@ -541,37 +525,46 @@ __global__ void beam_seed_groups_kernel(int B, int W, int Wg, long start_id, int
   }
   if (i < B * (W / Wg)) done[i] = 0;
 }
+}  // namespace
 
-// The search of st_attn_beam_search (lim == nullptr) and st_attn_beam_search_ex: one loop, in which the constrained form swaps
-// st_softmax_topk / st_beam_select for st_beam_ban_topk / st_beam_select_hist.  st_attn_beam_search_div (div != nullptr, with lim):
-// the same loop with a seed in every group, B * G done flags and st_beam_select_groups for the selection.
-int attn_beam_run(const st_attn_params* p, const float* cnn_feature, int B, int W, int max_length, long start_id, long end_id,
-                  void* workspace, size_t workspace_bytes, long* rec_tok, float* rec_cost, int* rec_par, uint8_t* rec_end, float* rec_alpha,
-                  const BeamLimits* lim, void* stream, const char* who, const BeamGroups* div = nullptr) {
-  if (check_common(p, nullptr, who)) return 1;
-  ST_CHECK(cnn_feature && workspace && rec_tok && rec_cost && rec_par && rec_end && B > 0, "%s: bad arguments", who);
-  ST_CHECK(W >= 1 && W <= 8, "%s: beam width must be 1..8 (got %d)", who, W);
-  ST_CHECK(max_length >= 1, "%s: max_length must be >= 1 (got %d)", who, max_length);
+extern "C" size_t st_attn_beam_workspace_bytes(const st_attn_params* p, int B, int W, int max_length, const st_beam_opts* opts,
+                                               size_t* last_paths_offset) {
+  const st_beam_opts o = beam_opts(opts);
+  if (last_paths_offset) *last_paths_offset = 0;
+  if (!p || B <= 0 || W < 1 || W > 8 || max_length < 1 || o.num_groups < 1 || W % o.num_groups != 0 || !layers_ok(p)) return 0;
+  if (o.keep_paths && max_length + 1 > ST_BEAM_MAX_HIST) return 0;
+  const BPlan q = make_bplan(p, B, W, o.keep_paths ? max_length + 1 : 0, o.num_groups);
+  if (last_paths_offset && o.keep_paths) *last_paths_offset = q.hist[max_length & 1];
+  return q.total;
+}
+
+extern "C" int st_attn_beam_search(const st_attn_params* p, const float* cnn_feature, int B, int W, int max_length,
+                                   long start_id, long end_id, void* workspace, size_t workspace_bytes,
+                                   long* rec_tok, float* rec_cost, int* rec_par, uint8_t* rec_end, float* rec_alpha,
+                                   const st_beam_opts* opts, void* stream) {
+  if (check_common(p, nullptr, "st_attn_beam_search")) return 1;
+  ST_CHECK(cnn_feature && workspace && rec_tok && rec_cost && rec_par && rec_end && B > 0, "st_attn_beam_search: bad arguments");
+  ST_CHECK(W >= 1 && W <= 8, "st_attn_beam_search: beam width must be 1..8 (got %d)", W);
+  ST_CHECK(max_length >= 1, "st_attn_beam_search: max_length must be >= 1 (got %d)", max_length);
   const st_rnn_params& r = p->rnn;
-  ST_CHECK(r.w_lin && r.b_lin, "%s: null vocabulary projection", who);
-  // the paths are kept whenever they fit (n-gram blocking needs them; without them the selection is st_beam_select's)
-  const int hist_ld = lim && max_length + 1 <= ST_BEAM_MAX_HIST ? max_length + 1 : 0;
-  if (lim) {
-    ST_CHECK(lim->min_length >= 0, "%s: min_length must be >= 0 (got %d)", who, lim->min_length);
-    ST_CHECK(lim->ngram >= 0 && lim->ngram <= ST_BEAM_MAX_NGRAM, "%s: no_repeat_ngram_size must be 0..%d (got %d)", who, ST_BEAM_MAX_NGRAM, lim->ngram);
-    ST_CHECK(lim->n_suppress >= 0 && lim->n_suppress <= ST_BEAM_MAX_SUPPRESS && (lim->n_suppress == 0 || lim->suppress),
-             "%s: at most %d suppressed tokens (got %d)", who, ST_BEAM_MAX_SUPPRESS, lim->n_suppress);
-    ST_CHECK(lim->ngram == 0 || hist_ld > 0, "%s: n-gram blocking needs max_length + 1 <= %d (got %d)", who, ST_BEAM_MAX_HIST, max_length + 1);
-    ST_CHECK(r.V <= ST_BEAM_MAX_VOCAB, "%s: V=%d exceeds the ban bitmap's %d entries", who, r.V, ST_BEAM_MAX_VOCAB);
-  }
-  if (div) {
-    ST_CHECK(lim, "%s: the diverse search takes its constraints", who);
-    ST_CHECK(div->G >= 1 && W % div->G == 0, "%s: the %d slots do not split into %d groups", who, W, div->G);
-    ST_CHECK(div->penalty >= 0.f && div->penalty < INFINITY, "%s: diversity_penalty must be finite and >= 0 (got %g)", who, (double)div->penalty);
-  }
-  const int G = div ? div->G : 1;
+  ST_CHECK(r.w_lin && r.b_lin, "st_attn_beam_search: null vocabulary projection");
+  const st_beam_opts o = beam_opts(opts);
+  ST_CHECK(o.min_length >= 0, "st_attn_beam_search: min_length must be >= 0 (got %d)", o.min_length);
+  ST_CHECK(o.ngram >= 0 && o.ngram <= ST_BEAM_MAX_NGRAM, "st_attn_beam_search: no_repeat_ngram_size must be 0..%d (got %d)", ST_BEAM_MAX_NGRAM, o.ngram);
+  ST_CHECK(o.n_suppress >= 0 && o.n_suppress <= ST_BEAM_MAX_SUPPRESS && (o.n_suppress == 0 || o.suppress),
+           "st_attn_beam_search: at most %d suppressed tokens (got %d)", ST_BEAM_MAX_SUPPRESS, o.n_suppress);
+  ST_CHECK(!o.keep_paths || max_length + 1 <= ST_BEAM_MAX_HIST, "st_attn_beam_search: keeping the paths needs max_length + 1 <= %d (got %d)",
+           ST_BEAM_MAX_HIST, max_length + 1);
+  ST_CHECK(o.ngram == 0 || o.keep_paths, "st_attn_beam_search: n-gram blocking needs keep_paths");
+  ST_CHECK(o.num_groups >= 1 && W % o.num_groups == 0, "st_attn_beam_search: the %d slots do not split into %d groups", W, o.num_groups);
+  ST_CHECK(o.diversity_penalty >= 0.f && o.diversity_penalty < INFINITY, "st_attn_beam_search: diversity_penalty must be finite and >= 0 (got %g)",
+           (double)o.diversity_penalty);
+  // the ban kernel runs iff there is something to ban; an empty ban set gives st_softmax_topk's bits
+  const bool bans = o.min_length > 0 || o.ngram > 0 || o.n_suppress > 0;
+  ST_CHECK(!bans || r.V <= ST_BEAM_MAX_VOCAB, "st_attn_beam_search: V=%d exceeds the ban bitmap's %d entries", r.V, ST_BEAM_MAX_VOCAB);
+  const int hist_ld = o.keep_paths ? max_length + 1 : 0, G = o.num_groups;
   const BPlan q = make_bplan(p, B, W, hist_ld, G);
-  ST_CHECK(workspace_bytes >= q.total, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, q.total);
+  ST_CHECK(workspace_bytes >= q.total, "st_attn_beam_search: workspace too small (%zu < %zu)", workspace_bytes, q.total);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   char* ws = reinterpret_cast<char*>(workspace);
   const int dt = r.dtype, H = r.H, E = r.E, L = r.L, P = p->P, A = p->A, F = p->F, Vp = st_up8(r.V), n = q.n, k = q.k;
@@ -587,12 +580,8 @@ int attn_beam_run(const st_attn_params* p, const float* cnn_feature, int B, int 
 
   if (prepare(p, cnn_feature, B, ws, q, stream)) return 1;
   int* hist[2] = {reinterpret_cast<int*>(ws + q.hist[0]), reinterpret_cast<int*>(ws + q.hist[1])};
-  if (!div)
-    hipLaunchKernelGGL(beam_seed_kernel, dim3((n + 255) / 256), dim3(256), 0, st, B, W, start_id, slot, rec_tok, rec_cost, rec_par, done,
-                       hist_ld ? hist[0] : nullptr, hist_ld);
-  else
-    hipLaunchKernelGGL(beam_seed_groups_kernel, dim3((n + 255) / 256), dim3(256), 0, st, B, W, W / G, start_id, slot, rec_tok, rec_cost, rec_par,
-                       done, hist_ld ? hist[0] : nullptr, hist_ld);
+  hipLaunchKernelGGL(beam_seed_kernel, dim3((n + 255) / 256), dim3(256), 0, st, B, W, W / G, start_id, slot, rec_tok, rec_cost, rec_par, done,
+                     hist_ld ? hist[0] : nullptr, hist_ld);
   ST_LAUNCH_CHECK();
   // h0 (c0) repeated over the layers (rnn_attn.py:62), then scattered to the slots of its image
   if (replicate_rows_launch(ws + q.h0, ws + q.h[1], (long)B * H, L, dt, st)) return 1;
@@ -615,65 +604,14 @@ int attn_beam_run(const st_attn_params* p, const float* cnn_feature, int B, int 
     float* ncost = rec_cost + (size_t)(t + 1) * n;
     int* npar = rec_par + (size_t)(t + 1) * n;
     uint8_t* end_t = rec_end + (size_t)t * n;
-    // the top-k launch: with nothing to ban (always so without lim; the diverse search may come with empty limits) the plain one
-    const bool bans = lim && (!div || lim->min_length > 0 || lim->ngram > 0 || lim->n_suppress > 0);
     if (!bans) {
       if (st_softmax_topk(logits, Vp, n, r.V, k, tp, ti, 0, stream)) return 1;
-    } else if (st_beam_ban_topk(logits, Vp, n, r.V, k, hist_ld ? hist[t & 1] : nullptr, hist_ld, t + 1, lim->ngram, lim->suppress, lim->n_suppress,
-                                end_id, t < lim->min_length, tp, ti, stream)) return 1;   // the path of fringe t has t + 1 tokens
-    // the selection: paths are inherited whenever they are kept (hist_ld > 0, which needs lim)
-    if (div) {
-      if (st_beam_select_groups(tok, cost, done, tp, ti, B, W, G, k, end_id, div->penalty, ntok, ncost, npar, end_t, gidx,
-                                hist_ld ? hist[t & 1] : nullptr, hist_ld ? hist[(t + 1) & 1] : nullptr, hist_ld, t + 1, stream)) return 1;
-    } else if (!hist_ld) {
-      if (st_beam_select(tok, cost, done, tp, ti, B, W, k, end_id, ntok, ncost, npar, end_t, gidx, stream)) return 1;
-    } else if (st_beam_select_hist(tok, cost, done, tp, ti, B, W, k, end_id, ntok, ncost, npar, end_t, gidx, hist[t & 1], hist[(t + 1) & 1], hist_ld,
-                                   t + 1, stream)) return 1;
+    } else if (st_beam_ban_topk(logits, Vp, n, r.V, k, hist_ld ? hist[t & 1] : nullptr, hist_ld, t + 1, o.ngram, o.suppress, o.n_suppress,
+                                end_id, t < o.min_length, tp, ti, stream)) return 1;       // the path of fringe t has t + 1 tokens
+    if (st_beam_select(tok, cost, done, tp, ti, B, W, G, k, end_id, o.diversity_penalty, ntok, ncost, npar, end_t, gidx,
+                       hist_ld ? hist[t & 1] : nullptr, hist_ld ? hist[(t + 1) & 1] : nullptr, hist_ld, t + 1, stream)) return 1;
     if (st_gather_state(ws + q.h[1], gidx, ws + q.h[0], L, n, n, H, dt, stream)) return 1;   // a child inherits its parent's state
     if (lstm && st_gather_state(ws + q.c[1], gidx, ws + q.c[0], L, n, n, H, dt, stream)) return 1;
   }
   return 0;
-}
-}  // namespace
-
-extern "C" size_t st_attn_beam_workspace_bytes(const st_attn_params* p, int B, int W) {
-  if (!p || B <= 0 || W < 1 || W > 8 || !layers_ok(p)) return 0;
-  return make_bplan(p, B, W).total;
-}
-
-extern "C" int st_attn_beam_search(const st_attn_params* p, const float* cnn_feature, int B, int W, int max_length,
-                                   long start_id, long end_id, void* workspace, size_t workspace_bytes,
-                                   long* rec_tok, float* rec_cost, int* rec_par, uint8_t* rec_end, float* rec_alpha, void* stream) {
-  return attn_beam_run(p, cnn_feature, B, W, max_length, start_id, end_id, workspace, workspace_bytes, rec_tok, rec_cost, rec_par, rec_end,
-                       rec_alpha, nullptr, stream, "st_attn_beam_search");
-}
-
-extern "C" size_t st_attn_beam_ex_workspace_bytes(const st_attn_params* p, int B, int W, int max_length) {
-  if (!p || B <= 0 || W < 1 || W > 8 || max_length < 1 || !layers_ok(p)) return 0;
-  return make_bplan(p, B, W, max_length + 1 <= ST_BEAM_MAX_HIST ? max_length + 1 : 0).total;
-}
-
-extern "C" int st_attn_beam_search_ex(const st_attn_params* p, const float* cnn_feature, int B, int W, int max_length,
-                                      long start_id, long end_id, void* workspace, size_t workspace_bytes,
-                                      long* rec_tok, float* rec_cost, int* rec_par, uint8_t* rec_end, float* rec_alpha,
-                                      int min_length, int ngram, const long* suppress, int n_suppress, void* stream) {
-  const BeamLimits lim = {min_length, ngram, suppress, n_suppress};
-  return attn_beam_run(p, cnn_feature, B, W, max_length, start_id, end_id, workspace, workspace_bytes, rec_tok, rec_cost, rec_par, rec_end,
-                       rec_alpha, &lim, stream, "st_attn_beam_search_ex");
-}
-
-extern "C" size_t st_attn_beam_div_workspace_bytes(const st_attn_params* p, int B, int W, int max_length, int num_groups) {
-  if (!p || B <= 0 || W < 1 || W > 8 || max_length < 1 || num_groups < 1 || W % num_groups != 0 || !layers_ok(p)) return 0;
-  return make_bplan(p, B, W, max_length + 1 <= ST_BEAM_MAX_HIST ? max_length + 1 : 0, num_groups).total;
-}
-
-extern "C" int st_attn_beam_search_div(const st_attn_params* p, const float* cnn_feature, int B, int W, int max_length,
-                                       long start_id, long end_id, void* workspace, size_t workspace_bytes,
-                                       long* rec_tok, float* rec_cost, int* rec_par, uint8_t* rec_end, float* rec_alpha,
-                                       int min_length, int ngram, const long* suppress, int n_suppress, int num_groups, float diversity_penalty,
-                                       void* stream) {
-  const BeamLimits lim = {min_length, ngram, suppress, n_suppress};
-  const BeamGroups div = {num_groups, diversity_penalty};
-  return attn_beam_run(p, cnn_feature, B, W, max_length, start_id, end_id, workspace, workspace_bytes, rec_tok, rec_cost, rec_par, rec_end,
-                       rec_alpha, &lim, stream, "st_attn_beam_search_div", &div);
 }

@@ -757,104 +757,29 @@ extern "C" int st_beam_ban_topk(const float* logits, int ldl, int n, int V, int 
 // Outputs: new tok / cost, the parent slot of every new node, gather[b*W + w] = row of the parent's recurrent state.
 // HIST: every new node also inherits its parent's path: hist_out[b*W + rank] = hist_in[b*W + parent][0 .. hist_len) + its own token
 // (rows of hist_ld int32; an empty slot gets zeros), copied by the image's 64 threads -- what st_beam_ban_topk reads next iteration.
-template <bool HIST>
-__global__ __launch_bounds__(64) void beam_select_kernel(const long* __restrict__ tok, const float* __restrict__ cost, uint8_t* __restrict__ done,
-                                                         const float* __restrict__ top_p, const long* __restrict__ top_id, int W, int k, long end_id,
-                                                         long* __restrict__ new_tok, float* __restrict__ new_cost, int* __restrict__ parent,
-                                                         uint8_t* __restrict__ ended_rec, int* __restrict__ gather,
-                                                         const int* __restrict__ hist_in, int* __restrict__ hist_out, int hist_ld, int hist_len) {
-  __shared__ float cc[64];
-  __shared__ int any_live;
-  __shared__ int new_par[64], new_word[64];                  // HIST: parent slot (-1: empty) and token of the new slots
-  const int b = blockIdx.x, c = threadIdx.x;
-  const bool was_done = done[b] != 0;
-  if (c == 0) any_live = 0;
-  __syncthreads();
-  if (c < W) {
-    const bool occupied = cost[b * W + c] < INFINITY;
-    const bool ended = occupied && tok[b * W + c] == end_id && !was_done;
-    ended_rec[b * W + c] = ended ? 1 : 0;
-    if (occupied && !ended && !was_done) any_live = 1;
-  }
-  __syncthreads();
-  const bool finished = was_done || !any_live;
-  if (c == 0) done[b] = finished ? 1 : 0;
-  float my = INFINITY;
-  const int n = W * k;
-  if (c < n && !finished) {
-    const int w = c / k, j = c - w * k;                      // successor j in ascending probability = top-k entry k-1-j
-    const float cw = cost[b * W + w];
-    if (cw < INFINITY && tok[b * W + w] != end_id)
-      my = cw + (float)(-log((double)top_p[(long)(b * W + w) * k + (k - 1 - j)]));
-  }
-  cc[c] = c < n ? my : INFINITY;
-  __syncthreads();
-  if (c < n) {
-    int rank = 0;                                            // stable: ties keep candidate order
-    for (int o = 0; o < n; ++o) rank += (cc[o] < my || (cc[o] == my && o < c)) ? 1 : 0;
-    if (rank < W) {
-      const int w = c / k, j = c - w * k;
-      const bool ok = my < INFINITY;
-      new_cost[b * W + rank] = ok ? my : INFINITY;
-      new_tok[b * W + rank] = ok ? top_id[(long)(b * W + w) * k + (k - 1 - j)] : 0;
-      parent[b * W + rank] = ok ? w : -1;
-      gather[b * W + rank] = b * W + (ok ? w : 0);
-      if constexpr (HIST) { new_par[rank] = ok ? w : -1; new_word[rank] = ok ? (int)top_id[(long)(b * W + w) * k + (k - 1 - j)] : 0; }
-    }
-  }
-  if constexpr (HIST) {
-    __syncthreads();
-    const int len = hist_len + 1;
-    for (int e = c; e < W * len; e += 64) {
-      const int r = e / len, pos = e - r * len, par = new_par[r];
-      hist_out[(long)(b * W + r) * hist_ld + pos] = pos == hist_len ? new_word[r] : (par >= 0 ? hist_in[(long)(b * W + par) * hist_ld + pos] : 0);
-    }
-  }
-}
-
-extern "C" int st_beam_select(const long* tok, const float* cost, uint8_t* done, const float* top_p, const long* top_id, int B, int W, int k,
-                              long end_id, long* new_tok, float* new_cost, int* parent, uint8_t* ended, int* gather, void* stream) {
-  ST_CHECK(tok && cost && done && top_p && top_id && new_tok && new_cost && parent && ended && gather, "st_beam_select: null pointer");
-  ST_CHECK(B > 0 && W >= 1 && k >= 1 && k <= W && W * k <= 64, "st_beam_select: need 1 <= k <= W and W * k <= 64 (got W=%d k=%d)", W, k);
-  hipLaunchKernelGGL(beam_select_kernel<false>, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), tok, cost, done, top_p, top_id, W, k,
-                     end_id, new_tok, new_cost, parent, ended, gather, nullptr, nullptr, 0, 0);
-  ST_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int st_beam_select_hist(const long* tok, const float* cost, uint8_t* done, const float* top_p, const long* top_id, int B, int W, int k,
-                                   long end_id, long* new_tok, float* new_cost, int* parent, uint8_t* ended, int* gather,
-                                   const int* hist_in, int* hist_out, int hist_ld, int hist_len, void* stream) {
-  ST_CHECK(tok && cost && done && top_p && top_id && new_tok && new_cost && parent && ended && gather && hist_in && hist_out && hist_in != hist_out,
-           "st_beam_select_hist: null pointer (or hist_in == hist_out)");
-  ST_CHECK(B > 0 && W >= 1 && k >= 1 && k <= W && W * k <= 64, "st_beam_select_hist: need 1 <= k <= W and W * k <= 64 (got W=%d k=%d)", W, k);
-  ST_CHECK(hist_len >= 1 && hist_len + 1 <= hist_ld && hist_len + 1 <= ST_BEAM_MAX_HIST,
-           "st_beam_select_hist: need 1 <= hist_len and hist_len + 1 <= min(hist_ld, %d) (got %d, ld %d)", ST_BEAM_MAX_HIST, hist_len, hist_ld);
-  hipLaunchKernelGGL(beam_select_kernel<true>, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), tok, cost, done, top_p, top_id, W, k,
-                     end_id, new_tok, new_cost, parent, ended, gather, hist_in, hist_out, hist_ld, hist_len);
-  ST_LAUNCH_CHECK();
-  return 0;
-}
-
+//
 // Diverse (group) beam search, Vijayakumar et al. 2018: the W slots of an image are G groups of W' = W / G, group g = slots
-// g*W' .. (g+1)*W' - 1, each a search of its own (its own harvest flags, its own done[b*G + g], parents inside the group).
-// All W*k raw costs are formed at once, as beam_select_kernel forms them.  Then the groups run in the order 0 .. G-1: a candidate
+// g*W' .. (g+1)*W' - 1, each a search of its own (its own harvest flags, its own done[b*G + g], parents inside the group); G = 1 is
+// the search above.  All W*k raw costs are formed at once.  Then the groups run in the order 0 .. G-1: a candidate
 // (node w, word v) of group g gets key = fl32(raw + fl32(lambda * n_v)), n_v = the number of occupied new slots of groups 0 .. g-1
 // that hold v (a count; chosen[] in LDS, -1 = empty), and the group's W' best by a stable ranking of key fill its slots in rank
-// order.  The recorded cost is raw: the penalty decides this step's selection only.  The keys of a group are ranked across lanes
-// (one wave), so one barrier closes each group: it publishes the group's words to the next.  G = 1: beam_select_kernel's outputs.
+// order.  The recorded cost is raw: the penalty decides this step's selection only.  The keys of a group are ranked over an LDS
+// array (a loop the compiler unrolls into wide LDS reads; lane reads would cost one crossbar latency per key), so a group has two
+// barriers: one publishes its keys, one its words to the next group and to the HIST copy.  With G = 1 that is the barrier count
+// of a single-beam selection.
 template <bool HIST>
-__global__ __launch_bounds__(64) void beam_select_groups_kernel(const long* __restrict__ tok, const float* __restrict__ cost, uint8_t* __restrict__ done,
-                                                                const float* __restrict__ top_p, const long* __restrict__ top_id, int W, int G, int k,
-                                                                long end_id, float lambda, long* __restrict__ new_tok, float* __restrict__ new_cost,
-                                                                int* __restrict__ parent, uint8_t* __restrict__ ended_rec, int* __restrict__ gather,
-                                                                const int* __restrict__ hist_in, int* __restrict__ hist_out, int hist_ld, int hist_len) {
+__global__ __launch_bounds__(64) void beam_select_kernel(const long* __restrict__ tok, const float* __restrict__ cost, uint8_t* __restrict__ done,
+                                                         const float* __restrict__ top_p, const long* __restrict__ top_id, int W, int G, int k,
+                                                         long end_id, float lambda, long* __restrict__ new_tok, float* __restrict__ new_cost,
+                                                         int* __restrict__ parent, uint8_t* __restrict__ ended_rec, int* __restrict__ gather,
+                                                         const int* __restrict__ hist_in, int* __restrict__ hist_out, int hist_ld, int hist_len) {
   __shared__ int live_g[64];                                 // per group: a live slot exists
   __shared__ int chosen[64];                                 // word of every new slot chosen so far (-1: empty)
   __shared__ int new_par[64];                                // HIST: parent slot of the new slots (-1: empty)
+  __shared__ float keys[64];                                 // keys of the group in hand, by candidate
   const int b = blockIdx.x, c = threadIdx.x;
   const int Wg = W / G, n = W * k, ng = Wg * k;              // slots and candidates of a group
-  live_g[c] = 0;
+  if (c < G) live_g[c] = 0;
   __syncthreads();
   if (c < W) {
     const bool was_done = done[b * G + c / Wg] != 0;
@@ -871,21 +796,20 @@ __global__ __launch_bounds__(64) void beam_select_groups_kernel(const long* __re
   if (c < n) {
     const bool finished = done[b * G + mine] != 0 || !live_g[mine];
     const float cw = cost[b * W + w];
-    word = (int)top_id[(long)(b * W + w) * k + (k - 1 - j)];
-    if (!finished && cw < INFINITY && tok[b * W + w] != end_id)
+    if (!finished && cw < INFINITY && tok[b * W + w] != end_id) {   // only a finite candidate's word is ever read
+      word = (int)top_id[(long)(b * W + w) * k + (k - 1 - j)];
       raw = cw + (float)(-log((double)top_p[(long)(b * W + w) * k + (k - 1 - j)]));
+    }
   }
-  __syncthreads();                                           // every read of done[] lies before its update
-  if (c < G) done[b * G + c] = (done[b * G + c] != 0 || !live_g[c]) ? 1 : 0;
   for (int g = 0; g < G; ++g) {
     int n_v = 0;
     for (int s = 0; s < g * Wg; ++s) n_v += chosen[s] == word ? 1 : 0;
     const float key = raw < INFINITY ? __fadd_rn(raw, __fmul_rn(lambda, (float)n_v)) : INFINITY;
+    keys[c] = key;
+    __syncthreads();                                         // the keys are published; and every read of done[] lies before its update
+    if (g == 0 && c < G) done[b * G + c] = (done[b * G + c] != 0 || !live_g[c]) ? 1 : 0;
     int rank = 0;                                            // stable: ties keep candidate order
-    for (int o = g * ng; o < (g + 1) * ng; ++o) {
-      const float ko = __shfl(key, o, 64);
-      rank += (ko < key || (ko == key && o < c)) ? 1 : 0;
-    }
+    for (int o = g * ng; o < (g + 1) * ng; ++o) rank += (keys[o] < key || (keys[o] == key && o < c)) ? 1 : 0;
     if (mine == g && rank < Wg) {
       const int slot = g * Wg + rank;
       const bool ok = raw < INFINITY;
@@ -896,7 +820,7 @@ __global__ __launch_bounds__(64) void beam_select_groups_kernel(const long* __re
       chosen[slot] = ok ? word : -1;
       if constexpr (HIST) new_par[slot] = ok ? w : -1;
     }
-    __syncthreads();
+    if (HIST || g + 1 < G) __syncthreads();                  // the group's words (and keys[] free again) for the next group, or the copy below
   }
   if constexpr (HIST) {
     const int len = hist_len + 1;
@@ -907,24 +831,24 @@ __global__ __launch_bounds__(64) void beam_select_groups_kernel(const long* __re
   }
 }
 
-extern "C" int st_beam_select_groups(const long* tok, const float* cost, uint8_t* done, const float* top_p, const long* top_id, int B, int W, int G,
-                                     int k, long end_id, float diversity_penalty, long* new_tok, float* new_cost, int* parent, uint8_t* ended,
-                                     int* gather, const int* hist_in, int* hist_out, int hist_ld, int hist_len, void* stream) {
-  ST_CHECK(tok && cost && done && top_p && top_id && new_tok && new_cost && parent && ended && gather, "st_beam_select_groups: null pointer");
-  ST_CHECK(B > 0 && W >= 1 && k >= 1 && k <= W && W * k <= 64, "st_beam_select_groups: need 1 <= k <= W and W * k <= 64 (got W=%d k=%d)", W, k);
-  ST_CHECK(G >= 1 && W % G == 0, "st_beam_select_groups: the %d slots do not split into %d groups", W, G);
-  ST_CHECK(diversity_penalty >= 0.f && diversity_penalty < INFINITY, "st_beam_select_groups: diversity_penalty must be finite and >= 0 (got %g)",
+extern "C" int st_beam_select(const long* tok, const float* cost, uint8_t* done, const float* top_p, const long* top_id, int B, int W, int G,
+                              int k, long end_id, float diversity_penalty, long* new_tok, float* new_cost, int* parent, uint8_t* ended,
+                              int* gather, const int* hist_in, int* hist_out, int hist_ld, int hist_len, void* stream) {
+  ST_CHECK(tok && cost && done && top_p && top_id && new_tok && new_cost && parent && ended && gather, "st_beam_select: null pointer");
+  ST_CHECK(B > 0 && W >= 1 && k >= 1 && k <= W && W * k <= 64, "st_beam_select: need 1 <= k <= W and W * k <= 64 (got W=%d k=%d)", W, k);
+  ST_CHECK(G >= 1 && W % G == 0, "st_beam_select: the %d slots do not split into %d groups", W, G);
+  ST_CHECK(diversity_penalty >= 0.f && diversity_penalty < INFINITY, "st_beam_select: diversity_penalty must be finite and >= 0 (got %g)",
            (double)diversity_penalty);
   ST_CHECK((hist_in == nullptr) == (hist_out == nullptr) && (!hist_in || hist_in != hist_out),
-           "st_beam_select_groups: hist_in and hist_out are both null or two different buffers");
+           "st_beam_select: hist_in and hist_out are both null or two different buffers");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (hist_in) {
     ST_CHECK(hist_len >= 1 && hist_len + 1 <= hist_ld && hist_len + 1 <= ST_BEAM_MAX_HIST,
-             "st_beam_select_groups: need 1 <= hist_len and hist_len + 1 <= min(hist_ld, %d) (got %d, ld %d)", ST_BEAM_MAX_HIST, hist_len, hist_ld);
-    hipLaunchKernelGGL(beam_select_groups_kernel<true>, dim3(B), dim3(64), 0, st, tok, cost, done, top_p, top_id, W, G, k, end_id, diversity_penalty,
+             "st_beam_select: need 1 <= hist_len and hist_len + 1 <= min(hist_ld, %d) (got %d, ld %d)", ST_BEAM_MAX_HIST, hist_len, hist_ld);
+    hipLaunchKernelGGL(beam_select_kernel<true>, dim3(B), dim3(64), 0, st, tok, cost, done, top_p, top_id, W, G, k, end_id, diversity_penalty,
                        new_tok, new_cost, parent, ended, gather, hist_in, hist_out, hist_ld, hist_len);
   } else {
-    hipLaunchKernelGGL(beam_select_groups_kernel<false>, dim3(B), dim3(64), 0, st, tok, cost, done, top_p, top_id, W, G, k, end_id, diversity_penalty,
+    hipLaunchKernelGGL(beam_select_kernel<false>, dim3(B), dim3(64), 0, st, tok, cost, done, top_p, top_id, W, G, k, end_id, diversity_penalty,
                        new_tok, new_cost, parent, ended, gather, nullptr, nullptr, 0, 0);
   }
   ST_LAUNCH_CHECK();

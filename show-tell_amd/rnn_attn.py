@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import AttnGrads, AttnParams, check, dtype_code, lib, ref
+from ._lib import AttnGrads, AttnParams, BeamOpts, check, dtype_code, lib, ref
 from ._lib import ptr as _cp, stream as _stream
 from .rnn import (CAP_MAX, Decoder, ce_loss, ce_loss_backward, check_caption_args, check_input_ids, check_label_smoothing,
                   check_weight_args, logits_grad, loss_terms, pack_row_weights, sample_lengths, scheduled_loss_inputs, unpack_rows, up8)
@@ -305,11 +305,11 @@ class RNN_Attn(Decoder):
         search that keeps paths (max_length + 1 <= 64) adds hist [B][W][max_length+1] int32, the path of every slot of the last
         fringe as the search itself kept it.
         `min_length`, `no_repeat_ngram_size`, `suppress_tokens` and `length_penalty` constrain the search as in
-        RNN.beam_search (beam.py); with any of the first three set the call is st_attn_beam_search_ex.
-        `num_beam_groups` = G > 1 is diverse beam search as in RNN.beam_search (beam.py's docstring has the rule): one
-        st_attn_beam_search_div call; the hypotheses are then, per image, a list of G lists (each entry with its alphas under
+        RNN.beam_search (beam.py); they travel in the call's st_beam_opts.
+        `num_beam_groups` = G > 1 is diverse beam search as in RNN.beam_search (beam.py's docstring has the rule), the same
+        st_attn_beam_search call; the hypotheses are then, per image, a list of G lists (each entry with its alphas under
         `return_alphas`), the records keep their layout (beam.group_records cuts a group out) and hist is handed out whenever
-        the paths fit (max_length + 1 <= 64).  With G = 1 the call and its result are what they were."""
+        the paths fit (max_length + 1 <= 64).  With G = 1 the result is that of the single beam."""
         from .beam import ST_BEAM_MAX_HIST, BeamConstraints, check_groups, replay_groups, replay_hypotheses
         if not 1 <= beam_width <= 8:
             raise ValueError(f"beam_width must be 1..8 (got {beam_width})")
@@ -321,12 +321,14 @@ class RNN_Attn(Decoder):
             prm, keep, featc, B, P = self._decode_inputs(cnn_feature)
             W, T = beam_width, max_length
             n = B * W
-            if G > 1:
-                nbytes = lib().st_attn_beam_div_workspace_bytes(C.byref(prm), B, W, T, G)
-            elif bc.active:
-                nbytes = lib().st_attn_beam_ex_workspace_bytes(C.byref(prm), B, W, T)
-            else:
-                nbytes = lib().st_attn_beam_workspace_bytes(C.byref(prm), B, W)
+            keep_paths = bc.keep_paths or (G > 1 and T + 1 <= ST_BEAM_MAX_HIST)
+            opts = None                                                                # the plain search
+            if G > 1 or bc.active:
+                sup, n_sup = bc.suppress_on(featc.device)
+                bo = BeamOpts(bc.min_length, bc.ngram, _cp(sup), n_sup, int(keep_paths), G, lam)
+                opts = C.byref(bo)
+            paths_at = C.c_size_t(0)
+            nbytes = lib().st_attn_beam_workspace_bytes(C.byref(prm), B, W, T, opts, C.byref(paths_at))
             ws = torch.empty(nbytes, device=featc.device, dtype=torch.uint8)
             # the records share one buffer, so that the search ends in ONE device-to-host copy
             layout = [("tok", torch.long, (T + 1, B, W)), ("cost", torch.float32, (T + 1, B, W)), ("par", torch.int32, (T + 1, B, W)),
@@ -340,28 +342,13 @@ class RNN_Attn(Decoder):
                 o += (nb + 255) // 256 * 256
             rec = torch.empty(o, device=featc.device, dtype=torch.uint8)
             view = {name: rec[offs[name][0]:offs[name][0] + offs[name][1]].view(dt).view(shape) for name, dt, shape in layout}
-            if G > 1:
-                sup, n_sup = bc.suppress_on(featc.device)
-                check(lib().st_attn_beam_search_div(C.byref(prm), _cp(featc), B, W, T, int(start_id), int(end_id), _cp(ws), nbytes,
-                                                    _cp(view["tok"]), _cp(view["cost"]), _cp(view["par"]), _cp(view["end"]),
-                                                    _cp(view.get("alpha")), bc.min_length, bc.ngram, _cp(sup), n_sup, G, lam, _stream()),
-                      "st_attn_beam_search_div")
-            elif bc.active:
-                sup, n_sup = bc.suppress_on(featc.device)
-                check(lib().st_attn_beam_search_ex(C.byref(prm), _cp(featc), B, W, T, int(start_id), int(end_id), _cp(ws), nbytes,
-                                                   _cp(view["tok"]), _cp(view["cost"]), _cp(view["par"]), _cp(view["end"]),
-                                                   _cp(view.get("alpha")), bc.min_length, bc.ngram, _cp(sup), n_sup, _stream()),
-                      "st_attn_beam_search_ex")
-            else:
-                check(lib().st_attn_beam_search(C.byref(prm), _cp(featc), B, W, T, int(start_id), int(end_id), _cp(ws), nbytes,
-                                                _cp(view["tok"]), _cp(view["cost"]), _cp(view["par"]), _cp(view["end"]),
-                                                _cp(view.get("alpha")), _stream()), "st_attn_beam_search")
+            check(lib().st_attn_beam_search(C.byref(prm), _cp(featc), B, W, T, int(start_id), int(end_id), _cp(ws), nbytes,
+                                            _cp(view["tok"]), _cp(view["cost"]), _cp(view["par"]), _cp(view["end"]),
+                                            _cp(view.get("alpha")), opts, _stream()), "st_attn_beam_search")
             host = rec.cpu().numpy()
             hist = None
-            if return_records and (bc.keep_paths or (G > 1 and T + 1 <= ST_BEAM_MAX_HIST)):
-                # the two path buffers follow the unconstrained plan in the workspace (showtell_hip.h); the last fringe's is T & 1
-                base, nb = lib().st_attn_beam_workspace_bytes(C.byref(prm), B, W), n * (T + 1) * 4
-                off = base + (T & 1) * ((nb + 255) // 256 * 256)
+            if return_records and keep_paths:                                      # the last fringe's path buffer, where the planner put it
+                off, nb = paths_at.value, n * (T + 1) * 4
                 hist = ws[off:off + nb].view(torch.int32).view(B, W, T + 1).cpu().numpy()
         npdt = {torch.long: np.int64, torch.float32: np.float32, torch.int32: np.int32, torch.uint8: np.uint8}
         h = {name: host[offs[name][0]:offs[name][0] + offs[name][1]].view(npdt[dt]).reshape(shape) for name, dt, shape in layout}

@@ -34,7 +34,7 @@ def _mirrored_structs():
             (_lib.ConvB2bDesc, "st_conv_b2b_desc"), (_lib.ConvC3c1Desc, "st_conv_c3c1_desc"), (_lib.BnActDesc, "st_bn_act_desc"),
             (_lib.RnnParams, "st_rnn_params"), (_lib.RnnGrads, "st_rnn_grads"), (_lib.AttnParams, "st_attn_params"),
             (_lib.AttnGrads, "st_attn_grads"), (_lib.PackedSeq, "st_packed_seq"), (_lib.ImageBatchDesc, "st_image_batch_desc"),
-            (_lib.LossTerms, "st_loss_terms"), (_lib.DropoutDesc, "st_dropout")]
+            (_lib.LossTerms, "st_loss_terms"), (_lib.DropoutDesc, "st_dropout"), (_lib.BeamOpts, "st_beam_opts")]
 
 
 def layout_errors(structs):
@@ -194,7 +194,7 @@ def test_struct_sizes_match_the_header():
 
 def test_every_mirrored_struct_has_the_headers_layout():
     structs = _mirrored_structs()
-    assert len(structs) == 16 and sum(len(c._fields_) for c, _ in structs) == 273
+    assert len(structs) == 17 and sum(len(c._fields_) for c, _ in structs) == 280
     from showtell_amd import _lib
     mirrored = {c for c, _ in structs}
     assert {v for v in vars(_lib).values() if isinstance(v, type) and issubclass(v, ctypes.Structure) and v is not ctypes.Structure} == mirrored

@@ -380,7 +380,7 @@ def test_planners_and_entry_points_refuse_the_layer_count_before_any_launch(L):
                        sample=lib().st_rnn_sample_workspace_bytes(C.byref(p), 2), attn=lib().st_attn_workspace_bytes(C.byref(a), C.byref(s)),
                        attn_greedy=lib().st_attn_greedy_workspace_bytes(C.byref(a), 2),
                        attn_sample=lib().st_attn_sample_workspace_bytes(C.byref(a), 2),
-                       attn_beam=lib().st_attn_beam_workspace_bytes(C.byref(a), 2, 4))
+                       attn_beam=lib().st_attn_beam_workspace_bytes(C.byref(a), 2, 4, 14, None, None))
             assert all(v == 0 for v in got.values()), (cell, dtype, got)
             with pytest.raises(ShowTellHipError, match=f"num_layers={L} out of range"):
                 check(lib().st_rnn_forward(C.byref(p), C.byref(s), None, None, 0, None, 0, 0, None, 0, None, None, None), "st_rnn_forward")

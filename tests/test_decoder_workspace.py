@@ -2,8 +2,10 @@
 
 tests/golden/decoder_workspace_bytes.json holds what every st_*_workspace_bytes planner of the recurrent decoders (and
 st_rnn_vocab_ld) returned for the table below, recorded from the library before the planners were moved onto the shared
-arena of csrc/decoder_host.h; the planners must reproduce every byte count.  `python tests/test_decoder_workspace.py`
-rewrites the fixture from the library -- for an intended layout change only."""
+arena of csrc/decoder_host.h; the planners must reproduce every byte count.  The st_attn_beam_workspace_bytes keys that name
+max_length, keep_paths and G hold what the separate planners of the constrained and the diverse search returned before the
+one planner with st_beam_opts replaced them (keep_paths0 at max_length 64: those planners kept no paths there).
+`python tests/test_decoder_workspace.py` rewrites the fixture from the library -- for an intended layout change only."""
 import ctypes as C
 import json
 import os
@@ -47,6 +49,7 @@ ATTN_SHAPES = {
 }
 VOCAB_LD = (50, 2040, 2047, 2048, 2049, 10000)
 BEAM_WIDTHS = (1, 8)
+BEAM_LENGTHS = (14, 63, 64)                                   # 63: the longest search that keeps paths (ST_BEAM_MAX_HIST = 64)
 CELLS = ("gru", "lstm")
 DTYPES = ("f32", "bf16")
 
@@ -92,7 +95,16 @@ def table():
                 out["st_attn_greedy_workspace_bytes" + tag] = lib.st_attn_greedy_workspace_bytes(C.byref(p), B)
                 out["st_attn_sample_workspace_bytes" + tag] = lib.st_attn_sample_workspace_bytes(C.byref(p), B)
                 for W in BEAM_WIDTHS:
-                    out["st_attn_beam_workspace_bytes%s/W%d" % (tag, W)] = lib.st_attn_beam_workspace_bytes(C.byref(p), B, W)
+                    out["st_attn_beam_workspace_bytes%s/W%d" % (tag, W)] = plain = lib.st_attn_beam_workspace_bytes(C.byref(p), B, W, 14, None, None)
+                    for T in BEAM_LENGTHS:
+                        keep = int(T + 1 <= 64)
+                        for G in sorted({1, W}):
+                            o, off = _lib.BeamOpts(0, 0, None, 0, keep, G, 0.0), C.c_size_t(77)
+                            key = "st_attn_beam_workspace_bytes%s/W%d/max_length%d/keep_paths%d/G%d" % (tag, W, T, keep, G)
+                            out[key] = lib.st_attn_beam_workspace_bytes(C.byref(p), B, W, T, C.byref(o), C.byref(off))
+                            # the last fringe's paths: buffer T & 1 of the two that follow the plain plan, each padded to 256 bytes
+                            assert off.value == (plain + (T & 1) * ((B * W * (T + 1) * 4 + 255) // 256 * 256) if keep else 0), key
+                        assert lib.st_attn_beam_workspace_bytes(C.byref(p), B, W, T, None, C.byref(off)) == plain and off.value == 0
     return out
 
 

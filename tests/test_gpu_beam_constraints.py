@@ -194,8 +194,9 @@ def test_ban_topk_at_the_largest_vocabulary():
 
 @pytest.mark.parametrize("name", ["plain-gru-fp32", "plain-gru-bf16", "attn-lstm-fp32", "attn-lstm-bf16"])
 def test_defaults_and_an_empty_ban_set_give_the_unconstrained_records(name):
-    """Every constraint at its default runs st_softmax_topk / st_beam_select (st_attn_beam_search) as before; suppress_tokens=[]
-    runs st_beam_ban_topk / st_beam_select_hist (st_attn_beam_search_ex) with an empty ban set.  Array for array the same."""
+    """Every constraint at its default runs st_softmax_topk and st_beam_select without paths (st_attn_beam_search without options);
+    suppress_tokens=[] is a constrained search with nothing to ban: st_softmax_topk again, and st_beam_select with the paths kept
+    (st_attn_beam_search with keep_paths).  Array for array the same."""
     from showtell_amd.beam import beam_search_records
     kind, cell, dtype, W, B, vocab = CASES[name]
     m, feat = _model(kind, cell, dtype, vocab), K.features(kind, B).cuda()
@@ -272,7 +273,7 @@ def test_length_penalty_ranks_the_replayed_hypotheses(name, cname):
 @pytest.mark.parametrize("bw,nh,dtype", [(4, 3, "fp32"), (8, 2, "fp32"), (4, 1, "bf16"), (9, 1, "fp32")])
 def test_constrained_device_selection_equals_host_bookkeeping(bw, nh, dtype, cname):
     """test_beam_search_device_selection_equals_host_bookkeeping with the constraints on: the device loop (st_beam_ban_topk +
-    st_beam_select_hist) and beam_search_host (paths kept beside its Node table, successors from st_beam_ban_topk) give the same
+    st_beam_select with its paths) and beam_search_host (paths kept beside its Node table, successors from st_beam_ban_topk) give the same
     sequences; bw = 9 exceeds W * k <= 64 and takes the host path by itself, where the hypotheses must still obey the constraints."""
     from showtell_amd.beam import beam_search, beam_search_host
     cons = K.CONSTRAINTS[cname]
@@ -345,16 +346,24 @@ def test_limits_are_rejected_loudly(kind, cell):
         from showtell_amd._lib import check, lib
         from showtell_amd.rnn import _cp, _stream
         prm, keep, featc, B, P = m._decode_inputs(feat)
-        nb = lib().st_attn_beam_ex_workspace_bytes(C.byref(prm), B, 4, 64)
-        assert nb == lib().st_attn_beam_workspace_bytes(C.byref(prm), B, 4)           # max_length = 64: no path buffers
-        assert lib().st_attn_beam_ex_workspace_bytes(C.byref(prm), B, 4, 14) > nb
-        ws = torch.empty(nb, device="cuda", dtype=torch.uint8)
+        from showtell_amd._lib import BeamOpts
+
+        def opts(ngram=0, n_suppress=0, keep_paths=1):
+            return C.byref(BeamOpts(0, ngram, _cp(tok), n_suppress, keep_paths, 1, 0.0))
+
+        def planned(mlen, o):
+            return lib().st_attn_beam_workspace_bytes(C.byref(prm), B, 4, mlen, o, None)
+
         tok = torch.empty(65, B, 4, device="cuda", dtype=torch.long); cost = torch.empty(65, B, 4, device="cuda")
+        nb = planned(64, opts(keep_paths=0))
+        assert nb == planned(64, None) == planned(14, None) > 0                       # max_length = 64: no path buffers
+        assert planned(14, opts()) > nb and planned(64, opts()) == 0                  # ... and none can be asked for
+        ws = torch.empty(nb, device="cuda", dtype=torch.uint8)
         par = torch.empty(65, B, 4, device="cuda", dtype=torch.int32); end = torch.empty(64, B, 4, device="cuda", dtype=torch.uint8)
-        for mlen, g, ns in ((64, 2, 0), (14, 17, 0), (14, 0, 65), (14, -1, 0)):
+        for mlen, g, ns, kp in ((64, 2, 0, 0), (14, 17, 0, 1), (14, 0, 65, 1), (14, -1, 0, 1), (14, 2, 0, 0), (64, 0, 0, 1)):
             with pytest.raises(ShowTellHipError):
-                check(lib().st_attn_beam_search_ex(C.byref(prm), _cp(featc), B, 4, mlen, START, END, _cp(ws), nb, _cp(tok), _cp(cost), _cp(par),
-                                                   _cp(end), None, 0, g, _cp(tok), ns, _stream()), "st_attn_beam_search_ex")
+                check(lib().st_attn_beam_search(C.byref(prm), _cp(featc), B, 4, mlen, START, END, _cp(ws), nb, _cp(tok), _cp(cost), _cp(par),
+                                                _cp(end), None, opts(g, ns, kp), _stream()), "st_attn_beam_search")
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
 """Diverse (group) beam search on the GPU (num_beam_groups, diversity_penalty): the selection kernel against a numpy float32
-replica on hand-built fringes, G = 1 against st_beam_select / st_beam_select_hist bit for bit, the searches' records walked group by
+replica on hand-built fringes, G = 1 against the recorded outputs of the single-beam kernel it replaced, the searches' records walked group by
 group by the float64 oracle, the returned hypotheses against the replayed groups, and the loud failures.
 
 The walk is tests/_diverse_beam_cases.check_group_records: test_gpu_beam_constraints.py's method per group.  The oracle is
@@ -16,6 +16,7 @@ gap at a cut of the oracle's own runs (1.1e-4 nats over the six decoders, test_d
 largest fp32 SEL of 1.6e-5, so that check C discriminates at every cut of the fp32 cases.
 """
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -92,7 +93,7 @@ def _records(case, lam, setting):
 
 
 # ====================================================================================================================
-# (a), (b) st_beam_select_groups on hand-built fringes
+# (a), (b) st_beam_select on hand-built fringes
 # ====================================================================================================================
 
 def _select_groups(tok, cost, done, p, ids, G, lam, hist=None, hist_len=0, k=None):
@@ -111,9 +112,9 @@ def _select_groups(tok, cost, done, p, ids, G, lam, hist=None, hist_len=0, k=Non
     if hist is not None:
         h_in = torch.from_numpy(hist).to(dev)
         h_out = torch.full_like(h_in, -7)
-    check(lib().st_beam_select_groups(_cp(t_tok), _cp(t_cost), _cp(t_done), _cp(t_p), _cp(t_i), B, W, G, k, END, float(lam), _cp(o_tok),
-                                      _cp(o_cost), _cp(o_par), _cp(o_end), _cp(o_g), _cp(h_in), _cp(h_out),
-                                      hist.shape[1] if hist is not None else 0, hist_len, _stream()), "st_beam_select_groups")
+    check(lib().st_beam_select(_cp(t_tok), _cp(t_cost), _cp(t_done), _cp(t_p), _cp(t_i), B, W, G, k, END, float(lam), _cp(o_tok),
+                               _cp(o_cost), _cp(o_par), _cp(o_end), _cp(o_g), _cp(h_in), _cp(h_out),
+                               hist.shape[1] if hist is not None else 0, hist_len, _stream()), "st_beam_select")
     out = dict(tok=o_tok.cpu().numpy(), cost=o_cost.cpu().numpy(), par=o_par.cpu().numpy(), end=o_end.cpu().numpy(),
                gather=o_g.cpu().numpy().reshape(B, W), done=t_done.cpu().numpy().reshape(B, -1))
     if hist is not None:
@@ -162,45 +163,42 @@ def test_selection_kernel_against_the_replica(W, G, k, with_hist):
 
 @pytest.mark.parametrize("W,k", [(4, 4), (6, 5), (8, 8), (1, 1)])
 def test_one_group_is_the_plain_selection_bit_for_bit(W, k):
-    from showtell_amd._lib import check, lib
-    from showtell_amd.rnn import _cp, _stream
+    """G = 1, lambda = 0 reproduces, bit for bit, every output that the single-beam selection kernel of the parent commit (its
+    two entry points, without and with paths; the fixture's note names the commit) wrote for the same inputs on an MI355X"""
+    from tests._util import GOLDEN
+    want = np.load(os.path.join(GOLDEN, "beam_select_parent.npz"))
     tok, cost, done, p, ids = D.hand_fringes(W, 1, k)
-    B = tok.shape[0]
     hist_len, ld = 5, 9
     hist = _hist_for(tok, hist_len, ld)
     for with_hist in (False, True):
         got = _select_groups(tok, cost, done, p, ids, 1, 0.0, hist if with_hist else None, hist_len)
-        dev = "cuda"
-        t_done = torch.from_numpy(done.copy()).to(dev).view(-1)
-        o_tok = torch.full((B, W), -7, device=dev, dtype=torch.long); o_cost = torch.full((B, W), -7.0, device=dev)
-        o_par = torch.full((B, W), -7, device=dev, dtype=torch.int32); o_end = torch.full((B, W), 7, device=dev, dtype=torch.uint8)
-        o_g = torch.full((B * W,), -7, device=dev, dtype=torch.int32)
-        ins = [torch.from_numpy(x).to(dev) for x in (tok, cost, p, ids)]                   # kept alive over the call
-        args = [_cp(ins[0]), _cp(ins[1]), _cp(t_done), _cp(ins[2]), _cp(ins[3]), B, W, k, END, _cp(o_tok), _cp(o_cost), _cp(o_par), _cp(o_end),
-                _cp(o_g)]
-        if with_hist:
-            h_in = torch.from_numpy(hist).to(dev); h_out = torch.full_like(h_in, -7)
-            check(lib().st_beam_select_hist(*args, _cp(h_in), _cp(h_out), ld, hist_len, _stream()), "st_beam_select_hist")
-            assert np.array_equal(got["hist"], h_out.cpu().numpy())
-        else:
-            check(lib().st_beam_select(*args, _stream()), "st_beam_select")
-        assert np.array_equal(got["tok"], o_tok.cpu().numpy()) and np.array_equal(got["par"], o_par.cpu().numpy())
-        assert np.array_equal(got["cost"].view(np.int32), o_cost.cpu().numpy().view(np.int32))
-        assert np.array_equal(got["end"], o_end.cpu().numpy()) and np.array_equal(got["gather"].reshape(-1), o_g.cpu().numpy())
-        assert np.array_equal(got["done"].reshape(-1), t_done.cpu().numpy())
+        pre = f"W{W}_k{k}_{'hist' if with_hist else 'plain'}_"
+        assert sorted(key[len(pre):] for key in want.files if key.startswith(pre)) == sorted(got)
+        for key, arr in got.items():
+            arr = arr.view(np.int32) if key == "cost" else arr
+            assert arr.dtype == want[pre + key].dtype and np.array_equal(arr.reshape(-1), want[pre + key].reshape(-1)), (with_hist, key)
 
 
 def test_one_group_leaves_the_call_path_untouched(monkeypatch):
-    """num_beam_groups = 1, diversity_penalty = 0 are the calls of before: the new entry points, made to raise, are never reached,
-    and the results are the same"""
+    """num_beam_groups = 1, diversity_penalty = 0 are the calls of before: the selection is never reached with G != 1 or a penalty,
+    the attention search never with num_groups != 1, and the results are the same"""
     from showtell_amd import _lib, beam, rnn_attn
 
     real = _lib.lib()
 
     class Guard:
+        def st_beam_select(self, *a):
+            if a[7] != 1 or a[10] != 0.0:                                          # G, diversity_penalty
+                raise AssertionError("st_beam_select reached with one group")
+            return real.st_beam_select(*a)
+
+        def st_attn_beam_search(self, *a):
+            opts = a[14]
+            if opts is not None and opts._obj.num_groups != 1:
+                raise AssertionError("st_attn_beam_search reached with one group")
+            return real.st_attn_beam_search(*a)
+
         def __getattr__(self, name):
-            if name in ("st_beam_select_groups", "st_attn_beam_search_div", "st_attn_beam_div_workspace_bytes"):
-                raise AssertionError(f"{name} reached with one group")
             return getattr(real, name)
 
     for case in ("plain-gru-fp32", "attn-lstm-fp32"):
@@ -353,25 +351,45 @@ def test_c_entry_points_refuse_and_leave_the_outputs_alone():
     ins = [torch.from_numpy(x).to(dev) for x in (tok, cost)] + [t_done] + [torch.from_numpy(x).to(dev) for x in (p, ids)]
     for G, lam in ((4, 0.5), (2, -1.0), (2, float("nan"))):
         with pytest.raises(ShowTellHipError):
-            check(lib().st_beam_select_groups(*[_cp(x) for x in ins], 4, 6, G, 6, END, lam, *[_cp(x) for x in outs], None, None, 0, 0,
-                                              _stream()), "st_beam_select_groups")
+            check(lib().st_beam_select(*[_cp(x) for x in ins], 4, 6, G, 6, END, lam, *[_cp(x) for x in outs], None, None, 0, 0,
+                                       _stream()), "st_beam_select")
     torch.cuda.synchronize()
     assert all((x == (7 if x.dtype == torch.uint8 else -7)).all() for x in outs) and (t_done == 5).all()
-    # st_attn_beam_search_div
+    # st_attn_beam_search
+    from showtell_amd._lib import BeamOpts
     m, feat = _model("attn-gru-fp32"), K.features("attn", 3).cuda()
     prm, keep, featc, B, P = m._decode_inputs(feat)
     W = 6
-    nb = lib().st_attn_beam_div_workspace_bytes(C.byref(prm), B, W, T, 3)
-    assert nb > lib().st_attn_beam_ex_workspace_bytes(C.byref(prm), B, W, T) > 0
-    assert lib().st_attn_beam_div_workspace_bytes(C.byref(prm), B, W, T, 1) == lib().st_attn_beam_ex_workspace_bytes(C.byref(prm), B, W, T)
-    assert lib().st_attn_beam_div_workspace_bytes(C.byref(prm), B, W, T, 4) == 0 == lib().st_attn_beam_div_workspace_bytes(C.byref(prm), B, W, T, 0)
+
+    def opts(G=1, lam=0.0, keep_paths=1, ngram=0):
+        return C.byref(BeamOpts(0, ngram, None, 0, keep_paths, G, lam))
+
+    def planned(max_length, o):
+        off = C.c_size_t(77)
+        return lib().st_attn_beam_workspace_bytes(C.byref(prm), B, W, max_length, o, C.byref(off)), off.value
+
+    nb, off3 = planned(T, opts(3))
+    kept, off1 = planned(T, opts(1))                                               # the constrained search's plan of before
+    plain, off0 = planned(T, None)
+    assert nb > kept > plain > 0 and off0 == 0 and off1 == off3 == plain + (T & 1) * ((B * W * (T + 1) * 4 + 255) // 256 * 256)
+    assert planned(T, opts(1, keep_paths=0)) == (plain, 0)
+    assert planned(T, opts(4)) == (0, 0) == planned(T, opts(0))
+    assert planned(64, opts(1)) == (0, 0) and planned(64, opts(1, keep_paths=0))[0] == planned(64, None)[0] == plain
     ws = torch.empty(nb, device=dev, dtype=torch.uint8)
     r_tok = torch.full((T + 1, B, W), -7, device=dev, dtype=torch.long); r_cost = torch.full((T + 1, B, W), -7.0, device=dev)
     r_par = torch.full((T + 1, B, W), -7, device=dev, dtype=torch.int32); r_end = torch.full((T, B, W), 7, device=dev, dtype=torch.uint8)
-    for G, lam, nbytes in ((4, 0.5, nb), (0, 0.5, nb), (3, -1.0, nb), (3, float("nan"), nb), (3, 0.5, nb - 256)):
+    for G, lam, nbytes, kp, ng, Tn in ((4, 0.5, nb, 1, 0, T), (0, 0.5, nb, 1, 0, T), (3, -1.0, nb, 1, 0, T), (3, float("nan"), nb, 1, 0, T),
+                                       (3, 0.5, nb - 256, 1, 0, T), (1, 0.0, nb, 0, 2, T), (1, 0.0, nb, 1, 0, 64)):
+        if Tn != T:                                                                # records long enough for the refused call
+            big = [torch.full((Tn + 1, B, W), -7, device=dev, dtype=x.dtype) for x in (r_tok, r_cost, r_par)] + \
+                  [torch.full((Tn, B, W), 7, device=dev, dtype=torch.uint8)]
+        recs = (r_tok, r_cost, r_par, r_end) if Tn == T else big
         with pytest.raises(ShowTellHipError):
-            check(lib().st_attn_beam_search_div(C.byref(prm), _cp(featc), B, W, T, START, END, _cp(ws), nbytes, _cp(r_tok), _cp(r_cost),
-                                                _cp(r_par), _cp(r_end), None, 0, 0, None, 0, G, lam, _stream()), "st_attn_beam_search_div")
+            check(lib().st_attn_beam_search(C.byref(prm), _cp(featc), B, W, Tn, START, END, _cp(ws), nbytes, *[_cp(x) for x in recs], None,
+                                            opts(G, lam, kp, ng), _stream()), "st_attn_beam_search")
+        if Tn != T:
+            torch.cuda.synchronize()
+            assert all((x == (7 if x.dtype == torch.uint8 else -7)).all() for x in big)
     torch.cuda.synchronize()
     assert (r_tok == -7).all() and (r_cost == -7).all() and (r_par == -7).all() and (r_end == 7).all()
 

@@ -2,16 +2,17 @@
 L = 5, B = 256 images, W = 5, max_length = 25), plain GRU and attention GRU (F = 2048, P = 49, A = 512).  Four calls, in
 alternating rounds in one process (host clock around whole searches, each of which ends in a device-to-host copy):
 
-  plain    beam_search(...) with every constraint at its default: st_softmax_topk + st_beam_select
-  empty    suppress_tokens=[]: st_beam_ban_topk + st_beam_select_hist with an empty ban set
+  plain    beam_search(...) with every constraint at its default: st_softmax_topk + st_beam_select without paths
+  empty    suppress_tokens=[]: nothing to ban, so st_softmax_topk again, + st_beam_select with the paths kept
   g3       no_repeat_ngram_size=3
   all      min_length=5, no_repeat_ngram_size=3, suppress_tokens=[<pad>, <start>, <unk>]
 
 The yardstick is the unconstrained search of ANOTHER build of the library, measured in the same rounds: ST_YARDSTICK_LIB names a
-libshowtell_hip.so built from the commit to compare with (without it the tool times the four calls alone).  A random decoder
+libshowtell_hip.so built from the commit to compare with (one that exports this tree's set of entry points: another is refused; without it the tool times the four calls alone).  A random decoder
 never emits <end>, so every image stays live for all 25 iterations: the most work a search can do."""
 import ctypes as C
 import os
+import subprocess
 import sys
 import time
 
@@ -31,7 +32,15 @@ CALLS = {"plain": {}, "empty": dict(suppress_tokens=[]), "g3": dict(no_repeat_ng
 
 
 def _other_build(path):
-    """the entry points of another build of the library, bound like _lib's own (the ones it has)"""
+    """the entry points of another build of the library, bound like _lib's own.  It gets this tree's signatures, so a build that
+    exports another set of st_ entry points (an ABI before or after this one) is refused before anything is launched"""
+    def exports(p):
+        out = subprocess.check_output(["nm", "-D", "--defined-only", p], text=True)
+        return {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("st_")}
+    theirs, mine = exports(path), exports(_lib.LIB_PATH)
+    if theirs != mine:
+        sys.exit(f"ST_YARDSTICK_LIB={path} exports other entry points than this tree's library "
+                 f"(only there: {sorted(theirs - mine)}, only here: {sorted(mine - theirs)}): its calls cannot be bound with this tree's signatures")
     cdll = C.CDLL(path)
     b = _lib._Bound.__new__(_lib._Bound)
     b.st_last_error = cdll.st_last_error

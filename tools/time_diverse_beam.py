@@ -2,18 +2,19 @@
 B = 256 images, W = 6, max_length = 25), plain GRU and attention GRU (F = 2048, P = 49, A = 512).  In alternating rounds in one
 process (host clock around whole searches, each of which ends in a device-to-host copy):
 
-  G=1            beam_search(...) with num_beam_groups=1: the launches of before (st_softmax_topk + st_beam_select)
-  G=2, 3, 6      num_beam_groups=G, diversity_penalty=0.5: st_beam_select_groups for the selection
+  G=1            beam_search(...) with num_beam_groups=1: the single beam (st_softmax_topk + st_beam_select with one group)
+  G=2, 3, 6      num_beam_groups=G, diversity_penalty=0.5: the same st_beam_select launch over G groups
   G=2, 3, 6 all  the same with min_length=5, no_repeat_ngram_size=3, suppress_tokens=[<pad>, <start>, <unk>]
   all            the three constraints with one group: what the rows above are to be compared with
   rec G=1, 6     plain GRU only: beam.beam_search_records, the device loop and its copies without the host-side replay of the
                  hypotheses (which runs once per group); compared with each other they show the selection launch alone
 
 The yardstick is the single-beam search of ANOTHER build of the library, measured in the same rounds: ST_YARDSTICK_LIB names a
-libshowtell_hip.so built from the commit to compare with (without it the tool times its own calls alone).  A random decoder
+libshowtell_hip.so built from the commit to compare with (one that exports this tree's set of entry points: another is refused; without it the tool times its own calls alone).  A random decoder
 never emits <end>, so every group stays live for all 25 iterations: the most work a search can do."""
 import ctypes as C
 import os
+import subprocess
 import sys
 import time
 
@@ -38,7 +39,15 @@ RECORDS = {"rec G=1": dict(num_beam_groups=1), "rec G=6": dict(num_beam_groups=6
 
 
 def _other_build(path):
-    """the entry points of another build of the library, bound like _lib's own (the ones it has)"""
+    """the entry points of another build of the library, bound like _lib's own.  It gets this tree's signatures, so a build that
+    exports another set of st_ entry points (an ABI before or after this one) is refused before anything is launched"""
+    def exports(p):
+        out = subprocess.check_output(["nm", "-D", "--defined-only", p], text=True)
+        return {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("st_")}
+    theirs, mine = exports(path), exports(_lib.LIB_PATH)
+    if theirs != mine:
+        sys.exit(f"ST_YARDSTICK_LIB={path} exports other entry points than this tree's library "
+                 f"(only there: {sorted(theirs - mine)}, only here: {sorted(mine - theirs)}): its calls cannot be bound with this tree's signatures")
     cdll = C.CDLL(path)
     b = _lib._Bound.__new__(_lib._Bound)
     b.st_last_error = cdll.st_last_error
