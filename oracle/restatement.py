@@ -522,14 +522,17 @@ def attn_beam_step_bf16_storage(params, ctx, tok, state, par_next=None, cell="gr
     return logp, alpha.reshape(B * W, -1), (new if par_next is None else beam_gather_state(new, par_next, W))
 
 
-def beam_free_run(step, state, B, W, T, start_id=1, end_id=2, cost_dtype=np.float64, keep=None):
+def beam_free_run(step, state, B, W, T, start_id=1, end_id=2, cost_dtype=np.float64, keep=None, candidates=None, gather_par=None):
     """beam_search.py:45-97 for B images at once over fixed (image, slot) rows, driven by the step functions above:
     ``step(tok (B, W), state) -> (logp, [alpha,] new state)``.  The search is the oracle's own (free running).  Bookkeeping
     as st_beam_select / beam.beam_search_host: candidates node-major, a node's W successors in ascending probability, cut
     by a stable sort on the cumulative cost (accumulated in ``cost_dtype``: np.float32 reproduces the reference under
     NumPy 2), <end> nodes harvested at the start of the next iteration, an image without live nodes is finished.  Returns
     the records dict(tok, cost, par [T+1][B][W], end [T][B][W]) that beam.replay_hypotheses reads.  ``keep(t, out, cost_t,
-    live)`` receives each iteration's step output, the fringe costs and the live mask."""
+    live)`` receives each iteration's step output, the fringe costs and the live mask.  Two hooks restate a variant of the search
+    (constraints, a seeded fault) without a second copy of the selection: ``candidates(t, logp, tok, par) -> (tv, ti)`` gives every
+    node's successors in descending log p (tok, par: the records so far) in place of its top W, and ``gather_par(par[t + 1])`` the
+    parent row the new state is gathered by."""
     tok = np.zeros((T + 1, B, W), np.int64); tok[0, :, 0] = start_id
     cost = np.full((T + 1, B, W), np.inf, cost_dtype); cost[0, :, 0] = 0
     par = np.full((T + 1, B, W), -1, np.int32)
@@ -538,8 +541,11 @@ def beam_free_run(step, state, B, W, T, start_id=1, end_id=2, cost_dtype=np.floa
     for t in range(T):
         out = step(torch.from_numpy(tok[t]), state)
         logp, new = out[0], out[-1]
-        k = min(W, logp.shape[1])
-        tv, ti = torch.topk(logp, k, dim=1)                                                  # beam_search.py:84
+        if candidates is None:
+            tv, ti = torch.topk(logp, min(W, logp.shape[1]), dim=1)                          # beam_search.py:84
+        else:
+            tv, ti = candidates(t, logp, tok, par)
+        k = tv.shape[1]
         tv, ti = tv.numpy().astype(cost_dtype), ti.numpy()
         occupied = np.isfinite(cost[t])
         ended = occupied & (tok[t] == end_id) & ~done[:, None]
@@ -557,7 +563,7 @@ def beam_free_run(step, state, B, W, T, start_id=1, end_id=2, cost_dtype=np.floa
         tok[t + 1] = np.where(ok, np.take_along_axis(ti[:, ::-1].reshape(B, W * k), order, 1), 0)
         par[t + 1] = np.where(ok, order // k, -1)
         cost[t + 1] = np.where(ok, ncost, np.inf)
-        state = beam_gather_state(new, par[t + 1], W)
+        state = beam_gather_state(new, par[t + 1] if gather_par is None else gather_par(par[t + 1]), W)
     return dict(tok=tok, cost=cost, par=par, end=end)
 
 

@@ -9,7 +9,7 @@ tests/test_attention_geometry_inputs.py (CPU).  Nothing here needs a GPU.
   storage_distance what bf16 storage alone does to each gradient: the copy with rounding at make_plan's storage points
   beam_step_copy a copy of R.attn_beam_step_bf16_storage with the slot fault
   greedy_walk    the storage restatement at W = 1 walked along given tokens (its own arg-max when none are given)
-  beam_floor     tests/test_gpu_beam_bench_shape.py's `_floor` recipe on given inputs
+  beam_floor     tests/_beam_oracle.py's beam_distance, fp32 against float64 arithmetic, on given inputs
 """
 import functools
 
@@ -18,6 +18,8 @@ import torch
 import torch.nn.functional as F
 
 from oracle import restatement as R
+from tests._beam_oracle import StepOracle, beam_distance  # noqa: F401
+from tests._util import _bf16
 
 V = 50
 STEPS = 25          # RNN_Attn.cap_max_size
@@ -49,10 +51,6 @@ CASES = {
     "wide_feat": dict(E=16, F=4104, A=16, H=16, P=9, L=1, lens=[3, 2], seed=3, scale=16.0),
     "many_rows": dict(E=16, F=48, A=40, H=16, P=10, L=1, lens=_lens_many_rows(), seed=5, scale=9.0),
 }
-
-
-def _bf16(t):
-    return t.bfloat16().float()
 
 
 def features(B, Fd, P, seed, bf16):
@@ -271,16 +269,15 @@ def greedy_walk(params, feat, cell, storage, dt=torch.float64, tokens=None, star
     """The restatement of st_attn_greedy (R.attn_beam_*_bf16_storage at W = 1; `storage`: rounded to bf16 where the bf16 kernels
     store).  Step t is fed tokens[:, t - 1] (the start token at t = 0) from the walk's OWN state; without `tokens` it feeds its
     own arg-max.  Returns (logp (B, STEPS, V), alpha (B, STEPS, P), arg-max ids (B, STEPS))."""
-    p = {k: v.to(dt) for k, v in params.items()}
+    orc = StepOracle("attn", cell, params, feat, 1, storage, dt)
     B = feat.shape[0]
-    with torch.no_grad():
-        ctx, state = R.attn_beam_init_bf16_storage(p, feat.to(dt), 1, cell, storage)
-        tok = torch.full((B, 1), start_id, dtype=torch.long)
-        lps, als, ids = [], [], []
-        for t in range(STEPS):
-            logp, alpha, state = R.attn_beam_step_bf16_storage(p, ctx, tok, state, None, cell, storage)
-            lps.append(logp); als.append(alpha); ids.append(logp.max(1)[1])
-            tok = (ids[-1] if tokens is None else tokens[:, t]).view(B, 1)
+    _, state = orc.start()
+    tok = torch.full((B, 1), start_id, dtype=torch.long)
+    lps, als, ids = [], [], []
+    for t in range(STEPS):
+        logp, alpha, state = orc.step(tok, state)
+        lps.append(logp); als.append(alpha); ids.append(logp.max(1)[1])
+        tok = (ids[-1] if tokens is None else tokens[:, t]).view(B, 1)
     return torch.stack(lps, 1), torch.stack(als, 1), torch.stack(ids, 1)
 
 
@@ -305,63 +302,19 @@ def greedy_gap(bf16):
     return 4 * max(greedy_floor(case, cell, bf16)[0] for case in GREEDY_CASES for cell in ("gru", "lstm"))
 
 
-class BeamOracle:
-    """tests/test_gpu_beam_bench_shape.py's `_Oracle("attn", ...)` on any step function: follow() walks given records"""
-
-    def __init__(self, cell, params, feat, W, storage, dt=torch.float64, slot_fault=False):
-        self.cell, self.W, self.storage, self.B, self.fault = cell, W, storage, feat.shape[0], slot_fault
-        self.p = {k: v.to(dt) for k, v in params.items()}
-        with torch.no_grad():
-            self.ctx, self.state0 = R.attn_beam_init_bf16_storage(self.p, feat.to(dt), W, cell, storage)
-
-    @torch.no_grad()
-    def step(self, tok, state, par_next=None):
-        return beam_step_copy(self.p, self.ctx, tok, state, par_next, self.cell, self.storage, self.fault)
-
-    def free_run(self):
-        return R.beam_free_run(lambda tok, st: self.step(tok, st), self.state0, self.B, self.W, BEAM_T, 1, 2, np.float64)
-
-    def follow(self, rec):
-        """(no torch.no_grad() around the yields: two of these generators are walked in step, and a suspended one would hold it)"""
-        state = self.state0
-        for t in range(rec["end"].shape[0]):
-            logp, alpha, state = self.step(rec["tok"][t], state, rec["par"][t + 1])
-            yield t, logp, alpha
-
-
-def beam_distance(a, b, rec, W):
-    """max |d nll| of the recorded children (words, every token) and the alpha distances over the live rows between two
-    oracles walking the same records: the quantities checks B and D of tests/test_gpu_beam_bench_shape.py bound"""
-    out = dict(nll=0.0, nll_word=0.0, a_max=0.0, a_l2=0.0)
-    B = rec["tok"].shape[1]
-    done = np.zeros(B, bool)
-    for (t, lpa, ala), (_, lpb, alb) in zip(a.follow(rec), b.follow(rec)):
-        live = np.isfinite(rec["cost"][t]) & ~rec["end"][t].astype(bool) & ~done[:, None]
-        done = done | ~live.any(1)
-        live &= ~done[:, None]
-        bb, ww = np.nonzero(rec["par"][t + 1] >= 0)
-        if bb.size:
-            rows = torch.from_numpy(bb * W + rec["par"][t + 1][bb, ww])
-            col = torch.from_numpy(rec["tok"][t + 1][bb, ww])
-            d = (lpa[rows, col].double() - lpb[rows, col].double()).abs()
-            out["nll"] = max(out["nll"], d.max().item())
-            if (col != 2).any():
-                out["nll_word"] = max(out["nll_word"], d[col != 2].max().item())
-        if live.any():
-            lr = torch.from_numpy(live.reshape(-1))
-            d = ala.double()[lr] - alb.double()[lr]
-            out["a_max"] = max(out["a_max"], d.abs().max().item())
-            out["a_l2"] = max(out["a_l2"], (d.norm(dim=1) / alb.double()[lr].norm(dim=1)).max().item())
-    return out
+def beam_oracle(cell, params, feat, W, storage, dt=torch.float64, slot_fault=False):
+    """the attention decoder's StepOracle; with `slot_fault` on beam_step_copy's faulted step"""
+    fn = (lambda o, tok, state: beam_step_copy(o.p, o.ctx, tok, state, None, o.cell, o.storage, True)) if slot_fault else None
+    return StepOracle("attn", cell, params, feat, W, storage, dt, fn)
 
 
 @functools.lru_cache(maxsize=None)
 def beam_floor(case, cell, bf16, W):
-    """`_floor` of tests/test_gpu_beam_bench_shape.py on this case: fp32 against float64 arithmetic of the same restatement,
-    teacher-forced on the float64 oracle's own free-running records of FLOOR_IMAGES images"""
+    """fp32 against float64 arithmetic of the same restatement, teacher-forced on the float64 oracle's own free-running records of
+    FLOOR_IMAGES images"""
     params, feat = params_of(case, cell, bf16), beam_features(case, bf16)
-    o64 = BeamOracle(cell, params, feat, W, bf16)
-    return beam_distance(BeamOracle(cell, params, feat, W, bf16, torch.float32), o64, o64.free_run(), W)
+    o64 = beam_oracle(cell, params, feat, W, bf16)
+    return beam_distance(beam_oracle(cell, params, feat, W, bf16, torch.float32), o64, o64.free_run(BEAM_T))
 
 
 def storage_distance(case, cell):

@@ -27,6 +27,7 @@ import torch
 from oracle import restatement as R
 from tests import _attention_geometry_cases as G
 from tests import _dropout_cases as D
+from tests._beam_oracle import StepOracle, beam_distance
 from tests.test_gpu_decoder_bench_shape import GRAD_L2, GRAD_MAX, ROW_L2, _bf16, _bf16_params, _rel_l2, _rel_max, _row_l2
 
 V = 50
@@ -591,64 +592,21 @@ def beam_inputs(family, cell, bf16):
     return params, G.features(FLOOR_IMAGES, ATTN["F"], ATTN["P"], c["seed"] + 500, bf16)
 
 
-class BeamOracle:
-    """the storage restatement of one decoder's beam step on one batch (R.*_beam_*_bf16_storage): its own free-running search, or
-    the walk along given records, as tests/test_gpu_beam_bench_shape.py's _Oracle with a max_length of its own"""
-
-    def __init__(self, family, cell, params, feat, storage, dt=torch.float64):
-        self.family, self.cell, self.storage, self.B = family, cell, storage, feat.shape[0]
-        self.p = {k: v.to(dt) for k, v in params.items()}
-        with torch.no_grad():
-            if family == "plain":
-                self.ctx, self.state0 = None, R.rnn_beam_init_bf16_storage(self.p, feat.to(dt), BEAM_W, cell, storage)
-            else:
-                self.ctx, self.state0 = R.attn_beam_init_bf16_storage(self.p, feat.to(dt), BEAM_W, cell, storage)
-
-    @torch.no_grad()
-    def step(self, tok, state, par_next=None):
-        if self.family == "plain":
-            logp, state = R.rnn_beam_step_bf16_storage(self.p, tok, state, par_next, self.cell, self.storage)
-            return logp, None, state
-        return R.attn_beam_step_bf16_storage(self.p, self.ctx, tok, state, par_next, self.cell, self.storage)
-
-    def free_run(self):
-        return R.beam_free_run(lambda tok, st: self.step(tok, st), self.state0, self.B, BEAM_W, BEAM_T, 1, 2, np.float64)
-
-    def follow(self, rec):
-        state = self.state0
-        for t in range(rec["end"].shape[0]):
-            logp, alpha, state = self.step(rec["tok"][t], state, rec["par"][t + 1])
-            yield t, logp, alpha
+def beam_oracle(family, cell, params, feat, storage, dt=torch.float64):
+    """the storage restatement of one decoder's beam step on one batch at the beam width of the case"""
+    return StepOracle(family, cell, params, feat, BEAM_W, storage, dt)
 
 
 @functools.lru_cache(maxsize=None)
 def beam_floor(family, cell, bf16):
-    """`_floor` of tests/test_gpu_beam_bench_shape.py on these inputs: fp32 against float64 arithmetic of the same restatement,
-    teacher-forced on the float64 oracle's own free-running records of FLOOR_IMAGES images.  Returns dict(nll_word, nll, a_max, a_l2,
-    harvested: share of the first BEAM_IMAGES images with a finished hypothesis)"""
+    """fp32 against float64 arithmetic of the same restatement, teacher-forced on the float64 oracle's own free-running records of
+    FLOOR_IMAGES images (tests/_beam_oracle.beam_distance).  Returns dict(nll_word, nll, a_max, a_l2, harvested: share of the first
+    BEAM_IMAGES images with a finished hypothesis)"""
     params, feat = beam_inputs(family, cell, bf16)
-    o64, o32 = BeamOracle(family, cell, params, feat, bf16), BeamOracle(family, cell, params, feat, bf16, torch.float32)
-    rec = o64.free_run()
-    out = dict(nll=0.0, nll_word=0.0, a_max=0.0, a_l2=0.0, harvested=float(rec["end"][:, :BEAM_IMAGES].any((0, 2)).mean()))
-    done = np.zeros(feat.shape[0], bool)
-    for (t, lp64, a64), (_, lp32, a32) in zip(o64.follow(rec), o32.follow(rec)):
-        live = np.isfinite(rec["cost"][t]) & ~rec["end"][t].astype(bool) & ~done[:, None]
-        done = done | ~live.any(1)
-        live &= ~done[:, None]
-        bb, ww = np.nonzero(rec["par"][t + 1] >= 0)
-        if bb.size:
-            rows = torch.from_numpy(bb * BEAM_W + rec["par"][t + 1][bb, ww])
-            col = torch.from_numpy(rec["tok"][t + 1][bb, ww])
-            d = (lp32[rows, col].double() - lp64[rows, col]).abs()
-            out["nll"] = max(out["nll"], d.max().item())
-            if (col != 2).any():
-                out["nll_word"] = max(out["nll_word"], d[col != 2].max().item())
-        if a64 is not None and live.any():
-            lr = torch.from_numpy(live.reshape(-1))
-            d = a32.double()[lr] - a64[lr]
-            out["a_max"] = max(out["a_max"], d.abs().max().item())
-            out["a_l2"] = max(out["a_l2"], (d.norm(dim=1) / a64[lr].norm(dim=1)).max().item())
-    return out
+    o64 = beam_oracle(family, cell, params, feat, bf16)
+    rec = o64.free_run(BEAM_T)
+    return dict(beam_distance(beam_oracle(family, cell, params, feat, bf16, torch.float32), o64, rec),
+                harvested=float(rec["end"][:, :BEAM_IMAGES].any((0, 2)).mean()))
 
 
 # (family, cell, bf16) -> (|d nll| of words, of every token, max |d alpha|, worst per-row relative L2 of alpha) of beam_floor; the
@@ -666,7 +624,7 @@ BEAM_FLOORS = {
 
 
 def beam_bounds(family, cell, bf16):
-    """((words, every token), (alpha max, alpha rel_l2) or None) as _check_records of tests/test_gpu_beam_bench_shape.py takes them"""
+    """((words, every token), (alpha max, alpha rel_l2) or None) as check_records of tests/_beam_oracle.py takes them"""
     w, a, amax, al2 = BEAM_FLOORS[(family, cell, bf16)]
     return (4 * w, 4 * a), ((4 * amax, 4 * al2) if family == "attn" else None)
 
@@ -743,33 +701,29 @@ def sched_uniforms(seed=23):
 
 
 def sched_roll_in(family, cell, bf16, u, ids=None, dt=torch.float64):
-    """tests/_scheduled_sampling_cases.py's roll_in (without its faults) on the case's inputs, stepping its _Decoder: ids None: the
+    """tests/_scheduled_sampling_cases.py's roll_in (without its faults) on the case's inputs, stepping its walker: ids None: the
     oracle mixes its own tokens, else it walks the given input ids.  Returns (input_ids (B, T), replaced (B, T), lp (B, T, V))."""
     from tests import _scheduled_sampling_cases as K
 
-    class Decoder(K._Decoder):
-        def __init__(self):
-            params, feat, _, _ = (problem if family == "plain" else attn_problem)(SCHED_CASE, cell, bf16)
-            self.kind, self.cell, self.st = "rnn" if family == "plain" else "attn", cell, bf16
-            self.p, self.feat = {k: v.to(dt) for k, v in params.items()}, feat.to(dt)
-            self.B, self.V = feat.shape[0], params["linear.weight"].shape[0]
-    _, _, cap, lens = (problem if family == "plain" else attn_problem)(SCHED_CASE, cell, bf16)
-    dec = Decoder()
+    params, feat, cap, lens = (problem if family == "plain" else attn_problem)(SCHED_CASE, cell, bf16)
+    kind = "rnn" if family == "plain" else "attn"
+    start, step = K.walker(kind, cell, params, feat, bf16, dt)
+    Vn = params["linear.weight"].shape[0]
     B, T = cap.shape
-    rep = torch.from_numpy(K.mix_rule(dec.kind, lens, u[0].numpy(), SCHED_P))
+    rep = torch.from_numpy(K.mix_rule(kind, lens, u[0].numpy(), SCHED_P))
     out = cap.clone() if ids is None else ids.clone()
-    lps = torch.zeros(B, T, dec.V, dtype=dt)
+    lps = torch.zeros(B, T, Vn, dtype=dt)
     with torch.no_grad():
-        lp, state = dec.start()
-        first = 0 if dec.kind == "rnn" else 1              # the first slot a step's logits decide
-        if dec.kind != "rnn":
-            lp, state = dec.step(out[:, 0], state)
+        lp, state = start()
+        first = 0 if kind == "rnn" else 1              # the first slot a step's logits decide
+        if kind != "rnn":
+            lp, state = step(out[:, 0], state)
         for j in range(first, max(lens) - 1 + first):
             lps[:, j] = lp
             if ids is None:
                 out[:, j] = torch.where(rep[:, j], K._draw(lp, u[1][:, j]), out[:, j])
             if j + 1 < max(lens) - 1 + first:
-                lp, state = dec.step(out[:, j], state)
+                lp, state = step(out[:, j], state)
     return out, rep, lps
 
 

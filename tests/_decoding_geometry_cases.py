@@ -9,7 +9,7 @@ a GPU.
   paths         pure-Python mirror of the launch arithmetic of a decoding call (csrc/decode.hip, csrc/sample.hip, beam.py)
   Walk          one step of the decoder over n rows in float64, rounded to bf16 where the bf16 kernels store (`storage`: R._cells_storage's
                 rule), with the seeded faults of the step
-  BeamOracle    the walk over (image, slot) rows: the `orc` of tests/test_gpu_beam_bench_shape.py's _check_records, and its own search
+  beam_oracle   the walk over (image, slot) rows: the `orc` of tests/_beam_oracle.py's check_records; beam_search its own search
   sample_walk, roll_in    the oracle's own draws (with a fault), or the walk along given tokens
   judge_*       what the GPU test asserts of a call's output, as functions of that output alone: the CPU test hands them the
                 output of a faulty oracle and they must raise
@@ -22,11 +22,11 @@ import numpy as np
 import torch
 
 from oracle import restatement as R
-from tests import _beam_constraints_cases as BK
 from tests import _decoder_geometry_cases as Y
 from tests import _nucleus_cases as N
 from tests import _scheduled_sampling_cases as K
 from tests import test_sample_inputs as I
+from tests._beam_oracle import StepOracle, as_recorded, beam_distance, check_records
 from tests._decoder_depth_cases import END_BOOST
 from tests.test_gpu_decoder_bench_shape import _bf16, _bf16_params
 
@@ -221,89 +221,44 @@ def _with_pad(logits, lp):
 # beam search
 # ====================================================================================================================
 
-class BeamOracle:
-    """The walk over fixed (image, slot) rows b * W + w: `follow` is what _check_records of tests/test_gpu_beam_bench_shape.py reads,
-    `free_run` the oracle's own search (R.beam_free_run with the seeded faults of the selection)"""
-
-    def __init__(self, walk, feat, W):
-        self.walk, self.W, self.B = walk, W, feat.shape[0]
-        _, st = walk.start(feat)
-        self.state0 = tuple(None if s is None else s.repeat_interleave(W, 1) for s in st)
-
-    def step(self, tok, state, par_next=None):
-        logits, new = self.walk.step(np.asarray(tok).reshape(-1), state)
-        return torch.log_softmax(logits, 1), logits, (new if par_next is None else R.beam_gather_state(new, par_next, self.W))
-
-    def follow(self, rec):
-        state = self.state0
-        for t in range(rec["end"].shape[0]):
-            logp, _, state = self.step(rec["tok"][t], state, rec["par"][t + 1])
-            yield t, logp, None
-
-    def free_run(self, T=BEAM_T):
-        B, W, fault = self.B, self.W, self.walk.fault
-        tok = np.zeros((T + 1, B, W), np.int64); tok[0, :, 0] = START
-        cost = np.full((T + 1, B, W), np.inf); cost[0, :, 0] = 0
-        par = np.full((T + 1, B, W), -1, np.int32)
-        end = np.zeros((T, B, W), np.uint8)
-        done = np.zeros(B, bool)
-        state = self.state0
-        for t in range(T):
-            logp, logits, new = self.step(tok[t].clip(max=self.walk.V - 1), state)
-            k = min(W, logp.shape[1])
-            if fault == "last_word_never":
-                logp = logp.clone(); logp[:, -1] = -np.inf
-            if fault == "topk_over_pad":
-                logp = _with_pad(logits, logp)
-            tv, ti = torch.topk(logp, k, dim=1)
-            tv, ti = tv.numpy(), ti.numpy()
-            occupied = np.isfinite(cost[t])
-            ended = occupied & (tok[t] == END) & ~done[:, None]
-            live = occupied & ~ended & ~done[:, None]
-            done |= ~live.any(1)
-            live &= ~done[:, None]
-            end[t] = ended
-            cand = cost[t][:, :, None] - tv[:, ::-1].reshape(B, W, k)
-            flat = np.where(live[:, :, None], cand, np.inf).reshape(B, W * k)
-            order = np.argsort(flat, axis=1, kind="stable")[:, :W]
-            ncost = np.take_along_axis(flat, order, 1)
-            ok = np.isfinite(ncost)
-            tok[t + 1] = np.where(ok, np.take_along_axis(ti[:, ::-1].reshape(B, W * k), order, 1), 0)
-            par[t + 1] = np.where(ok, order // k, -1)
-            cost[t + 1] = np.where(ok, ncost, np.inf)
-            state = R.beam_gather_state(new, np.where(ok, 0, -1) if fault == "child_of_slot0" else par[t + 1], W)
-        return dict(tok=tok, cost=cost.astype(np.float32), par=par, end=end)
+def beam_oracle(walk, feat, W):
+    """The walk over fixed (image, slot) rows b * W + w as tests/_beam_oracle.py's StepOracle: every step, the feature step
+    included, is the walk's own, with its fault"""
+    def step(orc, tok, state):
+        orc.logits, new = walk.step(np.asarray(tok).reshape(-1).clip(max=walk.V - 1), state)
+        return torch.log_softmax(orc.logits, 1), None, new
+    orc = StepOracle("plain", walk.cell, walk.p, feat, W, walk.st, walk.p["linear.bias"].dtype, step)
+    orc.state0 = tuple(None if s is None else s.repeat_interleave(W, 1) for s in walk.start(feat)[1])
+    return orc
 
 
-class _Pairs:
-    """a BeamOracle as tests/_beam_constraints_cases.py's check_records reads it"""
+def beam_search(walk, feat, W, T=BEAM_T):
+    """the oracle's own search (R.beam_free_run), with the walk's fault of the selection if it has one"""
+    orc, fault = beam_oracle(walk, feat, W), walk.fault
 
-    def __init__(self, orc):
-        self.orc = orc
-
-    def follow(self, rec):
-        for t, logp, _ in self.orc.follow(rec):
-            yield t, logp
+    def candidates(t, logp, tok, par):
+        k = min(W, logp.shape[1])
+        if fault == "last_word_never":
+            logp = logp.clone(); logp[:, -1] = -np.inf
+        if fault == "topk_over_pad":
+            logp = _with_pad(orc.logits, logp)
+        return torch.topk(logp, k, dim=1)
+    return as_recorded(orc.free_run(T, candidates=candidates,
+                                    gather_par=(lambda par: np.where(par >= 0, 0, -1)) if fault == "child_of_slot0" else None))
 
 
 @functools.lru_cache(maxsize=None)
 def oracle_records(case, cell, bf16, W, fault=None):
-    return BeamOracle(Walk(case, cell, bf16, fault=fault), problem(case, cell, bf16)[1], W).free_run()
+    return beam_search(Walk(case, cell, bf16, fault=fault), problem(case, cell, bf16)[1], W)
 
 
 def judge_beam(rec, case, cell, bf16, W, tag="", cons=None):
-    """The records of a search walked by the oracle: _check_records of tests/test_gpu_beam_bench_shape.py (its checks A to C).  That
-    checker takes a live image to fill all W slots, which holds for V >= W; v_tiny at W = 8 and every constrained search go through
-    check_records of tests/_beam_constraints_cases.py instead, the same checks with the number of filled slots counted from the
-    candidates that exist (and, with `cons`, the ban rule)."""
-    from tests.test_gpu_beam_bench_shape import _check_records
+    """The records of a search walked by the oracle: check_records of tests/_beam_oracle.py (its checks A to C: the number of filled
+    slots is counted from the candidates that exist, v_tiny at W = 8 has 5 per node; with `cons`, the ban rule)"""
     V = CASES[case]["V"]
     assert ((rec["tok"] >= 0) & (rec["tok"] < V)).all(), (tag, "a recorded token outside the vocabulary")
-    orc = BeamOracle(Walk(case, cell, bf16), problem(case, cell, bf16)[1], W)
-    nll = beam_bound(case, cell, bf16)
-    if cons is None and V >= W:
-        return _check_records(rec, orc, (nll, nll), tag)
-    return BK.check_records(rec, _Pairs(orc), cons or (0, 0, None), nll, tag, rec.get("hist"))
+    orc = beam_oracle(Walk(case, cell, bf16), problem(case, cell, bf16)[1], W)
+    return check_records(rec, orc, beam_bound(case, cell, bf16), tag, cons, hist=rec.get("hist"))
 
 
 # ====================================================================================================================
@@ -470,18 +425,9 @@ def logit_scale(case, cell):
 def beam_floor(case, cell):
     """largest |d log p| of a recorded (parent, token) between the float64 oracle and its bf16-storage replica, both on the
     bf16-representable inputs and both following the replica's own search, over the case's beam widths"""
-    worst = 0.0
-    for W in CASES[case]["W"]:
-        rec = oracle_records(case, cell, True, W)
-        feat = problem(case, cell, True)[1]
-        o_st, o_pl = BeamOracle(Walk(case, cell, True), feat, W), BeamOracle(Walk(case, cell, True, storage=False), feat, W)
-        for (t, a, _), (_, b, _) in zip(o_st.follow(rec), o_pl.follow(rec)):
-            bb, ww = np.nonzero(rec["par"][t + 1] >= 0)
-            if bb.size:
-                rows = torch.from_numpy(bb * W + rec["par"][t + 1][bb, ww].astype(np.int64))
-                col = torch.from_numpy(rec["tok"][t + 1][bb, ww])
-                worst = max(worst, float((a[rows, col] - b[rows, col]).abs().max()))
-    return worst
+    feat = problem(case, cell, True)[1]
+    return max(beam_distance(beam_oracle(Walk(case, cell, True), feat, W), beam_oracle(Walk(case, cell, True, storage=False), feat, W),
+                             oracle_records(case, cell, True, W))["nll"] for W in CASES[case]["W"])
 
 
 @functools.lru_cache(maxsize=None)
@@ -548,7 +494,7 @@ SCHED_FLOORS = {
 
 
 def beam_bound(case, cell, bf16):
-    """NLL_ABS of _check_records, for words and <end> alike"""
+    """NLL_ABS of check_records, for words and <end> alike"""
     return 4 * BEAM_FLOORS[(case, cell)] if bf16 else FP32_REL * logit_scale(case, cell)
 
 

@@ -1,7 +1,7 @@
 """Shared by test_diverse_beam_inputs.py (CPU) and test_gpu_diverse_beam.py: the rule of diverse (group) beam search in plain
 Python (written from the text below, not from the kernel), the float64 oracle's own diverse search over the k-lists and over all V
-words of every node, a numpy float32 replica of one selection, and the walk of a search's records, group by group, against the
-oracle.
+words of every node and a numpy float32 replica of one selection.  The walk of a search's records, group by group, against the
+oracle is tests/_beam_oracle.py's check_records.
 
 The rule.  beam_width = W, num_beam_groups = G, W' = W / G, diversity_penalty = lam >= 0.
   * Slots g*W' .. (g+1)*W' - 1 are group g.  Fringe 0 holds <start> at cost 0 in slot g*W' of every group, the rest is empty (+inf).
@@ -22,10 +22,10 @@ import torch
 from oracle import restatement as R
 from tests import _beam_constraints_cases as K
 from tests._beam_constraints_cases import END, START, T
+from tests._beam_oracle import NONE, StepOracle, ban_mask, beam_distance, slot_paths
 
 INF = float("inf")
 LAMBDAS = (0.5, 2.0)                  # dyadic: lam * n is exact in every precision
-NONE = (0, 0, None)                   # no constraints
 # the decoders of the cases (fp32 and bf16 share them): (kind, cell, W, G, B, V); parameters and images are made as
 # _beam_constraints_cases makes those of its constraint set "all"
 DECODERS = {
@@ -74,17 +74,8 @@ def oracle(name, storage=False, dt=torch.float64):
     key = (name, storage, dt)
     if key not in _CACHE:
         kind, cell, W, G, B, vocab = DECODERS[name]
-        _CACHE[key] = K.Oracle(kind, cell, decoder_params(name), K.features(kind, B), W, storage, dt)
+        _CACHE[key] = StepOracle(kind, cell, decoder_params(name), K.features(kind, B), W, storage, dt)
     return _CACHE[key]
-
-
-def group_paths(tok, par, t, G):
-    """K.slot_paths for fringes whose roots sit in the first slot of every group"""
-    out = K.slot_paths(tok, par, t)
-    if t == 0:
-        Wg = tok.shape[2] // G
-        out[:, ::Wg, 0] = tok[0][:, ::Wg]
-    return out
 
 
 # ====================================================================================================================
@@ -129,7 +120,7 @@ def rule_image(raw, words, W, G, lam, member=False, sign=1.0, scope="earlier", o
 
 def free_run(orc, G, lam, cons=NONE, Tn=T, all_v=False, penalty_in_cost=False, sign=1.0, scope="earlier", member=False,
              unseeded=False, done_per_image=False, cross_parent=False, after_cut=False):
-    """The rule on K.Oracle, free running.  `all_v`: the candidates of a node are ALL its unbanned words, not its k most probable.
+    """The rule on a StepOracle, free running.  `all_v`: the candidates of a node are ALL its unbanned words, not its k most probable.
     The other keywords are the seeded faults of test_diverse_beam_inputs.py.  Returns the records and, per (iteration, image,
     group): `decided` [T][B][W] (the slot's candidate is not among its group's W' best by raw: the penalty chose it), `member_diff`
     [T][B][G] (a membership test in place of the count gives another chosen set), `gap` [T][B][G] (key distance between the last
@@ -150,9 +141,9 @@ def free_run(orc, G, lam, cons=NONE, Tn=T, all_v=False, penalty_in_cost=False, s
     state = orc.state0
     constrained = cons != NONE
     for t in range(Tn):
-        logp, new_state = orc.step(tok[t], state)
+        logp, _, new_state = orc.step(tok[t], state)
         logp = logp.double()
-        ban = torch.from_numpy(K.ban_mask(group_paths(tok, par, t, G), Vn, cons)) if constrained else torch.zeros(B * W, Vn, dtype=torch.bool)
+        ban = torch.from_numpy(ban_mask(slot_paths(tok, par, t, G), Vn, cons)) if constrained else torch.zeros(B * W, Vn, dtype=torch.bool)
         ranked = torch.sort(-(logp if after_cut else logp.masked_fill(ban, -np.inf)), dim=1, stable=True).indices.numpy()
         n_ok = (~ban).sum(1).numpy()
         lp, ban_np = logp.numpy(), ban.numpy()
@@ -287,117 +278,11 @@ def select_groups_f32(tok, cost, done, top_p, top_id, G, end_id, lam, hist_in=No
 
 
 # ====================================================================================================================
-# the walk: a diverse search's records, group by group, against the oracle, teacher-forced on them
+# the floor
 # ====================================================================================================================
-
-def check_group_records(rec, orc, G, lam, cons, nll_abs, tag, hist=None):
-    """K.check_records' method per group.  Exact: fringe 0 holds <start> at cost 0 in slot g*W' of every group and nothing else;
-    harvest flags and done per group; par = -1 exactly where cost = +inf; a parent is a live slot of its child's group; a live
-    group fills every slot for which an unbanned candidate exists; inside a group the keys fl32(cost + fl32(lam * n_v)) ascend, n_v
-    counted from the recorded tokens of the earlier groups at that step; no recorded token is banned for its parent; nothing is
-    harvested before min_length; `hist` [B][W][T+1] equals the paths along par.
-    Within nll_abs (B): the step cost against the oracle's unmasked -log p -- the recorded cost must not contain the penalty.
-    Within sel = 2 nll_abs (C), per group: over the oracle's unbanned candidates of the group's live nodes, keyed with lam * n_v,
-    every chosen candidate is at most sel above the W'-th key and every candidate more than sel below it is chosen.
-    No live slot is left out (asserted).  Returns the measured worst values."""
-    tok, cost, par, end = rec["tok"], rec["cost"], rec["par"], rec["end"].astype(bool)
-    Tn, B, W = end.shape
-    Wg = W // G
-    grp = np.arange(W) // Wg
-    roots = np.arange(W) % Wg == 0
-    m_len, sel = cons[0], 2 * nll_abs
-    f32 = np.float32
-    assert W % G == 0 and tok.shape == cost.shape == par.shape == (Tn + 1, B, W)
-    assert (tok[0][:, roots] == START).all() and (cost[0][:, roots] == 0).all(), (tag, "every group is seeded in its first slot")
-    assert np.isinf(cost[0][:, ~roots]).all() and (tok[0][:, ~roots] == 0).all() and (par[0] == -1).all(), (tag, "fringe 0")
-    done = np.zeros((B, G), bool)
-    m = dict(nll=0.0, chosen=-np.inf, missed=-np.inf, live=0, checked=0, harvested=0)
-    bad = []
-    for t, logp in orc.follow(rec):
-        logp = logp.double()
-        Vn = logp.shape[1]
-        k = min(W, Vn)
-        c_t = cost[t].astype(np.float64)
-        occupied = np.isfinite(c_t)
-        ended = occupied & (tok[t] == END) & ~done[:, grp]
-        assert np.array_equal(end[t], ended), (tag, t, "harvest flags per group")
-        assert not (ended.any() and t <= m_len), (tag, t, "harvested before min_length words")
-        m["harvested"] += int(ended.sum())
-        live = occupied & ~ended & ~done[:, grp]
-        done = done | ~live.reshape(B, G, Wg).any(2)
-        live &= ~done[:, grp]
-        n_c, n_p, n_t = cost[t + 1], par[t + 1], tok[t + 1]
-        filled = n_p >= 0
-        assert np.array_equal(filled, np.isfinite(n_c)), (tag, t, "par = -1 exactly where cost = +inf")
-        assert not filled[done[:, grp]].any(), (tag, t, "a finished group has a non-empty slot")
-        assert (n_p < W).all() and (n_t[~filled] == 0).all(), (tag, t)
-        bb, ww = np.nonzero(filled)
-        pw = n_p[bb, ww].astype(np.int64)
-        assert (pw // Wg == ww // Wg).all(), (tag, t, "a parent lies in its child's group")
-        assert live[bb, pw].all(), (tag, t, "the parent of a non-empty slot is a live slot")
-        assert (n_c[bb, ww] >= cost[t][bb, pw]).all(), (tag, t, "a child costs at least its parent")
-        # n_v of every recorded slot, and the keys of a group in slot order
-        earlier = filled[:, None, :] & (grp[None, None, :] < grp[None, :, None])          # (B, slot, earlier slot)
-        n_rec = ((n_t[:, :, None] == n_t[:, None, :]) & earlier).sum(2)
-        key_rec = np.where(filled, (n_c.astype(f32) + (f32(lam) * n_rec.astype(f32)).astype(f32)).astype(f32), f32(np.inf)).reshape(B, G, Wg)
-        assert (key_rec[:, :, :-1] <= key_rec[:, :, 1:]).all(), (tag, t, "the keys of a group ascend")
-        m["live"] += int(live.sum())
-        ban = K.ban_mask(group_paths(tok, par, t, G), Vn, cons)                            # (B * W, V)
-        n_cand = np.where(live, np.minimum(k, Vn - ban.reshape(B, W, Vn).sum(2)), 0).reshape(B, G, Wg).sum(2)
-        assert np.array_equal(filled.reshape(B, G, Wg).sum(2), np.minimum(Wg, n_cand)), (tag, t, "slots filled")
-        if bb.size == 0:
-            continue
-        assert not ban[bb * W + pw, n_t[bb, ww]].any(), (tag, t, "a recorded token is banned for its parent")
-        # B
-        rows = torch.from_numpy(bb * W + pw)
-        nll_o = -logp[rows, torch.from_numpy(n_t[bb, ww])].numpy()
-        nll_g = n_c[bb, ww].astype(np.float64) - c_t[bb, pw]
-        err = np.abs(nll_g - nll_o) - np.spacing(n_c[bb, ww].astype(f32)).astype(np.float64)
-        m["checked"] += int(bb.size)
-        m["nll"] = max(m["nll"], float(err.max()))
-        if err.max() > nll_abs:
-            i = int(err.argmax())
-            bad.append(("B", t, int(bb[i]), int(ww[i]), float(err[i])))
-        # C: per group, the oracle's unbanned candidates of the group's live nodes with their penalties
-        tv, ti = torch.topk(logp.masked_fill(torch.from_numpy(ban), -np.inf), k, dim=1)
-        tv, ti = tv.view(B, W, k).numpy(), ti.view(B, W, k).numpy()
-        n_o = ((ti[:, :, :, None] == n_t[:, None, None, :]) & earlier[:, :, None, :]).sum(3)      # (B, W, k)
-        cand = np.where(live[:, :, None], c_t[:, :, None] - tv + lam * n_o, np.inf)
-        kth = np.partition(cand.reshape(B, G, Wg * k), Wg - 1, axis=2)[:, :, Wg - 1]              # (B, G)
-        over = (c_t[bb, pw] + nll_o + lam * n_rec[bb, ww]) - kth[bb, ww // Wg]
-        over = np.where(np.isfinite(kth[bb, ww // Wg]), over, -np.inf)                            # fewer than W' candidates: all are chosen
-        m["chosen"] = max(m["chosen"], float(over.max()))
-        ident = np.arange(W)[None, :, None] * Vn + ti
-        chosen = np.where(filled, n_p.astype(np.int64) * Vn + n_t, -1)
-        present = (ident[:, :, :, None] == chosen[:, None, None, :]).any(3)
-        kth_w = np.where(np.isfinite(kth), kth, np.inf)[:, grp]
-        with np.errstate(invalid="ignore"):
-            below = np.where(present | ~np.isfinite(cand), -np.inf, kth_w[:, :, None] - cand)
-        m["missed"] = max(m["missed"], float(below.max()))
-        if over.max() > sel or below.max() > sel:
-            bad.append(("C", t, int(bb[int(over.argmax())]), float(over.max()), float(below.max())))
-    if hist is not None:
-        assert np.array_equal(hist.astype(np.int64), group_paths(tok, par, Tn, G)), (tag, "the kept paths are not the paths along par")
-    excluded = 1.0 - m["checked"] / max(1, int((par[1:] >= 0).sum()))
-    print(f"MEASURE {tag}: |d nll| {m['nll']:.2e} nats; selection: chosen above the W'-th key {m['chosen']:.2e}, missed below it "
-          f"{m['missed']:.2e}; live slots {m['live']}, harvested {m['harvested']}, checked {m['checked']}, excluded share {excluded}")
-    assert excluded == 0.0
-    assert not bad, (tag, nll_abs, bad[:8])
-    return m
-
 
 def floor(name, storage, lam, cons=NONE, Tn=T):
     """K.floor's method on the diverse free run: |d nll| of the restatement in fp32 against float64 arithmetic, both teacher-forced
     on the float64 oracle's own diverse search"""
-    G = DECODERS[name][3]
-    o64, o32 = oracle(name, storage), oracle(name, storage, torch.float32)
-    rec = free_run(o64, G, lam, cons, Tn)
-    W = o64.W
-    worst = 0.0
-    for (t, l64), (_, l32) in zip(o64.follow(rec), o32.follow(rec)):
-        bb, ww = np.nonzero(rec["par"][t + 1] >= 0)
-        if bb.size:
-            rows = torch.from_numpy(bb * W + rec["par"][t + 1][bb, ww].astype(np.int64))
-            col = torch.from_numpy(rec["tok"][t + 1][bb, ww])
-            worst = max(worst, float((l64[rows, col].double() - l32[rows, col].double()).abs().max()))
-    return worst
+    o64 = oracle(name, storage)
+    return beam_distance(oracle(name, storage, torch.float32), o64, free_run(o64, DECODERS[name][3], lam, cons, Tn))["nll"]

@@ -6,14 +6,11 @@ import torch
 import torch.nn.functional as F
 
 from oracle import restatement as R
+from tests._util import _bf16  # noqa: F401 (imported from here by other test modules)
 
 MOM32 = float(np.float32(0.1))                   # the kernel's momentum and 1 - momentum, in fp32
 KEEP32 = float(np.float32(1.0) - np.float32(0.1))
 RUNNING = ("running_mean", "running_var", "num_batches_tracked")
-
-
-def _bf16(t):
-    return t.bfloat16().float()
 
 
 def _params(seed, version=101):

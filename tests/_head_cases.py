@@ -21,6 +21,8 @@ import math
 
 import torch
 
+from tests._util import _bf16
+
 MOMENTUM, EPS = 0.01, 1e-5
 # name: (B, F, E, modes)
 CASES = {
@@ -65,10 +67,6 @@ def workspace_bytes(B, F, E, dtype):
     """st_head_workspace_bytes: dz [B][Ep], dz^T [E][Bp] and x^T [F][Bp] in the compute dtype, each at a 256-byte boundary."""
     es = 2 if dtype == "bfloat16" else 4
     return al256(B * up8(E) * es) + al256(E * up8(B) * es) + al256(F * up8(B) * es)
-
-
-def _bf16(t):
-    return t.bfloat16().float()
 
 
 @functools.lru_cache(maxsize=None)

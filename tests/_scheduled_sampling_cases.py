@@ -39,6 +39,7 @@ from oracle import restatement as R
 from tests import _dropout_cases as D
 from tests import _label_smoothing_cases as S
 from tests import _weighted_loss_cases as W
+from tests._beam_oracle import StepOracle
 
 CASES = {k: S.CASES[k] for k in ("gru777", "lstm1500", "gru130", "gru_fp32", "attn_fp32")}
 ROUTES = S.ROUTES                           # (case, ST_FUSED_CE): gru777 also on the launch chain
@@ -149,34 +150,19 @@ def mix_tokens(caption, drawn, replaced):
 FAULTS = ("flipped", "shifted", "past_length", "wrong_step")
 
 
-class _Decoder:
-    """The storage restatement of one case, stepping all B rows (W = 1) in `dt`."""
+def walker(kind, cell, params, feat, st, dt=torch.float64):
+    """The storage restatement stepping all B rows (W = 1) in `dt`: (start, step).  start() -> (plain: the log-probabilities of the
+    feature step, attention: None; the state after it / the root state); step(tok (B,), state) -> (log-probabilities, new state)."""
+    orc = StepOracle("plain" if kind == "rnn" else "attn", cell, params, feat, 1, st, dt)
 
-    def __init__(self, case, dt=torch.float64):
-        self.case, self.kind, self.cell, self.st = case, family(case), cell_of(case), storage(case)
-        self.p = {k: v.to(dt) for k, v in rollin_params(case).items()}
-        self.feat = inputs(case)[1].to(dt)
-        self.B = self.feat.shape[0]
-        self.V = self.p["linear.weight"].shape[0]
+    def start():
+        logits, state = orc.start()
+        return (None if logits is None else torch.log_softmax(logits, 1)), state
 
-    def start(self):
-        """plain: the state after the feature step and that step's log-probabilities; attention: the root state and None."""
-        p, cell, st, n = self.p, self.cell, self.st, self.B
-        if self.kind == "rnn":
-            Ln, Hd = R.num_layers_of(p), p["unit.weight_hh_l0"].shape[1]
-            h = self.feat.new_zeros(Ln, n, Hd)
-            c = self.feat.new_zeros(Ln, n, Hd) if cell != "gru" else None
-            top, h, c = R._cells_storage(p, R._store(self.feat, st), h, c, cell, st)
-            self.ctx = None
-            return torch.log_softmax(top @ p["linear.weight"].t() + p["linear.bias"], 1), (h, c)
-        self.ctx, state = R.attn_beam_init_bf16_storage(p, self.feat, 1, cell, st)
-        return None, state
-
-    def step(self, tok, state):
-        if self.kind == "rnn":
-            return R.rnn_beam_step_bf16_storage(self.p, tok.view(self.B, 1), state, None, self.cell, self.st)
-        lp, _, state = R.attn_beam_step_bf16_storage(self.p, self.ctx, tok.view(self.B, 1), state, None, self.cell, self.st)
+    def step(tok, state):
+        lp, _, state = orc.step(tok.view(orc.B, 1), state)
         return lp, state
+    return start, step
 
 
 def _draw(lp, u):
@@ -196,19 +182,20 @@ def roll_in(case, p=P, u=None, fault=None, ids=None, dt=torch.float64):
     u = uniforms(case) if u is None else u
     coin, du = u[0], u[1]
     B, T = cap.shape
-    dec = _Decoder(case, dt)
+    start, step = walker(kind, cell_of(case), rollin_params(case), inputs(case)[1], storage(case), dt)
+    Vn = rollin_params(case)["linear.weight"].shape[0]
     valid = torch.from_numpy(valid_slots(kind, lens if fault != "past_length" else [T + 1] * B, T))
     fire = (coin < np.float32(p)) if fault != "flipped" else ~(coin < np.float32(p))
     rep = valid & fire
     out = cap.clone() if ids is None else ids.clone()
     replaced = torch.zeros(B, T, dtype=torch.bool)
-    lps = torch.zeros(B, T, dec.V, dtype=dt)
+    lps = torch.zeros(B, T, Vn, dtype=dt)
     with torch.no_grad():
-        lp, state = dec.start()
-        prev = torch.full((B, dec.V), -float(np.log(dec.V)), dtype=dt)
+        lp, state = start()
+        prev = torch.full((B, Vn), -float(np.log(Vn)), dtype=dt)
         first = 0 if kind == "rnn" else 1                  # the first slot a step's logits decide
         if kind != "rnn":
-            lp, state = dec.step(out[:, 0], state)
+            lp, state = step(out[:, 0], state)
         for j in range(first, max(lens) - 1 + first):
             lps[:, j] = lp
             if ids is None:
@@ -219,7 +206,7 @@ def roll_in(case, p=P, u=None, fault=None, ids=None, dt=torch.float64):
                     replaced[:, dst] |= rep[:, j]
             prev = lp
             if j + 1 < max(lens) - 1 + first:
-                lp, state = dec.step(out[:, j], state)
+                lp, state = step(out[:, j], state)
     if ids is not None:
         replaced = rep
     return out, replaced, lps

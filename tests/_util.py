@@ -18,3 +18,8 @@ def load_fixture(name):
 
 def req_grad(params):
     return {k: (v.clone().requires_grad_(True) if v.is_floating_point() else v) for k, v in params.items()}
+
+
+def _bf16(t):
+    """t rounded to bf16, held in fp32"""
+    return t.bfloat16().float()

@@ -238,8 +238,8 @@ def test_slot_fault_moves_the_beam_checks(case, cell, W):
     ratios = []
     for bf16 in (False, True):
         params, feat = G.params_of(case, cell, bf16), G.beam_features(case, bf16)[:G.BEAM_IMAGES]
-        good = G.BeamOracle(cell, params, feat, W, bf16)
-        d = G.beam_distance(G.BeamOracle(cell, params, feat, W, bf16, slot_fault=True), good, good.free_run(), W)
+        good = G.beam_oracle(cell, params, feat, W, bf16)
+        d = G.beam_distance(G.beam_oracle(cell, params, feat, W, bf16, slot_fault=True), good, good.free_run(G.BEAM_T))
         nll, (a_max, a_l2) = _beam_bounds(case, cell, bf16)
         mult = 2 if bf16 else 10
         ratios.append(max(d["nll"] / nll[1], d["a_max"] / a_max, d["a_l2"] / a_l2) / mult)

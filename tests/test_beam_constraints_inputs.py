@@ -7,6 +7,7 @@ import torch
 
 from tests import _beam_constraints_cases as K
 from tests._beam_constraints_cases import END, START, T
+from tests._beam_oracle import StepOracle, as_recorded, check_records
 
 # the cases of test_gpu_beam_constraints.py, once per decoder (fp32 and bf16 share the parameters): (kind, cell, W, B, V)
 DECODERS = {"plain-gru": ("plain", "gru", 4, 24, 600), "plain-lstm": ("plain", "lstm", 4, 24, 600), "plain-gru-w8": ("plain", "gru", 8, 9, 2056),
@@ -23,8 +24,8 @@ _RUNS = {}
 def _run(name, cname):
     if (name, cname) not in _RUNS:
         kind, cell, W, B, vocab = DECODERS[name]
-        orc = K.Oracle(kind, cell, K.decoder_params(kind, cell, vocab, cname), K.features(kind, B), W, storage=False)
-        _RUNS[(name, cname)] = (orc, orc.free_run(K.CONSTRAINTS[cname]))
+        orc = StepOracle(kind, cell, K.decoder_params(kind, cell, vocab, cname), K.features(kind, B), W, storage=False)
+        _RUNS[(name, cname)] = (orc, K.free_run(orc, K.CONSTRAINTS[cname]))
     return _RUNS[(name, cname)]
 
 
@@ -127,9 +128,9 @@ def test_seeded_faults_are_caught_by_the_record_walk(name, fault):
     cname, kw = FAULTS[fault]
     orc, rec = _run(name, cname)
     cons = K.CONSTRAINTS[cname]
-    K.check_records(rec, orc, cons, NLL_ABS, f"{name} {cname} unbroken")
+    check_records(as_recorded(rec), orc, NLL_ABS, f"{name} {cname} unbroken", cons)
     with pytest.raises(AssertionError):
-        K.check_records(orc.free_run(cons, **kw), orc, cons, NLL_ABS, f"{name} {cname} {fault}")
+        check_records(as_recorded(K.free_run(orc, cons, **kw)), orc, NLL_ABS, f"{name} {cname} {fault}", cons)
 
 
 # ---- length-penalised ranking ------------------------------------------------------------------------------------------

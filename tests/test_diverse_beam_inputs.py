@@ -16,6 +16,7 @@ import torch
 from tests import _beam_constraints_cases as K
 from tests import _diverse_beam_cases as D
 from tests._beam_constraints_cases import END, START, T
+from tests._beam_oracle import as_recorded, check_records
 
 NLL_ABS = 4 * 2.5e-6          # the walk's bound on float64 records: 4 x the largest fp32 floor of test_gpu_diverse_beam
 MAIN = ("plain-gru", "plain-lstm", "attn-gru", "attn-lstm")     # cases 1, 2, 4 and 5
@@ -58,7 +59,7 @@ def test_the_penalty_decides_and_the_count_matters(name):
         assert filled >= 500 and decided >= 0.15 * filled
         if lam == 0.5:
             assert diff >= 20
-        D.check_group_records(rec, D.oracle(name), G, lam, D.NONE, NLL_ABS, f"{name} lam={lam} float64 free run")
+        check_records(as_recorded(rec), D.oracle(name), NLL_ABS, f"{name} lam={lam} float64 free run", D.NONE, G, lam)
 
 
 def _early(rec):
@@ -156,9 +157,9 @@ def test_seeded_faults_are_caught_by_the_group_walk(name, fault):
     lam, cname, kw = FAULTS[fault]
     G = D.DECODERS[name][3]
     cons = K.CONSTRAINTS[cname] if cname else D.NONE
-    D.check_group_records(_run(name, lam, cname), D.oracle(name), G, lam, cons, NLL_ABS, f"{name} unbroken")
+    check_records(as_recorded(_run(name, lam, cname)), D.oracle(name), NLL_ABS, f"{name} unbroken", cons, G, lam)
     with pytest.raises(AssertionError):
-        D.check_group_records(_run(name, lam, cname, **kw), D.oracle(name), G, lam, cons, NLL_ABS, f"{name} {fault}")
+        check_records(as_recorded(_run(name, lam, cname, **kw)), D.oracle(name), NLL_ABS, f"{name} {fault}", cons, G, lam)
 
 
 # ---- helpers ----------------------------------------------------------------------------------------------------------
@@ -168,7 +169,7 @@ def test_group_records_slices_and_rebases():
     rec = _run("attn-gru", 0.5)
     B, W = rec["tok"].shape[1:]
     full = dict(tok=rec["tok"], cost=rec["cost"].astype(np.float32), par=rec["par"], end=rec["end"],
-                hist=D.group_paths(rec["tok"], rec["par"], T, 3).astype(np.int32),
+                hist=K.slot_paths(rec["tok"], rec["par"], T, 3).astype(np.int32),
                 alpha=np.arange(T * B * W * 2, dtype=np.float32).reshape(T, B * W, 2))
     for g in range(3):
         r = group_records(full, g, 3)

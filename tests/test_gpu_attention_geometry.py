@@ -49,11 +49,11 @@ import torch
 import torch.nn as nn
 
 from tests import _attention_geometry_cases as G
+from tests._beam_oracle import check_records
 from tests.test_gpu_attention import VOCAB, _make
 from tests.test_gpu_attention_bench_shape import (ACCUM_L2, ACCUM_MAX, ALPHA_L2, ALPHA_MAX, F32_L2, F32_MAX, GRAD_L2, GRAD_MAX,
                                                   LOSS_REL, ROUTE_L2, ROUTE_MAX, ROW_SUM, _check_all_grads, _check_alphas,
                                                   _check_loss, _oracle)
-from tests.test_gpu_beam_bench_shape import _check_records
 from tests.test_gpu_decoder_bench_shape import _check_grads, _rel_l2, _rel_max
 
 pytestmark = pytest.mark.gpu
@@ -100,7 +100,7 @@ _CACHE = {}
 
 
 def _beam_bounds(case, cell, bf16):
-    """((words, every token), (alpha max, alpha rel_l2)) as _check_records takes them; <end> has no floor of its own here"""
+    """((words, every token), (alpha max, alpha rel_l2)) as check_records takes them; <end> has no floor of its own here"""
     nll, a_max, a_l2 = BEAM_BOUNDS[(case, cell, "bf16" if bf16 else "fp32")]
     return (nll, nll), (a_max, a_l2)
 
@@ -286,7 +286,7 @@ def test_beam_records_follow_the_oracle(case, cell, bf16, W):
     assert [[(s, c) for s, c, _ in h] for h in hyps] == replay_hypotheses(rec["tok"], rec["cost"], rec["par"], rec["end"], 1)
     assert (rec["par"][1:] >= 0).all(), "every image fills all W slots in every iteration"
     nll, alpha = _beam_bounds(case, cell, bf16)
-    _check_records(rec, G.BeamOracle(cell, params, feat, W, bf16), nll, f"C {_tag(case, cell, bf16)} W={W}", alpha_bounds=alpha)
+    check_records(rec, G.beam_oracle(cell, params, feat, W, bf16), nll, f"C {_tag(case, cell, bf16)} W={W}", alpha_bounds=alpha)
 
 
 # ====================================================================================================================

@@ -74,6 +74,7 @@ import pytest
 import torch
 
 from oracle import restatement as R
+from tests._beam_oracle import StepOracle, beam_distance, check_records
 from tests.test_gpu_attention_beam import _config3, _make
 from tests.test_gpu_decoder_bench_shape import _bf16, _bf16_params, _decoder
 
@@ -126,7 +127,6 @@ ALPHA = {
     ("gru", 8): (4 * 7.6e-6, 4 * 1.08e-4),                # 8.8e-6, 1.14e-4
     ("lstm", 8): (4 * 5.4e-5, 4 * 9.0e-4),                # 5.3e-5, 1.00e-3
 }
-ALPHA_SUM = 1e-5            # |sum - 1| of an fp32 softmax over 49 entries: 49 roundings of 6e-8 and the division; 1.7e-7
 # F: share of the 256 images whose first hypothesis the float64 and the fp32-arithmetic free-running oracle share (0.980, 0.957),
 # minus 0.1
 AGREE = {"gru": 0.980 - 0.1, "lstm": 0.957 - 0.1}       # 13/13, 13/13
@@ -228,38 +228,6 @@ def _assert_conditions(c, tag):
     assert c["live"] >= 0.4, (tag, c)               # at least 40 % of all (iteration, image, slot) entries are live
 
 
-class _Oracle:
-    """The storage oracle of one decoder on one batch: its own free-running search, or the walk along given records."""
-
-    def __init__(self, kind, cell, params, feat, W, storage=True, dt=torch.float64):
-        self.kind, self.cell, self.W, self.storage, self.B = kind, cell, W, storage, feat.shape[0]
-        self.p = {k: v.to(dt) for k, v in params.items()}
-        with torch.no_grad():
-            if kind == "plain":
-                self.ctx, self.state0 = None, R.rnn_beam_init_bf16_storage(self.p, feat.to(dt), W, cell, storage)
-            else:
-                self.ctx, self.state0 = R.attn_beam_init_bf16_storage(self.p, feat.to(dt), W, cell, storage)
-
-    def step(self, tok, state, par_next=None):
-        if self.kind == "plain":
-            logp, state = R.rnn_beam_step_bf16_storage(self.p, tok, state, par_next, self.cell, self.storage)
-            return logp, None, state
-        return R.attn_beam_step_bf16_storage(self.p, self.ctx, tok, state, par_next, self.cell, self.storage)
-
-    def free_run(self, cost_dtype=np.float64, keep=None):
-        with torch.no_grad():
-            return R.beam_free_run(lambda tok, st: self.step(tok, st), self.state0, self.B, self.W, T, START, END, cost_dtype, keep)
-
-    def follow(self, rec):
-        """yields (t, log_softmax rows (B*W, V), alpha (B*W, P) or None) of every iteration; one float64 block alive at a time"""
-        state = self.state0
-        with torch.no_grad():
-            for t in range(rec["end"].shape[0]):
-                logp, alpha, state = self.step(rec["tok"][t], state, rec["par"][t + 1])
-                yield t, logp, alpha
-                del logp, alpha
-
-
 def _base_params(kind, cell, Vv):
     if kind == "plain":
         return R.init_decoder_params(E, H, Vv, L, cell, seed=5)
@@ -278,106 +246,15 @@ def _family(kind, cell, Vv=V, W=5, conditions=True):
         _CACHE[key] = [params, torch.roll(feat, -ROTATE[kind], 0), None]
     ent = _CACHE[key]
     if conditions and ent[2] is None:
-        ent[2] = [_conditions(_Oracle(kind, cell, ent[0], ent[1][:n], W).free_run()) for n in COND_IMAGES[(kind, W)]]
+        ent[2] = [_conditions(StepOracle(kind, cell, ent[0], ent[1][:n], W, True).free_run(T)) for n in COND_IMAGES[(kind, W)]]
         for n, c in zip(COND_IMAGES[(kind, W)], ent[2]):
             _assert_conditions(c, f"{kind} {cell} V={Vv} W={W} first {n} images")
     return ent[0], ent[1]
 
 
 # ====================================================================================================================
-# the checker: A to D on one search's records
+# the checker (A to D on one search's records: tests/_beam_oracle.check_records), hypotheses, paths
 # ====================================================================================================================
-
-def _check_records(rec, orc, nll_abs, tag, alpha_bounds=None):
-    tok, cost, par, end = rec["tok"], rec["cost"], rec["par"], rec["end"].astype(bool)
-    Tn, B, W = end.shape
-    nll_word, nll_abs = nll_abs                                # (tokens other than <end>, every token)
-    sel = 2 * nll_abs                                          # two candidates, each off by at most NLL_ABS
-    assert tok.shape == cost.shape == par.shape == (Tn + 1, B, W) and cost.dtype == np.float32
-    # A: the root
-    assert (tok[0, :, 0] == START).all() and (cost[0, :, 0] == 0).all() and np.isinf(cost[0, :, 1:]).all() and (par[0] == -1).all()
-    done = np.zeros(B, bool)
-    m = dict(nll=0.0, nll_at=None, nll_w=0.0, chosen=-np.inf, missed=-np.inf, a_max=0.0, a_l2=0.0, a_sum=0.0, live=0, checked=0)
-    bad = []
-    for t, logp, alpha in orc.follow(rec):
-        c_t = cost[t].astype(np.float64)
-        occupied = np.isfinite(c_t)
-        ended = occupied & (tok[t] == END) & ~done[:, None]
-        assert np.array_equal(end[t], ended), (tag, t, "harvest flags")
-        live = occupied & ~ended & ~done[:, None]
-        done = done | ~live.any(1)
-        live &= ~done[:, None]
-        n_c, n_p, n_t = cost[t + 1], par[t + 1], tok[t + 1]
-        filled = n_p >= 0
-        assert np.array_equal(filled, np.isfinite(n_c)), (tag, t, "par = -1 exactly where cost = +inf")
-        assert not filled[done].any(), (tag, t, "a finished image has a non-empty slot")
-        # (the inputs keep every top-W probability far above the fp32 underflow, where -log p would be +inf: an empty slot)
-        assert filled[~done].all(), (tag, t, "a live image has W * V >= W candidates: every slot is filled")
-        assert (n_p < W).all() and (n_t[~filled] == 0).all(), (tag, t)
-        bb, ww = np.nonzero(filled)
-        pw = n_p[bb, ww].astype(np.int64)
-        assert live[bb, pw].all(), (tag, t, "the parent of a non-empty slot is a live slot")
-        with np.errstate(invalid="ignore"):
-            assert (n_c[:, :-1] <= n_c[:, 1:]).all(), (tag, t, "fringe costs ascend")
-        assert (n_c[bb, ww] >= cost[t][bb, pw]).all(), (tag, t, "a child costs at least its parent")
-        m["live"] += int(live.sum())
-        if bb.size == 0:
-            continue
-        # B: one number per live slot per iteration
-        rows = torch.from_numpy(bb * W + pw)
-        nll_o = -logp[rows, torch.from_numpy(n_t[bb, ww])].double().numpy()
-        nll_g = n_c[bb, ww].astype(np.float64) - c_t[bb, pw]
-        err = np.abs(nll_g - nll_o) - np.spacing(n_c[bb, ww]).astype(np.float64)
-        m["checked"] += int(bb.size)
-        i = int(err.argmax())
-        if err[i] > m["nll"]:
-            m["nll"], m["nll_at"] = float(err[i]), (t, int(bb[i]), int(ww[i]), int(pw[i]), int(n_t[bb[i], ww[i]]))
-        if err[i] > nll_abs:
-            bad.append(("B", t, int(bb[i]), int(ww[i]), float(err[i])))
-        word = n_t[bb, ww] != END
-        if word.any():
-            m["nll_w"] = max(m["nll_w"], float(err[word].max()))
-            if err[word].max() > nll_word:
-                j = int(np.where(word, err, -np.inf).argmax())
-                bad.append(("B word", t, int(bb[j]), int(ww[j]), float(err[j])))
-        # C: the oracle's candidates of all live parents; a parent's W best suffice for both statements
-        tv, ti = torch.topk(logp, min(W, logp.shape[1]), dim=1)
-        k = tv.shape[1]
-        tv, ti = tv.double().view(B, W, k).numpy(), ti.view(B, W, k).numpy()
-        cand = np.where(live[:, :, None], c_t[:, :, None] - tv, np.inf).reshape(B, W * k)
-        kth = np.partition(cand, W - 1, axis=1)[:, W - 1]                     # the oracle's W-th smallest (+inf: finished)
-        over = (c_t[bb, pw] + nll_o) - kth[bb]                                # chosen candidates: <= SEL
-        m["chosen"] = max(m["chosen"], float(over.max()))
-        Vk = logp.shape[1]
-        key = (np.arange(W)[None, :, None] * Vk + ti).reshape(B, W * k)
-        chosen = np.where(filled, n_p.astype(np.int64) * Vk + n_t, -1)
-        present = (key[:, :, None] == chosen[:, None, :]).any(2)
-        with np.errstate(invalid="ignore"):
-            below = np.where(present | ~np.isfinite(cand), -np.inf, kth[:, None] - cand)   # not chosen: how far below the W-th
-        m["missed"] = max(m["missed"], float(below.max()))
-        if over.max() > sel or below.max() > sel:
-            bad.append(("C", t, int(bb[int(over.argmax())]), float(over.max()), float(below.max())))
-        # D: the recorded attention map of every live row
-        if alpha is not None:
-            lr = torch.from_numpy(live.reshape(-1))
-            got, ref = torch.from_numpy(rec["alpha"][t]).double()[lr], alpha.double()[lr]
-            m["a_max"] = max(m["a_max"], (got - ref).abs().max().item())
-            m["a_l2"] = max(m["a_l2"], ((got - ref).norm(dim=1) / ref.norm(dim=1)).max().item())
-            m["a_sum"] = max(m["a_sum"], (got.sum(1) - 1).abs().max().item())
-            assert (got >= 0).all()
-    excluded = 1.0 - m["checked"] / max(1, int((par[1:] >= 0).sum()))
-    print(f"MEASURE {tag}: |d nll| of words {m['nll_w']:.2e}, of all tokens {m['nll']:.2e} nats at (t, b, w, parent, token) "
-          f"{m['nll_at']}; selection: chosen above the "
-          f"W-th {m['chosen']:.2e}, missed below it {m['missed']:.2e}; live share {m['live'] / float(Tn * B * W):.2f}; "
-          f"slots checked {m['checked']}, excluded share {excluded}"
-          + (f"; alpha max {m['a_max']:.2e} rel_l2 {m['a_l2']:.2e} |sum - 1| {m['a_sum']:.2e}" if alpha_bounds else ""))
-    assert excluded == 0.0
-    assert not bad, (tag, nll_abs, bad[:8])
-    assert m["nll_w"] <= nll_word and m["nll"] <= nll_abs and m["chosen"] <= sel and m["missed"] <= sel, (tag, m)
-    if alpha_bounds:
-        assert m["a_max"] <= alpha_bounds[0] and m["a_l2"] <= alpha_bounds[1] and m["a_sum"] <= ALPHA_SUM, (tag, m)
-    return m
-
 
 def _check_hypotheses(hyps, nh):
     for hyp in hyps:
@@ -445,7 +322,7 @@ def test_plain_beam5_records_follow_the_storage_oracle(cell, B):
             102: 512 - 16 < rows < 512, 13: rows < 512, 1: rows < 16}[B]
     params, feat = _family("plain", cell)
     rec = _plain_search(cell, B)
-    _check_records(rec, _Oracle("plain", cell, params, feat[:B], 5), NLL_ABS[("plain", cell, 5)], f"plain {cell} B={B} W=5")
+    check_records(rec, StepOracle("plain", cell, params, feat[:B], 5, True), NLL_ABS[("plain", cell, 5)], f"plain {cell} B={B} W=5")
 
 
 def test_plain_gru_ragged_vocabulary_width8():
@@ -455,14 +332,14 @@ def test_plain_gru_ragged_vocabulary_width8():
     assert COND_IMAGES[("plain", W)] == (B,)              # the input conditions are asserted on these 33 images
     params, feat = _family("plain", "gru", Vv, W)
     rec = _plain_search("gru", B, W, Vv)
-    _check_records(rec, _Oracle("plain", "gru", params, feat[:B], W), NLL_ABS[("plain", "gru", W)], "plain gru B=33 W=8 V=10003")
+    check_records(rec, StepOracle("plain", "gru", params, feat[:B], W, True), NLL_ABS[("plain", "gru", W)], "plain gru B=33 W=8 V=10003")
 
 
 def test_plain_gru_fp32_through_the_same_checker():
     """The fp32 kernels against the unrounded float64 oracle: only the summation order differs.  The floor of the checker."""
     params, feat = _family("plain", "gru")
     rec = _plain_search("gru", 256, dtype=torch.float32)
-    _check_records(rec, _Oracle("plain", "gru", params, feat, 5, storage=False), NLL_ABS_F32, "plain gru fp32 B=256 W=5")
+    check_records(rec, StepOracle("plain", "gru", params, feat, 5, storage=False), NLL_ABS_F32, "plain gru fp32 B=256 W=5")
 
 
 @pytest.mark.parametrize("cell", ["gru", "lstm"])
@@ -503,8 +380,8 @@ def test_attention_beam_records_follow_the_storage_oracle(cell, B, W):
         for s, c, a in hyp:
             want = np.stack([rec["alpha"][t - 1, b * W + rec["par"][t, b, w]] for t, w in paths[(tuple(s), c)]])
             assert a.dtype == torch.float32 and np.array_equal(a.numpy(), want), b
-    _check_records(rec, _Oracle("attn", cell, params, feat[:B], W), NLL_ABS[("attn", cell, W)], f"attention {cell} B={B} W={W}",
-                   alpha_bounds=ALPHA[(cell, W)])
+    check_records(rec, StepOracle("attn", cell, params, feat[:B], W, True), NLL_ABS[("attn", cell, W)], f"attention {cell} B={B} W={W}",
+                  alpha_bounds=ALPHA[(cell, W)])
 
 
 # G: the head's output against float64 Linear + BatchNorm1d(eval) of the GPU's pooled features, of max |ref|.  The head's
@@ -550,7 +427,7 @@ def test_end_to_end_configs4_images_to_beam_search(monkeypatch):
     assert hyps == beam.replay_hypotheses(rec["tok"], rec["cost"], rec["par"], rec["end"], 1)
     _check_hypotheses(hyps, 1)
     print("MEASURE G conditions of the GPU's search:", _conditions(rec))
-    _check_records(rec, _Oracle("plain", "gru", params, y.float().cpu(), 5), NLL_ABS[("plain", "gru", 5)], "G configs[4] 16 images")
+    check_records(rec, StepOracle("plain", "gru", params, y.float().cpu(), 5, True), NLL_ABS[("plain", "gru", 5)], "G configs[4] 16 images")
 
 
 # ====================================================================================================================
@@ -563,8 +440,8 @@ def _floor(kind, cell, B, W=5, Vv=V, storage=True):
     hypothesis the two free-running searches share"""
     from showtell_amd.beam import replay_hypotheses
     params, feat = _family(kind, cell, Vv, W, conditions=False)
-    o64 = _Oracle(kind, cell, params, feat[:B], W, storage)
-    o32 = _Oracle(kind, cell, params, feat[:B], W, storage, torch.float32)
+    o64 = StepOracle(kind, cell, params, feat[:B], W, storage)
+    o32 = StepOracle(kind, cell, params, feat[:B], W, storage, torch.float32)
     gaps = []
 
     def gap_of(t, out, cost_t, live):
@@ -573,30 +450,11 @@ def _floor(kind, cell, B, W=5, Vv=V, storage=True):
         c = np.sort(np.where(live[:, :, None], cost_t[:, :, None] - tv, np.inf).reshape(B, -1), axis=1)
         ok = np.isfinite(c[:, W])
         gaps.append(c[ok, W] - c[ok, W - 1])
-    rec = o64.free_run(keep=gap_of)
+    rec = o64.free_run(T, keep=gap_of)
     gap = np.concatenate(gaps)
-    out = dict(cond=_conditions(rec), gap_min=float(gap.min()), gap_q01=float(np.quantile(gap, 0.01)), nll=0.0, nll_word=0.0,
-               a_max=0.0, a_l2=0.0)
-    done = np.zeros(B, bool)
-    for (t, lp64, a64), (_, lp32, a32) in zip(o64.follow(rec), o32.follow(rec)):
-        live = np.isfinite(rec["cost"][t]) & ~rec["end"][t].astype(bool) & ~done[:, None]
-        done = done | ~live.any(1)
-        live &= ~done[:, None]
-        bb, ww = np.nonzero(rec["par"][t + 1] >= 0)
-        if bb.size:
-            rows = torch.from_numpy(bb * W + rec["par"][t + 1][bb, ww])
-            col = torch.from_numpy(rec["tok"][t + 1][bb, ww])
-            d = (lp32[rows, col].double() - lp64[rows, col]).abs()
-            out["nll"] = max(out["nll"], d.max().item())
-            if (col != END).any():
-                out["nll_word"] = max(out["nll_word"], d[col != END].max().item())
-        if a64 is not None and live.any():
-            lr = torch.from_numpy(live.reshape(-1))
-            d = a32.double()[lr] - a64[lr]
-            out["a_max"] = max(out["a_max"], d.abs().max().item())
-            out["a_l2"] = max(out["a_l2"], (d.norm(dim=1) / a64[lr].norm(dim=1)).max().item())
+    out = dict(cond=_conditions(rec), gap_min=float(gap.min()), gap_q01=float(np.quantile(gap, 0.01)), **beam_distance(o32, o64, rec))
     h64 = replay_hypotheses(rec["tok"], rec["cost"], rec["par"], rec["end"], 1)
-    r32 = o32.free_run()
+    r32 = o32.free_run(T)
     h32 = replay_hypotheses(r32["tok"], r32["cost"], r32["par"], r32["end"], 1)
     out["agree"] = float(np.mean([(a[0][0] if a else None) == (b[0][0] if b else None) for a, b in zip(h64, h32)]))
     return out

@@ -1,7 +1,7 @@
 """Constrained beam search on the GPU (min_length, no_repeat_ngram_size, suppress_tokens, length_penalty): the ban kernel
 against torch, the no-op identity, the searches' records walked by the float64 oracle, and the loud failures.
 
-The walk is the method of test_gpu_beam_bench_shape.py at small shapes (tests/_beam_constraints_cases.check_records): the oracle
+The walk is the method of test_gpu_beam_bench_shape.py at small shapes (tests/_beam_oracle.check_records): the oracle
 is teacher-forced on the GPU's own records and for every iteration, image and slot checks, exactly, the bookkeeping, that no
 recorded token is banned for its parent (ban sets from the plain-Python rule), that nothing is harvested before min_length and
 that the paths the search kept are the paths along `par`; and within a bound the step cost against the oracle's UNMASKED -log p
@@ -26,6 +26,7 @@ import torch
 
 from tests import _beam_constraints_cases as K
 from tests._beam_constraints_cases import END, START, T
+from tests._beam_oracle import StepOracle, check_records
 
 pytestmark = pytest.mark.gpu
 
@@ -234,9 +235,9 @@ def test_constrained_records_follow_the_oracle(name, cname):
     cons = K.CONSTRAINTS[cname]
     m, feat = _model(kind, cell, dtype, vocab, cname), K.features(kind, B)
     hyps, rec = _search(kind, m, feat.cuda(), W, 1, **_kw(cons))
-    orc = K.Oracle(kind, cell, K.decoder_params(kind, cell, vocab, cname), feat, W, storage=dtype == "bf16")
+    orc = StepOracle(kind, cell, K.decoder_params(kind, cell, vocab, cname), feat, W, storage=dtype == "bf16")
     assert rec["hist"].shape == (B, W, T + 1)                         # both decoder families hand out the paths they kept
-    K.check_records(rec, orc, cons, 4 * FLOOR[name], f"{name} {cname}", rec["hist"])
+    check_records(rec, orc, 4 * FLOOR[name], f"{name} {cname}", cons, hist=rec["hist"])
     for hyp in hyps:                                                  # well formed, and constrained
         for h in hyp:
             seq = h[0]
@@ -307,8 +308,8 @@ def test_host_fallback_at_w9_against_the_oracle_free_run(cname):
     margin = 2 * T * nll_abs
     m, feat = _model("plain", "gru", "fp32", 600, cname), K.features("plain", B)
     got = beam_search(m, feat.cuda(), W, 2, T, START, END, **_kw(cons))
-    orc = K.Oracle("plain", "gru", K.decoder_params("plain", "gru", 600, cname), feat, W, storage=False)
-    rec = orc.free_run(cons)
+    orc = StepOracle("plain", "gru", K.decoder_params("plain", "gru", 600, cname), feat, W, storage=False)
+    rec = K.free_run(orc, cons)
     want = replay_hypotheses(rec["tok"], rec["cost"], rec["par"], rec["end"], 2)
     safe = 0
     for b in range(B):

@@ -22,6 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from oracle import restatement as R
+from tests._util import _bf16  # noqa: F401 (imported from here by other test modules)
 
 pytestmark = pytest.mark.gpu
 
@@ -33,10 +34,6 @@ GRAD_L2 = 1e-2      # every gradient: A 5.3e-3, B 6.4e-3; SGD updates beyond one
 GRAD_MAX = 4e-2     # A 5.3e-3, B 6.6e-3; updates 5.3e-3; BN1d batch statistics 4.6e-6
 ROW_L2 = 3e-2       # per sample d loss / d feat: A 6.9e-3, B 7.0e-3
 BIAS_ELEM = 1e-2    # A linear.bias elementwise 2.1e-3 of max|ref|; B head Linear bias 5.0e-4 (grad), 7.3e-4 (update)
-
-
-def _bf16(t):
-    return t.bfloat16().float()
 
 
 def _bf16_params(params):

@@ -351,7 +351,7 @@ def test_beam_records_follow_the_oracle_at_eight_layers(family, cell, bf16):
     """W = 4, max_length = 8, 3 images of eight_long: the records walked as tests/test_gpu_beam_bench_shape.py walks them (its checks
     A to D); the plain decoders' device selection against the host bookkeeping as tests/test_gpu_beam.py compares them"""
     from showtell_amd.beam import beam_search_host, beam_search_records, replay_hypotheses
-    from tests.test_gpu_beam_bench_shape import _check_records
+    from tests._beam_oracle import check_records
     params, feat = Z.beam_inputs(family, cell, bf16)
     feat = feat[:Z.BEAM_IMAGES]
     W, T = Z.BEAM_W, Z.BEAM_T
@@ -376,7 +376,7 @@ def test_beam_records_follow_the_oracle_at_eight_layers(family, cell, bf16):
         assert rec["alpha"].shape == (T, Z.BEAM_IMAGES * W, Z.ATTN["P"])
         assert [[(s, cc) for s, cc, _ in h] for h in hyps] == replay_hypotheses(rec["tok"], rec["cost"], rec["par"], rec["end"], 1)
     assert rec["end"].any(), "some hypothesis ends within 8 words (Z.END_BOOST)"
-    _check_records(rec, Z.BeamOracle(family, cell, params, feat, bf16), nll, tag, alpha_bounds=alpha)
+    check_records(rec, Z.beam_oracle(family, cell, params, feat, bf16), nll, tag, alpha_bounds=alpha)
 
 
 # ====================================================================================================================

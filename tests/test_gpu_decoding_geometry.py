@@ -15,9 +15,8 @@ that every judge used here rejects the seeded faults, on the CPU):
   v_tiny     E = H = 16, L = 1, V = 5, B = 7: at W = 8 k = V = 5 < W, 40 candidates per image, a first fringe of 5 nodes in 8 slots
   tall_beam  E = H = 16, L = 1, V = 50, B = 130: W = 4 makes 520 rows per step, S = 4 makes 520 sampled rows: the two-row-tile cell kernel
 
-1  beam records (W in {4, 8}, max_length 8): walked by _check_records of tests/test_gpu_beam_bench_shape.py (v_tiny at W = 8, where a
-   live image cannot fill 8 slots from 5 candidates, by check_records of tests/_beam_constraints_cases.py, which counts the slots
-   from the candidates that exist); beam_search is the replay of the records; device against host selection; some hypothesis ends
+1  beam records (W in {4, 8}, max_length 8): walked by check_records of tests/_beam_oracle.py, which counts the filled slots from
+   the candidates that exist (v_tiny at W = 8: a live image cannot fill 8 slots from 5 candidates); beam_search is the replay of the records; device against host selection; some hypothesis ends
 2  constrained beam (e_wider, v2049; min_length 3, no_repeat_ngram_size 2, three suppressed ids): no recorded token banned for its
    parent, `hist` against the paths along `par`; an empty ban set gives the unconstrained records bit for bit
 3  sample(num_samples = 2 (tall_beam: 4), max_length = 6): unfiltered, and with top_k = 3 and top_p = 0.8; the oracle walks the GPU's tokens

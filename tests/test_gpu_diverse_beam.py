@@ -2,7 +2,7 @@
 replica on hand-built fringes, G = 1 against the recorded outputs of the single-beam kernel it replaced, the searches' records walked group by
 group by the float64 oracle, the returned hypotheses against the replayed groups, and the loud failures.
 
-The walk is tests/_diverse_beam_cases.check_group_records: test_gpu_beam_constraints.py's method per group.  The oracle is
+The walk is tests/_beam_oracle.check_records: test_gpu_beam_constraints.py's method per group.  The oracle is
 teacher-forced on the GPU's own records and checks, exactly, the bookkeeping of every group (seeding, harvest flags and done per
 group, parents inside the group, slots filled, keys ascending, no recorded token banned, hist = the paths along par) and, within a
 bound, the step cost against the oracle's unmasked -log p (B: the recorded cost must not contain the penalty) and the selection of
@@ -25,6 +25,7 @@ import torch
 from tests import _beam_constraints_cases as K
 from tests import _diverse_beam_cases as D
 from tests._beam_constraints_cases import END, START, T
+from tests._beam_oracle import check_records
 
 pytestmark = pytest.mark.gpu
 
@@ -255,7 +256,7 @@ def test_diverse_records_follow_the_oracle(case, lam, setting):
     hist = rec.get("hist")
     if setting == "all" or kind == "attn":
         assert hist is not None and hist.shape == (B, W, T + 1)                 # the paths the search kept
-    D.check_group_records(rec, D.oracle(name, storage=dtype == "bf16"), G, lam, cons, 4 * FLOOR[case], f"{case} lam={lam} {setting}", hist)
+    check_records(rec, D.oracle(name, storage=dtype == "bf16"), 4 * FLOOR[case], f"{case} lam={lam} {setting}", cons, G, lam, hist=hist)
     assert len(hyps) == B and all(len(h) == G for h in hyps)
     for per_image in hyps:
         for group in per_image:

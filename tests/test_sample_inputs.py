@@ -1,9 +1,9 @@
 """Inputs of the caption-sampling tests (tests/test_gpu_sample.py imports the builders and the oracle from here), and the
 proof, from the float64 oracle alone, that these inputs can catch a fault.  Nothing here needs a GPU.
 
-The oracle is oracle/restatement.py's teacher-forced storage restatement at W = 1 (`_cells_storage`,
-`rnn_beam_step_bf16_storage`, `attn_beam_init_bf16_storage`, `attn_beam_step_bf16_storage`) on bf16-representable weights,
-in float64; `Oracle.run` either draws its own tokens from the uniforms (free running) or walks given tokens.
+The oracle is oracle/restatement.py's teacher-forced storage restatement at W = 1 (tests/_beam_oracle.py's StepOracle:
+`_cells_storage`, `rnn_beam_step_bf16_storage`, `attn_beam_init_bf16_storage`, `attn_beam_step_bf16_storage`) on bf16-representable
+weights, in float64; `Oracle.run` either draws its own tokens from the uniforms (free running) or walks given tokens.
 
 A default-scaled decoder is nearly uniform over the vocabulary: every row has the same CDF and no check of "the token
 that u selects" could tell one row from another.  So the vocabulary projection and the cells' matrices (unit.weight_*) are
@@ -25,6 +25,8 @@ import pytest
 import torch
 
 from oracle import restatement as R
+from tests._beam_oracle import StepOracle
+from tests._util import _bf16
 
 START, END = 1, 2
 T = 25
@@ -49,10 +51,6 @@ SHAPES = {"plain": ((40, 1), (23, 11)), "attn": ((24, 1), (24, 3))}
 TEMPERATURES = {"plain": (1.0, 0.7), "attn": (1.0,)}
 
 _CACHE = {}
-
-
-def _bf16(t):
-    return t.bfloat16().float()
 
 
 def inv_temperature(temperature):
@@ -97,50 +95,38 @@ class Oracle:
 
     def __init__(self, kind, cell, params, feat, S, storage=True, dt=torch.float64):
         self.kind, self.cell, self.storage = kind, cell, storage
-        self.p = {k: v.to(dt) for k, v in params.items()}
-        self.feat = feat.to(dt).repeat_interleave(S, 0)
-        self.n = self.feat.shape[0]
+        self.orc = StepOracle(kind, cell, params, feat.repeat_interleave(S, 0), 1, storage, dt)
+        self.p, self.feat, self.n = self.orc.p, self.orc.feat, self.orc.B
 
     def run(self, u, temperature=1.0, ids=None, steps=T):
         """u (n, steps).  ids None: the oracle draws its own tokens (free running: the smallest v whose inclusive cumulative
         probability exceeds u; 0 after <end>); else it walks the given ids (n, steps), teacher-forced, its state never taken
         from anywhere else.  Returns (ids, logp (n, steps, V) = log_softmax(logits * inv_temperature) of every step, alphas
         (n, steps, P) or None)."""
-        p, cell, st, n = self.p, self.cell, self.storage, self.n
+        orc, n = self.orc, self.n
         it = inv_temperature(temperature)
-        Vn = p["linear.weight"].shape[0]
         out_ids = torch.zeros(n, steps, dtype=torch.long)
         lps, als = [], []
         fin = torch.zeros(n, dtype=torch.bool)
-        with torch.no_grad():
-            ctx = None
-            if self.kind == "plain":
-                Ln, Hd = R.num_layers_of(p), p["unit.weight_hh_l0"].shape[1]
-                h = self.feat.new_zeros(Ln, n, Hd)
-                c = self.feat.new_zeros(Ln, n, Hd) if cell != "gru" else None
-                top, h, c = R._cells_storage(p, R._store(self.feat, st), h, c, cell, st)     # step 0: the feature from a zero state
-                raw, alpha, state = top @ p["linear.weight"].t() + p["linear.bias"], None, (h, c)
+        raw, state = orc.start()                                             # plain: step 0 is the feature from a zero state
+        alpha = None
+        if raw is None:
+            raw, alpha, state = orc.step(torch.full((n, 1), START), state)
+        for t in range(steps):
+            lp = torch.log_softmax(raw * it, 1)
+            lps.append(lp)
+            als.append(alpha)
+            if ids is None:
+                cdf = lp.exp().cumsum(1)
+                tok = (cdf <= u[:, t].to(cdf.dtype)[:, None]).sum(1).clamp(max=orc.V - 1)
+                tok = torch.where(fin, torch.zeros_like(tok), tok)
             else:
-                ctx, state = R.attn_beam_init_bf16_storage(p, self.feat, 1, cell, st)
-                raw, alpha, state = R.attn_beam_step_bf16_storage(p, ctx, torch.full((n, 1), START), state, None, cell, st)
-            for t in range(steps):
-                lp = torch.log_softmax(raw * it, 1)
-                lps.append(lp)
-                als.append(alpha)
-                if ids is None:
-                    cdf = lp.exp().cumsum(1)
-                    tok = (cdf <= u[:, t].to(cdf.dtype)[:, None]).sum(1).clamp(max=Vn - 1)
-                    tok = torch.where(fin, torch.zeros_like(tok), tok)
-                else:
-                    tok = ids[:, t]
-                out_ids[:, t] = tok
-                fin |= tok == END
-                if t + 1 == steps:
-                    break
-                if self.kind == "plain":
-                    raw, state = R.rnn_beam_step_bf16_storage(p, tok.view(n, 1), state, None, cell, st)
-                else:
-                    raw, alpha, state = R.attn_beam_step_bf16_storage(p, ctx, tok.view(n, 1), state, None, cell, st)
+                tok = ids[:, t]
+            out_ids[:, t] = tok
+            fin |= tok == END
+            if t + 1 == steps:
+                break
+            raw, alpha, state = orc.step(tok.view(n, 1), state)
         return out_ids, torch.stack(lps, 1), (None if als[0] is None else torch.stack(als, 1))
 
 

@@ -29,6 +29,7 @@ import pytest
 import torch
 
 from oracle import restatement as R
+from tests._util import _bf16
 from tests.test_gpu_decoder_bench_shape import GRAD_L2, GRAD_MAX, LOSS_REL, ROW_L2, _captions, _rel_l2, _rel_max, _row_l2
 
 POWER = 20.0
@@ -51,10 +52,6 @@ SEEDS = {0: 11, 1: 12}
 OPS = ("load", "copy", "neg", "normal")
 DEC_REDRAW = 2.0               # single decoder tensors are re-drawn at twice their scale ("load", "copy")
 NORMAL_SCALE = 1.0             # nn.init.normal_ draws at the tensor's own scale
-
-
-def _bf16(t):
-    return t.bfloat16().float()
 
 
 def cell_of(family):
